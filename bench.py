@@ -229,7 +229,70 @@ def parse():
                          "protocol on CPU tensors over gloo (tests); prints a line with dry_run=true and value=null")
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help="(dry run) this rank exits non-zero: launcher error path")
     ap.add_argument("--dry-hang-rank", type=int, default=-1, help="(dry run) this rank never reaches the timed loop: watchdog path")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what rank 0's last timed step returned as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all; see dump_outputs), its noise draw pinned so that runs compare")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# --dump-outputs: the arrays of the last timed step's return value.  combined_rgb (the image) is stored whole up to
+# DUMP_WHOLE_ELEMS elements; every other array, and a larger image, as a fixed seeded sample of DUMP_SAMPLE_ELEMS of
+# its elements (flat indices from np.random.default_rng(DUMP_SEED), sorted; the static cloud: of its `count` valid rows)
+DUMP_KEYS = ("combined_rgb", "combined_rgb_static", "combined_rgb_dyn", "render_dyn_rgb", "render_dyn_mask", "geo_static_rgb",
+             "geo_static_mask", "st_pcl_rgb", "st_pcl_xyz")
+DUMP_WHOLE_ELEMS = 1 << 23
+DUMP_SAMPLE_ELEMS = 1 << 19
+DUMP_SEED = 20240501
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def pin_last_step_noise(model, rvr, n_steps, dev):
+    """The splat kernel draws its noise field from a per-stream {seed, draw number} state and advances the draw number
+    by one per view, so the field of a step depends on how many views its lane rendered before -- and the lane count
+    is probed by timing.  Set the state of the lane that renders step n_steps - 1 of the next timed region so that
+    step draws (DUMP_SEED, 0) whatever the lane count (the counter wraps modulo 2**64).  Outside the timed region."""
+    lane = (n_steps - 1) % rvr.n_lanes
+    states = []
+    for main, _ in rvr.lanes[:rvr.n_lanes]:
+        with torch.cuda.stream(main):
+            states.append(model.dyn_renderer.splat_rng_state(dev))
+    assert len({s.data_ptr() for s in states}) == len(states), "two lanes share a noise state: their draws interleave"
+    torch.cuda.synchronize(dev)
+    draws_before = (n_steps - 1) // rvr.n_lanes
+    states[lane].copy_(torch.tensor([DUMP_SEED, -draws_before], dtype=torch.int64))
+    torch.cuda.synchronize(dev)
+
+
+def dump_outputs(ret, out_dir):
+    """``ret``: the renderer's return value for one view (device tensors) -> out_dir/<name>.npy; returns {name: shape}"""
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    count = int(ret["st_pcl_rgb_count"].reshape(-1)[0].item()) if "st_pcl_rgb_count" in ret else None
+    arrays = {}
+    for k in DUMP_KEYS:
+        t = ret.get(k, None)
+        if not isinstance(t, torch.Tensor):
+            continue
+        if k.startswith("st_pcl_"):
+            t = t[0, :count]
+        a = t.detach().float().cpu().numpy()
+        whole = DUMP_WHOLE_ELEMS if k == "combined_rgb" else DUMP_SAMPLE_ELEMS
+        if a.size > whole:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLE_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        arrays[k] = a
+    if count is not None:
+        arrays["st_pcl_rgb_count"] = np.array([count], np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"dump of {total} bytes exceeds {DUMP_LIMIT_BYTES}"
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 # Several ranks: no arrangement probe (it would need collectives to agree on its outcome), one fixed arrangement per rank:
@@ -714,8 +777,13 @@ def main():
     gc.collect()
     gc.disable()  # no collector pauses inside the timed loop
     timed(max(2 * args.run_ahead + n_lanes, 24))
+    if args.dump_outputs:
+        pin_last_step_noise(model, rvr, args.steps, dev)
     elapsed = timed(args.steps)
     gc.enable()
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (now: the next render on the last step's lane overwrites its outputs)
+        dumped = dump_outputs(last["ret"], args.dump_outputs)
     gathered, cnt = last["gathered"], last["ret"]["st_pcl_rgb_count"]
     raster_status = last["ret"].get("geo_static_raster_status", None)
     ms0, ms1 = mem_probe["before"], mem_probe["after"]
@@ -1278,6 +1346,8 @@ def main():
                                       "not by streaming its inputs (DESIGN.md section 4)"},
             "cpu_baseline": cpu_baseline, "gnt": gnt, "variants": variants, "kernels": kernels,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
         emit(out)
     if world > 1:
         dist.barrier(device_ids=[local_rank])

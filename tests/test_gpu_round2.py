@@ -643,3 +643,34 @@ def test_bench_two_ranks_on_one_gpu():
     assert len(per_rank) == 2 and all(x > 0 for x in per_rank)
     assert b["config"]["gather_bytes_to_rank0"] == 3 * 96 * 160 * 4 * 10
     assert abs(b["value"] - 2 * 1e3 / b["ms_per_step"]) / b["value"] < 0.02  # whole-job rate: both ranks' views / max time
+
+
+def test_bench_dump_outputs_same_whatever_the_lane_count(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs, its noise draw pinned, so two runs with the same inputs
+    agree even when they keep a different number of views in flight (one lane vs three: the last step's lane has
+    rendered a different number of views before it)"""
+    import pathlib
+    import subprocess
+    import sys
+
+    root = pathlib.Path(__file__).resolve().parent.parent
+    got = []
+    for lanes in (1, 3):
+        d = tmp_path / f"lanes{lanes}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--height", "96", "--width", "160", "--frames", "4",
+                            "--steps", "7", "--warmup", "2", "--inflight", str(lanes), "--gnt-rays", "0", "--no-cpu-baseline",
+                            "--no-kernel-timing", "--no-scene-sweep", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        b, det = _bench_line_and_detail(r)
+        assert b["steps"] == 7 and b["config"]["views_in_flight"] == lanes
+        names = set(det["dumped_outputs"]["arrays"])
+        assert {p.stem for p in d.iterdir()} == names and {"combined_rgb", "render_dyn_mask", "st_pcl_rgb"} <= names
+        got.append({k: np.load(d / f"{k}.npy") for k in names})
+    a, b = got
+    assert a.keys() == b.keys()
+    assert a["combined_rgb"].shape == (1, 3, 96, 160) and a["st_pcl_rgb_count"][0] > 0
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape, k
+        # (the splat accumulates with float atomics: equal to rounding, as bench.py's own in-flight check)
+        np.testing.assert_allclose(a[k], b[k], rtol=0, atol=1e-5, err_msg=k)

@@ -653,3 +653,45 @@ def test_bench_compact_line_from_a_full_record_stays_under_4k():
     full["config"]["launch"] = "x" * 5000
     full["cpu_baseline"]["sample"] = "y" * 5000
     assert len(bench.compact_line(full).encode()) <= 4096
+
+
+def test_bench_dump_outputs_samples_within_budget(tmp_path):
+    """bench.py --dump-outputs: the image stored whole, every other array of a 1080p x 24 view (and the static cloud's valid
+    rows) as the same fixed sample, float32 / float64 only, at most 64 MB in all"""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    H, W, cap, count = 1080, 1920, 3_000_000, 2_000_000  # (a cloud of more valid rows than the sample holds)
+    g = torch.Generator().manual_seed(0)
+    img = lambda c: torch.rand(1, c, H, W, generator=g)  # noqa: E731
+    ret = {"combined_rgb": img(3), "combined_rgb_static": img(3), "combined_rgb_dyn": img(3), "render_dyn_rgb": img(3),
+           "render_dyn_mask": img(1) > 0.5, "geo_static_rgb": img(3), "geo_static_mask": img(1),
+           "st_pcl_rgb": torch.zeros(1, cap, 6), "st_pcl_xyz": torch.zeros(1, cap, 3),
+           "st_pcl_rgb_count": torch.tensor([count], dtype=torch.int64)}
+    ret["st_pcl_rgb"][0, :count] = 1.0
+    shapes = bench.dump_outputs(ret, tmp_path / "a")
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(f"{k}.npy" for k in shapes) and len(files) == 10
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 * 10**6
+    np.testing.assert_array_equal(got["combined_rgb"], ret["combined_rgb"].numpy())
+    assert got["st_pcl_rgb_count"].tolist() == [count]
+    n = bench.DUMP_SAMPLE_ELEMS
+    assert got["combined_rgb_dyn"].shape == (n,) and np.all(got["st_pcl_rgb"] == 1.0)  # (the cloud's valid rows only)
+    assert set(np.unique(got["render_dyn_mask"]).tolist()) == {0.0, 1.0}
+    # the sample is fixed: the same elements on every call
+    bench.dump_outputs(ret, tmp_path / "b")
+    for k in shapes:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / f"{k}.npy"), got[k])
+    # a small view is stored whole
+    small = {k: (v[..., :48, :64] if v.dim() == 4 else v) for k, v in ret.items() if not k.startswith("st_pcl")}
+    shapes = bench.dump_outputs(small, tmp_path / "c")
+    assert shapes["combined_rgb_static"] == [1, 3, 48, 64] and shapes["render_dyn_mask"] == [1, 1, 48, 64]
+
+
+def test_bench_rejects_zero_steps():
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
