@@ -436,6 +436,22 @@ int pgdvs_eval_psnr_sums(const float *pred_planar, const float *gt_hwc, const fl
                          float *pred_q, float *gt_q, const int64_t *count_dev, const int32_t *status_dev, double *sums,
                          void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
 
+/* ---- 8f-1, the caller's metric: the evaluator's masked SSIM for one view in one pass (pgdvs/engines/evaluator_pgdvs.py:190-283
+ * with pgdvs/utils/training.py:316-346 calculate_ssim: skimage 0.20 structural_similarity(gt, pred, full=True, channel_axis=2,
+ * data_range=2.0) -- per channel, 7x7 box means with scipy's "reflect" (half-sample symmetric) border, sample covariance
+ * 49/48, C1 = (0.01*2)^2, C2 = (0.03*2)^2, the full map without a border crop -- then sum(S*mask) / (sum(mask) + 1e-8) for
+ * the masks ones / eval_mask / 1 - eval_mask).  Inputs are quantised as for pgdvs_eval_psnr_sums; the window sums are exact
+ * in integers and S is formed from them in fp32 (skimage filters in float32: the two differ by ~1e-7 per mean).
+ *   pred_planar[3,H,W] raw render (combined_rgb); gt_hwc[H,W,3] raw ground truth; mask_hwc[H,W,3] eval_mask
+ *   ssim_map [3,H,W] (nullable): S
+ *   sums: DEVICE double[8] = sum S, sum S*m, sum S*(1-m), 3*H*W, sum m, sum (1-m), 0, 0 (the layout of the PSNR row, so that
+ *   both come back in one transfer); SSIM_k = sums[k] / (sums[3+k] + 1e-8).
+ *   H or W below 7 (skimage raises ValueError): PGDVS_ERR_INVALID, and the workspace query returns PGDVS_ERR_INVALID.
+ *   workspace >= pgdvs_eval_ssim_workspace_bytes(H,W) (40 bytes per 64x32 tile); deterministic (fixed-order sums). */
+int64_t pgdvs_eval_ssim_workspace_bytes(int H, int W);
+int pgdvs_eval_ssim_sums(const float *pred_planar, const float *gt_hwc, const float *mask_hwc, int H, int W, float *ssim_map,
+                         double *sums, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+
 /* ---- one native call per target view -------------------------------------------------
  * PGDVSRenderer.forward with static_renderer = StaticGeoPointRenderer, dyn_render_type = "softsplat",
  * batch item of size 1, render_stride 1, no tracker (pgdvs/renderers/pgdvs_renderer.py:84-178 ->

@@ -6,19 +6,13 @@
 // the view on this GPU; here the step enqueues two launches and reads eight doubles back (the six sums and the
 // geometry path's two status words).
 #include "common.h"
+#include "eval_quant.h"
 
 namespace pgdvs {
 
 constexpr int kEvalBlocks = 256;
 constexpr int kEvalThreads = 256;
 constexpr int kEvalSums = 6;  // sum d2, sum d2 m, sum d2 (1 - m), count, sum m, sum (1 - m)
-
-// (x.clamp(0, 1) -> nan_to_num(nan=0) -> (x * 255).byte().float() / 255.0), fp32 like torch
-__device__ __forceinline__ float quantise_u8(float x) {
-  x = x != x ? 0.0f : (x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x));
-  const float q = (float)(uint8_t)(x * 255.0f);
-  return q / 255.0f;
-}
 
 __global__ void __launch_bounds__(kEvalThreads)
 eval_partials_kernel(const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ mask, int P,

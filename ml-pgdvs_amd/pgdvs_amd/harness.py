@@ -3,10 +3,12 @@
 (pgdvs/engines/evaluator_pgdvs.py:26-188) around any renderer with the plugin contract -- to-device,
 ``forward`` under no_grad, clamp -> NaN to 0 -> quantise, ground truth resized to the render size,
 the evaluator's three masked PSNRs (``obtain_quantitative_nvidia`` :190-283 with
-``calculate_psnr`` pgdvs/utils/training.py:281-313) and ONE packed reduce of the metric sums to rank 0
-(the reference issues one ``torch.distributed.reduce`` per key, :183-186).  LPIPS and SSIM need
-third-party networks / skimage and are out of scope: their keys are not produced.  A few elementwise
-torch ops on final images; nothing here is on the rendering hot path."""
+``calculate_psnr`` pgdvs/utils/training.py:281-313), on request its three masked SSIMs (``calculate_ssim``
+training.py:316-346, skimage 0.20 ``structural_similarity``), and ONE packed reduce of the metric sums to rank 0
+(the reference issues one ``torch.distributed.reduce`` per key, :183-186).  LPIPS needs pretrained network weights and
+is out of scope: its keys are not produced.  On the GPU at render size the metrics are HIP passes (csrc/eval.hip,
+csrc/eval_ssim.hip); otherwise a few torch ops on final images.  SSIM's window sums are exact integers here, where
+skimage 0.20 filters in float32: the two differ by about 1e-7 on a masked mean."""
 import math
 import time
 from collections import OrderedDict
@@ -35,12 +37,47 @@ def masked_psnr(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor) -> f
     return 10 * math.log10(1.0 / mse)
 
 
+def _box7_sym(x: torch.Tensor) -> torch.Tensor:
+    """7x7 box mean over the last two axes with scipy.ndimage's "reflect" border (half-sample symmetric: -1 -> 0, -2 -> 1;
+    numpy's "symmetric", not torch's "reflect") -- ``uniform_filter(size=7)``."""
+    H, W = x.shape[-2:]
+
+    def sym(n):
+        i = torch.arange(-3, n + 3, device=x.device)
+        return torch.where(i < 0, -1 - i, torch.where(i >= n, 2 * n - 1 - i, i))
+
+    x = x.index_select(-2, sym(H)).index_select(-1, sym(W))
+    x = sum(x[..., k:k + H, :] for k in range(7))
+    return sum(x[..., k:k + W] for k in range(7)) / 49.0
+
+
+def masked_ssim(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor) -> float:
+    """calculate_ssim (training.py:316-346) on [3,H,W] images: skimage 0.20 ``structural_similarity(full=True,
+    channel_axis=2, data_range=2.0)`` restated in float64 -- per channel 7x7 box means with the symmetric border, sample
+    covariance 49/48, C1 = (0.01*2)^2, C2 = (0.03*2)^2, the full map without a border crop -- then
+    sum(S * mask) / (sum(mask) + 1e-8).  H or W below 7 raises ValueError, as skimage does."""
+    assert img1.ndim == 3 and img2.ndim == 3 and img1.shape == img2.shape
+    H, W = img1.shape[-2:]
+    if H < 7 or W < 7:
+        raise ValueError(f"masked_ssim: the image ({H} x {W}) is smaller than SSIM's 7 x 7 window")
+    a, b, m = img1.double(), img2.double(), mask.double()
+    assert float(a.min()) >= 0 and float(a.max()) <= 1 and float(b.min()) >= 0 and float(b.max()) <= 1
+    ux, uy = _box7_sym(a), _box7_sym(b)
+    uxx, uyy, uxy = _box7_sym(a * a), _box7_sym(b * b), _box7_sym(a * b)
+    cov_norm = 49.0 / 48.0
+    vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+    c1, c2 = (0.01 * 2.0) ** 2, (0.03 * 2.0) ** 2
+    S = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+    return float((S * m).sum() / (m.sum() + 1e-8))
+
+
 def to_device(batch: dict, device) -> dict:
     """``_to_gpu_func`` (pgdvs/engines/abstract.py:153-157): tensors move, everything else passes through"""
     return {k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
 
 
 METRIC_KEYS = ("psnr_full_combined", "psnr_dyn_combined", "psnr_static_combined")
+SSIM_KEYS = ("ssim_full_combined", "ssim_dyn_combined", "ssim_static_combined")  # eval_step(..., with_ssim=True)
 
 # measurement hook (bench.py): a dict set here accumulates the host wall time of eval_step's stages in seconds
 # ("to_device", "forward" = enqueue of the renderer, "metric_enqueue", "sync_read" = the step's one wait for the GPU,
@@ -49,14 +86,14 @@ STAGE_SECONDS = None
 
 
 @torch.no_grad()
-def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False):
+def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False, with_ssim=False):
     """One evaluator step on a batch of target views.  ``data`` is the reference's data dict (row A0) plus
     ``rgb_tgt[B,H,W,3]`` and ``eval_mask[B,H,W,3]`` (1 = dynamic region).  Returns the reference's
     ``metric_dict`` restricted to the in-scope keys: ``eval/count`` (int64) and the per-key SUMS over the
     batch (float32), reduced to rank 0 when a process group is up (device tensors then, as upstream; in a single process
     HOST tensors on both the fused GPU path and the torch path, so that a caller who accumulates them over steps never
-    mixes devices).  With ``return_images`` also the quantised prediction / ground truth and the
-    per-view values."""
+    mixes devices).  ``with_ssim`` adds the three masked SSIM sums (``SSIM_KEYS``, float32, reduced in the same packed
+    block).  With ``return_images`` also the quantised prediction / ground truth and the per-view values."""
     device = device if device is not None else next(iter(v for v in data.values() if isinstance(v, torch.Tensor))).device
     stages, t_prev = STAGE_SECONDS, time.perf_counter()
 
@@ -111,8 +148,12 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
                                   count_dev=cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None,
                                   status_dev=stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None)
                for i_b in range(n_batch)]
+        # (SSIM after the unchanged PSNR launches; its rows come back in the same transfer)
+        ssim_rows = [ops.eval_ssim_sums(comb[i_b], data_gpu["rgb_tgt"][i_b], data_gpu["eval_mask"][i_b])[0]
+                     for i_b in range(n_batch)] if with_ssim else []
         lap("metric_enqueue")
-        sums = ops.read_back_rows([r_[0] for r_ in res])  # (the step's synchronisation)
+        sums = ops.read_back_rows([r_[0] for r_ in res] + ssim_rows)  # (the step's synchronisation)
+        sums, ssim_sums = sums[:n_batch], sums[n_batch:]
         lap("sync_read")
         check_status(host_counts=[int(s_[6]) for s_ in sums] if cnts is not None else None,
                      host_status=[int(s_[7]) for s_ in sums] if stat is not None else None)
@@ -121,20 +162,23 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
             for j, k in enumerate(METRIC_KEYS):
                 mse = s_[j] / (s_[3 + j] + 1e-8)
                 per_view[k].append(0 if mse == 0 else 10 * math.log10(1.0 / mse))
+        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ())
+        if with_ssim:
+            per_view.update({k: [s_[j] / (s_[3 + j] + 1e-8) for s_ in ssim_sums] for j, k in enumerate(SSIM_KEYS)})
         # (a single process keeps the packed sums -- and so the metric tensors -- on the host: same dtypes and values, no
         # upload and no one-element kernels per step, and the caller's `.item()` costs nothing; ranks that reduce over
         # RCCL need them on the device, like upstream)
         multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
         if not multi:
             metric = {"eval/count": torch.tensor([n_batch], dtype=torch.int64)}
-            for k in METRIC_KEYS:
+            for k in keys:
                 metric[f"eval/{k}"] = torch.tensor(per_view[k], dtype=torch.float32).sum()
         else:
-            packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in METRIC_KEYS],
+            packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
                                   dtype=torch.float64, device=comb.device)
             packed = pdist.reduce_metrics(packed, dst=0)
             metric = {"eval/count": packed[:1].round().to(torch.int64)}
-            for j, k in enumerate(METRIC_KEYS):
+            for j, k in enumerate(keys):
                 metric[f"eval/{k}"] = packed[1 + j].to(torch.float32)
         lap("post")
         if return_images:
@@ -157,7 +201,8 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
         rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
         eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
         eval_mask = (eval_mask > 0).float()
-    per_view = {k: [] for k in METRIC_KEYS}
+    keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ())
+    per_view = {k: [] for k in keys}
     for i_b in range(n_batch):
         p, g = pred["combined"][i_b].to(rgb_gt.device), rgb_gt[i_b]
         m_dyn = eval_mask[i_b]
@@ -165,15 +210,19 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
         per_view["psnr_full_combined"].append(masked_psnr(g, p, torch.ones_like(g)))
         per_view["psnr_dyn_combined"].append(masked_psnr(g, p, m_dyn))
         per_view["psnr_static_combined"].append(masked_psnr(g, p, 1.0 - m_dyn))
+        if with_ssim:
+            per_view["ssim_full_combined"].append(masked_ssim(g, p, torch.ones_like(g)))
+            per_view["ssim_dyn_combined"].append(masked_ssim(g, p, m_dyn))
+            per_view["ssim_static_combined"].append(masked_ssim(g, p, 1.0 - m_dyn))
     # one packed reduce instead of one collective per key: [count, sums...] in float64 on the device
-    packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in METRIC_KEYS],
+    packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
                           dtype=torch.float64, device=rgb_gt.device)
     packed = pdist.reduce_metrics(packed, dst=0)
     multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
     if not multi:
         packed = packed.cpu()  # one process: host tensors on BOTH paths, whatever the inputs' dtypes and sizes were
     metric = {"eval/count": packed[:1].round().to(torch.int64)}
-    for j, k in enumerate(METRIC_KEYS):
+    for j, k in enumerate(keys):
         metric[f"eval/{k}"] = packed[1 + j].to(torch.float32)
     if return_images:
         return metric, {"pred": pred["combined"], "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}

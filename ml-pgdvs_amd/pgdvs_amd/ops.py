@@ -599,6 +599,31 @@ def eval_psnr_sums(pred_planar, gt_hwc, mask_hwc, want_images: bool = False, cou
     return sums, pq, gq
 
 
+def eval_ssim_sums(pred_planar, gt_hwc, mask_hwc, want_map: bool = False):
+    """The evaluator's masked SSIM statistics in one pass (``pgdvs_eval_ssim_sums``): pred[3,H,W] raw render, gt[H,W,3] raw,
+    mask[H,W,3] -> device float64[8] (sum S, sum S m, sum S (1-m), count, sum m, sum (1-m), 0, 0 -- the layout of
+    ``eval_psnr_sums``' row, so that ``read_back_rows`` brings both back in one transfer) and, with ``want_map``, the SSIM map
+    S[3,H,W].  Raises ValueError when H or W is below the 7x7 window, as skimage does."""
+    p = _req(pred_planar, torch.float32, "pred")
+    g = _req(gt_hwc, torch.float32, "gt")
+    m = _req(mask_hwc, torch.float32, "eval_mask")
+    _, H, W = p.shape
+    assert tuple(g.shape) == (H, W, 3) and tuple(m.shape) == (H, W, 3), (p.shape, g.shape, m.shape)
+    if H < 7 or W < 7:
+        raise ValueError(f"eval_ssim_sums: the image ({H} x {W}) is smaller than SSIM's 7 x 7 window")
+    lib = _lib.load()
+    nws = int(lib.pgdvs_eval_ssim_workspace_bytes(H, W))
+    if nws < 0:
+        _ws(nws, p.device)  # raises with the library's message
+    nws = (nws + 63) // 64 * 64
+    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # partials, then the eight doubles
+    sums = buf[nws:nws + 64].view(torch.float64)
+    smap = torch.empty_like(p) if want_map else None
+    check(lib.pgdvs_eval_ssim_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(smap), _ptr(sums), _ptr(buf), nws, _stream()),
+          "pgdvs_eval_ssim_sums")
+    return sums, smap
+
+
 _pinned_sums = {}
 
 
