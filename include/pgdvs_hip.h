@@ -452,6 +452,31 @@ int64_t pgdvs_eval_ssim_workspace_bytes(int H, int W);
 int pgdvs_eval_ssim_sums(const float *pred_planar, const float *gt_hwc, const float *mask_hwc, int H, int W, float *ssim_map,
                          double *sums, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
 
+/* ---- 8f-1, the caller's metric: the evaluator's masked LPIPS for one view (pgdvs/engines/evaluator_pgdvs.py:94-110,190-283
+ * with trainer_pgdvs.py:132-137 PerceptualLoss(model="net-lin", net="alex", use_gpu=False, version=0.1) -> nsff_lpips/
+ * dist_model.py:70-135, networks_basic.py:15-170, pretrained_networks.py:63-105).  Both images are quantised as for
+ * pgdvs_eval_psnr_sums and mapped to [-1, 1] (2 q - 1); NO ScalingLayer (PNetLin.forward compares the float version 0.1 with
+ * the string "0.1", so the shift / scale never applies on this protocol); AlexNet features[0:12] (conv 11x11/4 pad 2, ReLU,
+ * maxpool 3/2, conv 5x5 pad 2, ReLU, maxpool 3/2, conv 3x3 pad 1 + ReLU three times) on the fp32 matrix instruction, once for
+ * both images; per relu_k map normalize_tensor, squared difference, the 1x1 lin_k (no bias), and spatial_average with the
+ * mask's channel 0 resized to the map by torch's "nearest" rule (src = min(floor(dst * (float)in / out), in - 1)).
+ *   pred_planar[3,H,W] raw render (combined_rgb); gt_hwc[H,W,3] raw ground truth; mask_hwc[H,W,3] eval_mask (channel 0 used)
+ *   conv_weights: features.{0,3,6,8,10}.weight concatenated in that order, torch layout [Cout][Cin][k][k] (2468544 floats)
+ *   conv_biases:  features.{0,3,6,8,10}.bias concatenated (64 + 192 + 384 + 256 + 256 = 1152 floats)
+ *   lin_weights:  lin{0..4}.model.1.weight concatenated (1152 floats)
+ *   sums: DEVICE double[8] = LPIPS full, LPIPS dyn, LPIPS static, then h1 w1, sum m, sum (1 - m) of the relu1 map, 0, 0.
+ *   The kernel finishes the ratios: each of sums[0..2] is already sum_k sum(x_k m_k) / (sum(m_k) + 1e-8) over the five layers
+ *   (the division per layer precedes the sum over layers, so a row of plain sums could not carry it); the row keeps the
+ *   PSNR / SSIM rows' width so that all of them come back in one transfer.
+ *   H or W below 31 (the relu5 map would be empty) or H W >= 2^26: PGDVS_ERR_INVALID, and the workspace query returns
+ *   PGDVS_ERR_INVALID.  workspace >= pgdvs_lpips_workspace_bytes(H,W), laid out as (each region rounded up to 256 bytes):
+ *   x[2,3,H,W], relu1, pool1, relu2, pool2, relu3, relu4, relu5 (each [2,C,h,w] fp32, ground truth first), head partials.
+ *   Deterministic (fixed-order float64 sums). */
+int64_t pgdvs_lpips_workspace_bytes(int H, int W);
+int pgdvs_lpips_sums(const float *pred_planar, const float *gt_hwc, const float *mask_hwc, int H, int W, const float *conv_weights,
+                     const float *conv_biases, const float *lin_weights, double *sums, void *workspace, int64_t workspace_bytes,
+                     pgdvs_stream_t stream);
+
 /* ---- one native call per target view -------------------------------------------------
  * PGDVSRenderer.forward with static_renderer = StaticGeoPointRenderer, dyn_render_type = "softsplat",
  * batch item of size 1, render_stride 1, no tracker (pgdvs/renderers/pgdvs_renderer.py:84-178 ->

@@ -4,16 +4,18 @@
 ``forward`` under no_grad, clamp -> NaN to 0 -> quantise, ground truth resized to the render size,
 the evaluator's three masked PSNRs (``obtain_quantitative_nvidia`` :190-283 with
 ``calculate_psnr`` pgdvs/utils/training.py:281-313), on request its three masked SSIMs (``calculate_ssim``
-training.py:316-346, skimage 0.20 ``structural_similarity``), and ONE packed reduce of the metric sums to rank 0
-(the reference issues one ``torch.distributed.reduce`` per key, :183-186).  LPIPS needs pretrained network weights and
-is out of scope: its keys are not produced.  On the GPU at render size the metrics are HIP passes (csrc/eval.hip,
-csrc/eval_ssim.hip); otherwise a few torch ops on final images.  SSIM's window sums are exact integers here, where
-skimage 0.20 filters in float32: the two differ by about 1e-7 on a masked mean."""
+training.py:316-346, skimage 0.20 ``structural_similarity``) and its three masked LPIPS values (``PerceptualLoss(
+model="net-lin", net="alex", version=0.1)``, trainer_pgdvs.py:132-137, given the AlexNet and lin weights as an
+``LpipsAlex``), and ONE packed reduce of the metric sums to rank 0 (the reference issues one
+``torch.distributed.reduce`` per key, :183-186).  On the GPU at render size the metrics are HIP passes (csrc/eval.hip,
+csrc/eval_ssim.hip, csrc/lpips.hip); otherwise a few torch ops on final images.  SSIM's window sums are exact integers
+here, where skimage 0.20 filters in float32: the two differ by about 1e-7 on a masked mean."""
 import math
 import time
 from collections import OrderedDict
 
 import torch
+import torch.nn.functional as F
 
 from . import dist as pdist
 
@@ -71,6 +73,146 @@ def masked_ssim(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor) -> f
     return float((S * m).sum() / (m.sum() + 1e-8))
 
 
+# ---------------------------------------------------------------- LPIPS (nsff_lpips, the NVIDIA protocol)
+# AlexNet features[0:12] as pretrained_networks.py:63-105 slices them: (features index, kernel, stride, padding, pool before)
+_ALEX_CONVS = ((0, 11, 4, 2, False), (3, 5, 1, 2, True), (6, 3, 1, 1, True), (8, 3, 1, 1, False), (10, 3, 1, 1, False))
+_ALEX_SHAPES = ((64, 3, 11), (192, 64, 5), (384, 192, 3), (256, 384, 3), (256, 256, 3))
+# the ScalingLayer (networks_basic.py:145-157) the NVIDIA protocol never applies (see masked_lpips)
+_LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+_LPIPS_SCALE = (0.458, 0.448, 0.450)
+
+
+def _strip_module(sd: dict) -> dict:
+    return {k[7:] if k.startswith("module.") else k: v for k, v in sd.items()}
+
+
+class LpipsAlex:
+    """The weights of LPIPS v0.1 with the AlexNet backbone, on one device: ``features.{0,3,6,8,10}.{weight,bias}`` of
+    torchvision's ``alexnet`` and the five ``lin{k}.model.1.weight`` of ``nsff_lpips/weights/v0.1/alex.pth``.  Only the keys
+    it uses are read, and each must be present with its exact shape (other keys, e.g. the classifier's, are ignored).
+    ``backbone`` may also be in the reference's layout (a ``PNetLin`` state dict: ``net.slice{s}.{i}.*``, optionally with
+    ``module.`` prefixes), which then may carry the lin weights too.  Also holds the three packed buffers the C ABI takes."""
+
+    def __init__(self, backbone: dict, lin: dict = None, device="cpu"):
+        bb, ln = _strip_module(dict(backbone)), _strip_module(dict(lin)) if lin is not None else {}
+        slices = {0: 1, 3: 2, 6: 3, 8: 4, 10: 5}  # features index -> PNetLin slice
+
+        def pick(sd, names, what):
+            for n in names:
+                if n in sd:
+                    return torch.as_tensor(sd[n]).detach().to("cpu", torch.float32)
+            raise KeyError(f"LpipsAlex: {what} not found (looked for {', '.join(names)})")
+
+        self.convs, self.lins = [], []
+        for (i, *_), (co, ci, k) in zip(_ALEX_CONVS, _ALEX_SHAPES):
+            for kind, shape in (("weight", (co, ci, k, k)), ("bias", (co,))):
+                t = pick(bb, (f"features.{i}.{kind}", f"net.slice{slices[i]}.{i}.{kind}"), f"backbone {kind} of features.{i}")
+                if tuple(t.shape) != shape:
+                    raise ValueError(f"LpipsAlex: features.{i}.{kind} has shape {tuple(t.shape)}, expected {shape}")
+                self.convs.append(t)
+        for k, (co, _, _) in enumerate(_ALEX_SHAPES):
+            t = pick(ln if ln else bb, (f"lin{k}.model.1.weight",), f"lin{k}.model.1.weight")
+            if tuple(t.shape) != (1, co, 1, 1):
+                raise ValueError(f"LpipsAlex: lin{k}.model.1.weight has shape {tuple(t.shape)}, expected {(1, co, 1, 1)}")
+            self.lins.append(t)
+        d = torch.device(device)
+        self._move(torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d)
+
+    def _pack(self):
+        self.conv_weights = torch.cat([w.reshape(-1) for w in self.convs[0::2]])
+        self.conv_biases = torch.cat(self.convs[1::2])
+        self.lin_weights = torch.cat([w.reshape(-1) for w in self.lins])
+
+    def _move(self, device):
+        self.convs = [t.to(device) for t in self.convs]
+        self.lins = [t.to(device) for t in self.lins]
+        self._pack()
+        self.device = device
+        self._copies = {device: self}
+
+    def on(self, device) -> "LpipsAlex":
+        """these weights on ``device``: self, or a copy made once and kept"""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        c = self._copies.get(device)
+        if c is None:
+            c = LpipsAlex.__new__(LpipsAlex)
+            c.convs, c.lins = self.convs, self.lins
+            c._move(device)
+            self._copies[device] = c
+        return c
+
+    @classmethod
+    def from_files(cls, backbone_path, lin_path, device="cpu"):
+        """torchvision's AlexNet checkpoint (``alexnet-owt-*.pth``) and the reference's ``weights/v0.1/alex.pth`` (saved
+        with CUDA storages: loaded with ``map_location="cpu"``)."""
+        bb = torch.load(str(backbone_path), map_location="cpu", weights_only=True)
+        ln = torch.load(str(lin_path), map_location="cpu", weights_only=True) if lin_path is not None else None
+        return cls(bb, ln, device)
+
+    @classmethod
+    def from_engine_cfg(cls, engine_cfg, device="cpu"):
+        """``engine_cfg.lpips_weights: {backbone: <path>, lin: <path>}`` (configs/engine/evaluator_pgdvs.yaml) -> an
+        ``LpipsAlex``, or None when the key is absent or null (LPIPS then stays off)."""
+        spec = engine_cfg.get("lpips_weights", None) if hasattr(engine_cfg, "get") else getattr(engine_cfg, "lpips_weights", None)
+        if not spec:
+            return None
+        return cls.from_files(spec["backbone"], spec["lin"], device)
+
+
+def alex_features(x: torch.Tensor, weights: LpipsAlex):
+    """relu1..relu5 of AlexNet ``features[0:12]`` for a batch x[N,3,H,W] (float32 torch; pretrained_networks.py:63-105)."""
+    w = weights.on(x.device)
+    feats, h = [], x
+    for j, (_, k, st, pd, pool) in enumerate(_ALEX_CONVS):
+        if pool:
+            h = F.max_pool2d(h, kernel_size=3, stride=2)
+        h = F.relu(F.conv2d(h, w.convs[2 * j], w.convs[2 * j + 1], stride=st, padding=pd))
+        feats.append(h)
+    return feats
+
+
+def _lpips_torch(img1, img2, masks, weights, scaling_layer=False):
+    """LPIPS of [3,H,W] images in [0,1] for each of ``masks`` ([C,H,W], channel 0 used), the backbone run once."""
+    H, W = img1.shape[-2:]
+    if H < 31 or W < 31:
+        raise ValueError(f"masked_lpips: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
+    x = torch.stack([img1, img2]).float()
+    x = 2.0 * x - 1.0  # modify_rgb_range "0_1" -> "-1_1" (utils/rendering.py:26-77)
+    if scaling_layer:
+        shift = torch.tensor(_LPIPS_SHIFT, dtype=torch.float32, device=x.device)[None, :, None, None]
+        scale = torch.tensor(_LPIPS_SCALE, dtype=torch.float32, device=x.device)[None, :, None, None]
+        x = (x - shift) / scale
+    feats = alex_features(x, weights)
+    diffs = []
+    for f, lin in zip(feats, weights.on(x.device).lins):
+        f = f / (torch.sqrt(torch.sum(f ** 2, dim=1, keepdim=True)) + 1e-10)  # normalize_tensor
+        diffs.append(F.conv2d((f[0:1] - f[1:2]) ** 2, lin))  # [1,1,h,w]
+    out = []
+    for m in masks:
+        m = m[None, 0:1].float().to(x.device)
+        val = None
+        for d in diffs:  # spatial_average (networks_basic.py:15-25), then the sum over layers (:134-136)
+            mr = F.interpolate(m, size=[d.shape[2], d.shape[3]])
+            r = torch.sum(d * mr) / (torch.sum(mr) + 1e-8)
+            val = r if val is None else val + r
+        out.append(float(val))
+    return out
+
+
+def masked_lpips(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, weights: LpipsAlex, *, scaling_layer: bool = False) -> float:
+    """The evaluator's ``lpips_fn.forward(gt, pred, mask)`` (evaluator_pgdvs.py:190-283 with trainer_pgdvs.py:132-137) on
+    [3,H,W] images in [0,1] (already quantised) restated in float32 torch: 2 x - 1, AlexNet relu1..5 (``F.conv2d``,
+    ``F.max_pool2d``), normalize_tensor, squared difference, the 1x1 lin_k, then sum(x m) / (sum(m) + 1e-8) per layer with
+    the mask's channel 0 ``F.interpolate``d (nearest) to the layer, summed over the layers.  The reference never applies its
+    ScalingLayer on this protocol: ``PNetLin.forward`` tests ``self.version == "0.1"`` (a string) while the evaluator passes
+    ``version=0.1`` (a float), networks_basic.py:94-99 -- kept here as the ``masked_psnr`` quirk is; ``scaling_layer=True``
+    applies it (only to show that the difference is visible).  H or W below 31 raises ValueError (relu5 would be empty)."""
+    assert img1.ndim == 3 and img2.ndim == 3 and img1.shape == img2.shape
+    return _lpips_torch(img1, img2, [mask], weights, scaling_layer=scaling_layer)[0]
+
+
 def to_device(batch: dict, device) -> dict:
     """``_to_gpu_func`` (pgdvs/engines/abstract.py:153-157): tensors move, everything else passes through"""
     return {k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
@@ -78,6 +220,7 @@ def to_device(batch: dict, device) -> dict:
 
 METRIC_KEYS = ("psnr_full_combined", "psnr_dyn_combined", "psnr_static_combined")
 SSIM_KEYS = ("ssim_full_combined", "ssim_dyn_combined", "ssim_static_combined")  # eval_step(..., with_ssim=True)
+LPIPS_KEYS = ("lpips_full_combined", "lpips_dyn_combined", "lpips_static_combined")  # eval_step(..., lpips=LpipsAlex(...))
 
 # measurement hook (bench.py): a dict set here accumulates the host wall time of eval_step's stages in seconds
 # ("to_device", "forward" = enqueue of the renderer, "metric_enqueue", "sync_read" = the step's one wait for the GPU,
@@ -86,14 +229,16 @@ STAGE_SECONDS = None
 
 
 @torch.no_grad()
-def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False, with_ssim=False):
+def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False, with_ssim=False,
+              lpips=None):
     """One evaluator step on a batch of target views.  ``data`` is the reference's data dict (row A0) plus
     ``rgb_tgt[B,H,W,3]`` and ``eval_mask[B,H,W,3]`` (1 = dynamic region).  Returns the reference's
     ``metric_dict`` restricted to the in-scope keys: ``eval/count`` (int64) and the per-key SUMS over the
     batch (float32), reduced to rank 0 when a process group is up (device tensors then, as upstream; in a single process
     HOST tensors on both the fused GPU path and the torch path, so that a caller who accumulates them over steps never
     mixes devices).  ``with_ssim`` adds the three masked SSIM sums (``SSIM_KEYS``, float32, reduced in the same packed
-    block).  With ``return_images`` also the quantised prediction / ground truth and the per-view values."""
+    block).  ``lpips`` (an ``LpipsAlex``) adds the three masked LPIPS values (``LPIPS_KEYS``, float32, in the same block).
+    With ``return_images`` also the quantised prediction / ground truth and the per-view values."""
     device = device if device is not None else next(iter(v for v in data.values() if isinstance(v, torch.Tensor))).device
     stages, t_prev = STAGE_SECONDS, time.perf_counter()
 
@@ -151,9 +296,12 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
         # (SSIM after the unchanged PSNR launches; its rows come back in the same transfer)
         ssim_rows = [ops.eval_ssim_sums(comb[i_b], data_gpu["rgb_tgt"][i_b], data_gpu["eval_mask"][i_b])[0]
                      for i_b in range(n_batch)] if with_ssim else []
+        # (LPIPS last: the backbone runs once per image per view, for all three masks)
+        lpips_rows = [ops.lpips_sums(comb[i_b], data_gpu["rgb_tgt"][i_b], data_gpu["eval_mask"][i_b], lpips.on(comb.device))[0]
+                      for i_b in range(n_batch)] if lpips is not None else []
         lap("metric_enqueue")
-        sums = ops.read_back_rows([r_[0] for r_ in res] + ssim_rows)  # (the step's synchronisation)
-        sums, ssim_sums = sums[:n_batch], sums[n_batch:]
+        sums = ops.read_back_rows([r_[0] for r_ in res] + ssim_rows + lpips_rows)  # (the step's synchronisation)
+        sums, ssim_sums, lpips_sums = sums[:n_batch], sums[n_batch:n_batch + len(ssim_rows)], sums[n_batch + len(ssim_rows):]
         lap("sync_read")
         check_status(host_counts=[int(s_[6]) for s_ in sums] if cnts is not None else None,
                      host_status=[int(s_[7]) for s_ in sums] if stat is not None else None)
@@ -162,9 +310,11 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
             for j, k in enumerate(METRIC_KEYS):
                 mse = s_[j] / (s_[3 + j] + 1e-8)
                 per_view[k].append(0 if mse == 0 else 10 * math.log10(1.0 / mse))
-        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ())
+        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
         if with_ssim:
             per_view.update({k: [s_[j] / (s_[3 + j] + 1e-8) for s_ in ssim_sums] for j, k in enumerate(SSIM_KEYS)})
+        if lpips is not None:  # (the LPIPS row carries the finished values: include/pgdvs_hip.h)
+            per_view.update({k: [s_[j] for s_ in lpips_sums] for j, k in enumerate(LPIPS_KEYS)})
         # (a single process keeps the packed sums -- and so the metric tensors -- on the host: same dtypes and values, no
         # upload and no one-element kernels per step, and the caller's `.item()` costs nothing; ranks that reduce over
         # RCCL need them on the device, like upstream)
@@ -201,7 +351,7 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
         rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
         eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
         eval_mask = (eval_mask > 0).float()
-    keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ())
+    keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
     per_view = {k: [] for k in keys}
     for i_b in range(n_batch):
         p, g = pred["combined"][i_b].to(rgb_gt.device), rgb_gt[i_b]
@@ -214,6 +364,9 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
             per_view["ssim_full_combined"].append(masked_ssim(g, p, torch.ones_like(g)))
             per_view["ssim_dyn_combined"].append(masked_ssim(g, p, m_dyn))
             per_view["ssim_static_combined"].append(masked_ssim(g, p, 1.0 - m_dyn))
+        if lpips is not None:
+            for k, v in zip(LPIPS_KEYS, _lpips_torch(g, p, [torch.ones_like(g), m_dyn, 1.0 - m_dyn], lpips)):
+                per_view[k].append(v)
     # one packed reduce instead of one collective per key: [count, sums...] in float64 on the device
     packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
                           dtype=torch.float64, device=rgb_gt.device)

@@ -624,6 +624,63 @@ def eval_ssim_sums(pred_planar, gt_hwc, mask_hwc, want_map: bool = False):
     return sums, smap
 
 
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)  # AlexNet relu1..relu5
+LPIPS_MIN_SIZE = 31  # conv1 11x11/4 pad 2, then two 3/2 pools: relu5 is empty below this
+
+
+def lpips_map_sizes(H: int, W: int):
+    """[(h, w)] of relu1..relu5 and [(h, w)] of pool1, pool2 for an H x W image (the backbone's shape rule)."""
+    conv1 = ((H + 4 - 11) // 4 + 1, (W + 4 - 11) // 4 + 1)
+    pool1 = ((conv1[0] - 3) // 2 + 1, (conv1[1] - 3) // 2 + 1)
+    pool2 = ((pool1[0] - 3) // 2 + 1, (pool1[1] - 3) // 2 + 1)
+    return [conv1, pool1, pool2, pool2, pool2], [pool1, pool2]
+
+
+def _lpips_features(buf, H, W):
+    """relu1..relu5 as [2,C,h,w] views of the workspace (include/pgdvs_hip.h: x, relu1, pool1, relu2, pool2, relu3, relu4,
+    relu5, each region rounded up to 256 bytes)"""
+    relu, pool = lpips_map_sizes(H, W)
+    a256 = lambda b: (b + 255) // 256 * 256  # noqa: E731
+    off = a256(2 * 3 * H * W * 4)
+    out = []
+    for k, (C, (h, w)) in enumerate(zip(LPIPS_CHANNELS, relu)):
+        n = 2 * C * h * w
+        out.append(buf[off:off + 4 * n].view(torch.float32).view(2, C, h, w))
+        off += a256(4 * n)
+        if k < 2:
+            off += a256(4 * 2 * C * pool[k][0] * pool[k][1])
+    return out
+
+
+def lpips_sums(pred_planar, gt_hwc, mask_hwc, weights, want_features: bool = False):
+    """The evaluator's masked LPIPS of one view (``pgdvs_lpips_sums``): pred[3,H,W] raw render, gt[H,W,3] raw, mask[H,W,3]
+    (channel 0 used), ``weights`` a ``harness.LpipsAlex`` on the same device -> device float64[8] (LPIPS full, dyn, static,
+    then the relu1 map's pixel count, sum m, sum (1 - m), 0, 0 -- the width of ``eval_psnr_sums``' row, so that
+    ``read_back_rows`` brings them all back in one transfer) and, with ``want_features``, relu1..relu5 of both images as
+    [2,C,h,w] (ground truth first; views of the call's workspace).  Raises ValueError when H or W is below 31 (the relu5 map
+    would be empty)."""
+    p = _req(pred_planar, torch.float32, "pred")
+    g = _req(gt_hwc, torch.float32, "gt")
+    m = _req(mask_hwc, torch.float32, "eval_mask")
+    _, H, W = p.shape
+    assert tuple(g.shape) == (H, W, 3) and tuple(m.shape) == (H, W, 3), (p.shape, g.shape, m.shape)
+    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+        raise ValueError(f"lpips_sums: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
+    cw, cb, lw = (_req(t, torch.float32, n) for t, n in ((weights.conv_weights, "conv_weights"), (weights.conv_biases, "conv_biases"),
+                                                         (weights.lin_weights, "lin_weights")))
+    assert cw.device == p.device, (cw.device, p.device)
+    lib = _lib.load()
+    nws = int(lib.pgdvs_lpips_workspace_bytes(H, W))
+    if nws < 0:
+        _ws(nws, p.device)  # raises with the library's message
+    nws = (nws + 63) // 64 * 64
+    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # the network's maps and partials, then the eight doubles
+    sums = buf[nws:nws + 64].view(torch.float64)
+    check(lib.pgdvs_lpips_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw), _ptr(sums), _ptr(buf), nws, _stream()),
+          "pgdvs_lpips_sums")
+    return sums, (_lpips_features(buf, H, W) if want_features else None)
+
+
 _pinned_sums = {}
 
 
