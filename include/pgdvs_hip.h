@@ -477,6 +477,46 @@ int pgdvs_lpips_sums(const float *pred_planar, const float *gt_hwc, const float 
                      const float *conv_biases, const float *lin_weights, double *sums, void *workspace, int64_t workspace_bytes,
                      pgdvs_stream_t stream);
 
+/* ---- 8f-1, the caller's metric, DyCheck iPhone protocol (quant_type "dycheck_iphone", pgdvs/engines/evaluator_pgdvs.py:282-409
+ * through pgdvs/utils/dycheck/metrics.py:63-186): PSNR and SSIM of one view with the full mask and the covisibility mask, in
+ * one pass.  Both images are quantised as for pgdvs_eval_psnr_sums.  PSNR = -10/ln 10 ln(sum(d^2 m) / max(sum(m over 3
+ * channels), 1e-6)) with d over all three channels.  SSIM (modelled on tf.image.ssim): an 11-tap Gaussian (sigma 1.5, sum 1),
+ * k1 = 0.01, k2 = 0.03, max_val 1, the mask applied as a partial convolution, separably in two "valid" passes (first along W,
+ * then along H; each z' = conv(z m, f) 11 / conv(m, 1) where conv(m, 1) != 0, else 0, the next pass's mask conv(m, 1) != 0),
+ * variances clamped at 0, covariance clipped to sign(s01) min(sqrt(s00 s11), |s01|), then the mean over ALL (H-10)(W-10) 3
+ * map entries (a window that saw no mask gives exactly 1).  fp32 arithmetic, fixed-order float64 sums (deterministic).
+ *   pred_planar[3,H,W] raw render (combined_rgb); gt_hwc[H,W,3] raw ground truth; mask_hw[H,W] eval_mask (its one channel)
+ *   sums: DEVICE double[8] (the width of the PSNR row, so that all rows of a step come back in one transfer):
+ *     [0] sum d^2   [1] sum d^2 m   [2] sum S (full mask)   [3] 3 H W   [4] 3 sum m   [5] sum S (covisibility mask)
+ *     [6] (double)*count_dev (-1 when NULL)   [7] (double)*status_dev (0 when NULL), as in pgdvs_eval_psnr_sums
+ *   PSNR = -10/ln 10 ln(sums[0] / max(sums[3], 1e-6)), mPSNR likewise with sums[1] / max(sums[4], 1e-6) (an exact match or an
+ *   empty mask gives +inf, as upstream); SSIM = sums[2] / (3 (H-10)(W-10)), mSSIM = sums[5] / (3 (H-10)(W-10)).
+ *   H or W below 11 (upstream's map would be empty and its mean NaN): PGDVS_ERR_INVALID, and the workspace query returns
+ *   PGDVS_ERR_INVALID.  workspace >= pgdvs_dycheck_psnr_ssim_workspace_bytes(H,W) (64 bytes per 32x32 output tile). */
+int64_t pgdvs_dycheck_psnr_ssim_workspace_bytes(int H, int W);
+int pgdvs_dycheck_psnr_ssim_sums(const float *pred_planar, const float *gt_hwc, const float *mask_hw, int H, int W,
+                                 const int64_t *count_dev, const int32_t *status_dev, double *sums, void *workspace,
+                                 int64_t workspace_bytes, pgdvs_stream_t stream);
+
+/* ---- 8f-1, the caller's metric, DyCheck iPhone protocol: LPIPS of one view with the full mask and the covisibility mask
+ * (metrics.py:189-230 with lpips 0.1.4 LPIPS(net="alex", spatial=True), trainer_pgdvs.py:138-139).  Four images, quantised as for
+ * pgdvs_eval_psnr_sums: gt, pred, gt m, pred m, each im2tensor(., factor=1/2) = 2 x - 1 and passed through the ScalingLayer
+ * (shift [-.030,-.088,-.188], scale [.458,.448,.450]: version is the string "0.1" here); the AlexNet backbone of
+ * pgdvs_lpips_sums on all four; per layer normalize_tensor, squared difference and lin_k for the pairs (gt, pred) and
+ * (gt m, pred m); each lin map upsampled to H x W (bilinear, align_corners=False, source (dst + 0.5) in/out - 0.5 clamped at 0),
+ * summed over the layers; masked_mean = sum(v m) / max(sum(m), 1e-6) with the full mask on the first pair and eval_mask on the
+ * second.  The weights are packed as for pgdvs_lpips_sums.
+ *   mask_hw[H,W] eval_mask (its one channel)
+ *   sums: DEVICE double[8] = LPIPS full, LPIPS covisible, sum v (first pair), H W, sum v m (second pair), sum m, 0, 0.
+ *   H or W below 31 or H W >= 2^26: PGDVS_ERR_INVALID, and the workspace query returns PGDVS_ERR_INVALID.
+ *   workspace >= pgdvs_dycheck_lpips_workspace_bytes(H,W), laid out as (each region rounded up to 256 bytes): x[4,3,H,W], relu1,
+ *   pool1, relu2, pool2, relu3, relu4, relu5 (each [4,C,h,w] fp32), the five lin maps [2,h,w], the upsampling partials.
+ *   Deterministic (fixed-order float64 sums). */
+int64_t pgdvs_dycheck_lpips_workspace_bytes(int H, int W);
+int pgdvs_dycheck_lpips(const float *pred_planar, const float *gt_hwc, const float *mask_hw, int H, int W, const float *conv_weights,
+                        const float *conv_biases, const float *lin_weights, double *sums, void *workspace, int64_t workspace_bytes,
+                        pgdvs_stream_t stream);
+
 /* ---- one native call per target view -------------------------------------------------
  * PGDVSRenderer.forward with static_renderer = StaticGeoPointRenderer, dyn_render_type = "softsplat",
  * batch item of size 1, render_stride 1, no tracker (pgdvs/renderers/pgdvs_renderer.py:84-178 ->

@@ -15,14 +15,11 @@
 #include "common.h"
 #include "eval_quant.h"
 #include "gnt_mfma.h"
+#include "lpips_net.h"
 
 namespace pgdvs {
 
-// ---- the network (torchvision alexnet().features[0:12] and the LPIPS v0.1 lin layers)
-constexpr int kLpLayers = 5;
-constexpr int kLpCin[kLpLayers] = {3, 64, 192, 384, 256};
-constexpr int kLpCout[kLpLayers] = {64, 192, 384, 256, 256};
-constexpr int kLpKs[kLpLayers] = {11, 5, 3, 3, 3};
+// ---- the network (torchvision alexnet().features[0:12] and the LPIPS v0.1 lin layers): shapes in lpips_net.h
 
 // ---- the convolution: block tile 64 output channels x 128 output pixels, K in steps of 16; four waves in 2 x 2, a wave's
 // 32 x 64 is 2 x 4 tiles of the 16x16x4 instruction.  Every Cout is a multiple of 64.
@@ -263,18 +260,15 @@ lpips_final_kernel(const double *__restrict__ partials, LpipsFinalArgs a, double
 
 // ---- shapes and the workspace
 struct LpipsPlan {
-  int h[kLpLayers], w[kLpLayers];  // relu_k map sizes
-  int ph[2], pw[2];                // pool1 / pool2 outputs
-  int64_t off_x, off_relu[kLpLayers], off_pool[2], off_part, total;
+  LpipsNetPlan net;  // x[2,3,H,W] and the backbone's maps
+  int64_t off_part, total;
   int head_block0[kLpLayers + 1];
 };
 
 static int conv_out(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
 static int pool_out(int n) { return (n - 3) / 2 + 1; }
-static int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
 
-// false: the image is too small for the backbone (an empty relu5 map) or too large for the 32-bit pixel indices
-static bool lpips_plan(int H, int W, LpipsPlan &pl) {
+bool lpips_net_plan(int H, int W, int n_img, LpipsNetPlan &pl) {
   if (H < 31 || W < 31 || (int64_t)H * W >= (1ll << 26)) return false;
   pl.h[0] = conv_out(H, 11, 4, 2);
   pl.w[0] = conv_out(W, 11, 4, 2);
@@ -291,31 +285,39 @@ static bool lpips_plan(int H, int W, LpipsPlan &pl) {
   if (pl.h[4] < 1 || pl.w[4] < 1) return false;
   int64_t o = 0;
   pl.off_x = o;
-  o += align256((int64_t)2 * 3 * H * W * 4);
+  o += lpips_align256((int64_t)n_img * 3 * H * W * 4);
   for (int k = 0; k < kLpLayers; ++k) {
     pl.off_relu[k] = o;
-    o += align256((int64_t)2 * kLpCout[k] * pl.h[k] * pl.w[k] * 4);
+    o += lpips_align256((int64_t)n_img * kLpCout[k] * pl.h[k] * pl.w[k] * 4);
     if (k < 2) {
       pl.off_pool[k] = o;
-      o += align256((int64_t)2 * kLpCout[k] * pl.ph[k] * pl.pw[k] * 4);
+      o += lpips_align256((int64_t)n_img * kLpCout[k] * pl.ph[k] * pl.pw[k] * 4);
     }
   }
+  pl.end = o;
+  return true;
+}
+
+static bool lpips_plan(int H, int W, LpipsPlan &pl) {
+  if (!lpips_net_plan(H, W, 2, pl.net)) return false;
+  int64_t o = pl.net.end;
   pl.off_part = o;
   int nb = 0;
   for (int k = 0; k < kLpLayers; ++k) {
     pl.head_block0[k] = nb;
-    nb += (pl.h[k] * pl.w[k] + kHdThreads - 1) / kHdThreads;
+    nb += (pl.net.h[k] * pl.net.w[k] + kHdThreads - 1) / kHdThreads;
   }
   pl.head_block0[kLpLayers] = nb;
-  o += align256((int64_t)nb * kHdSums * 8);
+  o += lpips_align256((int64_t)nb * kHdSums * 8);
   pl.total = o;
   return true;
 }
 
+// the convolution over n_img images: one GEMM column per output pixel of every image
 template <int KS, int ST, int PD>
-static void launch_conv(const float *in, const float *w, const float *b, float *out, int Cin, int Hin, int Win, int Cout, int Hout,
-                        int Wout, hipStream_t st, const char *name) {
-  const int P = 2 * Hout * Wout;
+static void launch_conv(const float *in, const float *w, const float *b, float *out, int n_img, int Cin, int Hin, int Win, int Cout,
+                        int Hout, int Wout, hipStream_t st, const char *name) {
+  const int P = n_img * Hout * Wout;
   PGDVS_LAUNCH(name, (lpips_conv_kernel<KS, ST, PD>), dim3((unsigned)((P + kCvBN - 1) / kCvBN), (unsigned)(Cout / kCvBM)), dim3(kCvThreads),
                0, st, in, w, b, out, Cin, Hin, Win, Cout, Hout, Wout, P);
 }
@@ -323,6 +325,33 @@ static void launch_conv(const float *in, const float *w, const float *b, float *
 static void launch_pool(const float *in, float *out, int n_planes, int Hin, int Win, int Hout, int Wout, hipStream_t st, const char *name) {
   const int64_t n = (int64_t)n_planes * Hout * Wout;
   PGDVS_LAUNCH(name, lpips_maxpool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, in, out, n_planes, Hin, Win, Hout, Wout);
+}
+
+void lpips_net_weights(const float *conv_weights, const float *conv_biases, const float *lin_weights, const float *(&wk)[kLpLayers],
+                       const float *(&bk)[kLpLayers], const float *(&lk)[kLpLayers]) {
+  size_t ow = 0, ob = 0;
+  for (int k = 0; k < kLpLayers; ++k) {
+    wk[k] = conv_weights + ow;
+    bk[k] = conv_biases + ob;
+    lk[k] = lin_weights + ob;
+    ow += (size_t)kLpCout[k] * kLpCin[k] * kLpKs[k] * kLpKs[k];
+    ob += (size_t)kLpCout[k];
+  }
+}
+
+void lpips_net_forward(char *ws, const LpipsNetPlan &pl, int n_img, int H, int W, const float *const (&wk)[kLpLayers],
+                       const float *const (&bk)[kLpLayers], hipStream_t st) {
+  const float *x = reinterpret_cast<const float *>(ws + pl.off_x);
+  float *relu[kLpLayers], *pool[2];
+  for (int k = 0; k < kLpLayers; ++k) relu[k] = reinterpret_cast<float *>(ws + pl.off_relu[k]);
+  for (int k = 0; k < 2; ++k) pool[k] = reinterpret_cast<float *>(ws + pl.off_pool[k]);
+  launch_conv<11, 4, 2>(x, wk[0], bk[0], relu[0], n_img, 3, H, W, 64, pl.h[0], pl.w[0], st, "lpips_conv1");
+  launch_pool(relu[0], pool[0], n_img * 64, pl.h[0], pl.w[0], pl.ph[0], pl.pw[0], st, "lpips_pool1");
+  launch_conv<5, 1, 2>(pool[0], wk[1], bk[1], relu[1], n_img, 64, pl.ph[0], pl.pw[0], 192, pl.h[1], pl.w[1], st, "lpips_conv2");
+  launch_pool(relu[1], pool[1], n_img * 192, pl.h[1], pl.w[1], pl.ph[1], pl.pw[1], st, "lpips_pool2");
+  launch_conv<3, 1, 1>(pool[1], wk[2], bk[2], relu[2], n_img, 192, pl.ph[1], pl.pw[1], 384, pl.h[2], pl.w[2], st, "lpips_conv3");
+  launch_conv<3, 1, 1>(relu[2], wk[3], bk[3], relu[3], n_img, 384, pl.h[2], pl.w[2], 256, pl.h[3], pl.w[3], st, "lpips_conv4");
+  launch_conv<3, 1, 1>(relu[3], wk[4], bk[4], relu[4], n_img, 256, pl.h[3], pl.w[3], 256, pl.h[4], pl.w[4], st, "lpips_conv5");
 }
 
 }  // namespace pgdvs
@@ -352,32 +381,16 @@ PGDVS_API int pgdvs_lpips_sums(const float *pred_planar, const float *gt_hwc, co
   }
   hipStream_t st = as_stream(stream);
   char *ws = reinterpret_cast<char *>(workspace);
-  float *x = reinterpret_cast<float *>(ws + pl.off_x);
-  float *relu[kLpLayers], *pool[2];
-  for (int k = 0; k < kLpLayers; ++k) relu[k] = reinterpret_cast<float *>(ws + pl.off_relu[k]);
-  for (int k = 0; k < 2; ++k) pool[k] = reinterpret_cast<float *>(ws + pl.off_pool[k]);
+  float *x = reinterpret_cast<float *>(ws + pl.net.off_x);
+  float *relu[kLpLayers];
+  for (int k = 0; k < kLpLayers; ++k) relu[k] = reinterpret_cast<float *>(ws + pl.net.off_relu[k]);
   const float *wk[kLpLayers], *bk[kLpLayers], *lk[kLpLayers];
-  {
-    size_t ow = 0, ob = 0;
-    for (int k = 0; k < kLpLayers; ++k) {
-      wk[k] = conv_weights + ow;
-      bk[k] = conv_biases + ob;
-      lk[k] = lin_weights + ob;
-      ow += (size_t)kLpCout[k] * kLpCin[k] * kLpKs[k] * kLpKs[k];
-      ob += (size_t)kLpCout[k];
-    }
-  }
+  lpips_net_weights(conv_weights, conv_biases, lin_weights, wk, bk, lk);
   const int P = H * W;
   PGDVS_LAUNCH("lpips_prep", lpips_prep_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, pred_planar, gt_hwc, P, x);
-  launch_conv<11, 4, 2>(x, wk[0], bk[0], relu[0], 3, H, W, 64, pl.h[0], pl.w[0], st, "lpips_conv1");
-  launch_pool(relu[0], pool[0], 2 * 64, pl.h[0], pl.w[0], pl.ph[0], pl.pw[0], st, "lpips_pool1");
-  launch_conv<5, 1, 2>(pool[0], wk[1], bk[1], relu[1], 64, pl.ph[0], pl.pw[0], 192, pl.h[1], pl.w[1], st, "lpips_conv2");
-  launch_pool(relu[1], pool[1], 2 * 192, pl.h[1], pl.w[1], pl.ph[1], pl.pw[1], st, "lpips_pool2");
-  launch_conv<3, 1, 1>(pool[1], wk[2], bk[2], relu[2], 192, pl.ph[1], pl.pw[1], 384, pl.h[2], pl.w[2], st, "lpips_conv3");
-  launch_conv<3, 1, 1>(relu[2], wk[3], bk[3], relu[3], 384, pl.h[2], pl.w[2], 256, pl.h[3], pl.w[3], st, "lpips_conv4");
-  launch_conv<3, 1, 1>(relu[3], wk[4], bk[4], relu[4], 256, pl.h[3], pl.w[3], 256, pl.h[4], pl.w[4], st, "lpips_conv5");
+  lpips_net_forward(ws, pl.net, 2, H, W, wk, bk, st);
   LpipsHeadArgs ha;
-  for (int k = 0; k < kLpLayers; ++k) ha.l[k] = LpipsHeadLayer{relu[k], lk[k], kLpCout[k], pl.h[k], pl.w[k], pl.head_block0[k]};
+  for (int k = 0; k < kLpLayers; ++k) ha.l[k] = LpipsHeadLayer{relu[k], lk[k], kLpCout[k], pl.net.h[k], pl.net.w[k], pl.head_block0[k]};
   ha.mask = mask_hwc;
   ha.H = H;
   ha.W = W;
@@ -385,7 +398,7 @@ PGDVS_API int pgdvs_lpips_sums(const float *pred_planar, const float *gt_hwc, co
   PGDVS_LAUNCH("lpips_head", lpips_head_kernel, dim3((unsigned)pl.head_block0[kLpLayers]), dim3(kHdThreads), 0, st, ha, partials);
   LpipsFinalArgs fa;
   for (int k = 0; k <= kLpLayers; ++k) fa.block0[k] = pl.head_block0[k];
-  for (int k = 0; k < kLpLayers; ++k) fa.pixels[k] = (double)pl.h[k] * (double)pl.w[k];
+  for (int k = 0; k < kLpLayers; ++k) fa.pixels[k] = (double)pl.net.h[k] * (double)pl.net.w[k];
   PGDVS_LAUNCH("lpips_final", lpips_final_kernel, dim3(1), dim3(kHdSums * kWave), 0, st, (const double *)partials, fa, sums);
   return check_launch("lpips_sums");
 }

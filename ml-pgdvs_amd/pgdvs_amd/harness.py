@@ -213,6 +213,112 @@ def masked_lpips(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, wei
     return _lpips_torch(img1, img2, [mask], weights, scaling_layer=scaling_layer)[0]
 
 
+# ---------------------------------------------------------------- the DyCheck iPhone protocol (quant_type "dycheck_iphone")
+# obtain_quantitative_dycheck_iphone (evaluator_pgdvs.py:282-409) through pgdvs/utils/dycheck/metrics.py:63-230: PSNR, SSIM and
+# LPIPS per view with a full mask and with the covisibility mask eval_mask[H,W,1].  The restatements below take [3,H,W] images
+# in [0,1] (already quantised) and a [1,H,W] (or [H,W]) mask, work in float32 torch elementwise and reduce in float64.
+QUANT_TYPES = ("nvidia", "dycheck_iphone")
+
+
+def _mask_hw(mask: torch.Tensor) -> torch.Tensor:
+    return (mask[0] if mask.ndim == 3 else mask).float()
+
+
+def masked_psnr_dycheck(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor) -> float:
+    """compute_psnr (metrics.py:63-90): -10/ln 10 ln(masked_mean(d^2, m)), masked_mean = sum(x m) / max(sum(m broadcast to the
+    three channels), 1e-6).  An exact match -- or an empty mask, 0 / 1e-6 -- gives +inf, as upstream."""
+    a, b, m = img1.float(), img2.float(), _mask_hw(mask).to(img1.device)
+    d2 = (a - b) ** 2
+    num = float((d2 * m).double().sum())
+    den = max(3.0 * float(m.double().sum()), 1e-6)
+    mse = num / den
+    return math.inf if mse == 0 else -10.0 / math.log(10.0) * math.log(mse)
+
+
+def dycheck_filter(device="cpu") -> torch.Tensor:
+    """metrics.py:148-153: the 11-tap Gaussian, sigma 1.5, normalised to sum 1 (float64, rounded once to float32)"""
+    f = torch.exp(-0.5 * ((torch.arange(11, dtype=torch.float64) - 5) / 1.5) ** 2)
+    return (f / f.sum()).float().to(device)
+
+
+def _partial_conv(z: torch.Tensor, m: torch.Tensor, f: torch.Tensor, dim: int):
+    """one pass of metrics.py:155-168 along ``dim`` (-1 = W, -2 = H) of z[C,H,W] with the shared mask m[H,W], mode "valid":
+    z' = conv(z m, f) 11 / conv(m, 1) where conv(m, 1) != 0, else 0; returns (z', conv(m, 1) != 0)"""
+    zu = (z * m).unfold(dim, 11, 1)  # [..., 11] windows
+    mu = m.unfold(dim, 11, 1)
+    zc = (zu * f).sum(-1)
+    mc = mu.sum(-1)
+    return torch.where(mc != 0, zc * 11.0 / mc, torch.zeros_like(zc)), (mc != 0).float()
+
+
+def masked_ssim_dycheck(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor) -> float:
+    """compute_ssim (metrics.py:93-186, modelled on tf.image.ssim): the five moments through the separable partial convolution
+    (W pass, then H pass), variances clamped at 0, the covariance clipped to sign(s01) min(sqrt(s00 s11), |s01|), k1 = 0.01,
+    k2 = 0.03, max_val 1, then the mean over ALL (H-10)(W-10) 3 entries of the map (a window without mask contributes 1:
+    an empty mask gives 1).  H or W below 11 raises ValueError (upstream's mean of an empty map is NaN)."""
+    H, W = img1.shape[-2:]
+    if H < 11 or W < 11:
+        raise ValueError(f"masked_ssim_dycheck: the image ({H} x {W}) is smaller than SSIM's 11 x 11 window")
+    a, b, m = img1.float(), img2.float(), _mask_hw(mask).to(img1.device)
+    f = dycheck_filter(a.device)
+
+    def filt(z):
+        z1, m1 = _partial_conv(z, m, f, -1)
+        return _partial_conv(z1, m1, f, -2)[0]
+
+    mu0, mu1 = filt(a), filt(b)
+    mu00, mu11, mu01 = mu0 * mu0, mu1 * mu1, mu0 * mu1
+    s00 = torch.clamp(filt(a * a) - mu00, min=0.0)
+    s11 = torch.clamp(filt(b * b) - mu11, min=0.0)
+    s01 = filt(a * b) - mu01
+    s01 = torch.sign(s01) * torch.minimum(torch.sqrt(s00 * s11), torch.abs(s01))
+    c1, c2 = 0.01 ** 2, 0.03 ** 2
+    S = ((2 * mu01 + c1) * (2 * s01 + c2)) / ((mu00 + mu11 + c1) * (s00 + s11 + c2))
+    return float(S.double().mean())
+
+
+def _lpips_dycheck_torch(img1, img2, masks, weights):
+    """lpips 0.1.4 LPIPS(net="alex", spatial=True) as compute_lpips (metrics.py:189-230) calls it, for each of ``masks``
+    ([H,W] each): the pair (img1 m, img2 m) -> im2tensor(factor=1/2) -> ScalingLayer -> AlexNet -> per layer normalize_tensor,
+    squared difference, lin_k, bilinear upsampling to H x W (align_corners=False, by size), summed; then masked_mean with m."""
+    H, W = img1.shape[-2:]
+    if H < 31 or W < 31:
+        raise ValueError(f"masked_lpips_dycheck: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
+    ms = [m.float().to(img1.device) for m in masks]
+    x = torch.stack([t for m in ms for t in (img1.float() * m, img2.float() * m)])  # [2 n, 3, H, W]
+    x = x / 0.5 - 1.0
+    shift = torch.tensor(_LPIPS_SHIFT, dtype=torch.float32, device=x.device)[None, :, None, None]
+    scale = torch.tensor(_LPIPS_SCALE, dtype=torch.float32, device=x.device)[None, :, None, None]
+    x = (x - shift) / scale
+    feats = alex_features(x, weights)
+    val = None
+    for f, lin in zip(feats, weights.on(x.device).lins):
+        f = f / (torch.sqrt(torch.sum(f ** 2, dim=1, keepdim=True)) + 1e-10)
+        d = F.conv2d((f[0::2] - f[1::2]) ** 2, lin)  # [n,1,h,w]
+        up = F.interpolate(d, size=(H, W), mode="bilinear", align_corners=False)
+        val = up if val is None else val + up
+    return [float((val[i, 0] * m).double().sum() / max(float(m.double().sum()), 1e-6)) for i, m in enumerate(ms)]
+
+
+def masked_lpips_dycheck(img1: torch.Tensor, img2: torch.Tensor, mask: torch.Tensor, weights: LpipsAlex) -> float:
+    """compute_lpips (metrics.py:189-230) on [3,H,W] images in [0,1] (already quantised) and a [1,H,W] mask, restated in float32
+    torch: the images are multiplied by the mask BEFORE the network, mapped by 2 x - 1 and the ScalingLayer (applied here:
+    LPIPS's version is the string "0.1"), AlexNet relu1..5, normalize_tensor, squared difference, lin_k, each layer's map
+    upsampled bilinearly to H x W and summed, then sum(v m) / max(sum(m), 1e-6).  The full-mask value is this with m = 1.
+    H or W below 31 raises ValueError."""
+    assert img1.ndim == 3 and img2.ndim == 3 and img1.shape == img2.shape
+    return _lpips_dycheck_torch(img1, img2, [_mask_hw(mask)], weights)[0]
+
+
+def quant_type_from_engine_cfg(engine_cfg) -> str:
+    """``engine_cfg.quant_type`` (configs/engine/evaluator_pgdvs.yaml; "nvidia" when absent) -> the ``quant_type`` of
+    ``eval_step``.  An unknown value raises ValueError, as trainer_pgdvs.py:86-91 does."""
+    q = engine_cfg.get("quant_type", "nvidia") if hasattr(engine_cfg, "get") else getattr(engine_cfg, "quant_type", "nvidia")
+    if q not in QUANT_TYPES:
+        raise ValueError(q)
+    return q
+
+
 def to_device(batch: dict, device) -> dict:
     """``_to_gpu_func`` (pgdvs/engines/abstract.py:153-157): tensors move, everything else passes through"""
     return {k: v.to(device) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
@@ -222,6 +328,9 @@ METRIC_KEYS = ("psnr_full_combined", "psnr_dyn_combined", "psnr_static_combined"
 SSIM_KEYS = ("ssim_full_combined", "ssim_dyn_combined", "ssim_static_combined")  # eval_step(..., with_ssim=True)
 LPIPS_KEYS = ("lpips_full_combined", "lpips_dyn_combined", "lpips_static_combined")  # eval_step(..., lpips=LpipsAlex(...))
 
+DYCHECK_KEYS = ("psnr_combined", "ssim_combined", "mpsnr_combined", "mssim_combined")  # eval_step(..., quant_type="dycheck_iphone")
+DYCHECK_LPIPS_KEYS = ("lpips_combined", "mlpips_combined")  # ... and lpips=LpipsAlex(...)
+
 # measurement hook (bench.py): a dict set here accumulates the host wall time of eval_step's stages in seconds
 # ("to_device", "forward" = enqueue of the renderer, "metric_enqueue", "sync_read" = the step's one wait for the GPU,
 # "post"); None = no timing
@@ -230,7 +339,7 @@ STAGE_SECONDS = None
 
 @torch.no_grad()
 def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False, with_ssim=False,
-              lpips=None):
+              lpips=None, quant_type="nvidia"):
     """One evaluator step on a batch of target views.  ``data`` is the reference's data dict (row A0) plus
     ``rgb_tgt[B,H,W,3]`` and ``eval_mask[B,H,W,3]`` (1 = dynamic region).  Returns the reference's
     ``metric_dict`` restricted to the in-scope keys: ``eval/count`` (int64) and the per-key SUMS over the
@@ -238,7 +347,18 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
     HOST tensors on both the fused GPU path and the torch path, so that a caller who accumulates them over steps never
     mixes devices).  ``with_ssim`` adds the three masked SSIM sums (``SSIM_KEYS``, float32, reduced in the same packed
     block).  ``lpips`` (an ``LpipsAlex``) adds the three masked LPIPS values (``LPIPS_KEYS``, float32, in the same block).
-    With ``return_images`` also the quantised prediction / ground truth and the per-view values."""
+    With ``return_images`` also the quantised prediction / ground truth and the per-view values.
+    ``quant_type`` selects the evaluator's metric protocol (evaluator_pgdvs.py:137-143; ``quant_type_from_engine_cfg``): the
+    default "nvidia" is all of the above; "dycheck_iphone" returns ``eval/count`` and ``DYCHECK_KEYS`` instead -- plus
+    ``DYCHECK_LPIPS_KEYS`` with ``lpips`` -- for an ``eval_mask[B,H,W,1]`` (csrc/eval_dycheck.hip on the fused path).  There
+    SSIM is always on, so ``with_ssim=True`` raises ValueError, as does an eval_mask whose last dimension is not 1."""
+    if quant_type not in QUANT_TYPES:
+        raise ValueError(quant_type)
+    if quant_type == "dycheck_iphone":
+        if with_ssim:
+            raise ValueError("eval_step: with_ssim does not apply to quant_type 'dycheck_iphone' (its SSIM is always computed)")
+        if data["eval_mask"].shape[-1] != 1:
+            raise ValueError(f"eval_step: quant_type 'dycheck_iphone' takes eval_mask[B,H,W,1], got {tuple(data['eval_mask'].shape)}")
     device = device if device is not None else next(iter(v for v in data.values() if isinstance(v, torch.Tensor))).device
     stages, t_prev = STAGE_SECONDS, time.perf_counter()
 
@@ -280,6 +400,8 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
             ops.check_raster_status(ret.get("geo_static_raster_status", None))
 
     comb = ret["combined_rgb"]
+    if quant_type == "dycheck_iphone":
+        return _eval_dycheck(ret, data_gpu, n_batch, check_status, lap, return_images, lpips)
     if (comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(data_gpu["rgb_tgt"].shape[1:3])
             and data_gpu["rgb_tgt"].dtype == torch.float32 and data_gpu["eval_mask"].dtype == torch.float32):
         # GPU, render size == ground-truth size (render_stride 1): quantisation and the three masked sums of a view in ONE
@@ -379,4 +501,93 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
         metric[f"eval/{k}"] = packed[1 + j].to(torch.float32)
     if return_images:
         return metric, {"pred": pred["combined"], "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}
+    return metric
+
+
+def _metric_dict(n_batch, keys, per_view, device, multi):
+    """eval/count and the per-key float32 sums: host tensors in a single process, one packed reduce to rank 0 otherwise"""
+    if not multi:
+        metric = {"eval/count": torch.tensor([n_batch], dtype=torch.int64)}
+        for k in keys:
+            metric[f"eval/{k}"] = torch.tensor(per_view[k], dtype=torch.float32).sum()
+        return metric
+    packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
+                          dtype=torch.float64, device=device)
+    packed = pdist.reduce_metrics(packed, dst=0)
+    metric = {"eval/count": packed[:1].round().to(torch.int64)}
+    for j, k in enumerate(keys):
+        metric[f"eval/{k}"] = packed[1 + j].to(torch.float32)
+    return metric
+
+
+def _eval_dycheck(ret, data_gpu, n_batch, check_status, lap, return_images, lpips):
+    """eval_step's metrics under quant_type "dycheck_iphone" (obtain_quantitative_dycheck_iphone, evaluator_pgdvs.py:282-409)"""
+    from . import ops
+
+    comb = ret["combined_rgb"]
+    keys = DYCHECK_KEYS + (DYCHECK_LPIPS_KEYS if lpips is not None else ())
+    per_view = {k: [] for k in keys}
+    multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+    to_db = lambda s_, n_: math.inf if s_ / max(n_, 1e-6) == 0 else -10.0 / math.log(10.0) * math.log(s_ / max(n_, 1e-6))  # noqa: E731
+    if (comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(data_gpu["rgb_tgt"].shape[1:3])
+            and data_gpu["rgb_tgt"].dtype == torch.float32 and data_gpu["eval_mask"].dtype == torch.float32):
+        # GPU at render size: one PSNR + SSIM pass per view (csrc/eval_dycheck.hip) carrying the geometry path's status words,
+        # the LPIPS pass on request, and ONE host read for the batch
+        cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
+        cnts = cnts.reshape(-1) if isinstance(cnts, torch.Tensor) and cnts.is_cuda and cnts.dtype == torch.int64 else None
+        stat = ret.get("geo_static_raster_status", None)
+        stat = stat.reshape(-1) if isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.int32 else None
+        gt, em = data_gpu["rgb_tgt"], data_gpu["eval_mask"]
+        rows = [ops.dycheck_psnr_ssim_sums(comb[i_b], gt[i_b], em[i_b],
+                                           count_dev=cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None,
+                                           status_dev=stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None)
+                for i_b in range(n_batch)]
+        lp_rows = [ops.dycheck_lpips(comb[i_b], gt[i_b], em[i_b], lpips.on(comb.device)) for i_b in range(n_batch)] if lpips is not None else []
+        lap("metric_enqueue")
+        sums = ops.read_back_rows(rows + lp_rows)  # (the step's synchronisation)
+        sums, lp_sums = sums[:n_batch], sums[n_batch:]
+        lap("sync_read")
+        check_status(host_counts=[int(s_[6]) for s_ in sums] if cnts is not None else None,
+                     host_status=[int(s_[7]) for s_ in sums] if stat is not None else None)
+        H, W = comb.shape[2:]
+        n_map = 3.0 * (H - 10) * (W - 10)
+        for s_ in sums:
+            per_view["psnr_combined"].append(to_db(s_[0], s_[3]))
+            per_view["ssim_combined"].append(s_[2] / n_map)
+            per_view["mpsnr_combined"].append(to_db(s_[1], s_[4]))
+            per_view["mssim_combined"].append(s_[5] / n_map)
+        for s_ in lp_sums:
+            per_view["lpips_combined"].append(s_[0])
+            per_view["mlpips_combined"].append(s_[1])
+        metric = _metric_dict(n_batch, keys, per_view, comb.device, multi)
+        lap("post")
+        if return_images:
+            pred = quantize_like_evaluator(comb)
+            gtq = quantize_like_evaluator(gt.permute(0, 3, 1, 2))
+            return metric, {"pred": pred, "gt": gtq, "eval_mask": em.permute(0, 3, 1, 2), "per_view": per_view, "ret": ret}
+        return metric
+    check_status()
+    pred = quantize_like_evaluator(comb)
+    rgb_gt = quantize_like_evaluator(data_gpu["rgb_tgt"].permute(0, 3, 1, 2))
+    eval_mask = data_gpu["eval_mask"].permute(0, 3, 1, 2)
+    _, _, rh, rw = pred.shape
+    if rgb_gt.shape[2] != rh or rgb_gt.shape[3] != rw:  # render_stride != 1 (:80-92)
+        rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
+        eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
+        eval_mask = (eval_mask > 0).float()
+    for i_b in range(n_batch):
+        p, g = pred[i_b].to(rgb_gt.device), rgb_gt[i_b]
+        m = eval_mask[i_b, 0]
+        ones = torch.ones_like(m)
+        per_view["psnr_combined"].append(masked_psnr_dycheck(g, p, ones))
+        per_view["ssim_combined"].append(masked_ssim_dycheck(g, p, ones))
+        per_view["mpsnr_combined"].append(masked_psnr_dycheck(g, p, m))
+        per_view["mssim_combined"].append(masked_ssim_dycheck(g, p, m))
+        if lpips is not None:
+            full, covis = _lpips_dycheck_torch(g, p, [ones, m], lpips)
+            per_view["lpips_combined"].append(full)
+            per_view["mlpips_combined"].append(covis)
+    metric = _metric_dict(n_batch, keys, per_view, rgb_gt.device, multi)
+    if return_images:
+        return metric, {"pred": pred, "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}
     return metric

@@ -681,6 +681,70 @@ def lpips_sums(pred_planar, gt_hwc, mask_hwc, weights, want_features: bool = Fal
     return sums, (_lpips_features(buf, H, W) if want_features else None)
 
 
+def _dycheck_mask(mask, H, W, what):
+    """eval_mask of the DyCheck protocol, [H,W,1] (or [H,W]) -> a contiguous [H,W] float32 tensor"""
+    m = mask[..., 0] if mask.ndim == 3 else mask
+    if tuple(m.shape) != (H, W) or (mask.ndim == 3 and mask.shape[-1] != 1):
+        raise ValueError(f"{what}: eval_mask must be [H,W,1] (got {tuple(mask.shape)} for a {H} x {W} image)")
+    return _req(m.contiguous(), torch.float32, "eval_mask")
+
+
+DYCHECK_SSIM_MIN_SIZE = 11  # the 11-tap window in "valid" mode: the map is (H - 10) x (W - 10)
+
+
+def dycheck_psnr_ssim_sums(pred_planar, gt_hwc, mask_hw1, count_dev=None, status_dev=None):
+    """The DyCheck iPhone protocol's PSNR and SSIM of one view, full and covisible, in one pass
+    (``pgdvs_dycheck_psnr_ssim_sums``): pred[3,H,W] raw render, gt[H,W,3] raw, mask[H,W,1] -> device float64[8] (sum d2,
+    sum d2 m, sum S full, 3HW, 3 sum m, sum S covisible, then ``count_dev`` -- -1 when None -- and ``status_dev`` -- 0 when
+    None -- as in ``eval_psnr_sums``' row, so that ``read_back_rows`` brings it back with the others; include/pgdvs_hip.h).
+    Raises ValueError when H or W is below the 11-tap window."""
+    p = _req(pred_planar, torch.float32, "pred")
+    g = _req(gt_hwc, torch.float32, "gt")
+    _, H, W = p.shape
+    assert tuple(g.shape) == (H, W, 3), (p.shape, g.shape)
+    m = _dycheck_mask(mask_hw1, H, W, "dycheck_psnr_ssim_sums")
+    if H < DYCHECK_SSIM_MIN_SIZE or W < DYCHECK_SSIM_MIN_SIZE:
+        raise ValueError(f"dycheck_psnr_ssim_sums: the image ({H} x {W}) is smaller than SSIM's 11 x 11 window")
+    lib = _lib.load()
+    nws = int(lib.pgdvs_dycheck_psnr_ssim_workspace_bytes(H, W))
+    if nws < 0:
+        _ws(nws, p.device)  # raises with the library's message
+    nws = (nws + 63) // 64 * 64
+    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # partials, then the eight doubles
+    sums = buf[nws:nws + 64].view(torch.float64)
+    cd = _req(count_dev, torch.int64, "count_dev") if count_dev is not None else None
+    sd = _req(status_dev, torch.int32, "status_dev") if status_dev is not None else None
+    check(lib.pgdvs_dycheck_psnr_ssim_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cd), _ptr(sd), _ptr(sums), _ptr(buf), nws, _stream()),
+          "pgdvs_dycheck_psnr_ssim_sums")
+    return sums
+
+
+def dycheck_lpips(pred_planar, gt_hwc, mask_hw1, weights):
+    """The DyCheck iPhone protocol's LPIPS of one view, full and covisible (``pgdvs_dycheck_lpips``): pred[3,H,W] raw render,
+    gt[H,W,3] raw, mask[H,W,1], ``weights`` a ``harness.LpipsAlex`` on the same device -> device float64[8] (LPIPS full,
+    LPIPS covisible, sum v, HW, sum v m, sum m, 0, 0; include/pgdvs_hip.h).  Raises ValueError when H or W is below 31."""
+    p = _req(pred_planar, torch.float32, "pred")
+    g = _req(gt_hwc, torch.float32, "gt")
+    _, H, W = p.shape
+    assert tuple(g.shape) == (H, W, 3), (p.shape, g.shape)
+    m = _dycheck_mask(mask_hw1, H, W, "dycheck_lpips")
+    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
+        raise ValueError(f"dycheck_lpips: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
+    cw, cb, lw = (_req(t, torch.float32, n) for t, n in ((weights.conv_weights, "conv_weights"), (weights.conv_biases, "conv_biases"),
+                                                         (weights.lin_weights, "lin_weights")))
+    assert cw.device == p.device, (cw.device, p.device)
+    lib = _lib.load()
+    nws = int(lib.pgdvs_dycheck_lpips_workspace_bytes(H, W))
+    if nws < 0:
+        _ws(nws, p.device)  # raises with the library's message
+    nws = (nws + 63) // 64 * 64
+    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # the network's maps and partials, then the eight doubles
+    sums = buf[nws:nws + 64].view(torch.float64)
+    check(lib.pgdvs_dycheck_lpips(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw), _ptr(sums), _ptr(buf), nws, _stream()),
+          "pgdvs_dycheck_lpips")
+    return sums
+
+
 _pinned_sums = {}
 
 
