@@ -517,6 +517,31 @@ int pgdvs_dycheck_lpips(const float *pred_planar, const float *gt_hwc, const flo
                         const float *conv_biases, const float *lin_weights, double *sums, void *workspace, int64_t workspace_bytes,
                         pgdvs_stream_t stream);
 
+/* ---- 8f-3 DyCheck, the loader's per-item depth range (pgdvs/datasets/dycheck_iphone_eval.py:455-524): the spatial sources'
+ * world points moved into the target camera, np.quantile(z, 0.1 / 0.9) clamped by the scene's near / far as the constant
+ * range, then every static point that projects into the image overwrites its pixel with z -+ 1e-4 (the last point wins).
+ * Bit-identical to the loader's numpy path (pgdvs_amd/datasets/dycheck_iphone.py depth_range_numpy):
+ *   depth [V,H,W] float32 (depth_f64 = 0) or float64 (depth_f64 = 1): the points' type T, as numpy promotes it
+ *   dyn_mask [V,H,W] float32, static where == 0
+ *   rays [V,12] float32: per view M = c2w[:3,:3] @ inverse(K[:3,:3]) row-major and the origin c2w[:3,3], as
+ *     _get_rays_single_image (base.py:507-546) forms them with torch; d = fma(M[:,1], v, M[:,0] u) + M[:,2] (torch's CPU bmm
+ *     order), X = o + d depth in T
+ *   inv_raw_c2w_tgt[16], inv_c2w_tgt[16], K_tgt[9]: HOST doubles holding float32 values (numpy's float32 inverses of the
+ *     target's raw camera-to-world and of flat_cam_tgt's c2w, and flat_cam_tgt's K[:3,:3]); any other value is rejected
+ *   near, far: the scene's bounds
+ *   depth_range [H,W,2] float32 output; quantiles: DEVICE double[2] (nullable) = np.quantile(z, 0.1), np.quantile(z, 0.9)
+ *   as computed in T (NaN when z holds a NaN)
+ * Products follow numpy's BLAS order (fused multiply-adds, k ascending; DESIGN.md 8f-3 DyCheck); the quantiles are exact
+ * order statistics (radix select on the order-preserving bit patterns, -0.0 counted as +0.0) combined by numpy's _lerp.
+ * V, H or W < 1, or V H W >= 2^31: PGDVS_ERR_INVALID, and the workspace query returns PGDVS_ERR_INVALID.
+ * workspace >= pgdvs_dycheck_depth_range_workspace_bytes(V,H,W,depth_f64): the keys (V H W x sizeof(T)), a per-pixel int32,
+ * the radix histograms and a small state block. */
+int64_t pgdvs_dycheck_depth_range_workspace_bytes(int V, int H, int W, int depth_f64);
+int pgdvs_dycheck_depth_range(const void *depth, int depth_f64, const float *dyn_mask, const float *rays, int V, int H, int W,
+                              const double *inv_raw_c2w_tgt, const double *inv_c2w_tgt, const double *K_tgt, double near_v,
+                              double far_v, float *depth_range, double *quantiles, void *workspace, int64_t workspace_bytes,
+                              pgdvs_stream_t stream);
+
 /* ---- one native call per target view -------------------------------------------------
  * PGDVSRenderer.forward with static_renderer = StaticGeoPointRenderer, dyn_render_type = "softsplat",
  * batch item of size 1, render_stride 1, no tracker (pgdvs/renderers/pgdvs_renderer.py:84-178 ->

@@ -1,7 +1,7 @@
 """Mirror of ``pgdvs.datasets.combined.CombinedDataset`` (pgdvs/datasets/combined.py:31-80): one index space
 over the datasets named in ``dataset_list[mode]``, in sorted-name order so that every worker sees the same
-order.  Loaders mirrored here are used directly; the two that are out of scope (``nvidia_vis``,
-``dycheck_iphone_eval``) resolve to the reference's own classes when that package is importable."""
+order.  Loaders mirrored here are used directly; the one that is out of scope (``nvidia_vis``) resolves to the
+reference's own class when that package is importable."""
 import bisect
 import importlib
 
@@ -11,10 +11,10 @@ _MIRRORED = {
     "nvidia_eval": ("pgdvs_amd.datasets.nvidia_eval", "NvidiaDynEvaluationDataset"),
     "nvidia_eval_pure_geo": ("pgdvs_amd.datasets.nvidia_eval", "NvidiaDynPureGeoEvaluationDataset"),
     "mono_vis": ("pgdvs_amd.datasets.mono_vis", "MonoVisualizationDataset"),
+    "dycheck_iphone_eval": ("pgdvs_amd.datasets.dycheck_iphone", "DyCheckiPhoneEvaluationDataset"),
 }
 _UPSTREAM = {
     "nvidia_vis": ("pgdvs.datasets.nvidia_vis", "NvidiaDynVisualizationDataset"),
-    "dycheck_iphone_eval": ("pgdvs.datasets.dycheck_iphone_eval", "DyCheckiPhoneEvaluationDataset"),
 }
 
 

@@ -745,6 +745,36 @@ def dycheck_lpips(pred_planar, gt_hwc, mask_hw1, weights):
     return sums
 
 
+def dycheck_depth_range(depth, dyn_mask, rays, inv_raw_c2w_tgt, inv_c2w_tgt, K_tgt, near, far, quantiles=None):
+    """The DyCheck loader's per-pixel depth range (``pgdvs_dycheck_depth_range``; include/pgdvs_hip.h): depth[V,H,W] float32
+    or float64 and dyn_mask[V,H,W] on the GPU, rays[V,12] float32 on the GPU (per view ``M`` row-major and the origin, as
+    ``datasets.dycheck_iphone.ray_constants`` forms them), the target's numpy float32 inverses ``inv_raw_c2w_tgt[4,4]`` and
+    ``inv_c2w_tgt[4,4]`` and ``K_tgt[3,3]``, the scene's ``near`` / ``far`` -> depth_range[H,W,2] float32 on the GPU,
+    bit-identical to ``depth_range_numpy``.  ``quantiles``: optional device float64[2] that receives np.quantile(z, 0.1 / 0.9)."""
+    if depth.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"dycheck_depth_range: depth must be float32 or float64, got {depth.dtype}")
+    d = _req(depth, depth.dtype, "depth")
+    m = _req(dyn_mask, torch.float32, "dyn_mask")
+    r = _req(rays, torch.float32, "rays")
+    if d.ndim != 3 or tuple(m.shape) != tuple(d.shape) or tuple(r.shape) != (d.shape[0], 12):
+        raise ValueError(f"dycheck_depth_range: shapes depth {tuple(d.shape)}, dyn_mask {tuple(m.shape)}, rays {tuple(r.shape)}")
+    V, H, W = (int(x) for x in d.shape)
+    f64 = int(d.dtype == torch.float64)
+    mats = []
+    for a, n in ((inv_raw_c2w_tgt, 16), (inv_c2w_tgt, 16), (K_tgt, 9)):
+        a = np.ascontiguousarray(np.asarray(a), dtype=np.float64).reshape(-1)
+        assert a.size == n, a.shape
+        mats.append((C.c_double * n)(*a.tolist()))
+    if quantiles is not None:
+        assert quantiles.is_cuda and quantiles.dtype == torch.float64 and quantiles.numel() >= 2 and quantiles.is_contiguous()
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_dycheck_depth_range_workspace_bytes(V, H, W, f64), d.device)
+    out = torch.empty((H, W, 2), dtype=torch.float32, device=d.device)
+    check(lib.pgdvs_dycheck_depth_range(_ptr(d), f64, _ptr(m), _ptr(r), V, H, W, mats[0], mats[1], mats[2], float(near), float(far),
+                                        _ptr(out), _ptr(quantiles), _ptr(ws), ws.numel(), _stream()), "pgdvs_dycheck_depth_range")
+    return out
+
+
 _pinned_sums = {}
 
 
