@@ -12,6 +12,11 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE 
 on rank 0; for N > 1 it is launched through torch.distributed.run (one rank per GPU, RCCL),
 frames are sharded across ranks (weak scaling: K views per rank) and the final image
 stacks are gathered to rank 0 inside the timed region.
+
+A plain run does only what that line needs: set-up, warm-up (with the probe that picks how many views are kept in
+flight), the timed steps, ``--dump-outputs`` and the line.  Everything else it can measure or check -- the steady-state
+rate, the in-flight agreement check, per-kernel HIP-event times and the roofline, the latency of one view, the
+evaluator's loop, the scene / configuration variants, the CPU baseline and the GNT sub-benchmark -- runs with ``--full``.
 """
 import argparse
 import contextlib
@@ -201,6 +206,9 @@ def parse():
     ap.add_argument("--views", type=int, default=4, help="distinct target views kept resident and cycled")
     ap.add_argument("--scene", choices=list(SCENES), default="nominal",
                     help="statistics of the synthetic video (pgdvs_amd.synth.make_video); the headline is 'nominal'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (see the module docstring); the --no-* "
+                         "flags and --gnt-rays below choose among those legs, which a plain run skips")
     ap.add_argument("--no-scene-sweep", action="store_true", help="skip the `variants.scenes` objects (the other scenes at this size)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true", help="skip the HIP-event per-kernel pass")
@@ -793,7 +801,7 @@ def main():
     # a short timed region (the driver's --steps 20) spends a visible share filling and draining the lanes: the
     # steady-state rate of the same loop is reported beside it (never `value`)
     steady = None
-    if args.steps < 100 and world == 1:
+    if args.full and args.steps < 100 and world == 1:
         e2 = timed(200)
         steady = {"frames_per_s": round(200 / e2, 2), "steps": 200,
                   "note": "same loop and lane count over 200 views, measured right after the timed region; not the headline value"}
@@ -825,25 +833,26 @@ def main():
     ops.check_raster_status(raster_status)  # (the last view's status word; every view renders the same cloud)
     assert rvr.row_bound is None or n_static < rvr.row_bound, \
         f"the static cloud ({n_static} rows) filled its buffer of {rvr.row_bound} rows: rows may have been dropped"
-    # concurrency must not change results: the same view (fixed noise field) alone on one lane and on every lane at once
-    torch.cuda.synchronize()
-    alone = rvr.render(check_view, 0)[0]["combined_rgb"]
-    rvr.join()
-    torch.cuda.synchronize()
-    alone = alone.clone()  # (after the join: this stream has not seen the lane's work before)
-    together = [rvr.render(check_view, li)[0]["combined_rgb"] for li in range(n_lanes)]
-    rvr.join()
-    torch.cuda.synchronize()
-    # (the splat accumulates with float atomics, so the comparison is to rounding, not bit-exact)
-    assert all(torch.allclose(t_, alone, rtol=0, atol=1e-5) for t_ in together), "in-flight views disagree with the sequential result"
-    del together
+    if args.full:
+        # concurrency must not change results: the same view (fixed noise field) alone on one lane and on every lane at once
+        torch.cuda.synchronize()
+        alone = rvr.render(check_view, 0)[0]["combined_rgb"]
+        rvr.join()
+        torch.cuda.synchronize()
+        alone = alone.clone()  # (after the join: this stream has not seen the lane's work before)
+        together = [rvr.render(check_view, li)[0]["combined_rgb"] for li in range(n_lanes)]
+        rvr.join()
+        torch.cuda.synchronize()
+        # (the splat accumulates with float atomics, so the comparison is to rounding, not bit-exact)
+        assert all(torch.allclose(t_, alone, rtol=0, atol=1e-5) for t_ in together), "in-flight views disagree with the sequential result"
+        del together
     n_dyn = int(views[0]["dyn_mask_src_temporal"][0, 0].sum().item())
 
     # ---------------- per-kernel durations with HIP events on the launch stream
     kernels = {}
     roofline = None
     roofline_kernels = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         n_prof = min(args.steps, 5)
         buf = ctypes.create_string_buffer(1 << 16)
         lib.pgdvs_prof_report(buf, len(buf))  # clear
@@ -925,31 +934,33 @@ def main():
 
     # ---------------- latency of ONE view (nothing else in flight): the throughput above comes from overlapping
     # `inflight` independent views; this is the time a single view takes from first launch to last kernel
-    torch.cuda.synchronize()
-    # (one lane with a second stream for the dynamic branch, whatever arrangement the throughput loop runs: a view alone is
-    # the static branch's chain with the dynamic branch beside it)
-    rvr.set_lanes(1, True, False)
-    for j in range(3):
-        rvr.render(views[j % n_views], 0)
-    rvr.join()
-    torch.cuda.synchronize()
-    lat = []
-    for j in range(12):  # (every rank, so that all ranks reach the end of the run together; rank 0 reports its own)
-        l0 = time.perf_counter()
-        rvr.render(views[j % n_views], 0)
+    latency_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        # (one lane with a second stream for the dynamic branch, whatever arrangement the throughput loop runs: a view alone is
+        # the static branch's chain with the dynamic branch beside it)
+        rvr.set_lanes(1, True, False)
+        for j in range(3):
+            rvr.render(views[j % n_views], 0)
         rvr.join()
         torch.cuda.synchronize()
-        lat.append((time.perf_counter() - l0) * 1e3)
-    lat = sorted(lat[2:])
-    latency_ms = {"median": round(lat[len(lat) // 2], 3), "min": round(lat[0], 3), "views": len(lat),
-                  "note": "one view in flight on one lane (second stream for the dynamic branch), wall clock around enqueue + synchronize"}
-    rvr.set_lanes(*lane_cfg)
+        lat = []
+        for j in range(12):  # (every rank, so that all ranks reach the end of the run together; rank 0 reports its own)
+            l0 = time.perf_counter()
+            rvr.render(views[j % n_views], 0)
+            rvr.join()
+            torch.cuda.synchronize()
+            lat.append((time.perf_counter() - l0) * 1e3)
+        lat = sorted(lat[2:])
+        latency_ms = {"median": round(lat[len(lat) // 2], 3), "min": round(lat[0], 3), "views": len(lat),
+                      "note": "one view in flight on one lane (second stream for the dynamic branch), wall clock around enqueue + synchronize"}
+        rvr.set_lanes(*lane_cfg)
 
     # ---------------- what a drop-in caller of pgdvs.engines gets: the reference's evaluator renders ONE view, then
     # synchronises for its metrics (evaluator_pgdvs.py:36-188) -- the same workload through harness.eval_step, one view
     # at a time, ground truth = a source frame (the values do not matter for the timing)
     eval_loop = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         ev_views = []
         for d_ in views:
             e_ = dict(d_)
@@ -990,7 +1001,7 @@ def main():
 
     # ---------------- informational variants (never `value`)
     variants = None
-    if rank == 0 and world == 1 and not args.no_kernel_timing:
+    if args.full and rank == 0 and world == 1 and not args.no_kernel_timing:
         variants = {}
         # what the reference's own flow would time per view -- it aggregates the static cloud ONCE per scene at dataset
         # construction (nvidia_eval_pure_geo.py:166-178) and only renders per target view
@@ -1030,7 +1041,7 @@ def main():
     # different cameras, far more newly visible pixels per frame), noisy depth with flying pixels at object borders --
     # with the counters of every fast path's exit
     scene_stats = None
-    if rank == 0 and world == 1 and not args.no_scene_sweep:
+    if args.full and rank == 0 and world == 1 and not args.no_scene_sweep:
         scene_stats = {}
 
         def stats_of(rv, vs, label, arrangements=None):
@@ -1119,7 +1130,7 @@ def main():
     # exact for a loop whose per-pixel cost does not depend on the pixel).  configs[0] (256 x 256 x 4) runs in
     # full as well, and the HIP renderer is checked against it through the evaluator-shaped harness.
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as orc
 
         cores = orc.num_threads()
@@ -1184,7 +1195,7 @@ def main():
     # peak), so -- as BASELINE.md section 3 prescribes -- it is reported on a ray subset as
     # TFLOP/s and is not part of `value` (whose static image comes from the point renderer).
     gnt = None
-    if rank == 0 and world == 1 and args.gnt_rays > 0:
+    if args.full and rank == 0 and world == 1 and args.gnt_rays > 0:
         from pgdvs_amd.models.gnt.models.transformer_network import GNT
 
         torch.manual_seed(0)

@@ -591,7 +591,7 @@ def test_bench_line_contract_small_workload():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--height", "96", "--width", "160", "--frames", "4",
-                        "--steps", "12", "--warmup", "3", "--gnt-rays", "128"], capture_output=True, text=True, timeout=1500)
+                        "--steps", "12", "--warmup", "3", "--gnt-rays", "128", "--full"], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     b, det = _bench_line_and_detail(r)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -614,6 +614,29 @@ def test_bench_line_contract_small_workload():
     assert det["kernels"] and det["variants"]["scenes"] and det["variants"]["configs"] and det["gnt"]["parity_vs_torch_statement"]
     on_disk = json.loads(open(os.path.join(root, "gpurun_out", "bench_detail.json")).read())
     assert on_disk["value"] == b["value"]
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """`bench.py` without --full: the line carries the contract's keys and the timed region's figures, and none of the
+    legs that only --full runs (per-kernel pass, latency, evaluator loop, variants, CPU baseline, GNT) has run"""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--height", "96", "--width", "160", "--frames", "4",
+                        "--steps", "12", "--warmup", "3"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    b, det = _bench_line_and_detail(r)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in b, k
+    assert b["n_gpus"] == 1 and b["steps"] == 12 and b["warmup"] == 3 and b["value"] > 0 and b["higher_is_better"] is True
+    assert b["dtype"] == "f32" and b["unit"] == "frames/s" and abs(b["value"] - 1e3 / b["ms_per_step"]) / b["value"] < 0.02
+    assert b["roofline_path"]["frac"] > 0 and b["config"]["views_in_flight"] >= 1
+    for k in ("roofline", "cpu_baseline", "steady_state", "latency_ms", "eval_step_frames_per_s", "gnt"):
+        assert b[k] is None, k
+    assert det["value"] == b["value"] and not det["kernels"] and det["variants"] is None and det["eval_step"] is None
 
 
 def test_bench_two_ranks_on_one_gpu():

@@ -692,6 +692,31 @@ def test_bench_dump_outputs_samples_within_budget(tmp_path):
     assert shapes["combined_rgb_static"] == [1, 3, 48, 64] and shapes["render_dyn_mask"] == [1, 1, 48, 64]
 
 
+def test_bench_full_is_opt_in_and_a_plain_record_makes_a_line(monkeypatch):
+    """`--full` (every leg beyond the headline) is off unless given; the record of a plain run -- no roofline, CPU baseline,
+    latency, evaluator loop, steady state, GNT, kernels or variants -- still reduces to a line with the contract's keys"""
+    import importlib.util
+    import json
+
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline is True
+    full = json.loads((ROOT / "profiles" / "r05_bench_line.json").read_text())
+    plain = dict(full, roofline=None, roofline_kernels=None, cpu_baseline=None, latency_ms=None, eval_step_frames_per_s=None,
+                 eval_step=None, steady_state=None, gnt=None, variants=None, kernels={})
+    b = json.loads(bench.compact_line(plain))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data"):
+        assert b[k] == full[k], k
+    assert b["config"]["workload"].startswith("1920x1080")
+    assert b["roofline"] is None and b["cpu_baseline"] is None and b["gnt"] is None and b["roofline_path"]["frac"] > 0
+
+
 def test_bench_rejects_zero_steps():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--steps must be at least 1" in r.stderr

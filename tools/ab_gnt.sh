@@ -11,7 +11,7 @@ for r in 1 2; do
   for v in old new; do
     cp gpurun_ab_$v.so "$LIB"
     echo -n "$v: "
-    python bench.py --steps 4 --warmup 2 --inflight 1 --no-cpu-baseline --no-kernel-timing --no-scene-sweep --height 270 --width 480 --frames 24 2>/dev/null |
+    python bench.py --full --steps 4 --warmup 2 --inflight 1 --no-cpu-baseline --no-kernel-timing --no-scene-sweep --height 270 --width 480 --frames 24 2>/dev/null |
       python -c "import sys,json; g=json.loads(sys.stdin.read().strip().splitlines()[-1])['gnt']; print(g['tflops'], g['frac_of_peak'], g['ms_transformer_A14'], g['repetitions']['tflops_min'], g['repetitions']['tflops_max'])"
   done
 done

@@ -2,7 +2,7 @@
 # round 4: the one-native-call-per-view path against the per-op arrangement, lanes and stream pairs
 cd "${GRAFT_REPO_ROOT:?}" || exit 1
 mkdir -p gpurun_out/r04
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --gnt-rays 0 --no-scene-sweep"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --gnt-rays 0 --no-scene-sweep"
 run() { name=$1; shift; echo "== $name: $*"; "$@" > gpurun_out/r04/$name.json 2> gpurun_out/r04/$name.err || { echo "FAILED $name"; tail -5 gpurun_out/r04/$name.err; }
   python - "$name" <<'PY'
 import json,sys

@@ -6,7 +6,7 @@ for q in 4 8 12; do
   for lanes in 3 5 7; do
     for ss in --side-stream --no-side-stream; do
       echo -n "queues=$q lanes=$lanes $ss: "
-      GPU_MAX_HW_QUEUES=$q python bench.py --steps 100 --warmup 5 --no-cpu-baseline --gnt-rays 0 --no-kernel-timing --no-scene-sweep --inflight $lanes $ss 2>/dev/null |
+      GPU_MAX_HW_QUEUES=$q python bench.py --full --steps 100 --warmup 5 --no-cpu-baseline --gnt-rays 0 --no-kernel-timing --no-scene-sweep --inflight $lanes $ss 2>/dev/null |
         python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['latency_ms']['median'], d.get('host_enqueue_ms_per_step'))"
     done
   done
