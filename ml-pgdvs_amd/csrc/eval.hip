@@ -6,7 +6,7 @@
 // the view on this GPU; here the step enqueues two launches and reads eight doubles back (the six sums and the
 // geometry path's two status words).
 #include "common.h"
-#include "eval_quant.h"
+#include "eval_common.h"
 
 namespace pgdvs {
 
@@ -37,23 +37,12 @@ eval_partials_kernel(const float *__restrict__ pred, const float *__restrict__ g
       acc[5] += (double)ms;
     }
   }
-  __shared__ double s[kEvalThreads / 64][kEvalSums];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < kEvalSums; ++k) {
-    double v = acc[k];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) s[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kEvalSums) {
-    double v = 0.0;
-    for (int w = 0; w < kEvalThreads / 64; ++w) v += s[w][threadIdx.x];
-    partials[(size_t)blockIdx.x * kEvalSums + threadIdx.x] = v;
-  }
+  __shared__ double red[kEvalThreads / kWave][kEvalSums];
+  block_partials<kEvalSums, kEvalThreads>(threadIdx.x, acc, red, partials + (size_t)blockIdx.x * kEvalSums);
 }
 
-// fixed-order final sum: the result does not depend on scheduling
+// fixed-order final sum: the result does not depend on scheduling.  (One thread per sum adds the blocks sequentially, not
+// ordered_block_sum's lane-strided order: its last bits are the PSNR sums'.)
 // (+ the renderer's two device-side status words, so that the step reads everything back in ONE transfer: sums[6] = the
 // static cloud's row count or -1 without one, sums[7] = the rasteriser's status word or 0)
 __global__ void eval_final_kernel(const double *__restrict__ partials, double *__restrict__ sums, const int64_t *__restrict__ count_dev,

@@ -2,7 +2,7 @@
 // obtain_quantitative_dycheck_iphone through pgdvs/utils/dycheck/metrics.py:63-230), for one view: PSNR, SSIM and LPIPS with
 // a full mask and with the covisibility mask eval_mask[H,W,1].
 //
-// psnr_ssim  ONE pass per view.  The PSNR pass's 8-bit quantisation (eval_quant.h); the squared differences and the mask sum of
+// psnr_ssim  ONE pass per view.  The PSNR pass's 8-bit quantisation (eval_common.h); the squared differences and the mask sum of
 //            masked_mean (metrics.py:63-90: sum(d^2 m) / max(sum(m broadcast to 3 channels), 1e-6)) in float64; and the two
 //            partial-convolution SSIM maps (metrics.py:93-186, modelled on tf.image.ssim: an 11-tap Gaussian with sigma 1.5,
 //            applied separably with mode "valid", first along W, then along H; each pass forms
@@ -20,7 +20,7 @@
 #include <cmath>
 
 #include "common.h"
-#include "eval_quant.h"
+#include "eval_common.h"
 #include "lpips_net.h"
 
 namespace pgdvs {
@@ -150,34 +150,19 @@ dycheck_ssim_partials_kernel(const float *__restrict__ pred, const float *__rest
     __syncthreads();  // (the next channel overwrites the tile and the moments)
   }
   const double v[kDcSums] = {(double)ssim, psnr[0], psnr[1], psnr[2]};
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
-#pragma unroll
-  for (int k = 0; k < kDcSums; ++k) {
-    double s = v[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (tid < kDcSums) {
-    double s = 0.0;
-    for (int w = 0; w < kDcThreads / kWave; ++w) s += red[w][tid];
-    partials[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kDcSums + tid] = s;
-  }
+  block_partials<kDcSums, kDcThreads>(tid, v, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kDcSums);
 }
 
-// fixed-order final sums (wave k reduces one sum; lane l takes the blocks l, l + 64, ... in order, then a fixed shuffle tree)
-// into the row: sum d2, sum d2 m, sum S (full), 3 H W, 3 sum m, sum S (covisible), *count_dev, *status_dev
+// fixed-order final sums (wave k reduces one sum with ordered_block_sum) into the row: sum d2, sum d2 m, sum S (full), 3 H W,
+// 3 sum m, sum S (covisible), *count_dev, *status_dev
 __global__ void __launch_bounds__(5 * kWave)
 dycheck_ssim_final_kernel(const double *__restrict__ partials, int n_blocks, double count, const int64_t *__restrict__ count_dev,
                           const int32_t *__restrict__ status_dev, double *__restrict__ sums) {
   // wave k -> (the mask's blocks, partial slot, row slot): 0 d2, 1 d2 m, 2 S full, 3 m, 4 S covisible
-  const int lane = threadIdx.x & (kWave - 1), k = threadIdx.x / kWave;
+  const int k = threadIdx.x / kWave;
   const int src_mask = k == 2 ? 0 : 1, src_slot = k == 0 ? 1 : (k == 1 ? 2 : (k == 3 ? 3 : 0)), dst = k < 3 ? k : k + 1;
-  const double *base = partials + (size_t)src_mask * n_blocks * kDcSums + src_slot;
-  double v = 0.0;
-  for (int b = lane; b < n_blocks; b += kWave) v += base[(size_t)b * kDcSums];
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  if (lane == 0) sums[dst] = k == 3 ? 3.0 * v : v;
+  const double v = ordered_block_sum(partials + (size_t)src_mask * n_blocks * kDcSums + src_slot, 0, n_blocks, kDcSums);
+  if ((threadIdx.x & (kWave - 1)) == 0) sums[dst] = k == 3 ? 3.0 * v : v;
   if (threadIdx.x == 0) {
     sums[3] = count;
     sums[6] = count_dev ? (double)*count_dev : -1.0;
@@ -305,30 +290,16 @@ __global__ void __launch_bounds__(kDlThreads) dycheck_lpips_upsample_kernel(DlFi
     acc[1] += (double)(v1 * mm);
     acc[2] += (double)mm;
   }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < kDlSums; ++k) {
-    double s = acc[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kDlSums) {
-    double s = 0.0;
-    for (int w = 0; w < kDlThreads / kWave; ++w) s += red[w][threadIdx.x];
-    partials[(size_t)blockIdx.x * kDlSums + threadIdx.x] = s;
-  }
+  block_partials<kDlSums, kDlThreads>(threadIdx.x, acc, red, partials + (size_t)blockIdx.x * kDlSums);
 }
 
 // the row: LPIPS full, LPIPS covisible (masked_mean: sum / max(sum m, 1e-6)), sum v0, H W, sum v1 m, sum m, 0, 0
 __global__ void __launch_bounds__(kDlSums * kWave)
 dycheck_lpips_final_kernel(const double *__restrict__ partials, double pixels, double *__restrict__ sums) {
   __shared__ double tot[kDlSums];
-  const int lane = threadIdx.x & (kWave - 1), k = threadIdx.x / kWave;
-  double v = 0.0;
-  for (int b = lane; b < kDlFinalBlocks; b += kWave) v += partials[(size_t)b * kDlSums + k];
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  if (lane == 0) tot[k] = v;
+  const int k = threadIdx.x / kWave;
+  const double v = ordered_block_sum(partials + k, 0, kDlFinalBlocks, kDlSums);
+  if ((threadIdx.x & (kWave - 1)) == 0) tot[k] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
     sums[0] = tot[0] / (pixels > 1e-6 ? pixels : 1e-6);

@@ -1,7 +1,7 @@
 // SURVEY 8f-1, the evaluator's masked SSIM (pgdvs/engines/evaluator_pgdvs.py:190-283 through
 // pgdvs/utils/training.py:316-346 calculate_ssim = skimage 0.20 structural_similarity(full=True, channel_axis=2,
 // data_range=2.0) -> sum(S * mask) / (sum(mask) + 1e-8)) as ONE pass per view: the same 8-bit quantisation as the PSNR
-// pass (eval_quant.h), the five 7x7 box sums of every channel EXACTLY in integers (separable: a horizontal then a
+// pass (eval_common.h), the five 7x7 box sums of every channel EXACTLY in integers (separable: a horizontal then a
 // vertical sliding sum over a haloed tile in LDS, scipy's half-sample-symmetric "reflect" border), S from those sums in
 // fp32, and the masked sums in float64 (a thread's 8 rows of one channel are summed in fp32 first).  Upstream this is a
 // device-to-host copy and three skimage calls per view, each running 15 float32 box filters on the CPU.
@@ -12,7 +12,7 @@
 // is, after cancelling the common scales, (2 Sa Sb + c1)(2 Dab + c2) / ((Sa^2 + Sb^2 + c1)(Daa + Dbb + c2)) with
 // Dab = 49 Sab - Sa Sb, c1 = C1 (49*255)^2 and c2 = C2 48*49*255^2.  Every integer there is below 2^31.
 #include "common.h"
-#include "eval_quant.h"
+#include "eval_common.h"
 
 namespace pgdvs {
 
@@ -168,30 +168,16 @@ eval_ssim_partials_kernel(const float *__restrict__ pred, const float *__restric
     }
     __syncthreads();  // (the next channel overwrites the tile)
   }
-  const int lane = tid & (kWave - 1), wave = tid / kWave;
-#pragma unroll
-  for (int k = 0; k < kSsimSums; ++k) {
-    double v = acc[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < kSsimSums) {
-    double v = 0.0;
-    for (int w = 0; w < kSsimThreads / kWave; ++w) v += red[w][tid];
-    partials[(size_t)blockIdx.x * kSsimSums + tid] = v;
-  }
+  block_partials<kSsimSums, kSsimThreads>(tid, acc, red, partials + (size_t)blockIdx.x * kSsimSums);
 }
 
-// fixed-order final sum (wave k reduces sum k; lane l takes the blocks l, l + 64, ... in order, then a fixed shuffle
-// tree): the result does not depend on scheduling.  Layout of the PSNR row: sums[3] = 3HW, sums[6..7] = 0.
+// fixed-order final sum (wave k reduces sum k with ordered_block_sum): the result does not depend on scheduling.  Layout of
+// the PSNR row: sums[3] = 3HW, sums[6..7] = 0.
 __global__ void __launch_bounds__(kSsimSums * kWave)
 eval_ssim_final_kernel(const double *__restrict__ partials, int n_blocks, double count, double *__restrict__ sums) {
-  const int lane = threadIdx.x & (kWave - 1), k = threadIdx.x / kWave;
-  double v = 0.0;
-  for (int b = lane; b < n_blocks; b += kWave) v += partials[(size_t)b * kSsimSums + k];
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  if (lane == 0) sums[k < 3 ? k : k + 1] = v;
+  const int k = threadIdx.x / kWave;
+  const double v = ordered_block_sum(partials + k, 0, n_blocks, kSsimSums);
+  if ((threadIdx.x & (kWave - 1)) == 0) sums[k < 3 ? k : k + 1] = v;
   if (threadIdx.x == 0) {
     sums[3] = count;
     sums[6] = 0.0;

@@ -1,6 +1,6 @@
 // SURVEY 8f-1, the evaluator's masked LPIPS (pgdvs/engines/evaluator_pgdvs.py:94-110,190-283 through
 // pgdvs/utils/nsff_lpips: PerceptualLoss(model="net-lin", net="alex", version=0.1), trainer_pgdvs.py:132-137) for one view:
-//   prep   the PSNR pass's 8-bit quantisation (eval_quant.h), then 2 q - 1 (modify_rgb_range "0_1" -> "-1_1"), into ONE
+//   prep   the PSNR pass's 8-bit quantisation (eval_common.h), then 2 q - 1 (modify_rgb_range "0_1" -> "-1_1"), into ONE
 //          [2,3,H,W] batch, ground truth first: every backbone layer runs once for both images (upstream runs the backbone
 //          on both images for each of the three masks).  No ScalingLayer: PNetLin.forward tests `version == "0.1"` against a
 //          string while the evaluator passes the float 0.1 (networks_basic.py:94-99), so the shift / scale never applies.
@@ -13,7 +13,7 @@
 //          "nearest" rule, evaluated in-kernel; fixed-order float64 block partials.
 //   final  per layer sum(x m) / (sum(m) + 1e-8) for the masks ones / eval_mask / 1 - eval_mask, summed over the layers.
 #include "common.h"
-#include "eval_quant.h"
+#include "eval_common.h"
 #include "gnt_mfma.h"
 #include "lpips_net.h"
 
@@ -207,19 +207,7 @@ __global__ void __launch_bounds__(kHdThreads) lpips_head_kernel(LpipsHeadArgs a,
     v[3] = (double)m;
     v[4] = (double)ms;
   }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < kHdSums; ++k) {
-    double s = v[k];
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kHdSums) {
-    double s = 0.0;
-    for (int w = 0; w < kHdThreads / kWave; ++w) s += red[w][threadIdx.x];
-    partials[(size_t)blockIdx.x * kHdSums + threadIdx.x] = s;
-  }
+  block_partials<kHdSums, kHdThreads>(threadIdx.x, v, red, partials + (size_t)blockIdx.x * kHdSums);
 }
 
 struct LpipsFinalArgs {
@@ -227,17 +215,15 @@ struct LpipsFinalArgs {
   double pixels[kLpLayers];  // h w of each relu map: the sum of the all-ones mask
 };
 
-// wave k reduces sum k of every layer: lane l takes the layer's blocks l, l + 64, ... in order, then a fixed shuffle tree;
-// thread 0 forms the ratios in the reference's order (per layer, then the sum over the layers 0..4).  Deterministic.
+// wave k reduces sum k of every layer's blocks (ordered_block_sum); thread 0 forms the ratios in the reference's order (per
+// layer, then the sum over the layers 0..4).  Deterministic.
 __global__ void __launch_bounds__(kHdSums * kWave)
 lpips_final_kernel(const double *__restrict__ partials, LpipsFinalArgs a, double *__restrict__ sums) {
   __shared__ double tot[kLpLayers][kHdSums];
-  const int lane = threadIdx.x & (kWave - 1), k = threadIdx.x / kWave;
+  const int k = threadIdx.x / kWave;
   for (int L = 0; L < kLpLayers; ++L) {
-    double v = 0.0;
-    for (int b = a.block0[L] + lane; b < a.block0[L + 1]; b += kWave) v += partials[(size_t)b * kHdSums + k];
-    for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-    if (lane == 0) tot[L][k] = v;
+    const double v = ordered_block_sum(partials + k, a.block0[L], a.block0[L + 1], kHdSums);
+    if ((threadIdx.x & (kWave - 1)) == 0) tot[L][k] = v;
   }
   __syncthreads();
   if (threadIdx.x == 0) {

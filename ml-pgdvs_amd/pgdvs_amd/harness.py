@@ -173,25 +173,31 @@ def alex_features(x: torch.Tensor, weights: LpipsAlex):
     return feats
 
 
+def _lpips_layers(x, weights, scaling_layer):
+    """LPIPS's per-layer distance maps of image pairs x[2n,3,H,W] in [0,1] (pair i = x[2i] vs x[2i+1]): 2 x - 1 (modify_rgb_range
+    "0_1" -> "-1_1", utils/rendering.py:26-77; im2tensor's x / 0.5 - 1 is the same exact map), optionally the ScalingLayer,
+    AlexNet relu1..5, normalize_tensor, the squared difference and the 1x1 lin_k -> one [n,1,h,w] map per layer"""
+    x = 2.0 * x - 1.0
+    if scaling_layer:
+        shift = torch.tensor(_LPIPS_SHIFT, dtype=torch.float32, device=x.device)[None, :, None, None]
+        scale = torch.tensor(_LPIPS_SCALE, dtype=torch.float32, device=x.device)[None, :, None, None]
+        x = (x - shift) / scale
+    diffs = []
+    for f, lin in zip(alex_features(x, weights), weights.on(x.device).lins):
+        f = f / (torch.sqrt(torch.sum(f ** 2, dim=1, keepdim=True)) + 1e-10)  # normalize_tensor
+        diffs.append(F.conv2d((f[0::2] - f[1::2]) ** 2, lin))
+    return diffs
+
+
 def _lpips_torch(img1, img2, masks, weights, scaling_layer=False):
     """LPIPS of [3,H,W] images in [0,1] for each of ``masks`` ([C,H,W], channel 0 used), the backbone run once."""
     H, W = img1.shape[-2:]
     if H < 31 or W < 31:
         raise ValueError(f"masked_lpips: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
-    x = torch.stack([img1, img2]).float()
-    x = 2.0 * x - 1.0  # modify_rgb_range "0_1" -> "-1_1" (utils/rendering.py:26-77)
-    if scaling_layer:
-        shift = torch.tensor(_LPIPS_SHIFT, dtype=torch.float32, device=x.device)[None, :, None, None]
-        scale = torch.tensor(_LPIPS_SCALE, dtype=torch.float32, device=x.device)[None, :, None, None]
-        x = (x - shift) / scale
-    feats = alex_features(x, weights)
-    diffs = []
-    for f, lin in zip(feats, weights.on(x.device).lins):
-        f = f / (torch.sqrt(torch.sum(f ** 2, dim=1, keepdim=True)) + 1e-10)  # normalize_tensor
-        diffs.append(F.conv2d((f[0:1] - f[1:2]) ** 2, lin))  # [1,1,h,w]
+    diffs = _lpips_layers(torch.stack([img1, img2]).float(), weights, scaling_layer)
     out = []
     for m in masks:
-        m = m[None, 0:1].float().to(x.device)
+        m = m[None, 0:1].float().to(img1.device)
         val = None
         for d in diffs:  # spatial_average (networks_basic.py:15-25), then the sum over layers (:134-136)
             mr = F.interpolate(m, size=[d.shape[2], d.shape[3]])
@@ -285,16 +291,8 @@ def _lpips_dycheck_torch(img1, img2, masks, weights):
     if H < 31 or W < 31:
         raise ValueError(f"masked_lpips_dycheck: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
     ms = [m.float().to(img1.device) for m in masks]
-    x = torch.stack([t for m in ms for t in (img1.float() * m, img2.float() * m)])  # [2 n, 3, H, W]
-    x = x / 0.5 - 1.0
-    shift = torch.tensor(_LPIPS_SHIFT, dtype=torch.float32, device=x.device)[None, :, None, None]
-    scale = torch.tensor(_LPIPS_SCALE, dtype=torch.float32, device=x.device)[None, :, None, None]
-    x = (x - shift) / scale
-    feats = alex_features(x, weights)
     val = None
-    for f, lin in zip(feats, weights.on(x.device).lins):
-        f = f / (torch.sqrt(torch.sum(f ** 2, dim=1, keepdim=True)) + 1e-10)
-        d = F.conv2d((f[0::2] - f[1::2]) ** 2, lin)  # [n,1,h,w]
+    for d in _lpips_layers(torch.stack([t for m in ms for t in (img1.float() * m, img2.float() * m)]), weights, True):
         up = F.interpolate(d, size=(H, W), mode="bilinear", align_corners=False)
         val = up if val is None else val + up
     return [float((val[i, 0] * m).double().sum() / max(float(m.double().sum()), 1e-6)) for i, m in enumerate(ms)]
@@ -399,108 +397,53 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
         else:
             ops.check_raster_status(ret.get("geo_static_raster_status", None))
 
-    comb = ret["combined_rgb"]
+    comb, gt, em = ret["combined_rgb"], data_gpu["rgb_tgt"], data_gpu["eval_mask"]
     if quant_type == "dycheck_iphone":
-        return _eval_dycheck(ret, data_gpu, n_batch, check_status, lap, return_images, lpips)
-    if (comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(data_gpu["rgb_tgt"].shape[1:3])
-            and data_gpu["rgb_tgt"].dtype == torch.float32 and data_gpu["eval_mask"].dtype == torch.float32):
-        # GPU, render size == ground-truth size (render_stride 1): quantisation and the three masked sums of a view in ONE
-        # pass (csrc/eval.hip), one host read for the whole batch
-        # (the device-side status words of the geometry path ride along in the same block: ONE host read per batch)
+        keys, fused_rows, view_values = DYCHECK_KEYS + (DYCHECK_LPIPS_KEYS if lpips is not None else ()), _dycheck_rows, _dycheck_view
+    else:
+        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
+        fused_rows, view_values = _nvidia_rows, _nvidia_view
+    multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+    if (comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(gt.shape[1:3])
+            and gt.dtype == torch.float32 and em.dtype == torch.float32):
+        # GPU, render size == ground-truth size (render_stride 1): the protocol's HIP passes per view, the first of which
+        # quantises and carries the geometry path's device-side status words, and ONE host read for the batch
         cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
         cnts = cnts.reshape(-1) if isinstance(cnts, torch.Tensor) and cnts.is_cuda and cnts.dtype == torch.int64 else None
         stat = ret.get("geo_static_raster_status", None)
         stat = stat.reshape(-1) if isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.int32 else None
-        res = [ops.eval_psnr_sums(comb[i_b], data_gpu["rgb_tgt"][i_b], data_gpu["eval_mask"][i_b], want_images=return_images,
-                                  count_dev=cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None,
-                                  status_dev=stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None)
-               for i_b in range(n_batch)]
-        # (SSIM after the unchanged PSNR launches; its rows come back in the same transfer)
-        ssim_rows = [ops.eval_ssim_sums(comb[i_b], data_gpu["rgb_tgt"][i_b], data_gpu["eval_mask"][i_b])[0]
-                     for i_b in range(n_batch)] if with_ssim else []
-        # (LPIPS last: the backbone runs once per image per view, for all three masks)
-        lpips_rows = [ops.lpips_sums(comb[i_b], data_gpu["rgb_tgt"][i_b], data_gpu["eval_mask"][i_b], lpips.on(comb.device))[0]
-                      for i_b in range(n_batch)] if lpips is not None else []
+        cd = [cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None for i_b in range(n_batch)]
+        sd = [stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None for i_b in range(n_batch)]
+        groups, images = fused_rows(comb, gt, em, cd, sd, with_ssim, lpips, return_images)
         lap("metric_enqueue")
-        sums = ops.read_back_rows([r_[0] for r_ in res] + ssim_rows + lpips_rows)  # (the step's synchronisation)
-        sums, ssim_sums, lpips_sums = sums[:n_batch], sums[n_batch:n_batch + len(ssim_rows)], sums[n_batch + len(ssim_rows):]
+        host = ops.read_back_rows([r_ for rows, _ in groups for r_ in rows])  # (the step's synchronisation)
         lap("sync_read")
-        check_status(host_counts=[int(s_[6]) for s_ in sums] if cnts is not None else None,
-                     host_status=[int(s_[7]) for s_ in sums] if stat is not None else None)
-        per_view = {k: [] for k in METRIC_KEYS}
-        for s_ in sums:
-            for j, k in enumerate(METRIC_KEYS):
-                mse = s_[j] / (s_[3 + j] + 1e-8)
-                per_view[k].append(0 if mse == 0 else 10 * math.log10(1.0 / mse))
-        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
-        if with_ssim:
-            per_view.update({k: [s_[j] / (s_[3 + j] + 1e-8) for s_ in ssim_sums] for j, k in enumerate(SSIM_KEYS)})
-        if lpips is not None:  # (the LPIPS row carries the finished values: include/pgdvs_hip.h)
-            per_view.update({k: [s_[j] for s_ in lpips_sums] for j, k in enumerate(LPIPS_KEYS)})
-        # (a single process keeps the packed sums -- and so the metric tensors -- on the host: same dtypes and values, no
-        # upload and no one-element kernels per step, and the caller's `.item()` costs nothing; ranks that reduce over
-        # RCCL need them on the device, like upstream)
-        multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-        if not multi:
-            metric = {"eval/count": torch.tensor([n_batch], dtype=torch.int64)}
-            for k in keys:
-                metric[f"eval/{k}"] = torch.tensor(per_view[k], dtype=torch.float32).sum()
-        else:
-            packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
-                                  dtype=torch.float64, device=comb.device)
-            packed = pdist.reduce_metrics(packed, dst=0)
-            metric = {"eval/count": packed[:1].round().to(torch.int64)}
-            for j, k in enumerate(keys):
-                metric[f"eval/{k}"] = packed[1 + j].to(torch.float32)
+        check_status(host_counts=[int(s_[6]) for s_ in host[:n_batch]] if cnts is not None else None,
+                     host_status=[int(s_[7]) for s_ in host[:n_batch]] if stat is not None else None)
+        vals = [[v for j, (_, values) in enumerate(groups) for v in values(host[j * n_batch + i_b])] for i_b in range(n_batch)]
+        per_view = {k: [v[j] for v in vals] for j, k in enumerate(keys)}
+        # (a single process keeps the metric tensors on the host: no upload and no one-element kernels per step)
+        metric = _metric_dict(n_batch, keys, per_view, comb.device, multi)
         lap("post")
         if return_images:
-            return metric, {"pred": torch.stack([r_[1] for r_ in res]), "gt": torch.stack([r_[2] for r_ in res]),
-                            "eval_mask": data_gpu["eval_mask"].permute(0, 3, 1, 2), "per_view": per_view, "ret": ret}
+            pred, gtq = images()
+            return metric, {"pred": pred, "gt": gtq, "eval_mask": em.permute(0, 3, 1, 2), "per_view": per_view, "ret": ret}
         return metric
     check_status()
-    pred = OrderedDict({"combined": ret["combined_rgb"].clamp(0.0, 1.0)})
-    for k in pred:
-        if torch.any(torch.isnan(pred[k])):
-            pred[k] = torch.nan_to_num(pred[k], nan=0.0)
-    rgb_gt = data_gpu["rgb_tgt"].permute(0, 3, 1, 2).clamp(0.0, 1.0)
-    eval_mask = data_gpu["eval_mask"].permute(0, 3, 1, 2)
     # quantise first, as if the images had been written to disk and read back (:70-77)
-    rgb_gt = (rgb_gt * 255).byte().float() / 255.0
-    for k in pred:
-        pred[k] = (pred[k] * 255).byte().float() / 255.0
-    _, _, rh, rw = pred["combined"].shape
+    pred = quantize_like_evaluator(comb)
+    rgb_gt = quantize_like_evaluator(gt.permute(0, 3, 1, 2))
+    eval_mask = em.permute(0, 3, 1, 2)
+    _, _, rh, rw = pred.shape
     if rgb_gt.shape[2] != rh or rgb_gt.shape[3] != rw:  # render_stride != 1 (:80-92)
         rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
         eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
         eval_mask = (eval_mask > 0).float()
-    keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
-    per_view = {k: [] for k in keys}
-    for i_b in range(n_batch):
-        p, g = pred["combined"][i_b].to(rgb_gt.device), rgb_gt[i_b]
-        m_dyn = eval_mask[i_b]
-        # calculate_psnr asserts on [0,1] inputs; a bicubically resized ground truth can overshoot, as upstream
-        per_view["psnr_full_combined"].append(masked_psnr(g, p, torch.ones_like(g)))
-        per_view["psnr_dyn_combined"].append(masked_psnr(g, p, m_dyn))
-        per_view["psnr_static_combined"].append(masked_psnr(g, p, 1.0 - m_dyn))
-        if with_ssim:
-            per_view["ssim_full_combined"].append(masked_ssim(g, p, torch.ones_like(g)))
-            per_view["ssim_dyn_combined"].append(masked_ssim(g, p, m_dyn))
-            per_view["ssim_static_combined"].append(masked_ssim(g, p, 1.0 - m_dyn))
-        if lpips is not None:
-            for k, v in zip(LPIPS_KEYS, _lpips_torch(g, p, [torch.ones_like(g), m_dyn, 1.0 - m_dyn], lpips)):
-                per_view[k].append(v)
-    # one packed reduce instead of one collective per key: [count, sums...] in float64 on the device
-    packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
-                          dtype=torch.float64, device=rgb_gt.device)
-    packed = pdist.reduce_metrics(packed, dst=0)
-    multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-    if not multi:
-        packed = packed.cpu()  # one process: host tensors on BOTH paths, whatever the inputs' dtypes and sizes were
-    metric = {"eval/count": packed[:1].round().to(torch.int64)}
-    for j, k in enumerate(keys):
-        metric[f"eval/{k}"] = packed[1 + j].to(torch.float32)
+    vals = [view_values(rgb_gt[i_b], pred[i_b].to(rgb_gt.device), eval_mask[i_b], with_ssim, lpips) for i_b in range(n_batch)]
+    per_view = {k: [v[j] for v in vals] for j, k in enumerate(keys)}
+    metric = _metric_dict(n_batch, keys, per_view, rgb_gt.device, multi)
     if return_images:
-        return metric, {"pred": pred["combined"], "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}
+        return metric, {"pred": pred, "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}
     return metric
 
 
@@ -511,6 +454,7 @@ def _metric_dict(n_batch, keys, per_view, device, multi):
         for k in keys:
             metric[f"eval/{k}"] = torch.tensor(per_view[k], dtype=torch.float32).sum()
         return metric
+    # one packed reduce instead of one collective per key: [count, sums...] in float64 on the device
     packed = torch.tensor([float(n_batch)] + [float(torch.tensor(per_view[k], dtype=torch.float32).sum()) for k in keys],
                           dtype=torch.float64, device=device)
     packed = pdist.reduce_metrics(packed, dst=0)
@@ -520,74 +464,62 @@ def _metric_dict(n_batch, keys, per_view, device, multi):
     return metric
 
 
-def _eval_dycheck(ret, data_gpu, n_batch, check_status, lap, return_images, lpips):
-    """eval_step's metrics under quant_type "dycheck_iphone" (obtain_quantitative_dycheck_iphone, evaluator_pgdvs.py:282-409)"""
+# Each protocol's part of eval_step.  *_rows (the fused path) enqueues the protocol's rows for every view -> ([(the views' rows,
+# host row -> that row's values in key order)], () -> the quantised pred / gt [B,3,H,W] for return_images); *_view (the torch
+# path) is one view's values in key order from quantised gt / pred [3,H,W] and eval_mask [C,H,W].
+def _nvidia_rows(comb, gt, em, cd, sd, with_ssim, lpips, want_images):
+    """csrc/eval.hip: quantisation and the three masked PSNR sums of a view in one pass; then SSIM (csrc/eval_ssim.hip) and
+    LPIPS (csrc/lpips.hip: the backbone runs once per image per view, for all three masks) on request"""
     from . import ops
 
-    comb = ret["combined_rgb"]
-    keys = DYCHECK_KEYS + (DYCHECK_LPIPS_KEYS if lpips is not None else ())
-    per_view = {k: [] for k in keys}
-    multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+    n = comb.shape[0]
+    psnr = [ops.eval_psnr_sums(comb[i], gt[i], em[i], want_images=want_images, count_dev=cd[i], status_dev=sd[i]) for i in range(n)]
+
+    def psnr_values(s_):
+        mses = [s_[j] / (s_[3 + j] + 1e-8) for j in range(3)]
+        return [0 if mse == 0 else 10 * math.log10(1.0 / mse) for mse in mses]
+
+    groups = [([r_[0] for r_ in psnr], psnr_values)]
+    if with_ssim:
+        groups.append(([ops.eval_ssim_sums(comb[i], gt[i], em[i])[0] for i in range(n)],
+                       lambda s_: [s_[j] / (s_[3 + j] + 1e-8) for j in range(3)]))
+    if lpips is not None:  # (the LPIPS row carries the finished values: include/pgdvs_hip.h)
+        w = lpips.on(comb.device)
+        groups.append(([ops.lpips_sums(comb[i], gt[i], em[i], w)[0] for i in range(n)], lambda s_: s_[:3]))
+    return groups, lambda: (torch.stack([r_[1] for r_ in psnr]), torch.stack([r_[2] for r_ in psnr]))
+
+
+def _nvidia_view(g, p, m_dyn, with_ssim, lpips):
+    # calculate_psnr asserts on [0,1] inputs; a bicubically resized ground truth can overshoot, as upstream
+    masks = [torch.ones_like(g), m_dyn, 1.0 - m_dyn]
+    vals = [masked_psnr(g, p, m) for m in masks]
+    if with_ssim:
+        vals += [masked_ssim(g, p, m) for m in masks]
+    if lpips is not None:
+        vals += _lpips_torch(g, p, masks, lpips)
+    return vals
+
+
+def _dycheck_rows(comb, gt, em, cd, sd, with_ssim, lpips, want_images):
+    """obtain_quantitative_dycheck_iphone (evaluator_pgdvs.py:282-409): one PSNR + SSIM pass per view (csrc/eval_dycheck.hip),
+    the LPIPS pass on request"""
+    from . import ops
+
+    n = comb.shape[0]
+    n_map = 3.0 * (comb.shape[2] - 10) * (comb.shape[3] - 10)
     to_db = lambda s_, n_: math.inf if s_ / max(n_, 1e-6) == 0 else -10.0 / math.log(10.0) * math.log(s_ / max(n_, 1e-6))  # noqa: E731
-    if (comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(data_gpu["rgb_tgt"].shape[1:3])
-            and data_gpu["rgb_tgt"].dtype == torch.float32 and data_gpu["eval_mask"].dtype == torch.float32):
-        # GPU at render size: one PSNR + SSIM pass per view (csrc/eval_dycheck.hip) carrying the geometry path's status words,
-        # the LPIPS pass on request, and ONE host read for the batch
-        cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
-        cnts = cnts.reshape(-1) if isinstance(cnts, torch.Tensor) and cnts.is_cuda and cnts.dtype == torch.int64 else None
-        stat = ret.get("geo_static_raster_status", None)
-        stat = stat.reshape(-1) if isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.int32 else None
-        gt, em = data_gpu["rgb_tgt"], data_gpu["eval_mask"]
-        rows = [ops.dycheck_psnr_ssim_sums(comb[i_b], gt[i_b], em[i_b],
-                                           count_dev=cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None,
-                                           status_dev=stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None)
-                for i_b in range(n_batch)]
-        lp_rows = [ops.dycheck_lpips(comb[i_b], gt[i_b], em[i_b], lpips.on(comb.device)) for i_b in range(n_batch)] if lpips is not None else []
-        lap("metric_enqueue")
-        sums = ops.read_back_rows(rows + lp_rows)  # (the step's synchronisation)
-        sums, lp_sums = sums[:n_batch], sums[n_batch:]
-        lap("sync_read")
-        check_status(host_counts=[int(s_[6]) for s_ in sums] if cnts is not None else None,
-                     host_status=[int(s_[7]) for s_ in sums] if stat is not None else None)
-        H, W = comb.shape[2:]
-        n_map = 3.0 * (H - 10) * (W - 10)
-        for s_ in sums:
-            per_view["psnr_combined"].append(to_db(s_[0], s_[3]))
-            per_view["ssim_combined"].append(s_[2] / n_map)
-            per_view["mpsnr_combined"].append(to_db(s_[1], s_[4]))
-            per_view["mssim_combined"].append(s_[5] / n_map)
-        for s_ in lp_sums:
-            per_view["lpips_combined"].append(s_[0])
-            per_view["mlpips_combined"].append(s_[1])
-        metric = _metric_dict(n_batch, keys, per_view, comb.device, multi)
-        lap("post")
-        if return_images:
-            pred = quantize_like_evaluator(comb)
-            gtq = quantize_like_evaluator(gt.permute(0, 3, 1, 2))
-            return metric, {"pred": pred, "gt": gtq, "eval_mask": em.permute(0, 3, 1, 2), "per_view": per_view, "ret": ret}
-        return metric
-    check_status()
-    pred = quantize_like_evaluator(comb)
-    rgb_gt = quantize_like_evaluator(data_gpu["rgb_tgt"].permute(0, 3, 1, 2))
-    eval_mask = data_gpu["eval_mask"].permute(0, 3, 1, 2)
-    _, _, rh, rw = pred.shape
-    if rgb_gt.shape[2] != rh or rgb_gt.shape[3] != rw:  # render_stride != 1 (:80-92)
-        rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
-        eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
-        eval_mask = (eval_mask > 0).float()
-    for i_b in range(n_batch):
-        p, g = pred[i_b].to(rgb_gt.device), rgb_gt[i_b]
-        m = eval_mask[i_b, 0]
-        ones = torch.ones_like(m)
-        per_view["psnr_combined"].append(masked_psnr_dycheck(g, p, ones))
-        per_view["ssim_combined"].append(masked_ssim_dycheck(g, p, ones))
-        per_view["mpsnr_combined"].append(masked_psnr_dycheck(g, p, m))
-        per_view["mssim_combined"].append(masked_ssim_dycheck(g, p, m))
-        if lpips is not None:
-            full, covis = _lpips_dycheck_torch(g, p, [ones, m], lpips)
-            per_view["lpips_combined"].append(full)
-            per_view["mlpips_combined"].append(covis)
-    metric = _metric_dict(n_batch, keys, per_view, rgb_gt.device, multi)
-    if return_images:
-        return metric, {"pred": pred, "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}
-    return metric
+    groups = [([ops.dycheck_psnr_ssim_sums(comb[i], gt[i], em[i], count_dev=cd[i], status_dev=sd[i]) for i in range(n)],
+               lambda s_: [to_db(s_[0], s_[3]), s_[2] / n_map, to_db(s_[1], s_[4]), s_[5] / n_map])]
+    if lpips is not None:
+        w = lpips.on(comb.device)
+        groups.append(([ops.dycheck_lpips(comb[i], gt[i], em[i], w) for i in range(n)], lambda s_: s_[:2]))
+    return groups, lambda: (quantize_like_evaluator(comb), quantize_like_evaluator(gt.permute(0, 3, 1, 2)))
+
+
+def _dycheck_view(g, p, mask, with_ssim, lpips):
+    m = mask[0]
+    ones = torch.ones_like(m)
+    vals = [masked_psnr_dycheck(g, p, ones), masked_ssim_dycheck(g, p, ones), masked_psnr_dycheck(g, p, m), masked_ssim_dycheck(g, p, m)]
+    if lpips is not None:
+        vals += _lpips_dycheck_torch(g, p, [ones, m], lpips)
+    return vals

@@ -576,26 +576,55 @@ def view_geo_host_stats():
     return int(calls.value), float(secs.value)
 
 
+def _images(pred_planar, gt_hwc, mask_hwc=None):
+    """pred[3,H,W] and gt[H,W,3] -- and, given, mask[H,W,3] -- of a metric-row call as float32 GPU tensors -> p, g, m, H, W"""
+    p = _req(pred_planar, torch.float32, "pred")
+    g = _req(gt_hwc, torch.float32, "gt")
+    m = _req(mask_hwc, torch.float32, "eval_mask") if mask_hwc is not None else None
+    _, H, W = p.shape
+    assert tuple(g.shape) == (H, W, 3) and (m is None or tuple(m.shape) == (H, W, 3)), (p.shape, g.shape, getattr(m, "shape", None))
+    return p, g, m, H, W
+
+
+def _min_size(what: str, H: int, W: int, n: int, limit: str) -> None:
+    if H < n or W < n:
+        raise ValueError(f"{what}: the image ({H} x {W}) is smaller than {limit}")
+
+
+def _lpips_weights(weights, device):
+    """the three packed buffers of a ``harness.LpipsAlex`` (on ``device``) as the C ABI takes them"""
+    cw, cb, lw = (_req(t, torch.float32, n) for t, n in ((weights.conv_weights, "conv_weights"), (weights.conv_biases, "conv_biases"),
+                                                         (weights.lin_weights, "lin_weights")))
+    assert cw.device == device, (cw.device, device)
+    return cw, cb, lw
+
+
+def _metric_row(name: str, nbytes: int, device, *args):
+    """The common tail of the metric-row entry points, which all end in (sums, workspace, workspace_bytes, stream): the
+    workspace query's answer ``nbytes`` (negative: raises with the library's message) rounded up to 64 bytes, ONE buffer
+    holding the workspace and then the eight doubles, and the call ``name(*args, ...)`` -> (the row float64[8], the buffer)."""
+    nws = int(nbytes)
+    if nws < 0:
+        _ws(nws, device)  # raises with the library's message
+    nws = (nws + 63) // 64 * 64
+    buf = torch.empty(nws + 64, dtype=torch.uint8, device=device)
+    sums = buf[nws:nws + 64].view(torch.float64)
+    check(getattr(_lib.load(), name)(*args, _ptr(sums), _ptr(buf), nws, _stream()), name)
+    return sums, buf
+
+
 def eval_psnr_sums(pred_planar, gt_hwc, mask_hwc, want_images: bool = False, count_dev=None, status_dev=None):
     """The evaluator's per-view statistics in one pass (``pgdvs_eval_psnr_sums``): pred[3,H,W] raw render, gt[H,W,3] raw,
     mask[H,W,3] -> device float64[8] (sum d2, sum d2 m, sum d2 (1-m), count, sum m, sum (1-m), then ``count_dev`` -- int64[1],
     -1 when None -- and ``status_dev`` -- int32[1], 0 when None -- as doubles, so that one transfer brings everything back)
     and, with ``want_images``, the quantised prediction / ground truth [3,H,W]."""
-    p = _req(pred_planar, torch.float32, "pred")
-    g = _req(gt_hwc, torch.float32, "gt")
-    m = _req(mask_hwc, torch.float32, "eval_mask")
-    _, H, W = p.shape
-    assert tuple(g.shape) == (H, W, 3) and tuple(m.shape) == (H, W, 3), (p.shape, g.shape, m.shape)
-    lib = _lib.load()
-    nws = int(lib.pgdvs_eval_psnr_workspace_bytes())
-    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # partials, then the eight doubles
-    sums = buf[nws:nws + 64].view(torch.float64)
+    p, g, m, H, W = _images(pred_planar, gt_hwc, mask_hwc)
     pq = torch.empty_like(p) if want_images else None
     gq = torch.empty_like(p) if want_images else None
     cd = _req(count_dev, torch.int64, "count_dev") if count_dev is not None else None
     sd = _req(status_dev, torch.int32, "status_dev") if status_dev is not None else None
-    check(lib.pgdvs_eval_psnr_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(pq), _ptr(gq), _ptr(cd), _ptr(sd), _ptr(sums), _ptr(buf), nws,
-                                   _stream()), "pgdvs_eval_psnr_sums")
+    sums, _ = _metric_row("pgdvs_eval_psnr_sums", _lib.load().pgdvs_eval_psnr_workspace_bytes(), p.device,
+                          _ptr(p), _ptr(g), _ptr(m), H, W, _ptr(pq), _ptr(gq), _ptr(cd), _ptr(sd))
     return sums, pq, gq
 
 
@@ -604,28 +633,17 @@ def eval_ssim_sums(pred_planar, gt_hwc, mask_hwc, want_map: bool = False):
     mask[H,W,3] -> device float64[8] (sum S, sum S m, sum S (1-m), count, sum m, sum (1-m), 0, 0 -- the layout of
     ``eval_psnr_sums``' row, so that ``read_back_rows`` brings both back in one transfer) and, with ``want_map``, the SSIM map
     S[3,H,W].  Raises ValueError when H or W is below the 7x7 window, as skimage does."""
-    p = _req(pred_planar, torch.float32, "pred")
-    g = _req(gt_hwc, torch.float32, "gt")
-    m = _req(mask_hwc, torch.float32, "eval_mask")
-    _, H, W = p.shape
-    assert tuple(g.shape) == (H, W, 3) and tuple(m.shape) == (H, W, 3), (p.shape, g.shape, m.shape)
-    if H < 7 or W < 7:
-        raise ValueError(f"eval_ssim_sums: the image ({H} x {W}) is smaller than SSIM's 7 x 7 window")
-    lib = _lib.load()
-    nws = int(lib.pgdvs_eval_ssim_workspace_bytes(H, W))
-    if nws < 0:
-        _ws(nws, p.device)  # raises with the library's message
-    nws = (nws + 63) // 64 * 64
-    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # partials, then the eight doubles
-    sums = buf[nws:nws + 64].view(torch.float64)
+    p, g, m, H, W = _images(pred_planar, gt_hwc, mask_hwc)
+    _min_size("eval_ssim_sums", H, W, 7, "SSIM's 7 x 7 window")
     smap = torch.empty_like(p) if want_map else None
-    check(lib.pgdvs_eval_ssim_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(smap), _ptr(sums), _ptr(buf), nws, _stream()),
-          "pgdvs_eval_ssim_sums")
+    sums, _ = _metric_row("pgdvs_eval_ssim_sums", _lib.load().pgdvs_eval_ssim_workspace_bytes(H, W), p.device,
+                          _ptr(p), _ptr(g), _ptr(m), H, W, _ptr(smap))
     return sums, smap
 
 
 LPIPS_CHANNELS = (64, 192, 384, 256, 256)  # AlexNet relu1..relu5
 LPIPS_MIN_SIZE = 31  # conv1 11x11/4 pad 2, then two 3/2 pools: relu5 is empty below this
+_LPIPS_LIMIT = "AlexNet's 31 x 31 minimum (relu5 would be empty)"
 
 
 def lpips_map_sizes(H: int, W: int):
@@ -659,25 +677,11 @@ def lpips_sums(pred_planar, gt_hwc, mask_hwc, weights, want_features: bool = Fal
     ``read_back_rows`` brings them all back in one transfer) and, with ``want_features``, relu1..relu5 of both images as
     [2,C,h,w] (ground truth first; views of the call's workspace).  Raises ValueError when H or W is below 31 (the relu5 map
     would be empty)."""
-    p = _req(pred_planar, torch.float32, "pred")
-    g = _req(gt_hwc, torch.float32, "gt")
-    m = _req(mask_hwc, torch.float32, "eval_mask")
-    _, H, W = p.shape
-    assert tuple(g.shape) == (H, W, 3) and tuple(m.shape) == (H, W, 3), (p.shape, g.shape, m.shape)
-    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
-        raise ValueError(f"lpips_sums: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
-    cw, cb, lw = (_req(t, torch.float32, n) for t, n in ((weights.conv_weights, "conv_weights"), (weights.conv_biases, "conv_biases"),
-                                                         (weights.lin_weights, "lin_weights")))
-    assert cw.device == p.device, (cw.device, p.device)
-    lib = _lib.load()
-    nws = int(lib.pgdvs_lpips_workspace_bytes(H, W))
-    if nws < 0:
-        _ws(nws, p.device)  # raises with the library's message
-    nws = (nws + 63) // 64 * 64
-    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # the network's maps and partials, then the eight doubles
-    sums = buf[nws:nws + 64].view(torch.float64)
-    check(lib.pgdvs_lpips_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw), _ptr(sums), _ptr(buf), nws, _stream()),
-          "pgdvs_lpips_sums")
+    p, g, m, H, W = _images(pred_planar, gt_hwc, mask_hwc)
+    _min_size("lpips_sums", H, W, LPIPS_MIN_SIZE, _LPIPS_LIMIT)
+    cw, cb, lw = _lpips_weights(weights, p.device)
+    sums, buf = _metric_row("pgdvs_lpips_sums", _lib.load().pgdvs_lpips_workspace_bytes(H, W), p.device,
+                            _ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw))
     return sums, (_lpips_features(buf, H, W) if want_features else None)
 
 
@@ -698,51 +702,25 @@ def dycheck_psnr_ssim_sums(pred_planar, gt_hwc, mask_hw1, count_dev=None, status
     sum d2 m, sum S full, 3HW, 3 sum m, sum S covisible, then ``count_dev`` -- -1 when None -- and ``status_dev`` -- 0 when
     None -- as in ``eval_psnr_sums``' row, so that ``read_back_rows`` brings it back with the others; include/pgdvs_hip.h).
     Raises ValueError when H or W is below the 11-tap window."""
-    p = _req(pred_planar, torch.float32, "pred")
-    g = _req(gt_hwc, torch.float32, "gt")
-    _, H, W = p.shape
-    assert tuple(g.shape) == (H, W, 3), (p.shape, g.shape)
+    p, g, _, H, W = _images(pred_planar, gt_hwc)
     m = _dycheck_mask(mask_hw1, H, W, "dycheck_psnr_ssim_sums")
-    if H < DYCHECK_SSIM_MIN_SIZE or W < DYCHECK_SSIM_MIN_SIZE:
-        raise ValueError(f"dycheck_psnr_ssim_sums: the image ({H} x {W}) is smaller than SSIM's 11 x 11 window")
-    lib = _lib.load()
-    nws = int(lib.pgdvs_dycheck_psnr_ssim_workspace_bytes(H, W))
-    if nws < 0:
-        _ws(nws, p.device)  # raises with the library's message
-    nws = (nws + 63) // 64 * 64
-    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # partials, then the eight doubles
-    sums = buf[nws:nws + 64].view(torch.float64)
+    _min_size("dycheck_psnr_ssim_sums", H, W, DYCHECK_SSIM_MIN_SIZE, "SSIM's 11 x 11 window")
     cd = _req(count_dev, torch.int64, "count_dev") if count_dev is not None else None
     sd = _req(status_dev, torch.int32, "status_dev") if status_dev is not None else None
-    check(lib.pgdvs_dycheck_psnr_ssim_sums(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cd), _ptr(sd), _ptr(sums), _ptr(buf), nws, _stream()),
-          "pgdvs_dycheck_psnr_ssim_sums")
-    return sums
+    return _metric_row("pgdvs_dycheck_psnr_ssim_sums", _lib.load().pgdvs_dycheck_psnr_ssim_workspace_bytes(H, W), p.device,
+                       _ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cd), _ptr(sd))[0]
 
 
 def dycheck_lpips(pred_planar, gt_hwc, mask_hw1, weights):
     """The DyCheck iPhone protocol's LPIPS of one view, full and covisible (``pgdvs_dycheck_lpips``): pred[3,H,W] raw render,
     gt[H,W,3] raw, mask[H,W,1], ``weights`` a ``harness.LpipsAlex`` on the same device -> device float64[8] (LPIPS full,
     LPIPS covisible, sum v, HW, sum v m, sum m, 0, 0; include/pgdvs_hip.h).  Raises ValueError when H or W is below 31."""
-    p = _req(pred_planar, torch.float32, "pred")
-    g = _req(gt_hwc, torch.float32, "gt")
-    _, H, W = p.shape
-    assert tuple(g.shape) == (H, W, 3), (p.shape, g.shape)
+    p, g, _, H, W = _images(pred_planar, gt_hwc)
     m = _dycheck_mask(mask_hw1, H, W, "dycheck_lpips")
-    if H < LPIPS_MIN_SIZE or W < LPIPS_MIN_SIZE:
-        raise ValueError(f"dycheck_lpips: the image ({H} x {W}) is smaller than AlexNet's 31 x 31 minimum (relu5 would be empty)")
-    cw, cb, lw = (_req(t, torch.float32, n) for t, n in ((weights.conv_weights, "conv_weights"), (weights.conv_biases, "conv_biases"),
-                                                         (weights.lin_weights, "lin_weights")))
-    assert cw.device == p.device, (cw.device, p.device)
-    lib = _lib.load()
-    nws = int(lib.pgdvs_dycheck_lpips_workspace_bytes(H, W))
-    if nws < 0:
-        _ws(nws, p.device)  # raises with the library's message
-    nws = (nws + 63) // 64 * 64
-    buf = torch.empty(nws + 64, dtype=torch.uint8, device=p.device)  # the network's maps and partials, then the eight doubles
-    sums = buf[nws:nws + 64].view(torch.float64)
-    check(lib.pgdvs_dycheck_lpips(_ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw), _ptr(sums), _ptr(buf), nws, _stream()),
-          "pgdvs_dycheck_lpips")
-    return sums
+    _min_size("dycheck_lpips", H, W, LPIPS_MIN_SIZE, _LPIPS_LIMIT)
+    cw, cb, lw = _lpips_weights(weights, p.device)
+    return _metric_row("pgdvs_dycheck_lpips", _lib.load().pgdvs_dycheck_lpips_workspace_bytes(H, W), p.device,
+                       _ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw))[0]
 
 
 def dycheck_depth_range(depth, dyn_mask, rays, inv_raw_c2w_tgt, inv_c2w_tgt, K_tgt, near, far, quantiles=None):
