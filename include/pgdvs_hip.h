@@ -542,6 +542,29 @@ int pgdvs_dycheck_depth_range(const void *depth, int depth_f64, const float *dyn
                               double far_v, float *depth_range, double *quantiles, void *workspace, int64_t workspace_bytes,
                               pgdvs_stream_t stream);
 
+/* ---- 8f-3 NVIDIA, the NVIDIA-family loaders' per-item depth range (pgdvs/datasets/nvidia_eval.py:446-456, nvidia_vis.py,
+ * mono_vis.py): the spatial sources' world points moved into the target camera, near = max(1e-16, 0.8 min z) and
+ * far = max(2e-16, 1.2 np.quantile(z, 0.9)).  Bit-identical to the loaders' numpy path (pgdvs_amd/datasets/nvidia_eval.py:
+ * depth_range_from_points over the concatenated compute_pcl of every view):
+ *   depth [V,H,W] float32
+ *   rays [V,12] float32: per view M = c2w[:3,:3] @ inv(K[:3,:3]) row-major and the origin c2w[:3,3], formed on the host as
+ *     compute_pcl forms them (nvidia_eval.ray_constants); d = fma(M[:,1], v, M[:,0] u) + M[:,2] (numpy's float32 BLAS order),
+ *     X = o + d depth rounded after the multiply and after the add
+ *   inv_c2w_tgt[16]: HOST doubles, numpy's float64 inverse of the target camera-to-world; z = row 2 of it @ [X,1] in float64
+ *   depth_range [2] float32 output (DEVICE); near_far: DEVICE double[2] (nullable) = the float64 (near, far) before the cast
+ * Products follow numpy's BLAS order (fused multiply-adds, k ascending; DESIGN.md 8f-3 DyCheck).  np.min and the quantile's
+ * two order statistics are exact (radix select on the order-preserving bit patterns, -0.0 counted as +0.0), combined by
+ * numpy's _lerp.  A NaN in z makes both NaN, so near / far become 1e-16 / 2e-16 (Python's max); infinite depths order as
+ * numpy orders them.
+ * V, H or W < 1, H W == 1 (a one-pixel view, which numpy unprojects as a matrix-vector product in another order), or
+ * V H W >= 2^31: PGDVS_ERR_INVALID, and the workspace query returns PGDVS_ERR_INVALID.
+ * workspace >= pgdvs_nvidia_depth_range_workspace_bytes(V,H,W): the keys (V H W x 8 bytes), the radix histograms and a
+ * small state block.  One stream, no host synchronisation. */
+int64_t pgdvs_nvidia_depth_range_workspace_bytes(int V, int H, int W);
+int pgdvs_nvidia_depth_range(const float *depth, const float *rays, int V, int H, int W, const double *inv_c2w_tgt,
+                             float *depth_range, double *near_far, void *workspace, int64_t workspace_bytes,
+                             pgdvs_stream_t stream);
+
 /* ---- one native call per target view -------------------------------------------------
  * PGDVSRenderer.forward with static_renderer = StaticGeoPointRenderer, dyn_render_type = "softsplat",
  * batch item of size 1, render_stride 1, no tracker (pgdvs/renderers/pgdvs_renderer.py:84-178 ->

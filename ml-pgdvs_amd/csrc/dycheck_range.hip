@@ -11,42 +11,21 @@
 //          (z + 1e-8), kept when 0 <= col <= W-1 and 0 <= row <= H-1 (no z > 0 test, as upstream), truncated, and the pixel
 //          keeps the largest flat index (numpy's fancy assignment: the last point wins) through atomicMax.
 // select   np.quantile(z, q, method="linear") for q = 0.1, 0.9: the two neighbouring ranks of each virtual index, found
-//          exactly by an MSB-first radix select over the keys (11-bit digits: 3 passes for float, 6 for double).  The four
-//          ranks run together: a histogram pass counts each key into the slot of the rank whose prefix it matches (ranks
-//          with equal prefixes share a slot, distinct prefixes are disjoint, so one LDS atomic per key at most), a one-block
-//          pass picks every rank's digit.  The last one interpolates with numpy's _lerp and clamps with near / far as
-//          Python's max / min compare.
+//          exactly by the shared radix select (radix_select.h: 3 passes for float, 6 for double, the four ranks together).
+//          The last select pass interpolates with numpy's _lerp and clamps with near / far as Python's max / min compare.
 // write    one thread per target pixel: the winning point's z -+ 1e-4 in T, or the constant range when no point hit it.
 #include <cmath>
 
 #include "common.h"
+#include "radix_select.h"
 
 namespace pgdvs {
 namespace {
 
-constexpr int kDigit = 11, kBins = 1 << kDigit, kRanks = 4, kBlock = 256;
-
-template <typename T> struct Key;
-template <> struct Key<float> {
-  typedef uint32_t U;
-  static constexpr int kBits = 32;
-  __device__ static U enc(float f) {
-    uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);  // -0.0 and +0.0 compare equal in numpy's partition
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  }
-  __device__ static float dec(U k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-};
-template <> struct Key<double> {
-  typedef uint64_t U;
-  static constexpr int kBits = 64;
-  __device__ static U enc(double f) {
-    uint64_t u = (uint64_t)__double_as_longlong(f == 0.0 ? 0.0 : f);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-  }
-  __device__ static double dec(U k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-  }
-};
+using radix::Key;
+using radix::kBins;
+using radix::kBlock;
+constexpr int kRanks = 4;
 
 __device__ __forceinline__ float fmaT(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fmaT(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -68,9 +47,7 @@ template <typename T> struct Params {
 };
 
 struct State {
-  unsigned long long prefix[kRanks];
-  uint32_t rem[kRanks];
-  int32_t slot[kRanks];
+  radix::Sel<kRanks> sel;
   uint32_t nan_seen;
   float lo32, hi32;
   double q[2];
@@ -126,126 +103,28 @@ __global__ void __launch_bounds__(kBlock) points_kernel(Params<T> p, typename Ke
   }
 }
 
-// every rank starts in slot 0 with an empty prefix (one shared first pass); remaining rank = the rank itself
 template <typename T> __global__ void init_kernel(Params<T> p, State *__restrict__ st) {
   if (threadIdx.x != 0) return;
-  for (int r = 0; r < kRanks; ++r) {
-    st->prefix[r] = 0;
-    st->rem[r] = (uint32_t)p.rank[r];
-    st->slot[r] = 0;
-  }
+  radix::sel_init<kRanks>(&st->sel, p.rank);
   st->nan_seen = 0;
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kBlock) hist_kernel(const typename Key<T>::U *__restrict__ keys, int64_t n, int pass,
-                                                      const State *__restrict__ st, uint32_t *__restrict__ hist) {
-  typedef typename Key<T>::U U;
-  __shared__ uint32_t h[kRanks][kBins];
-  for (int k = threadIdx.x; k < kRanks * kBins; k += kBlock) (&h[0][0])[k] = 0;
-  const int kb = Key<T>::kBits;
-  const int shift = kb - kDigit * (pass + 1) > 0 ? kb - kDigit * (pass + 1) : 0;
-  const int hs = kb - kDigit * pass;  // bits above this pass's digit: the prefix
-  bool act[kRanks];
-  U pre[kRanks];
-#pragma unroll
-  for (int r = 0; r < kRanks; ++r) {
-    act[r] = st->slot[r] == r;
-    pre[r] = (U)st->prefix[r];
-  }
-  __syncthreads();
-  const U dmask = (U)((1u << (hs - shift)) - 1u);
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const U k = keys[i];
-#pragma unroll
-    for (int r = 0; r < kRanks; ++r) {
-      if (act[r] && (pass == 0 || (k >> hs) == pre[r])) {
-        atomicAdd(&h[r][(int)((k >> shift) & dmask)], 1u);
-        break;
-      }
-    }
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < kRanks * kBins; k += kBlock) {
-    const uint32_t c = (&h[0][0])[k];
-    if (c) atomicAdd(&hist[k], c);
-  }
-}
-
-// numpy's _lerp: a + (b - a) t, or b - (b - a)(1 - t) where t >= 0.5 (all in T, no contraction)
-template <typename T> __device__ T lerp_np(T a, T b, T t) {
-  const T diff = b - a;
-  T r = a + diff * t;
-  if (t >= (T)0.5) r = b - diff * ((T)1 - t);
-  return r;
 }
 
 // one block, one wavefront per rank: pick this pass's digit of every rank; the last pass finishes the range
 template <typename T>
 __global__ void __launch_bounds__(kBlock) select_kernel(Params<T> p, int pass, int last_pass, State *__restrict__ st,
                                                         const uint32_t *__restrict__ hist) {
-  typedef typename Key<T>::U U;
-  const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int kb = Key<T>::kBits;
-  const int shift = kb - kDigit * (pass + 1) > 0 ? kb - kDigit * (pass + 1) : 0;
-  const int width = kb - kDigit * pass - shift;
-  const uint32_t *h = hist + (size_t)st->slot[r] * kBins;
-  const uint32_t rem = st->rem[r];
-  constexpr int kPer = kBins / 64;
-  uint32_t c = 0;
-  for (int b = 0; b < kPer; ++b) c += h[lane * kPer + b];
-  uint32_t incl = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  const uint32_t excl = incl - c;
-  const unsigned long long hit = __ballot(excl <= rem && rem < incl);
-  const int L = hit ? __builtin_ctzll(hit) : 63;  // always hit: rem < n = total count of the slot
-  int digit = 0;
-  uint32_t nrem = 0;
-  if (lane == L) {
-    uint32_t cum = excl;
-    for (int b = 0; b < kPer; ++b) {
-      const uint32_t hb = h[lane * kPer + b];
-      if (rem < cum + hb) {
-        digit = lane * kPer + b;
-        nrem = rem - cum;
-        break;
-      }
-      cum += hb;
-    }
-  }
-  digit = __shfl(digit, L, 64);
-  nrem = __shfl(nrem, L, 64);
-  __syncthreads();  // every wave has read the old state
-  if (lane == 0) {
-    const U old = pass == 0 ? (U)0 : (U)st->prefix[r];
-    st->prefix[r] = (unsigned long long)((old << width) | (U)digit);
-    st->rem[r] = nrem;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int a = 0; a < kRanks; ++a) {
-      int s = a;
-      for (int b = 0; b < a; ++b)
-        if (st->prefix[b] == st->prefix[a]) {
-          s = b;
-          break;
-        }
-      st->slot[a] = s;
-    }
-    if (pass == last_pass) {
-      T q[2];
-      for (int j = 0; j < 2; ++j)
-        q[j] = lerp_np(Key<T>::dec((U)st->prefix[2 * j]), Key<T>::dec((U)st->prefix[2 * j + 1]), p.gamma[j]);
-      if (st->nan_seen) q[0] = q[1] = (T)NAN;  // np.quantile returns NaN when z holds one
-      // Python's max(near, q) / min(far, q): q when q > near (resp. q < far), compared in T; else the bound
-      st->lo32 = q[0] > p.near_t ? (float)q[0] : p.near32;
-      st->hi32 = q[1] < p.far_t ? (float)q[1] : p.far32;
-      st->q[0] = (double)q[0];
-      st->q[1] = (double)q[1];
-    }
+  radix::select_digits<T, kRanks>(pass, &st->sel, hist);
+  if (threadIdx.x == 0 && pass == last_pass) {
+    T q[2];
+    for (int j = 0; j < 2; ++j)
+      q[j] = radix::lerp_np(radix::rank_value<T, kRanks>(&st->sel, 2 * j), radix::rank_value<T, kRanks>(&st->sel, 2 * j + 1),
+                            p.gamma[j]);
+    if (st->nan_seen) q[0] = q[1] = (T)NAN;  // np.quantile returns NaN when z holds one
+    // Python's max(near, q) / min(far, q): q when q > near (resp. q < far), compared in T; else the bound
+    st->lo32 = q[0] > p.near_t ? (float)q[0] : p.near32;
+    st->hi32 = q[1] < p.far_t ? (float)q[1] : p.far32;
+    st->q[0] = (double)q[0];
+    st->q[1] = (double)q[1];
   }
 }
 
@@ -281,25 +160,8 @@ Layout layout(int64_t n, int64_t hw, int key_bytes, int passes) {
   return l;
 }
 
-int passes_for(int key_bits) { return (key_bits + kDigit - 1) / kDigit; }
-
 bool shape_ok(int V, int H, int W) {
   return V > 0 && H > 0 && W > 0 && (int64_t)V * H * W < (1ll << 31);
-}
-
-// numpy's linear-method virtual index in T: (n - 1) q, the neighbours floor / floor + 1 (both the last element when the
-// index reaches n - 1), gamma = index - floor (numpy forms it in float64, then casts to T)
-template <typename T> void quantile_setup(int64_t n, T q, int64_t &a, int64_t &b, T &gamma) {
-  const T vi = (T)(n - 1) * q;
-  if (vi >= (T)(n - 1)) {
-    a = b = n - 1;
-    gamma = (T)((double)vi + 1.0);
-    return;
-  }
-  const T prev = std::floor(vi);
-  a = (int64_t)prev;
-  b = (int64_t)(prev + (T)1);
-  gamma = (T)((double)vi - (double)a);
 }
 
 template <typename T>
@@ -308,7 +170,7 @@ int run(const void *depth, const float *dyn_mask, const float *rays, int V, int 
         void *workspace, int64_t workspace_bytes, hipStream_t st) {
   typedef typename Key<T>::U U;
   const int64_t n = (int64_t)V * H * W, hw = (int64_t)H * W;
-  const int passes = passes_for(Key<T>::kBits);
+  const int passes = radix::passes_for(Key<T>::kBits);
   const Layout l = layout(n, hw, (int)sizeof(U), passes);
   if (!workspace || workspace_bytes < l.total) {
     set_error("pgdvs_dycheck_depth_range: workspace too small (%lld < %lld)", (long long)workspace_bytes, (long long)l.total);
@@ -325,8 +187,8 @@ int run(const void *depth, const float *dyn_mask, const float *rays, int V, int 
   for (int c = 0; c < 4; ++c) p.A2[c] = (T)inv_raw_c2w_tgt[8 + c];
   for (int k = 0; k < 12; ++k) p.B[k] = (T)inv_c2w_tgt[k];
   for (int k = 0; k < 9; ++k) p.K[k] = (T)K_tgt[k];
-  quantile_setup<T>(n, (T)0.1, p.rank[0], p.rank[1], p.gamma[0]);
-  quantile_setup<T>(n, (T)0.9, p.rank[2], p.rank[3], p.gamma[1]);
+  radix::quantile_setup<T>(n, (T)0.1, p.rank[0], p.rank[1], p.gamma[0]);
+  radix::quantile_setup<T>(n, (T)0.9, p.rank[2], p.rank[3], p.gamma[1]);
   p.near_t = (T)near_v;
   p.far_t = (T)far_v;
   p.near32 = (float)near_v;
@@ -344,10 +206,11 @@ int run(const void *depth, const float *dyn_mask, const float *rays, int V, int 
   }
   PGDVS_LAUNCH("dycheck_range_init", init_kernel<T>, dim3(1), dim3(64), 0, st, p, state);
   PGDVS_LAUNCH("dycheck_range_points", points_kernel<T>, dim3((unsigned)cdiv(n, kBlock)), dim3(kBlock), 0, st, p, keys, last, state);
-  const unsigned hgrid = (unsigned)std::min<int64_t>(cdiv(n, kBlock * 16), 1024);
+  const unsigned hgrid = radix::hist_grid(n);
   for (int pass = 0; pass < passes; ++pass) {
     uint32_t *hp = hist + (size_t)pass * kRanks * kBins;
-    PGDVS_LAUNCH("dycheck_range_hist", hist_kernel<T>, dim3(hgrid), dim3(kBlock), 0, st, keys, n, pass, state, hp);
+    PGDVS_LAUNCH("dycheck_range_hist", (radix::hist_kernel<T, kRanks>), dim3(hgrid), dim3(kBlock), 0, st, keys, n, pass,
+                 &state->sel, hp);
     PGDVS_LAUNCH("dycheck_range_select", select_kernel<T>, dim3(1), dim3(kBlock), 0, st, p, pass, passes - 1, state, hp);
   }
   PGDVS_LAUNCH("dycheck_range_write", write_kernel<T>, dim3((unsigned)cdiv(hw, kBlock)), dim3(kBlock), 0, st, p, last, state, out);
@@ -372,7 +235,7 @@ PGDVS_API int64_t pgdvs_dycheck_depth_range_workspace_bytes(int V, int H, int W,
     return PGDVS_ERR_INVALID;
   }
   const int kbits = depth_f64 ? 64 : 32;
-  return layout((int64_t)V * H * W, (int64_t)H * W, kbits / 8, passes_for(kbits)).total;
+  return layout((int64_t)V * H * W, (int64_t)H * W, kbits / 8, radix::passes_for(kbits)).total;
 }
 
 PGDVS_API int pgdvs_dycheck_depth_range(const void *depth, int depth_f64, const float *dyn_mask, const float *rays, int V, int H,

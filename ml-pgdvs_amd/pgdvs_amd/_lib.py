@@ -108,6 +108,8 @@ SIGNATURES.update({
     "pgdvs_dycheck_depth_range_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "pgdvs_dycheck_depth_range": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp, _i64,
                                        _vp]),
+    "pgdvs_nvidia_depth_range_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pgdvs_nvidia_depth_range": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

@@ -1,7 +1,6 @@
 """Mirror of ``pgdvs.datasets.combined.CombinedDataset`` (pgdvs/datasets/combined.py:31-80): one index space
 over the datasets named in ``dataset_list[mode]``, in sorted-name order so that every worker sees the same
-order.  Loaders mirrored here are used directly; the one that is out of scope (``nvidia_vis``) resolves to the
-reference's own class when that package is importable."""
+order.  Every loader the reference's evaluation and visualisation runs use is mirrored here."""
 import bisect
 import importlib
 
@@ -10,25 +9,17 @@ from torch.utils.data import Dataset
 _MIRRORED = {
     "nvidia_eval": ("pgdvs_amd.datasets.nvidia_eval", "NvidiaDynEvaluationDataset"),
     "nvidia_eval_pure_geo": ("pgdvs_amd.datasets.nvidia_eval", "NvidiaDynPureGeoEvaluationDataset"),
+    "nvidia_vis": ("pgdvs_amd.datasets.nvidia_vis", "NvidiaDynVisualizationDataset"),
     "mono_vis": ("pgdvs_amd.datasets.mono_vis", "MonoVisualizationDataset"),
     "dycheck_iphone_eval": ("pgdvs_amd.datasets.dycheck_iphone", "DyCheckiPhoneEvaluationDataset"),
-}
-_UPSTREAM = {
-    "nvidia_vis": ("pgdvs.datasets.nvidia_vis", "NvidiaDynVisualizationDataset"),
 }
 
 
 def dataset_class(name: str):
-    if name in _MIRRORED:
-        mod, cls = _MIRRORED[name]
-    elif name in _UPSTREAM:
-        mod, cls = _UPSTREAM[name]
-    else:
-        raise KeyError(f"unknown dataset {name!r}; known: {sorted(_MIRRORED) + sorted(_UPSTREAM)}")
-    try:
-        return getattr(importlib.import_module(mod), cls)
-    except ImportError as e:
-        raise ImportError(f"dataset {name!r} is not mirrored in pgdvs_amd and the reference package is not importable ({e})") from e
+    if name not in _MIRRORED:
+        raise KeyError(f"unknown dataset {name!r}; known: {sorted(_MIRRORED)}")
+    mod, cls = _MIRRORED[name]
+    return getattr(importlib.import_module(mod), cls)
 
 
 class CombinedDataset(Dataset):

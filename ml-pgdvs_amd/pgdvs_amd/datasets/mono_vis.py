@@ -13,7 +13,8 @@ small circular "bullet-time" offset whose radius follows the scene's near depth
 (``nvidia_vis.py:692-722``).
 
 Host-side numpy / PIL input plumbing, like ``datasets/nvidia_eval.py``; resizes that upstream
-does with OpenCV (only taken when files differ in size) use PIL filters.
+does with OpenCV (only taken when files differ in size) use PIL filters.  ``depth_range`` comes from
+``nvidia_eval.spatial_depth_range``: numpy with ``device=None``, the HIP op on a GPU ``device``.
 """
 import pathlib
 from math import acos, sin
@@ -23,7 +24,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from .nvidia_eval import _resize, compute_pcl, depth_range_from_points, read_flow_npz
+from .nvidia_eval import _resize, read_flow_npz, spatial_depth_range
 
 N_BT_REPS = 8
 
@@ -73,13 +74,14 @@ def bullet_time_offsets(focal, num_frames, sc, max_disp):
     return poses
 
 
-def render_path(all_K, all_c2w, near_depths, *, vis_center_time, n_render_frames, vis_time_interval, vis_bt_max_disp):
-    """[(time, index, c2w)] of the visualisation cameras of one scene (:113-197)"""
-    n = all_K.shape[0]
+def render_path(focal, all_c2w, near_depths, *, vis_center_time, n_render_frames, vis_time_interval, vis_bt_max_disp):
+    """[(time, index, c2w)] of the visualisation cameras of one scene (:113-197; nvidia_vis.py:158-260): ``focal`` sizes the
+    bullet-time offsets, ``near_depths`` their scale"""
+    n = all_c2w.shape[0]
     times = np.linspace(max(0, vis_center_time - vis_time_interval), min(n - 2, vis_center_time + vis_time_interval),
                         n_render_frames).tolist()
     bt_sc = 1.0 / (np.percentile(near_depths, 5) * 0.9)
-    offsets = bullet_time_offsets(all_K[0, 0, 0], len(times) // N_BT_REPS, bt_sc, vis_bt_max_disp) * (N_BT_REPS + 1)
+    offsets = bullet_time_offsets(focal, len(times) // N_BT_REPS, bt_sc, vis_bt_max_disp) * (N_BT_REPS + 1)
     path = []
     for i, t in enumerate(times):
         t0 = int(np.floor(t))
@@ -112,13 +114,14 @@ class MonoVisualizationDataset(Dataset):
 
     def __init__(self, *, data_root, max_hw, mode, rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
-                 vis_bt_max_disp=32, flow_consist_thres=1.0):
+                 vis_bt_max_disp=32, flow_consist_thres=1.0, device=None):
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
         self.n_src_views_spatial = n_src_views_spatial
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
+        self.depth_device = None if device is None else torch.device(device)
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
         self.c2w_dict, self.K_dict, self.valid_fs = {}, {}, []
@@ -128,7 +131,7 @@ class MonoVisualizationDataset(Dataset):
             all_K, all_c2w = np.array([c["K"] for c in cams]), np.array([c["c2w"] for c in cams])
             near = np.array([np.percentile(np.load(f)["depth"].reshape(-1), 5) for f in sorted((sd / "depths").glob("*.npz"))])
             self.c2w_dict[scene], self.K_dict[scene] = all_c2w.copy(), all_K.copy()
-            for t, i, c2w in render_path(all_K, all_c2w, near, vis_center_time=vis_center_time, n_render_frames=n_render_frames,
+            for t, i, c2w in render_path(all_K[0, 0, 0], all_c2w, near, vis_center_time=vis_center_time, n_render_frames=n_render_frames,
                                          vis_time_interval=vis_time_interval, vis_bt_max_disp=vis_bt_max_disp):
                 self.valid_fs.append([scene, sd, t, i, c2w, 1.0])
 
@@ -144,11 +147,11 @@ class MonoVisualizationDataset(Dataset):
         depth = _resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
         flat_cam = np.concatenate(([h, w], np.asarray(K).flatten(), np.asarray(c2w).flatten())).astype(np.float32)
         return {"rgb": rgb, "flat_cam": flat_cam, "dyn_mask": mask, "depth": depth, "dyn_rgb": rgb * mask[..., None],
-                "static_rgb": rgb * (1 - mask[..., None]), "pcl": compute_pcl(h, w, K, c2w, depth)}
+                "static_rgb": rgb * (1 - mask[..., None]), "K": np.asarray(K), "c2w": np.asarray(c2w)}
 
     def _stack_views(self, scene_dir, img_fs, frame_ids, all_c2w, all_K, tgt_shape):
         views = [self._source_view(scene_dir, img_fs[f], all_c2w[f], all_K[f], tgt_shape) for f in frame_ids]
-        return {k: (np.concatenate if k == "pcl" else np.stack)([v[k] for v in views], axis=0) for k in views[0]}
+        return {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
 
     def _read_flow(self, scene_dir, img_fs, a, b, tgt_shape):
         if a == b:
@@ -189,7 +192,7 @@ class MonoVisualizationDataset(Dataset):
             "flat_cam_tgt": F32(np.concatenate(([tgt_h, tgt_w], all_K[0].flatten(), tgt_c2w.flatten()))),
             "flat_cam_src_spatial": F32(spatial["flat_cam"]), "flat_cam_src_temporal": F32(temporal["flat_cam"]),
             "depth_src_temporal": F32(temporal["depth"])[..., None],
-            "depth_range": F32(depth_range_from_points(spatial["pcl"], tgt_c2w)),
+            "depth_range": spatial_depth_range(spatial, tgt_c2w, self.depth_device, type(self).__name__),
             "time_tgt": torch.FloatTensor([tgt_time]), "time_src_temporal": torch.FloatTensor(sel["temporal"]),
             "misc": {"scene_id": scene_id, "tgt_time": tgt_time, "tgt_idx": tgt_idx},
         }

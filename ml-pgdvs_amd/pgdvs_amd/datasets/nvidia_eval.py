@@ -16,6 +16,10 @@ differs from the 288-row target) use PIL's BOX / NEAREST filters.
 
 The pure-geometry variant builds the static cloud once per scene with the HIP aggregator
 (``aggregate_static_pcl``) instead of upstream's numpy loop.
+
+The per-item ``depth_range`` (:446-456) is computed in numpy with ``device=None``; with a GPU ``device`` by the HIP op
+``ops.nvidia_depth_range``, bit-identical (DESIGN.md, row 8f-3 NVIDIA), and then no host point cloud is formed.  The
+point clouds upstream computes for the temporal and tracker views and then discards are skipped on both paths.
 """
 import pathlib
 from collections import defaultdict
@@ -92,14 +96,19 @@ def select_spatial_frames(tgt_frame_id, tgt_cam_id, n_frames, c2w_all, n_views):
     return sorted(pool[i] for i in order[:n_views])
 
 
+def ray_constants(K, c2w):
+    """float32 (M = c2w[:3,:3] @ inv(K[:3,:3]), o = c2w[:3,3]) of one view, as compute_pcl forms them"""
+    K32, c32 = np.asarray(K, np.float32), np.asarray(c2w, np.float32)
+    return c32[:3, :3] @ np.linalg.inv(K32[:3, :3]).astype(np.float32), c32[:3, 3]
+
+
 def compute_pcl(h, w, K, c2w, depth):
     """_compute_pcl (:840-847): fp32 rays through integer pixel centres times z-depth."""
-    K32, c32 = np.asarray(K, np.float32), np.asarray(c2w, np.float32)
+    M, o = ray_constants(K, c2w)
     u, v = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
     pix = np.stack([u.reshape(-1), v.reshape(-1), np.ones(h * w, np.float32)], 0)
-    M = c32[:3, :3] @ np.linalg.inv(K32[:3, :3]).astype(np.float32)
     rays_d = (M @ pix).T
-    return c32[:3, 3][None, :] + rays_d * np.asarray(depth, np.float32).reshape(-1, 1)
+    return o[None, :] + rays_d * np.asarray(depth, np.float32).reshape(-1, 1)
 
 
 def depth_range_from_points(pcl_world, c2w_tgt):
@@ -108,6 +117,25 @@ def depth_range_from_points(pcl_world, c2w_tgt):
     homo = np.pad(pcl_world, ((0, 0), (0, 1)), "constant", constant_values=1)
     z = (np.linalg.inv(c2w_tgt) @ homo.T).T[:, 2]
     return np.array([max(1e-16, 0.8 * np.min(z)), max(2e-16, 1.2 * np.quantile(z, 0.9))])
+
+
+def spatial_depth_range(views, c2w_tgt, device=None, owner="NvidiaDynEvaluationDataset"):
+    """float32 depth_range[2] of the stacked spatial ``views`` (depth[V,H,W], K[V,4,4], c2w[V,4,4]) seen from ``c2w_tgt``:
+    depth_range_from_points over every view's compute_pcl with ``device=None``, else ``ops.nvidia_depth_range`` on that
+    device (bit-identical; no host points)"""
+    depths, Ks, c2ws = views["depth"], views["K"], views["c2w"]
+    h, w = depths.shape[1:3]
+    if device is None:
+        pcl = np.concatenate([compute_pcl(h, w, K, c2w, d) for K, c2w, d in zip(Ks, c2ws, depths)], axis=0)
+        return torch.from_numpy(np.ascontiguousarray(depth_range_from_points(pcl, c2w_tgt), dtype=np.float32))
+    if torch.utils.data.get_worker_info() is not None:
+        raise RuntimeError(f"{owner}(device=...) computes depth_range on the GPU, which forked DataLoader workers must not "
+                           "touch: use n_dataloader_workers=0 (or device=None)")
+    from .. import ops
+
+    rays = np.stack([np.concatenate([M.reshape(-1), o]) for M, o in (ray_constants(K, c2w) for K, c2w in zip(Ks, c2ws))])
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)  # noqa: E731
+    return ops.nvidia_depth_range(T(depths), T(rays), np.linalg.inv(c2w_tgt)).cpu()
 
 
 def _resize(arr, h, w, resample):
@@ -124,7 +152,7 @@ class NvidiaDynEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
-                 flow_consist_thres=1.0):
+                 flow_consist_thres=1.0, device=None):
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -135,6 +163,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_spatial = n_src_views_spatial
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
+        self.depth_device = None if device is None else torch.device(device)
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.depth_data_dir = root / raw_data_dir, root / depth_data_dir
         self.mask_data_dir, self.flow_data_dir = root / mask_data_dir, root / flow_data_dir
@@ -204,27 +233,37 @@ class NvidiaDynEvaluationDataset(Dataset):
         return raw
 
     # ------------------------------------------------------------------ one source view
+    def _aug_c2w(self, c2w):
+        """the camera-to-world of _compute_cam_info (:947-955); upstream's augment_cam("none") inverts twice, which this
+        loader's fixture does not see"""
+        return c2w
+
+    def _src_img_f(self, scene_id, frame_id):
+        """Frame i of the monocular video is camera i % 12 of time step i (:647-653)."""
+        return self.scene_img_dict[scene_id][frame_id][frame_id % N_CAMS]
+
     def _source_view(self, scene_id, frame_id, c2w, hwf, tgt_shape, with_geometry=True, img_f=None):
-        """image, flat camera and (optionally) dynamic mask / depth / world points of an input
-        frame (:728-838).  Frame i of the monocular video is camera i % 12 of time step i."""
+        """image, flat camera and (optionally) dynamic mask / depth / camera matrices of an input
+        frame (:728-838); spatial_depth_range makes the world points from depth, K and c2w."""
         h, w = tgt_shape
         if img_f is None:
-            img_f = self.scene_img_dict[scene_id][frame_id][frame_id % N_CAMS]
+            img_f = self._src_img_f(scene_id, frame_id)
         rgb = _resize(np.array(PIL.Image.open(img_f)), h, w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0
         K = np.eye(4)
         K[:3, :3] = hwf_to_K(*hwf, tgt_shape=tgt_shape)
+        c2w = self._aug_c2w(np.asarray(c2w))
         flat_cam = np.concatenate(([h, w], K.flatten(), np.asarray(c2w).flatten())).astype(np.float32)
         out = {"rgb": rgb, "flat_cam": flat_cam}
         if with_geometry:
             mask = self._read_mask(scene_id, frame_id, h, w).astype(np.float32)
             depth = _resize(self._read_depth(scene_id, frame_id), h, w, PIL.Image.Resampling.NEAREST)
             out.update(dyn_mask=mask, depth=depth, dyn_rgb=rgb * mask[..., None], static_rgb=rgb * (1 - mask[..., None]),
-                       pcl=compute_pcl(h, w, K, c2w, depth))
+                       K=K, c2w=c2w)
         return out
 
     def _stack_views(self, scene_id, frame_ids, all_c2w, all_hwf, tgt_shape):
         views = [self._source_view(scene_id, f, all_c2w[f], all_hwf[f], tgt_shape) for f in frame_ids]
-        return {k: (np.concatenate if k == "pcl" else np.stack)([v[k] for v in views], axis=0) for k in views[0]}
+        return {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
 
     # ------------------------------------------------------------------ item
     def _common_item(self, index):
@@ -274,7 +313,7 @@ class NvidiaDynEvaluationDataset(Dataset):
             "rgb_src_spatial": F32(spatial["rgb"]), "dyn_rgb_src_spatial": F32(spatial["dyn_rgb"]),
             "static_rgb_src_spatial": F32(spatial["static_rgb"]), "dyn_mask_src_spatial": F32(spatial["dyn_mask"])[..., None],
             "flat_cam_src_spatial": F32(spatial["flat_cam"]), "depth_src_spatial": F32(spatial["depth"])[..., None],
-            "depth_range": F32(depth_range_from_points(spatial["pcl"], c["all_c2w"][c["tgt_cam_id"]])),
+            "depth_range": spatial_depth_range(spatial, c["all_c2w"][c["tgt_cam_id"]], self.depth_device, type(self).__name__),
         })
         for side, key in (("fwd2tgt", "n_actual_fwd2tgt"), ("bwd2tgt", "n_actual_bwd2tgt")):
             tr = self._stack_views(scene_id, sel[side], c["all_c2w"], c["all_hwf"], c["tgt_shape"])

@@ -753,6 +753,31 @@ def dycheck_depth_range(depth, dyn_mask, rays, inv_raw_c2w_tgt, inv_c2w_tgt, K_t
     return out
 
 
+
+def nvidia_depth_range(depth, rays, inv_c2w_tgt, near_far=None):
+    """The NVIDIA-family loaders' per-item depth range (``pgdvs_nvidia_depth_range``; include/pgdvs_hip.h): depth[V,H,W]
+    float32 on the GPU, rays[V,12] float32 on the GPU (per view ``M`` row-major and the origin, as
+    ``datasets.nvidia_eval.ray_constants`` forms them), the target's numpy float64 ``inv_c2w_tgt[4,4]`` -> depth_range[2]
+    float32 on the GPU = (max(1e-16, 0.8 min z), max(2e-16, 1.2 np.quantile(z, 0.9))), bit-identical to
+    ``depth_range_from_points`` over the views' ``compute_pcl``.  ``near_far``: optional device float64[2] that receives the
+    float64 pair before the cast.  One-pixel views (H W == 1) are rejected."""
+    d = _req(depth, torch.float32, "depth")
+    r = _req(rays, torch.float32, "rays")
+    if d.ndim != 3 or tuple(r.shape) != (d.shape[0], 12):
+        raise ValueError(f"nvidia_depth_range: shapes depth {tuple(d.shape)}, rays {tuple(r.shape)}")
+    V, H, W = (int(x) for x in d.shape)
+    a = np.ascontiguousarray(np.asarray(inv_c2w_tgt), dtype=np.float64).reshape(-1)
+    assert a.size == 16, a.shape
+    mat = (C.c_double * 16)(*a.tolist())
+    if near_far is not None:
+        assert near_far.is_cuda and near_far.dtype == torch.float64 and near_far.numel() >= 2 and near_far.is_contiguous()
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_nvidia_depth_range_workspace_bytes(V, H, W), d.device)
+    out = torch.empty((2,), dtype=torch.float32, device=d.device)
+    check(lib.pgdvs_nvidia_depth_range(_ptr(d), _ptr(r), V, H, W, mat, _ptr(out), _ptr(near_far), _ptr(ws), ws.numel(),
+                                       _stream()), "pgdvs_nvidia_depth_range")
+    return out
+
 _pinned_sums = {}
 
 
