@@ -658,6 +658,23 @@ int pgdvs_view_geo_counters(const pgdvs_view_geo_desc *desc, const void *workspa
  * wall-clock seconds spent inside them (bench.py's host_enqueue figure); resets both. */
 void pgdvs_view_geo_host_stats(int64_t *calls, double *seconds);
 
+/* ---- visualiser export ---------------------------------------------------- */
+/* The visualiser's two image writers (pgdvs/engines/visualizer_pgdvs.py:118-139) up to the deflate: img_planar[B,3,H,W] ->
+ * out[B,H,1+3W] uint8, per row one PNG filter-type byte and then 3 W bytes R G B R G B ... (8-bit truecolour), ready for
+ * zlib and an IDAT chunk.  One streaming pass (csrc/png.hip): no workspace, no atomics; rows are independent.
+ *   quant     the image is clamped to [0, 1] first, as the visualiser does, then
+ *             0  x.mul(255).add_(0.5).clamp_(0, 255).to(uint8) -- torchvision.utils.save_image (*_combined.png): a float32
+ *                multiply and a float32 add, rounded separately, then truncation
+ *             1  (x * 255).astype(uint8) -- the numpy cast of *_gnt.png: float32 multiply, truncation
+ *             NaN gives 0 in both (upstream casts NaN to uint8, which is undefined: no value to match); +inf 255, -inf 0.
+ *   adaptive  0  filter type 0 on every row: out[..., 1:] is the packed [H,W,3] uint8 image
+ *             1  per row the PNG specification's filter (None, Sub, Up, Average, Paeth; bytes per pixel 3) with the least
+ *                sum over the filtered bytes of v < 128 ? v : 256 - v (libpng's default heuristic), the lowest type number
+ *                on a tie.  Integer sums: bit-exact whatever the reduction order.
+ * out needs no alignment.  Shapes: B, H, W >= 1 and B H (1 + 3 W) < 2^31, else PGDVS_ERR_INVALID. */
+int pgdvs_png_scanlines(const float *img_planar, int B, int H, int W, int quant, int adaptive, uint8_t *out,
+                        pgdvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

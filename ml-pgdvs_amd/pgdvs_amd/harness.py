@@ -335,6 +335,30 @@ DYCHECK_LPIPS_KEYS = ("lpips_combined", "mlpips_combined")  # ... and lpips=Lpip
 STAGE_SECONDS = None
 
 
+def _check_geo_status(ret, data_gpu, host_counts=None, host_status=None):
+    """Device-side status words of the geometry path (eval_step and vis_step wait for the GPU anyway): a static cloud whose
+    aggregation reported an error (count -1), filled its buffer (rows may have been dropped: the aggregation clamps at its
+    capacity) or outgrew the rasteriser's row bound would otherwise show up as a silently blank or truncated static image.
+    host_counts / host_status: the words as eval_step already read them back with its metric sums."""
+    from . import ops
+
+    cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
+    if isinstance(cnts, torch.Tensor):
+        cloud = ret.get("st_pcl_rgb", None)
+        values = host_counts if host_counts is not None else [int(c.item()) for c in cnts.reshape(-1)]
+        for n in values:
+            if n < 0:
+                raise ops.PgdvsHipError(f"st_pcl_rgb_count: device-side error flag set (count {n}); the output is not valid")
+            limited = cloud is not None and "_st_pcl_video" in data_gpu and cloud.shape[1] < data_gpu["_st_pcl_video"]["depths"].numel()
+            if limited and n >= cloud.shape[1]:
+                raise ops.PgdvsHipError(f"the aggregated static cloud filled its buffer of {cloud.shape[1]} rows (capacity-limited): "
+                                        "rows may have been dropped -- pass a larger capacity")
+    if host_status is not None:
+        ops.check_raster_status(torch.tensor(host_status, dtype=torch.int32))
+    else:
+        ops.check_raster_status(ret.get("geo_static_raster_status", None))
+
+
 @torch.no_grad()
 def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False, with_ssim=False,
               lpips=None, quant_type="nvidia"):
@@ -377,25 +401,7 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
     from . import ops
 
     def check_status(host_counts=None, host_status=None):
-        # device-side status words of the geometry path (the step synchronises for its metrics anyway): a static cloud whose
-        # aggregation reported an error (count -1), filled its buffer (rows may have been dropped: the aggregation clamps
-        # at its capacity) or outgrew the rasteriser's row bound would otherwise show up as a silently blank or truncated
-        # static image.  host_counts / host_status: the words as already read back with the metric sums.
-        cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
-        if isinstance(cnts, torch.Tensor):
-            cloud = ret.get("st_pcl_rgb", None)
-            values = host_counts if host_counts is not None else [int(c.item()) for c in cnts.reshape(-1)]
-            for n in values:
-                if n < 0:
-                    raise ops.PgdvsHipError(f"st_pcl_rgb_count: device-side error flag set (count {n}); the output is not valid")
-                limited = cloud is not None and "_st_pcl_video" in data_gpu and cloud.shape[1] < data_gpu["_st_pcl_video"]["depths"].numel()
-                if limited and n >= cloud.shape[1]:
-                    raise ops.PgdvsHipError(f"the aggregated static cloud filled its buffer of {cloud.shape[1]} rows (capacity-limited): "
-                                            "rows may have been dropped -- pass a larger capacity")
-        if host_status is not None:
-            ops.check_raster_status(torch.tensor(host_status, dtype=torch.int32))
-        else:
-            ops.check_raster_status(ret.get("geo_static_raster_status", None))
+        _check_geo_status(ret, data_gpu, host_counts, host_status)
 
     comb, gt, em = ret["combined_rgb"], data_gpu["rgb_tgt"], data_gpu["eval_mask"]
     if quant_type == "dycheck_iphone":
@@ -523,3 +529,94 @@ def _dycheck_view(g, p, mask, with_ssim, lpips):
     if lpips is not None:
         vals += _lpips_dycheck_torch(g, p, [ones, m], lpips)
     return vals
+
+
+# ---- the visualiser's loop (pgdvs/engines/visualizer_pgdvs.py:29-152) ----------------------------------------------------
+def _view_scanlines(img: torch.Tensor, quant: str):
+    """img[B,3,H,W] -> scanlines [B,H,1+3W] uint8: one HIP pass on a GPU float32 image (csrc/png.hip), png.py's torch / numpy
+    path otherwise"""
+    from . import png
+
+    if img.is_cuda and img.dtype == torch.float32:
+        from . import ops
+
+        return ops.png_scanlines(img, quant=quant, adaptive=True)
+    return png.filter_scanlines(png.QUANTIZERS[quant](img).permute(0, 2, 3, 1).contiguous().cpu(), adaptive=True)
+
+
+@torch.no_grad()
+def vis_step(model, data: dict, render_cfg, vis_dir, *, device=None, writer=None, disable_tqdm=True, return_ret=False):
+    """The body of ``PGDVSVisualizer.vis_model``'s loop for one batch: to-device, ``forward`` under no_grad, the geometry
+    path's status words checked as ``eval_step`` checks them, then per view ``vis_dir / split / scene_id /
+    {tgt_idx:05d}_combined.png`` from ``combined_rgb`` (``torchvision.utils.save_image``'s quantisation) and, when the
+    renderer returns ``static_coarse_rgb``, ``{tgt_idx:05d}_gnt.png`` from it (the truncating cast).  ``writer``: a
+    ``png.PngWriter`` that copies, deflates and writes behind this thread (the files are complete once it is closed);
+    without one the step writes each file before it returns.  Returns the paths (and ``ret`` with ``return_ret``)."""
+    import pathlib
+
+    from . import png
+
+    device = device if device is not None else next(iter(v for v in data.values() if isinstance(v, torch.Tensor))).device
+    data_gpu = to_device(data, device)
+    if model.training:
+        model.eval()
+    ret = model.forward(data_gpu, render_cfg=render_cfg, disable_tqdm=disable_tqdm, for_debug=False)
+    outputs = [("combined", ret["combined_rgb"], "save_image")]
+    if "static_coarse_rgb" in ret:  # the pure GNT result (:127-139)
+        outputs.append(("gnt", ret["static_coarse_rgb"], "truncate"))
+    lines = [(tag, _view_scanlines(img, quant), int(img.shape[2]), int(img.shape[3])) for tag, img, quant in outputs]
+    _check_geo_status(ret, data_gpu)
+    paths = []
+    misc = data["misc"]
+    for i_b in range(ret["combined_rgb"].shape[0]):
+        scene_dir = pathlib.Path(vis_dir) / misc[i_b].get("split", "") / misc[i_b]["scene_id"]
+        scene_dir.mkdir(parents=True, exist_ok=True)
+        for tag, scan, h, w in lines:
+            path = scene_dir / f"{misc[i_b]['tgt_idx']:05d}_{tag}.png"
+            if writer is not None:
+                writer.submit(path, scan[i_b])
+            else:
+                png.write_file(path, scan[i_b].cpu().numpy() if isinstance(scan, torch.Tensor) else scan[i_b], h, w)
+            paths.append(path)
+    return (paths, ret) if return_ret else paths
+
+
+def collate(batch: list) -> dict:
+    """``default_collate_fn`` (pgdvs/engines/abstract.py:18-30): tensors stacked, floats and lists of floats to a tensor,
+    everything else a list"""
+    def combine(values):
+        if isinstance(values[0], torch.Tensor):
+            return torch.stack(values, dim=0)
+        if isinstance(values[0], float) or (isinstance(values[0], list) and len(values[0]) > 0 and isinstance(values[0][0], float)):
+            return torch.Tensor(values)
+        return values
+
+    return {k: combine([x[k] for x in batch]) for k in batch[0].keys()}
+
+
+def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, writer=None):
+    """``vis_model``'s outer loop without Hydra: this rank's items in ``DistributedSampler(shuffle=False)`` order
+    (``dist.shard_indices``), ``batch_size`` of them per step (the per-process batch size), collated as upstream collates
+    them, at most ``ceil(min(len(dataset), n_max_data) / (batch_size * world))`` steps (``n_max_data <= 0``: all), each
+    through ``vis_step``.  The files go through one ``png.PngWriter``: the given one, which stays open for its owner to
+    close, or one made here and closed (every file complete) before the function returns.  Returns ``{scene_id:
+    directory}``.  The reference's mp4 step is not part of this."""
+    from . import png
+
+    if batch_size < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"vis_run: batch_size {batch_size}, rank {rank}, world {world}")
+    n_all = min(len(dataset), n_max_data) if n_max_data > 0 else len(dataset)
+    n_batches = int(math.ceil(n_all / (batch_size * world)))
+    indices = pdist.shard_indices(len(dataset), rank, world)
+    own = writer is None
+    w = png.PngWriter() if own else writer
+    dirs = {}
+    try:
+        for step in range(min(n_batches, int(math.ceil(len(indices) / batch_size)))):
+            batch = collate([dataset[i] for i in indices[step * batch_size:(step + 1) * batch_size]])
+            for path in vis_step(model, batch, render_cfg, vis_dir, device=device, writer=w):
+                dirs[path.parent.name] = path.parent
+    finally:
+        if own:
+            w.close()
+    return dirs

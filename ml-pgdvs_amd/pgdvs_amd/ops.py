@@ -778,6 +778,37 @@ def nvidia_depth_range(depth, rays, inv_c2w_tgt, near_far=None):
                                        _stream()), "pgdvs_nvidia_depth_range")
     return out
 
+
+PNG_QUANT = {"save_image": 0, "truncate": 1}
+
+
+def png_scanlines(img, *, quant="save_image", adaptive=True, out=None):
+    """The visualiser's image export up to the deflate (``pgdvs_png_scanlines``; include/pgdvs_hip.h): img[B,3,H,W] (or
+    [3,H,W]) float32 on the GPU, unclamped -> uint8 [B,H,1+3W]: per row a PNG filter-type byte, then the row's R G B bytes
+    quantised as ``quant`` says ("save_image": ``torchvision.utils.save_image``; "truncate": the ``*_gnt.png`` cast; both after
+    ``clamp(0, 1)``, NaN -> 0) and filtered (``adaptive``: libpng's default per-row choice among the five filter types;
+    otherwise type 0, so ``out[..., 1:]`` is the packed [H,W,3] image).  ``out``: a contiguous uint8 GPU tensor of
+    B H (1 + 3 W) elements to fill in place (any alignment)."""
+    if quant not in PNG_QUANT:
+        raise ValueError(f"png_scanlines: quant {quant!r} (one of {sorted(PNG_QUANT)})")
+    x = _req(img, torch.float32, "img")
+    if x.ndim == 3:
+        x = x[None]
+    if x.ndim != 4 or x.shape[1] != 3:
+        raise ValueError(f"png_scanlines: img [B,3,H,W] expected, got {tuple(x.shape)}")
+    B, _, H, W = (int(v) for v in x.shape)
+    shape = (B, H, 1 + 3 * W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == x.device and out.dtype == torch.uint8
+                and out.is_contiguous() and out.numel() == B * H * (1 + 3 * W)):
+            raise ValueError(f"png_scanlines: out must be a contiguous uint8 tensor of {shape} on {x.device}")
+    check(_lib.load().pgdvs_png_scanlines(_ptr(x), B, H, W, PNG_QUANT[quant], 1 if adaptive else 0, _ptr(out), _stream()),
+          "pgdvs_png_scanlines")
+    return out.view(shape)
+
+
 _pinned_sums = {}
 
 
