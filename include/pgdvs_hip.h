@@ -675,6 +675,21 @@ void pgdvs_view_geo_host_stats(int64_t *calls, double *seconds);
 int pgdvs_png_scanlines(const float *img_planar, int B, int H, int W, int quant, int adaptive, uint8_t *out,
                         pgdvs_stream_t stream);
 
+/* ---- evaluator export ------------------------------------------------------ */
+/* The images save_vis_for_eval writes for one view (pgdvs/engines/evaluator_pgdvs.py:417-465: *_gt.png :432-433,
+ * *_combined.png :435-440, *_gnt.png :442-452 / *_geo_static.png :453-465) up to the deflate, in ONE launch from the RAW
+ * images: gt_hwc[H,W,3] (channel-last, as the dataset gives it), pred_planar[3,H,W], static_planar[3,H,W] or NULL ->
+ * out[n,H,1+3W] uint8 with n = 2 or 3, in the order gt, pred, static; each image's scanlines as pgdvs_png_scanlines writes
+ * them with quant 1: clamp(0, 1), NaN -> 0, (x * 255) in float32, truncation.  (Upstream writes gt and pred from the
+ * evaluator's quantised images, (q / 255 * 255).astype(uint8); for every level q = 0..255 that is q again, so the cast of
+ * the clamped raw image gives the same bytes.)  adaptive as for pgdvs_png_scanlines; the bytes of each image are identical
+ * to pgdvs_png_scanlines(quant 1) on its planar form.  A row of the channel-last ground truth is already in PNG byte order
+ * and is read with contiguous 16-byte loads (W % 4 == 0 and a 16-byte aligned pointer; scalar loads otherwise).  No
+ * workspace, no atomics, integer sums; out needs no alignment, the inputs 4 bytes.  Shapes: H, W >= 1 and
+ * n H (1 + 3 W) < 2^31, adaptive 0 / 1, else PGDVS_ERR_INVALID. */
+int pgdvs_eval_export_scanlines(const float *pred_planar, const float *gt_hwc, const float *static_planar, int H, int W,
+                                int adaptive, uint8_t *out, pgdvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

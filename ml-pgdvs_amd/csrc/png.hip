@@ -18,6 +18,13 @@
 // Quantisation: clamp(0, 1) first; NaN -> 0 (upstream's NaN-to-uint8 cast is undefined behaviour).
 //   quant 0  x.mul(255).add_(0.5).clamp_(0, 255).to(uint8): multiply and add rounded separately (no fma), truncation
 //   quant 1  (x * 255).astype(uint8): truncation
+//
+// Evaluator export (pgdvs/engines/evaluator_pgdvs.py:417-465, save_vis_for_eval): the same row pass over the two or three
+// images of a view in ONE launch -- ground truth, prediction and, given, the static render, all with quant 1 (upstream's
+// quantise / 255 * 255 / cast chain is the truncating cast of the clamped raw image for every one of the 256 levels).  The
+// ground truth is channel-last: a row of it is already in PNG byte order, so it is staged with contiguous 16-byte loads
+// (stage_row<kHwc>) instead of three plane reads; everything behind the staging is scanline_row, shared with the
+// visualiser's kernel.
 #include "common.h"
 
 namespace pgdvs {
@@ -28,8 +35,11 @@ constexpr int kChunk = 2048;                     // pixels of a row held in LDS 
 constexpr int kLead = 8;                         // bytes in front of a chunk's first pixel: 5 unused, 3 of the pixel to its left
 constexpr int kWords = (kLead + 3 * kChunk + 8) / 4;  // + 8 bytes behind the last pixel that a tail group may read (never use)
 
+constexpr int kPlanar = 0;  // [3,H,W]: a row is three plane rows of W floats
+constexpr int kHwc = 1;     // [H,W,3]: a row is 3 W contiguous floats, already in PNG byte order
+
 struct Params {
-  const float *img;  // [B,3,H,W]
+  const float *img;  // [B,3,H,W] (kPlanar) or [H,W,3] (kHwc)
   uint8_t *out;      // [B,H,1+3W]
   int H, W;
   int quant, adaptive;
@@ -44,9 +54,41 @@ __device__ __forceinline__ uint32_t quantise(float x, int quant) {
   return (uint32_t)(int)v;
 }
 
-// Stage pixels [c0, c0 + n) of image row `row` (plane 0 of it at `src`) into `dst`: pixel c0 + i at bytes kLead + 3 i, the
-// pixel to the left of c0 (zero for c0 = 0) at bytes 5..7.  zero: the row above row 0.
+// Stage pixels [c0, c0 + n) of an image row (kPlanar: plane 0 of it at `src`; kHwc: its first float at `src`) into `dst`: pixel
+// c0 + i at bytes kLead + 3 i, the pixel to the left of c0 (zero for c0 = 0) at bytes 5..7.  zero: the row above row 0.
+template <int L>
 __device__ void stage_row(const Params &p, const float *__restrict__ src, bool zero, int c0, int n, uint32_t *__restrict__ dst) {
+  if (L == kHwc) {
+    // float 3 c0 + f of the row -> LDS byte kLead + f: one 16-byte load and one LDS word per thread and step
+    const float *__restrict__ row = src + 3 * (size_t)c0;
+    const int n_bytes = 3 * n, words = (n_bytes + 3) >> 2;
+    for (int q = threadIdx.x; q < words; q += kBlock) {
+      uint32_t v[4];
+      if (zero) {
+        v[0] = v[1] = v[2] = v[3] = 0u;
+      } else if (p.vec4) {  // (W % 4 == 0: 3 n is a multiple of 4, no read past the chunk)
+        const float4 f = *reinterpret_cast<const float4 *>(row + 4 * q);
+        v[0] = quantise(f.x, p.quant);
+        v[1] = quantise(f.y, p.quant);
+        v[2] = quantise(f.z, p.quant);
+        v[3] = quantise(f.w, p.quant);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = 4 * q + i < n_bytes ? quantise(row[4 * q + i], p.quant) : 0u;
+      }
+      dst[kLead / 4 + q] = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+    }
+    if (threadIdx.x == kBlock - 1) {
+      uint32_t halo = 0u;
+      if (!zero && c0 > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) halo |= quantise(row[c - 3], p.quant) << (8 * (c + 1));
+      }
+      dst[0] = 0u;
+      dst[1] = halo;
+    }
+    return;
+  }
   const size_t plane = (size_t)p.H * p.W;
   const int quads = (n + 3) >> 2;
   for (int q = threadIdx.x; q < quads; q += kBlock) {
@@ -165,18 +207,17 @@ __device__ __forceinline__ Groups groups_of(uint8_t *out_row, int c0, int n) {
   return g;
 }
 
-__global__ void __launch_bounds__(kBlock) png_scanlines_kernel(Params p) {
-  __shared__ uint32_t s_cur[kWords];
-  __shared__ uint32_t s_up[kWords];
-  __shared__ unsigned long long s_cost[kBlock / kWave][5];
-  __shared__ int s_type;
+// a workgroup's LDS (at namespace scope, so that a kernel that instantiates both layouts holds it once)
+__shared__ uint32_t s_cur[kWords];
+__shared__ uint32_t s_up[kWords];
+__shared__ unsigned long long s_cost[kBlock / kWave][5];
+__shared__ int s_type;
 
-  const int W = p.W, H = p.H;
-  const int b = blockIdx.x / H, y = blockIdx.x - b * H;
-  const size_t row_bytes = 1 + 3 * (size_t)W;
-  uint8_t *out_row = p.out + (size_t)blockIdx.x * row_bytes;
-  const float *cur = p.img + ((size_t)b * 3 * H + y) * W;
-  const float *up = y > 0 ? cur - W : cur;  // (row 0 has zeros above it: stage_row's `zero`)
+// One scanline by one workgroup: row y of an image in layout L (`cur`: plane 0 of the row / its first float) -> out_row[1 + 3 W]
+template <int L>
+__device__ __forceinline__ void scanline_row(const Params &p, const float *__restrict__ cur, int y, uint8_t *__restrict__ out_row) {
+  const int W = p.W;
+  const float *up = y > 0 ? cur - (L == kHwc ? 3 * W : W) : cur;  // (row 0 has zeros above it: stage_row's `zero`)
   const int n_chunks = (W + kChunk - 1) / kChunk;
   int type = 0;
 
@@ -185,8 +226,8 @@ __global__ void __launch_bounds__(kBlock) png_scanlines_kernel(Params p) {
     for (int ch = 0; ch < n_chunks; ++ch) {
       const int c0 = ch * kChunk, n = min(kChunk, W - c0);
       if (ch > 0) __syncthreads();
-      stage_row(p, cur, false, c0, n, s_cur);
-      stage_row(p, up, y == 0, c0, n, s_up);
+      stage_row<L>(p, cur, false, c0, n, s_cur);
+      stage_row<L>(p, up, y == 0, c0, n, s_up);
       __syncthreads();
       const Groups g = groups_of(out_row, c0, n);
       for (int gi = g.g_lo + (int)threadIdx.x; gi <= g.g_hi; gi += kBlock) {
@@ -236,8 +277,8 @@ __global__ void __launch_bounds__(kBlock) png_scanlines_kernel(Params p) {
     const int c0 = ch * kChunk, n = min(kChunk, W - c0);
     if (!p.adaptive || n_chunks > 1) {  // (otherwise the row pair is still staged)
       if (ch > 0) __syncthreads();
-      stage_row(p, cur, false, c0, n, s_cur);
-      if (type >= 2) stage_row(p, up, y == 0, c0, n, s_up);
+      stage_row<L>(p, cur, false, c0, n, s_cur);
+      if (type >= 2) stage_row<L>(p, up, y == 0, c0, n, s_up);
       __syncthreads();
     }
     const Groups g = groups_of(out_row, c0, n);
@@ -256,6 +297,42 @@ __global__ void __launch_bounds__(kBlock) png_scanlines_kernel(Params p) {
           if (u0 + j >= g.u_lo && u0 + j < g.u_hi) g.out[u0 + j] = (uint8_t)(f >> (8 * j));
       }
     }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) png_scanlines_kernel(Params p) {
+  const int H = p.H;
+  const int b = blockIdx.x / H, y = blockIdx.x - b * H;
+  scanline_row<kPlanar>(p, p.img + ((size_t)b * 3 * H + y) * p.W, y, p.out + (size_t)blockIdx.x * (1 + 3 * (size_t)p.W));
+}
+
+struct ExportParams {
+  const float *gt;      // [H,W,3]
+  const float *planar[2];  // pred, static (or null): [3,H,W]
+  uint8_t *out;         // [n,H,1+3W]: gt, pred, static
+  int H, W, adaptive;
+  int vec4_gt, vec4_planar[2];
+};
+
+// image = blockIdx.x / H: 0 the channel-last ground truth, 1 the prediction, 2 the static render (block-uniform branch)
+__global__ void __launch_bounds__(kBlock) eval_export_scanlines_kernel(ExportParams e) {
+  const int H = e.H, W = e.W;
+  const int img = blockIdx.x / H, y = blockIdx.x - img * H;
+  Params p;
+  p.out = e.out;
+  p.H = H;
+  p.W = W;
+  p.quant = 1;
+  p.adaptive = e.adaptive;
+  uint8_t *out_row = e.out + (size_t)blockIdx.x * (1 + 3 * (size_t)W);
+  if (img == 0) {
+    p.img = e.gt;
+    p.vec4 = e.vec4_gt;
+    scanline_row<kHwc>(p, e.gt + (size_t)y * 3 * W, y, out_row);
+  } else {
+    p.img = img == 1 ? e.planar[0] : e.planar[1];
+    p.vec4 = img == 1 ? e.vec4_planar[0] : e.vec4_planar[1];
+    scanline_row<kPlanar>(p, p.img + (size_t)y * W, y, out_row);
   }
 }
 
@@ -282,4 +359,30 @@ PGDVS_API int pgdvs_png_scanlines(const float *img_planar, int B, int H, int W, 
   p.vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(img_planar) & 15) == 0;
   PGDVS_LAUNCH("png_scanlines", png_scanlines_kernel, dim3((unsigned)(B * H)), dim3(kBlock), 0, as_stream(stream), p);
   return check_launch("pgdvs_png_scanlines");
+}
+
+PGDVS_API int pgdvs_eval_export_scanlines(const float *pred_planar, const float *gt_hwc, const float *static_planar, int H, int W,
+                                          int adaptive, uint8_t *out, pgdvs_stream_t stream) {
+  PGDVS_REQUIRE(pred_planar && gt_hwc && out, "pgdvs_eval_export_scanlines: null pointer");
+  const int n = static_planar ? 3 : 2;
+  PGDVS_REQUIRE(H >= 1 && W >= 1 && (int64_t)n * H * (1 + 3 * (int64_t)W) < (1ll << 31),
+                "pgdvs_eval_export_scanlines: bad shape H=%d W=%d (each >= 1, n H (1 + 3 W) < 2^31 for n = %d images)", H, W, n);
+  PGDVS_REQUIRE(adaptive == 0 || adaptive == 1, "pgdvs_eval_export_scanlines: adaptive %d (0 / 1)", adaptive);
+  PGDVS_REQUIRE(((reinterpret_cast<uintptr_t>(pred_planar) | reinterpret_cast<uintptr_t>(gt_hwc) |
+                  reinterpret_cast<uintptr_t>(static_planar)) & 3) == 0,
+                "pgdvs_eval_export_scanlines: an input image is not 4-byte aligned");
+  auto vec4 = [W](const float *q) { return (int)((W % 4 == 0) && (reinterpret_cast<uintptr_t>(q) & 15) == 0); };
+  ExportParams e;
+  e.gt = gt_hwc;
+  e.planar[0] = pred_planar;
+  e.planar[1] = static_planar;
+  e.out = out;
+  e.H = H;
+  e.W = W;
+  e.adaptive = adaptive;
+  e.vec4_gt = vec4(gt_hwc);
+  e.vec4_planar[0] = vec4(pred_planar);
+  e.vec4_planar[1] = static_planar ? vec4(static_planar) : 0;
+  PGDVS_LAUNCH("eval_export_scanlines", eval_export_scanlines_kernel, dim3((unsigned)(n * H)), dim3(kBlock), 0, as_stream(stream), e);
+  return check_launch("pgdvs_eval_export_scanlines");
 }

@@ -111,6 +111,7 @@ SIGNATURES.update({
     "pgdvs_nvidia_depth_range_workspace_bytes": (_i64, [_i, _i, _i]),
     "pgdvs_nvidia_depth_range": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_png_scanlines": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "pgdvs_eval_export_scanlines": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

@@ -9,7 +9,10 @@ model="net-lin", net="alex", version=0.1)``, trainer_pgdvs.py:132-137, given the
 ``LpipsAlex``), and ONE packed reduce of the metric sums to rank 0 (the reference issues one
 ``torch.distributed.reduce`` per key, :183-186).  On the GPU at render size the metrics are HIP passes (csrc/eval.hip,
 csrc/eval_ssim.hip, csrc/lpips.hip); otherwise a few torch ops on final images.  SSIM's window sums are exact integers
-here, where skimage 0.20 filters in float32: the two differ by about 1e-7 on a masked mean."""
+here, where skimage 0.20 filters in float32: the two differ by about 1e-7 on a masked mean.
+``eval_run`` is the loop around it (``run_eval_single_ckpt``, trainer_pgdvs.py:282-360, with what ``save_individual`` leaves:
+per-view records and images), able to run ahead of the GPU by up to three steps; ``vis_step`` / ``vis_run`` are the
+visualiser's."""
 import math
 import time
 from collections import OrderedDict
@@ -359,6 +362,146 @@ def _check_geo_status(ret, data_gpu, host_counts=None, host_status=None):
         ops.check_raster_status(ret.get("geo_static_raster_status", None))
 
 
+class _Laps:
+    """STAGE_SECONDS bookkeeping shared by the two halves of a step: ``lap(name)`` adds the host wall time since the last lap"""
+
+    def __init__(self):
+        self.stages, self.t_prev = STAGE_SECONDS, time.perf_counter()
+
+    def __call__(self, name):
+        if self.stages is not None:
+            now = time.perf_counter()
+            self.stages[name] = self.stages.get(name, 0.0) + (now - self.t_prev)
+            self.t_prev = now
+
+
+def _check_protocol(what, quant_type, with_ssim):
+    if quant_type not in QUANT_TYPES:
+        raise ValueError(quant_type)
+    if quant_type == "dycheck_iphone" and with_ssim:
+        raise ValueError(f"{what}: with_ssim does not apply to quant_type 'dycheck_iphone' (its SSIM is always computed)")
+
+
+class _LazyRing:
+    """the cached ``ops.RowRing`` of ``depth`` blocks for the device of the first rows enqueued (``eval_step``: depth 1, the
+    staging of ``ops.read_back_rows``; ``eval_run``: run_ahead + 1)"""
+
+    def __init__(self, depth=1):
+        self.depth, self.ring = depth, None
+
+    def enqueue(self, rows):
+        if self.ring is None:
+            from . import ops
+
+            self.ring = ops.row_ring(rows[0].device, self.depth)
+        return self.ring.enqueue(rows)
+
+    def finish(self, ticket):
+        return self.ring.finish(ticket)
+
+
+class _PendingStep:
+    """What ``_eval_enqueue`` leaves for ``_eval_finish``: on the fused path the enqueued rows' ticket in the row ring, on the
+    torch path the finished per-view values"""
+    __slots__ = ("fused", "n_batch", "keys", "device", "ret", "data", "data_gpu", "groups", "ticket", "ring", "images", "has_cnts",
+                 "has_stat", "per_view", "pred", "gt", "eval_mask", "exports")
+
+
+def _eval_enqueue(what, model, data, render_cfg, *, device, disable_tqdm, with_ssim, lpips, quant_type, want_images, ring, lap,
+                  export=False):
+    """The first half of an evaluator step: to-device, ``forward`` and, on the fused GPU path, the protocol's HIP passes per
+    view and the asynchronous copy of their rows into ``ring`` (``ops.RowRing``) -- nothing here waits for the GPU.  On the
+    torch path (CPU tensors, render size != ground-truth size) the whole step is computed here.  ``export``: also the
+    scanlines of the view's images (``save_individual``), on the fused path one ``ops.eval_export_scanlines`` launch per view
+    behind the metric passes, each with an event a ``PngWriter`` can wait for."""
+    from . import ops
+
+    _check_protocol(what, quant_type, with_ssim)
+    if quant_type == "dycheck_iphone" and data["eval_mask"].shape[-1] != 1:
+        raise ValueError(f"{what}: quant_type 'dycheck_iphone' takes eval_mask[B,H,W,1], got {tuple(data['eval_mask'].shape)}")
+    device = device if device is not None else next(iter(v for v in data.values() if isinstance(v, torch.Tensor))).device
+    data_gpu = to_device(data, device)
+    lap("to_device")
+    if model.training:
+        model.eval()
+    n_batch = data["rgb_src_temporal"].shape[0]
+    ret = model.forward(data_gpu, render_cfg=render_cfg, disable_tqdm=disable_tqdm, for_debug=False)
+    lap("forward")
+    comb, gt, em = ret["combined_rgb"], data_gpu["rgb_tgt"], data_gpu["eval_mask"]
+    if quant_type == "dycheck_iphone":
+        keys, fused_rows, view_values = DYCHECK_KEYS + (DYCHECK_LPIPS_KEYS if lpips is not None else ()), _dycheck_rows, _dycheck_view
+    else:
+        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
+        fused_rows, view_values = _nvidia_rows, _nvidia_view
+    pend = _PendingStep()
+    pend.n_batch, pend.keys, pend.ret, pend.data, pend.data_gpu, pend.exports = n_batch, keys, ret, data, data_gpu, None
+    statics = [(tag, ret[k]) for tag, k in (("gnt", "static_coarse_rgb"), ("geo_static", "geo_static_rgb")) if k in ret]
+    pend.fused = bool(comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(gt.shape[1:3])
+                      and gt.dtype == torch.float32 and em.dtype == torch.float32)
+    if pend.fused:
+        # GPU, render size == ground-truth size (render_stride 1): the protocol's HIP passes per view, the first of which
+        # quantises and carries the geometry path's device-side status words, and ONE host read for the batch
+        cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
+        cnts = cnts.reshape(-1) if isinstance(cnts, torch.Tensor) and cnts.is_cuda and cnts.dtype == torch.int64 else None
+        stat = ret.get("geo_static_raster_status", None)
+        stat = stat.reshape(-1) if isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.int32 else None
+        cd = [cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None for i_b in range(n_batch)]
+        sd = [stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None for i_b in range(n_batch)]
+        pend.groups, pend.images = fused_rows(comb, gt, em, cd, sd, with_ssim, lpips, want_images)
+        pend.has_cnts, pend.has_stat, pend.device, pend.eval_mask = cnts is not None, stat is not None, comb.device, em
+        lap("metric_enqueue")
+        pend.ring = ring
+        pend.ticket = ring.enqueue([r_ for rows, _ in pend.groups for r_ in rows])
+        if export:
+            pend.exports = []
+            # the first static image that fits rides in the view's export launch; another one (a renderer that returns both)
+            # takes a png_scanlines launch of its own
+            fast = [(tag, img) for tag, img in statics if img.is_cuda and img.dtype == torch.float32 and img.shape == comb.shape][:1]
+            for i_b in range(n_batch):
+                scan = ops.eval_export_scanlines(comb[i_b], gt[i_b], fast[0][1][i_b] if fast else None)
+                views = [("gt", scan[0]), ("combined", scan[1])] + ([(fast[0][0], scan[2])] if fast else [])
+                views += [(tag, _view_scanlines(img[i_b:i_b + 1], "truncate")[0]) for tag, img in statics if not fast or tag != fast[0][0]]
+                pend.exports.append((views, torch.cuda.current_stream(comb.device).record_event()))
+        return pend
+    _check_geo_status(ret, data_gpu)
+    # quantise first, as if the images had been written to disk and read back (:70-77)
+    pred = quantize_like_evaluator(comb)
+    rgb_gt = quantize_like_evaluator(gt.permute(0, 3, 1, 2))
+    eval_mask = em.permute(0, 3, 1, 2)
+    _, _, rh, rw = pred.shape
+    if rgb_gt.shape[2] != rh or rgb_gt.shape[3] != rw:  # render_stride != 1 (:80-92)
+        rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
+        eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
+        eval_mask = (eval_mask > 0).float()
+    vals = [view_values(rgb_gt[i_b], pred[i_b].to(rgb_gt.device), eval_mask[i_b], with_ssim, lpips) for i_b in range(n_batch)]
+    pend.per_view = {k: [v[j] for v in vals] for j, k in enumerate(keys)}
+    pend.pred, pend.gt, pend.eval_mask, pend.device = pred, rgb_gt, eval_mask, rgb_gt.device
+    if export:  # the evaluator's own images, quantised (and, with render_stride != 1, the resized ground truth) (:432-465)
+        outs = [("gt", rgb_gt), ("combined", pred)] + statics
+        lines = [(tag, _view_scanlines(img.float().cpu(), "truncate")) for tag, img in outs]
+        pend.exports = [([(tag, scan[i_b]) for tag, scan in lines], None) for i_b in range(n_batch)]
+    return pend
+
+
+def _eval_finish(pend, lap):
+    """The second half: the step's one wait for the GPU (its own block of the row ring), the status words, the per-view
+    values in key order -> ``{key: [value per view]}``.  Raises ``PgdvsHipError`` on a device-side status error."""
+    if not pend.fused:
+        return pend.per_view
+    n_batch = pend.n_batch
+    host = pend.ring.finish(pend.ticket)  # (the step's synchronisation)
+    lap("sync_read")
+    _check_geo_status(pend.ret, pend.data_gpu, host_counts=[int(s_[6]) for s_ in host[:n_batch]] if pend.has_cnts else None,
+                      host_status=[int(s_[7]) for s_ in host[:n_batch]] if pend.has_stat else None)
+    vals = [[v for j, (_, values) in enumerate(pend.groups) for v in values(host[j * n_batch + i_b])] for i_b in range(n_batch)]
+    pend.per_view = {k: [v[j] for v in vals] for j, k in enumerate(pend.keys)}
+    return pend.per_view
+
+
+def _multi_process():
+    return torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+
+
 @torch.no_grad()
 def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, return_images=False, with_ssim=False,
               lpips=None, quant_type="nvidia"):
@@ -373,83 +516,23 @@ def eval_step(model, data: dict, render_cfg, *, device=None, disable_tqdm=True, 
     ``quant_type`` selects the evaluator's metric protocol (evaluator_pgdvs.py:137-143; ``quant_type_from_engine_cfg``): the
     default "nvidia" is all of the above; "dycheck_iphone" returns ``eval/count`` and ``DYCHECK_KEYS`` instead -- plus
     ``DYCHECK_LPIPS_KEYS`` with ``lpips`` -- for an ``eval_mask[B,H,W,1]`` (csrc/eval_dycheck.hip on the fused path).  There
-    SSIM is always on, so ``with_ssim=True`` raises ValueError, as does an eval_mask whose last dimension is not 1."""
-    if quant_type not in QUANT_TYPES:
-        raise ValueError(quant_type)
-    if quant_type == "dycheck_iphone":
-        if with_ssim:
-            raise ValueError("eval_step: with_ssim does not apply to quant_type 'dycheck_iphone' (its SSIM is always computed)")
-        if data["eval_mask"].shape[-1] != 1:
-            raise ValueError(f"eval_step: quant_type 'dycheck_iphone' takes eval_mask[B,H,W,1], got {tuple(data['eval_mask'].shape)}")
-    device = device if device is not None else next(iter(v for v in data.values() if isinstance(v, torch.Tensor))).device
-    stages, t_prev = STAGE_SECONDS, time.perf_counter()
-
-    def lap(name):
-        nonlocal t_prev
-        if stages is not None:
-            now = time.perf_counter()
-            stages[name] = stages.get(name, 0.0) + (now - t_prev)
-            t_prev = now
-
-    data_gpu = to_device(data, device)
-    lap("to_device")
-    if model.training:
-        model.eval()
-    n_batch = data["rgb_src_temporal"].shape[0]
-    ret = model.forward(data_gpu, render_cfg=render_cfg, disable_tqdm=disable_tqdm, for_debug=False)
-    lap("forward")
-    from . import ops
-
-    def check_status(host_counts=None, host_status=None):
-        _check_geo_status(ret, data_gpu, host_counts, host_status)
-
-    comb, gt, em = ret["combined_rgb"], data_gpu["rgb_tgt"], data_gpu["eval_mask"]
-    if quant_type == "dycheck_iphone":
-        keys, fused_rows, view_values = DYCHECK_KEYS + (DYCHECK_LPIPS_KEYS if lpips is not None else ()), _dycheck_rows, _dycheck_view
-    else:
-        keys = METRIC_KEYS + (SSIM_KEYS if with_ssim else ()) + (LPIPS_KEYS if lpips is not None else ())
-        fused_rows, view_values = _nvidia_rows, _nvidia_view
-    multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-    if (comb.is_cuda and comb.dtype == torch.float32 and tuple(comb.shape[2:]) == tuple(gt.shape[1:3])
-            and gt.dtype == torch.float32 and em.dtype == torch.float32):
-        # GPU, render size == ground-truth size (render_stride 1): the protocol's HIP passes per view, the first of which
-        # quantises and carries the geometry path's device-side status words, and ONE host read for the batch
-        cnts = ret.get("st_pcl_rgb_count", data_gpu.get("st_pcl_rgb_count", None))
-        cnts = cnts.reshape(-1) if isinstance(cnts, torch.Tensor) and cnts.is_cuda and cnts.dtype == torch.int64 else None
-        stat = ret.get("geo_static_raster_status", None)
-        stat = stat.reshape(-1) if isinstance(stat, torch.Tensor) and stat.is_cuda and stat.dtype == torch.int32 else None
-        cd = [cnts[i_b:i_b + 1] if (cnts is not None and i_b < cnts.numel()) else None for i_b in range(n_batch)]
-        sd = [stat[i_b:i_b + 1] if (stat is not None and i_b < stat.numel()) else None for i_b in range(n_batch)]
-        groups, images = fused_rows(comb, gt, em, cd, sd, with_ssim, lpips, return_images)
-        lap("metric_enqueue")
-        host = ops.read_back_rows([r_ for rows, _ in groups for r_ in rows])  # (the step's synchronisation)
-        lap("sync_read")
-        check_status(host_counts=[int(s_[6]) for s_ in host[:n_batch]] if cnts is not None else None,
-                     host_status=[int(s_[7]) for s_ in host[:n_batch]] if stat is not None else None)
-        vals = [[v for j, (_, values) in enumerate(groups) for v in values(host[j * n_batch + i_b])] for i_b in range(n_batch)]
-        per_view = {k: [v[j] for v in vals] for j, k in enumerate(keys)}
-        # (a single process keeps the metric tensors on the host: no upload and no one-element kernels per step)
-        metric = _metric_dict(n_batch, keys, per_view, comb.device, multi)
-        lap("post")
+    SSIM is always on, so ``with_ssim=True`` raises ValueError, as does an eval_mask whose last dimension is not 1.
+    The step is ``_eval_enqueue`` followed at once by ``_eval_finish``; ``eval_run`` drives the same two halves with the
+    second up to three steps behind the first."""
+    lap = _Laps()
+    pend = _eval_enqueue("eval_step", model, data, render_cfg, device=device, disable_tqdm=disable_tqdm, with_ssim=with_ssim,
+                         lpips=lpips, quant_type=quant_type, want_images=return_images, ring=_LazyRing(1), lap=lap)
+    per_view = _eval_finish(pend, lap)
+    # (a single process keeps the metric tensors on the host: no upload and no one-element kernels per step)
+    metric = _metric_dict(pend.n_batch, pend.keys, per_view, pend.device, _multi_process())
+    if not pend.fused:
         if return_images:
-            pred, gtq = images()
-            return metric, {"pred": pred, "gt": gtq, "eval_mask": em.permute(0, 3, 1, 2), "per_view": per_view, "ret": ret}
+            return metric, {"pred": pend.pred, "gt": pend.gt, "eval_mask": pend.eval_mask, "per_view": per_view, "ret": pend.ret}
         return metric
-    check_status()
-    # quantise first, as if the images had been written to disk and read back (:70-77)
-    pred = quantize_like_evaluator(comb)
-    rgb_gt = quantize_like_evaluator(gt.permute(0, 3, 1, 2))
-    eval_mask = em.permute(0, 3, 1, 2)
-    _, _, rh, rw = pred.shape
-    if rgb_gt.shape[2] != rh or rgb_gt.shape[3] != rw:  # render_stride != 1 (:80-92)
-        rgb_gt = torch.nn.functional.interpolate(rgb_gt, size=(rh, rw), mode="bicubic", antialias=True, align_corners=True)
-        eval_mask = torch.nn.functional.interpolate(eval_mask, size=(rh, rw), mode="nearest")
-        eval_mask = (eval_mask > 0).float()
-    vals = [view_values(rgb_gt[i_b], pred[i_b].to(rgb_gt.device), eval_mask[i_b], with_ssim, lpips) for i_b in range(n_batch)]
-    per_view = {k: [v[j] for v in vals] for j, k in enumerate(keys)}
-    metric = _metric_dict(n_batch, keys, per_view, rgb_gt.device, multi)
+    lap("post")
     if return_images:
-        return metric, {"pred": pred, "gt": rgb_gt, "eval_mask": eval_mask, "per_view": per_view, "ret": ret}
+        pred, gtq = pend.images()
+        return metric, {"pred": pred, "gt": gtq, "eval_mask": pend.eval_mask.permute(0, 3, 1, 2), "per_view": per_view, "ret": pend.ret}
     return metric
 
 
@@ -594,6 +677,24 @@ def collate(batch: list) -> dict:
     return {k: combine([x[k] for x in batch]) for k in batch[0].keys()}
 
 
+def _run_batches(what, dataset, batch_size, n_max_data, rank, world):
+    """The item selection shared by ``vis_run`` and ``eval_run`` (run_eval_single_ckpt :290-331, vis_model): checks the
+    arguments now, then yields this rank's collated batches: its items in ``DistributedSampler(shuffle=False)`` order
+    (``dist.shard_indices``), ``batch_size`` per step, at most ``ceil(min(len(dataset), n_max_data) / (batch_size * world))``
+    steps (``n_max_data <= 0``: all)."""
+    if batch_size < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"{what}: batch_size {batch_size}, rank {rank}, world {world}")
+    n_all = min(len(dataset), n_max_data) if n_max_data > 0 else len(dataset)
+    n_batches = int(math.ceil(n_all / (batch_size * world)))
+    indices = pdist.shard_indices(len(dataset), rank, world)
+
+    def batches():
+        for step in range(min(n_batches, int(math.ceil(len(indices) / batch_size)))):
+            yield collate([dataset[i] for i in indices[step * batch_size:(step + 1) * batch_size]])
+
+    return batches()
+
+
 def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, writer=None):
     """``vis_model``'s outer loop without Hydra: this rank's items in ``DistributedSampler(shuffle=False)`` order
     (``dist.shard_indices``), ``batch_size`` of them per step (the per-process batch size), collated as upstream collates
@@ -603,20 +704,155 @@ def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1,
     directory}``.  The reference's mp4 step is not part of this."""
     from . import png
 
-    if batch_size < 1 or world < 1 or not 0 <= rank < world:
-        raise ValueError(f"vis_run: batch_size {batch_size}, rank {rank}, world {world}")
-    n_all = min(len(dataset), n_max_data) if n_max_data > 0 else len(dataset)
-    n_batches = int(math.ceil(n_all / (batch_size * world)))
-    indices = pdist.shard_indices(len(dataset), rank, world)
+    batches = _run_batches("vis_run", dataset, batch_size, n_max_data, rank, world)
     own = writer is None
     w = png.PngWriter() if own else writer
     dirs = {}
     try:
-        for step in range(min(n_batches, int(math.ceil(len(indices) / batch_size)))):
-            batch = collate([dataset[i] for i in indices[step * batch_size:(step + 1) * batch_size]])
+        for batch in batches:
             for path in vis_step(model, batch, render_cfg, vis_dir, device=device, writer=w):
                 dirs[path.parent.name] = path.parent
     finally:
         if own:
             w.close()
     return dirs
+
+
+# ---- the evaluator's loop (pgdvs/engines/trainer_pgdvs.py:282-360, evaluator_pgdvs.py:115-175, 411-465) ------------------
+# upstream's key order in a view's record (obtain_quantitative_nvidia :259-274, obtain_quantitative_dycheck_iphone :398-409)
+RECORD_KEYS = {
+    "nvidia": tuple(f"{m}_{r}_combined" for r in ("full", "dyn", "static") for m in ("psnr", "ssim", "lpips")),
+    "dycheck_iphone": ("psnr_combined", "ssim_combined", "lpips_combined", "mpsnr_combined", "mssim_combined", "mlpips_combined"),
+}
+MAX_RUN_AHEAD = 3
+
+
+def _write_record(path, info):
+    import os
+    import pickle
+
+    tmp = path.with_name(f".{path.name}.{os.getpid()}.tmp")
+    try:
+        with open(tmp, "wb") as f:
+            pickle.dump(info, f)
+        os.replace(tmp, path)
+    except BaseException:
+        try:
+            os.unlink(tmp)
+        except OSError:
+            pass
+        raise
+
+
+@torch.no_grad()
+def eval_run(model, dataset, render_cfg, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, quant_type="nvidia",
+             with_ssim=False, lpips=None, save_individual=False, info_dir=None, vis_dir=None, writer=None, run_ahead=0) -> dict:
+    """``run_eval_single_ckpt`` without Hydra: the items and steps of ``vis_run`` (``_run_batches``), each step the work of
+    ``eval_step`` (same keys, protocols and errors), the per-step float32 sums accumulated as upstream accumulates them.
+    Returns ``{"eval/count": int, "eval/<key>": the average (sum / count) as a float, ..., "sums": {"eval/count": int,
+    "eval/<key>": float}, "records": [{"name": "<split>/<scene_id>/<fname>" (None without the ids), "info": the view's
+    record}, ...]}``.  With ``world > 1`` the sums are reduced to rank 0 ONCE, at the end (``dist.reduce_metrics``; upstream
+    reduces every step); the other ranks return their own partial sums and averages.
+    ``save_individual`` (needs ``info_dir`` and ``vis_dir``) writes per view, with ``fname =
+    f"{tgt_frame_id:05d}_cam_{tgt_cam_id:03d}"``, ``<info_dir>/<split>/<scene_id>/<fname>_rank_<rank>.pkl`` -- the pickled
+    record: ``src_frame_ids``, then the view's values as Python floats under upstream's names in upstream's order, the
+    metrics not asked for left out -- and ``<vis_dir>/<split>/<scene_id>/<fname>_gt.png``, ``_combined.png``, ``_gnt.png``
+    (``static_coarse_rgb``) and ``_geo_static.png`` (``geo_static_rgb``) with upstream's pixels (NaN as 0), through ``writer``
+    (a ``png.PngWriter``, left open) or one made and closed here.  On the fused GPU path the scanlines are one
+    ``ops.eval_export_scanlines`` launch per view, on the torch path ``png.py``'s.
+    ``run_ahead`` = k (0..3): step j + k is enqueued before step j is finished; everything stays on the caller's stream in
+    the same order, so every result is that of k = 0 and only the waiting moves.  (``STAGE_SECONDS``, when set, gets the loop's
+    host time under ``eval_step``'s names, "post" including the records and the writer's submits.)  A status error of a view surfaces when the
+    view is finished, up to k steps after it was enqueued: nothing later is finished or written, an owned writer is closed
+    (the files of earlier views are complete) and the error is raised.  The torch path runs as k = 0."""
+    import collections
+    import pathlib
+
+    from . import png
+
+    _check_protocol("eval_run", quant_type, with_ssim)
+    if not (isinstance(run_ahead, int) and 0 <= run_ahead <= MAX_RUN_AHEAD):
+        raise ValueError(f"eval_run: run_ahead {run_ahead!r} (0 .. {MAX_RUN_AHEAD})")
+    if save_individual and (info_dir is None or vis_dir is None):
+        raise ValueError("eval_run: save_individual needs info_dir and vis_dir")
+    batches = _run_batches("eval_run", dataset, batch_size, n_max_data, rank, world)
+    if world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized() and (
+            torch.distributed.get_world_size() != world or torch.distributed.get_rank() != rank):
+        raise ValueError(f"eval_run: rank {rank} of world {world}, but the process group says rank {torch.distributed.get_rank()} of "
+                         f"{torch.distributed.get_world_size()}")
+    lap = _Laps()
+    ring = _LazyRing(run_ahead + 1)
+    own = save_individual and writer is None
+    w = png.PngWriter() if own else writer
+    record_keys = RECORD_KEYS[quant_type]
+    sums, records, pending = {}, [], collections.deque()
+    out_device = [torch.device("cpu")]
+
+    def finish(pend):
+        per_view = _eval_finish(pend, lap)
+        out_device[0] = pend.device
+        step = _metric_dict(pend.n_batch, pend.keys, per_view, pend.device, False)
+        for k_, v in step.items():  # (loss_sum[k] = loss_sum[k] + stats[k].cpu(), :341-343)
+            sums[k_] = sums[k_] + v if k_ in sums else v
+        misc = pend.data.get("misc", None)
+        for i_b in range(pend.n_batch):
+            info = {}
+            if "seq_ids" in pend.data:
+                info["src_frame_ids"] = pend.data["seq_ids"][i_b, 1:].cpu().numpy()
+            info.update({k_: float(per_view[k_][i_b]) for k_ in record_keys if k_ in per_view})
+            m = misc[i_b] if misc is not None else {}
+            named = all(k_ in m for k_ in ("scene_id", "tgt_frame_id", "tgt_cam_id"))
+            fname = f"{m['tgt_frame_id']:05d}_cam_{m['tgt_cam_id']:03d}" if named else None
+            rel = pathlib.PurePosixPath(m.get("split", "")) / m["scene_id"] / fname if named else None
+            records.append({"name": str(rel) if named else None, "info": info})
+            if not save_individual:
+                continue
+            if not named:
+                raise ValueError("eval_run: save_individual needs misc[i]['scene_id'], ['tgt_frame_id'] and ['tgt_cam_id']")
+            scene_info = pathlib.Path(info_dir) / m.get("split", "") / m["scene_id"]
+            scene_vis = pathlib.Path(vis_dir) / m.get("split", "") / m["scene_id"]
+            scene_info.mkdir(parents=True, exist_ok=True)
+            scene_vis.mkdir(parents=True, exist_ok=True)
+            _write_record(scene_info / f"{fname}_rank_{rank}.pkl", info)
+            views, ready = pend.exports[i_b]
+            for tag, scan in views:
+                w.submit(scene_vis / f"{fname}_{tag}.png", scan, ready=ready)
+        lap("post")
+
+    failed = False
+    try:
+        for batch in batches:
+            pending.append(_eval_enqueue("eval_run", model, batch, render_cfg, device=device, disable_tqdm=True, with_ssim=with_ssim,
+                                         lpips=lpips, quant_type=quant_type, want_images=False, ring=ring, lap=lap,
+                                         export=save_individual))
+            depth = run_ahead if pending[-1].fused else 0
+            while len(pending) > depth:
+                finish(pending.popleft())
+        while pending:
+            finish(pending.popleft())
+    except BaseException:
+        failed = True
+        raise
+    finally:
+        pending.clear()
+        if own:
+            try:
+                w.close()
+            except BaseException:
+                if not failed:  # (the loop's own error comes first)
+                    raise
+    count = int(sums["eval/count"].item()) if sums else 0
+    totals = {k_: float(v) for k_, v in sums.items() if k_ != "eval/count"}
+    if world > 1 and sums:  # ONE packed reduce for the run: [count, sums...] in float64
+        names = sorted(totals)
+        packed = torch.tensor([float(count)] + [totals[k_] for k_ in names], dtype=torch.float64, device=out_device[0])
+        reduced = pdist.reduce_metrics(packed.clone(), dst=0)
+        if rank == 0:
+            count = int(reduced[0].round().item())
+            totals = {k_: float(reduced[1 + j].to(torch.float32)) for j, k_ in enumerate(names)}
+    result = {"eval/count": count}
+    for k_, v in totals.items():  # (loss_sum[k] / loss_sum["eval/count"] in float32, :347)
+        result[k_] = float(torch.tensor(v, dtype=torch.float32) / torch.tensor([count], dtype=torch.int64))
+    result["sums"] = dict({"eval/count": count}, **totals)
+    result["records"] = records
+    return result

@@ -809,25 +809,81 @@ def png_scanlines(img, *, quant="save_image", adaptive=True, out=None):
     return out.view(shape)
 
 
-_pinned_sums = {}
+def eval_export_scanlines(pred, gt_hwc, static=None, adaptive=True, out=None):
+    """The evaluator's per-view image export up to the deflate in one launch (``pgdvs_eval_export_scanlines``;
+    include/pgdvs_hip.h): pred[3,H,W] raw render, gt_hwc[H,W,3] raw ground truth and, given, static[3,H,W] (the renderer's
+    ``static_coarse_rgb`` or ``geo_static_rgb``), float32 on the GPU -> uint8 [n,H,1+3W] with n = 2 or 3 in the order gt, pred,
+    static: each image's PNG scanlines under the truncating cast (``png_scanlines(quant="truncate")``'s bytes).  ``out``: a
+    contiguous uint8 GPU tensor of n H (1 + 3 W) elements to fill in place (any alignment)."""
+    p = _req(pred, torch.float32, "pred")
+    g = _req(gt_hwc, torch.float32, "gt")
+    s_ = _req(static, torch.float32, "static") if static is not None else None
+    if p.ndim != 3 or p.shape[0] != 3 or g.ndim != 3 or tuple(g.shape) != (p.shape[1], p.shape[2], 3) or (
+            s_ is not None and tuple(s_.shape) != tuple(p.shape)):
+        raise ValueError(f"eval_export_scanlines: pred [3,H,W], gt [H,W,3] and static [3,H,W] expected, got {tuple(p.shape)}, "
+                         f"{tuple(g.shape)}, {tuple(s_.shape) if s_ is not None else None}")
+    H, W = int(p.shape[1]), int(p.shape[2])
+    shape = (3 if s_ is not None else 2, H, 1 + 3 * W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=p.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == p.device and out.dtype == torch.uint8
+              and out.is_contiguous() and out.numel() == shape[0] * shape[1] * shape[2]):
+        raise ValueError(f"eval_export_scanlines: out must be a contiguous uint8 tensor of {shape} on {p.device}")
+    check(_lib.load().pgdvs_eval_export_scanlines(_ptr(p), _ptr(g), _ptr(s_), H, W, 1 if adaptive else 0, _ptr(out), _stream()),
+          "pgdvs_eval_export_scanlines")
+    return out.view(shape)
+
+
+class RowRing:
+    """Pinned staging for metric rows (8 float64 each) read back behind the GPU: ``depth`` row blocks, each with its own event,
+    so that up to ``depth`` steps' rows can be on their way at once.  ``enqueue(rows)`` copies [n] device rows
+    asynchronously on the current stream into the next block and records its event -> a ticket; ``finish(ticket)`` waits
+    for that block's event alone -> [n][8] Python floats.  Tickets are finished in the order they were taken, each before
+    its block comes round again (``depth`` enqueues later)."""
+
+    def __init__(self, depth: int = 1):
+        self.depth = int(depth)
+        self._blocks = [None] * self.depth
+        self._next = 0
+
+    def enqueue(self, rows):
+        n = len(rows)
+        slot = self._next
+        self._next = (slot + 1) % self.depth
+        ent = self._blocks[slot]
+        if ent is None or ent[0].shape[0] < n:
+            ent = self._blocks[slot] = (torch.empty((max(n, 8), 8), dtype=torch.float64).pin_memory(), torch.cuda.Event())
+        host, ev = ent
+        for i, r_ in enumerate(rows):
+            host[i].copy_(r_, non_blocking=True)
+        ev.record()
+        return slot, n
+
+    def finish(self, ticket):
+        slot, n = ticket
+        host, ev = self._blocks[slot]
+        ev.synchronize()
+        return host[:n].tolist()
+
+
+_row_rings = {}
+
+
+def row_ring(device, depth: int = 1) -> RowRing:
+    """the cached ``RowRing`` of ``depth`` blocks for ``device`` (pinning host memory is slow; one ring per device and depth)"""
+    key = (torch.device(device).index, int(depth))
+    ring = _row_rings.get(key)
+    if ring is None:
+        ring = _row_rings[key] = RowRing(depth)
+    return ring
 
 
 def read_back_rows(rows):
-    """[n] device tensors of 8 float64 each -> [n][8] Python floats, through ONE pinned staging block per device (cached):
+    """[n] device tensors of 8 float64 each -> [n][8] Python floats, through the device's cached one-block ``RowRing``:
     asynchronous copies on the current stream and one event wait, instead of a pageable `.cpu()` per step (which stages
     through a fresh host block and synchronises the whole stream)."""
-    dev = rows[0].device
-    n = len(rows)
-    ent = _pinned_sums.get(dev.index)
-    if ent is None or ent[0].shape[0] < n:
-        ent = (torch.empty((max(n, 8), 8), dtype=torch.float64).pin_memory(), torch.cuda.Event())
-        _pinned_sums[dev.index] = ent
-    host, ev = ent
-    for i, r_ in enumerate(rows):
-        host[i].copy_(r_, non_blocking=True)
-    ev.record()
-    ev.synchronize()
-    return host[:n].tolist()
+    ring = row_ring(rows[0].device, 1)
+    return ring.finish(ring.enqueue(rows))
 
 
 def checked_count(cnt, what: str) -> int:

@@ -110,7 +110,8 @@ class PngWriter:
 
     ``submit(path, scanlines)`` takes one image's scanlines [H,1+3W] uint8.  For a GPU tensor it takes a free slot of the ring
     of pinned host buffers (blocking only when all ``n_slots`` are in use), enqueues the device-to-host copy on the writer's
-    copy stream behind an event of the current (producing) stream, and returns; a worker thread waits for the copy's event,
+    copy stream behind an event of the current (producing) stream -- or behind ``ready``, an event the producer recorded when
+    the scanlines were enqueued, so that the copy does not wait for work enqueued since -- and returns; a worker thread waits for the copy's event,
     deflates, writes the file (temporary name, then rename) and frees the slot.  Host tensors / numpy arrays skip the copy
     stage.  ``close()`` (also on leaving a ``with`` block) drains the pool and re-raises the first worker exception.
     ``n_threads`` is fixed by the caller (default 8, at most ``MAX_THREADS``) and never derived from the machine's CPU
@@ -175,7 +176,7 @@ class PngWriter:
             if slot is not None:
                 self._release_slot(slot)
 
-    def submit(self, path, scanlines) -> None:
+    def submit(self, path, scanlines, ready=None) -> None:
         if self._closed:
             raise RuntimeError("PngWriter.submit after close()")
         if scanlines.ndim != 2 or (scanlines.shape[1] - 1) % 3 != 0 or scanlines.shape[1] < 4:
@@ -191,7 +192,7 @@ class PngWriter:
                 cs = self._copy_stream.get(dev.index)
                 if cs is None:
                     cs = self._copy_stream[dev.index] = torch.cuda.Stream(device=dev)
-                cs.wait_event(torch.cuda.current_stream(dev).record_event())
+                cs.wait_event(ready if ready is not None else torch.cuda.current_stream(dev).record_event())
                 host = slot[0][:src.numel()]
                 with torch.cuda.stream(cs):
                     host.copy_(src, non_blocking=True)
