@@ -5,7 +5,9 @@ and the per-ray reductions.  numpy fp32 restatement of
   pgdvs/models/gnt/ray_sampler.py:59-123          (sample_z_vals / sample_along_camera_ray)
   pgdvs/models/gnt/models/transformer_network.py:10-55,59-169,197-223,231-338,341-539
   pgdvs/models/gnt/renderer.py:207-300            (render_rays reductions)
-Pinned against tests/golden/gnt_small.npz (outputs of the reference modules themselves).
+  pgdvs/models/gnt/ray_sampler.py:10-56,183-212   (sample_pdf / sample_fine_pts, deterministic)
+Pinned against tests/golden/gnt_small.npz and, at the decision edges, gnt_edges_*.npz (outputs of the
+reference modules themselves).
 Only tests/, smoke() and bench.py's cpu_baseline may import this module.
 """
 from __future__ import annotations
@@ -35,6 +37,38 @@ def sample_along_camera_ray(ray_o, ray_d, depth_range, n_samples, inv_uniform=Tr
     return pts.astype(f32), z.astype(f32)
 
 
+def sample_pdf(bins, weights, n_samples):
+    """deterministic branch of ray_sampler.py:10-56.  bins[R,M+1], weights[R,M] -> samples[R,n_samples]"""
+    bins = bins.astype(f32)
+    M = weights.shape[1]
+    w = weights.astype(f32) + f32(1e-5)
+    pdf = w / w.sum(-1, keepdims=True, dtype=f32)
+    cdf = np.concatenate([np.zeros((w.shape[0], 1), f32), np.cumsum(pdf, -1, dtype=f32)], -1)  # [R,M+1]
+    u = np.broadcast_to(np.linspace(0.0, 1.0, n_samples, dtype=f32), (w.shape[0], n_samples))
+    above = (u[:, :, None] >= cdf[:, None, :M]).sum(-1)  # knots among the first M that are <= u
+    below = np.maximum(above - 1, 0)
+    take = lambda a, i: np.take_along_axis(a, i, 1)  # noqa: E731
+    denom = take(cdf, above) - take(cdf, below)
+    denom = np.where(denom < f32(1e-5), f32(1), denom)
+    t = (u - take(cdf, below)) / denom
+    return (take(bins, below) + t * (take(bins, above) - take(bins, below))).astype(f32)
+
+
+def sample_fine_z(inv_uniform, n_importance, weights, z_vals):
+    """ray_sampler.py:183-212, deterministic: the sorted union of the coarse depths and n_importance depths drawn
+    from the coarse weights"""
+    z_vals = z_vals.astype(f32)
+    w = weights[:, 1:-1]
+    if inv_uniform:
+        inv = f32(1) / z_vals
+        mid = f32(0.5) * (inv[:, 1:] + inv[:, :-1])
+        zs = f32(1) / sample_pdf(mid[:, ::-1], w[:, ::-1], n_importance)
+    else:
+        mid = f32(0.5) * (z_vals[:, 1:] + z_vals[:, :-1])
+        zs = sample_pdf(mid, w, n_importance)
+    return np.sort(np.concatenate([z_vals, zs.astype(f32)], -1), -1)
+
+
 # ---------------------------------------------------------------- projector (A13)
 def _grid_sample_ac(img_chw, px, py):
     """F.grid_sample(bilinear, zeros, align_corners=True) at pixel coords (px,py) of THIS map."""
@@ -57,15 +91,17 @@ def _grid_sample_ac(img_chw, px, py):
     return out
 
 
-def projector_compute(pts, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks=None):
+def projector_compute(pts, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks=None, geometry=False):
     """Projector.compute (projector.py:117-308).  pts[R,S,3]; src_rgbs[V,H,W,3];
     cams_src[V,34]; featmaps[V,C,hf,wf]; inv_masks[V,H,W,1] or None.
-    -> rgb_feat[R,S,V,3+C], ray_diff[R,S,V,4], mask_inbound[R,S,V,1], mask[R,S,V,1], mask_invalid"""
+    -> rgb_feat[R,S,V,3+C], ray_diff[R,S,V,4], mask_inbound[R,S,V,1], mask[R,S,V,1], mask_invalid;
+    with geometry also the decision quantities pix[R,S,V,2], pz[R,S,V,1] and (with masks) mval[R,S,V,1]"""
     R, S, _ = pts.shape
     V, H, W, _ = src_rgbs.shape
     flat = pts.reshape(-1, 3).astype(f32)
     h, w = f32(cams_src[0][0]), f32(cams_src[0][1])
     rgb_feat, ray_diff, m_in, m_inv = [], [], [], []
+    g_pix, g_pz, g_mv = [], [], []
     q_pos = cam_tgt[18:34].reshape(4, 4)[:3, 3].astype(f32)
     for v in range(V):
         blk = orc.cam_prep(cams_src[v])
@@ -85,9 +121,14 @@ def projector_compute(pts, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks=None
         rgb_feat.append(np.concatenate([rgb, feat], 0).T)  # [N,3+C]
         inb = (pix[:, 0] <= w - 1) & (pix[:, 0] >= 0) & (pix[:, 1] <= h - 1) & (pix[:, 1] >= 0)
         m_in.append((inb & in_front).astype(f32))
+        if geometry:
+            g_pix.append(pix)
+            g_pz.append(p[:, 2:3])
         if inv_masks is not None:
             mv = _grid_sample_ac(np.ascontiguousarray(inv_masks[v].transpose(2, 0, 1)), px_img, py_img)[0]
             m_inv.append((mv > 1e-3).astype(f32))
+            if geometry:
+                g_mv.append(mv[:, None])
         # compute_angle (:75-115)
         t_pos = cams_src[v][18:34].reshape(4, 4)[:3, 3].astype(f32)
         a = q_pos[None] - flat
@@ -107,6 +148,10 @@ def projector_compute(pts, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks=None
     else:
         out["mask_invalid"] = np.zeros_like(out["mask_inbound"])
         out["mask"] = out["mask_inbound"]
+    if geometry:
+        out.update(pix=st(g_pix, 2), pz=st(g_pz, 1))
+        if inv_masks is not None:
+            out["mval"] = st(g_mv, 1)
     return out
 
 
@@ -229,16 +274,28 @@ def gnt_forward(Wt, rgb_feat, ray_diff, mask, pts, ray_d):
     return np.concatenate([rgb, weights], 1).astype(f32), extras
 
 
-def render_rays(Wt, ray_o, ray_d, depth_range, n_samples, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks=None):
-    """render_rays coarse outputs (renderer.py:207-300) for rays of one batch item."""
+def render_rays(Wt, ray_o, ray_d, depth_range, n_samples, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks=None,
+                inv_uniform=True, n_fine=0, featmaps_fine=None):
+    """render_rays (renderer.py:207-412) for rays of one batch item; depth_range[1,2] or one row per ray
+    (depth_range_per_ray, :231-234).  -> the coarse outputs, or (coarse, fine) with n_fine > 0 (importance
+    re-sampling from the coarse weights and a second pass of the same network, single_net, :313-412)."""
     V = src_rgbs.shape[0]
-    pts, z = sample_along_camera_ray(ray_o, ray_d, np.broadcast_to(depth_range, (ray_o.shape[0], 2)), n_samples, True)
-    pr = projector_compute(pts, cam_tgt, src_rgbs, cams_src, featmaps, inv_masks)
-    out, ex = gnt_forward(Wt, pr["rgb_feat"], pr["ray_diff"], pr["mask"], pts, ray_d)
-    rgb, w = out[:, :3], out[:, 3:]
-    ret = {"rgb": rgb, "weights": w, "depth": (w * z).sum(-1),
-           "inbound_cnt": (w * pr["mask_inbound"][..., 0].sum(2) / f32(V)).sum(1),
-           "dyn_cnt": (w * pr["mask_invalid"][..., 0].sum(2) / f32(V)).sum(1)}
-    for k in ("view_entropy", "view_std", "view_std_normalized"):
-        ret[k] = (w[..., None] * ex[k]).sum(1)
-    return ret
+
+    def one_pass(pts, z, fm):
+        pr = projector_compute(pts, cam_tgt, src_rgbs, cams_src, fm, inv_masks)
+        out, ex = gnt_forward(Wt, pr["rgb_feat"], pr["ray_diff"], pr["mask"], pts, ray_d)
+        rgb, w = out[:, :3], out[:, 3:]
+        ret = {"rgb": rgb, "weights": w, "depth": (w * z).sum(-1),
+               "inbound_cnt": (w * pr["mask_inbound"][..., 0].sum(2) / f32(V)).sum(1),
+               "dyn_cnt": (w * pr["mask_invalid"][..., 0].sum(2) / f32(V)).sum(1)}
+        for k in ("view_entropy", "view_std", "view_std_normalized"):
+            ret[k] = (w[..., None] * ex[k]).sum(1)
+        return ret
+
+    pts, z = sample_along_camera_ray(ray_o, ray_d, np.broadcast_to(depth_range, (ray_o.shape[0], 2)), n_samples, inv_uniform)
+    coarse = one_pass(pts, z, featmaps)
+    if n_fine <= 0:
+        return coarse
+    z_all = sample_fine_z(inv_uniform, n_fine, coarse["weights"], z)
+    pts_f = (z_all[:, :, None] * ray_d[:, None, :] + ray_o[:, None, :]).astype(f32)
+    return coarse, one_pass(pts_f, z_all, featmaps if featmaps_fine is None else featmaps_fine)
