@@ -565,6 +565,31 @@ int pgdvs_nvidia_depth_range(const float *depth, const float *rays, int V, int H
                              float *depth_range, double *near_far, void *workspace, int64_t workspace_bytes,
                              pgdvs_stream_t stream);
 
+/* ---- 8f-3 NVIDIA, ZoeDepth inputs (pgdvs/datasets/nvidia_eval.py:869-945): the loader's alignment of a monocular depth
+ * prediction with the stored disparity-domain scale and shift, fused with the depth range above (:446-456).  Per pixel, in
+ * upstream's order and in the types NumPy 2 gives its three lines (the scale and shift come out of the .npz as 0-d float64
+ * arrays, which promote; NumPy 1.x would stay in float32 and is not what this entry computes):
+ *   raw_disp = 1.0 / (depth_pred + 1e-16)   float32: an add of float32(1e-16), then a correctly rounded divide
+ *   disp     = scale * raw_disp + shift     float64: multiply and add rounded separately (no fused multiply-add)
+ *   depth64  = 1 / (disp + 1e-16)           float64
+ *   depth    = float32(depth64)             round to nearest, +-inf above the float32 maximum
+ * A prediction of exactly 0 has raw_disp = 1e16; disp + 1e-16 == 0 gives inf, a negative one a negative depth; NaN
+ * predictions stay NaN (the canonical quiet NaN keeps its bits).
+ *   depth_pred [V,H,W] float32; scale_shift [V,2] HOST doubles (scale, shift per view); depth [V,H,W] float32 output
+ * With rays, inv_c2w_tgt and depth_range given (all three, or none), the range of pgdvs_nvidia_depth_range follows in the
+ * same pass over the pixels, with the world point formed from the float64 depth as upstream's float32 torch rays times a
+ * float64 numpy depth are: X = double(o) + double(d) * depth64, multiply and add rounded separately, d the float32
+ * direction of the entry above.  z, the order statistics, the NaN rule, -0.0 and the clamps are that entry's; the float64
+ * depth is never stored.  near_far (nullable) only with the range.
+ * With the three null it is the conversion alone (temporal and tracker views) and workspace may be null.
+ * V, H or W < 1, V H W >= 2^31, or H W == 1 with a range: PGDVS_ERR_INVALID; the workspace query (range path's size)
+ * returns PGDVS_ERR_INVALID for the same shapes, H W == 1 included.  One stream, no host synchronisation; the scale and
+ * shift are read before the call returns. */
+int64_t pgdvs_nvidia_zoe_depth_range_workspace_bytes(int V, int H, int W);
+int pgdvs_nvidia_zoe_depth_range(const float *depth_pred, const double *scale_shift, const float *rays, int V, int H, int W,
+                                 const double *inv_c2w_tgt, float *depth, float *depth_range, double *near_far,
+                                 void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+
 /* ---- one native call per target view -------------------------------------------------
  * PGDVSRenderer.forward with static_renderer = StaticGeoPointRenderer, dyn_render_type = "softsplat",
  * batch item of size 1, render_stride 1, no tracker (pgdvs/renderers/pgdvs_renderer.py:84-178 ->

@@ -110,6 +110,8 @@ SIGNATURES.update({
                                        _vp]),
     "pgdvs_nvidia_depth_range_workspace_bytes": (_i64, [_i, _i, _i]),
     "pgdvs_nvidia_depth_range": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "pgdvs_nvidia_zoe_depth_range_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pgdvs_nvidia_zoe_depth_range": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_png_scanlines": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "pgdvs_eval_export_scanlines": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),

@@ -4,15 +4,28 @@ Mirror of ``pgdvs.datasets.nvidia_eval.NvidiaDynEvaluationDataset``
 (pgdvs/datasets/nvidia_eval.py:59-1040) and of
 ``pgdvs.datasets.nvidia_eval_pure_geo.NvidiaDynPureGeoEvaluationDataset``
 (nvidia_eval_pure_geo.py:41-470) for the evaluation configuration the benchmark scripts
-use (raw resolution, no augmentation, DynIBaR disparities): same constructor keywords, same
-directory layout, same ``__getitem__`` keys / shapes / value conventions, so a
-``DataLoader`` over it feeds ``PGDVSRenderer.forward`` exactly like upstream's.
+use (raw resolution, no augmentation, DynIBaR disparities or aligned ZoeDepth predictions):
+same constructor keywords, same directory layout, same ``__getitem__`` keys / shapes / value
+conventions, so a ``DataLoader`` over it feeds ``PGDVSRenderer.forward`` exactly like upstream's.
 
-Host-side numpy + PIL only (this is input plumbing, not the hot path).  Differences, all
-outside what the golden fixture exercises: no zip containers, no ZoeDepth variants
-(``use_zoe_depth`` must be "none"), and resizes that upstream does with OpenCV (image
+Host-side numpy + PIL (this is input plumbing, not the hot path).  Differences, all outside
+what the golden fixtures exercise: resizes that upstream does with OpenCV (image
 ``INTER_AREA``, depth / evaluation mask ``INTER_NEAREST``; only taken when a file's size
 differs from the 288-row target) use PIL's BOX / NEAREST filters.
+
+ZoeDepth inputs (``use_zoe_depth`` = "moe" or one of ``{n,k,nk}_me_{med,trim}_{share,indiv}``,
+:116-160, :230-243, :869-945; evaluation loader only, the pure-geometry loader forces "none"
+and ``nvidia_vis`` refuses them): ``<zoe_depth_data_path>/<scene>/dense/zoe_depths_{n,k,nk}/
+<frame>.npz`` from a directory or from the members ``<stem>/<scene>/...`` of a zip opened
+lazily per process.  ``read_zoe_npz`` picks the file and the stored scale / shift (for "moe"
+the pair with the smallest |mean error|, ties to the first in ``zoe_k_dict``'s order),
+``zoe_align`` restates upstream's three lines.  Under NumPy 2 the stored 0-d float64 scale and
+shift promote, so the aligned depth and the spatial sources' cloud are float64 (NumPy 1.x
+would stay in float32; the fixture and the HIP op pin NumPy 2's result).  With a GPU ``device``
+a group of views whose files have the target size and the released dtypes goes through
+``ops.nvidia_zoe_depth`` instead: the spatial group gets depth and ``depth_range`` from one
+fused pass, the temporal and tracker groups the conversion alone, all bit-identical to the numpy
+path; any other file takes the numpy path for that group.
 
 The pure-geometry variant builds the static cloud once per scene with the HIP aggregator
 (``aggregate_static_pcl``) instead of upstream's numpy loop.
@@ -21,7 +34,10 @@ The per-item ``depth_range`` (:446-456) is computed in numpy with ``device=None`
 ``ops.nvidia_depth_range``, bit-identical (DESIGN.md, row 8f-3 NVIDIA), and then no host point cloud is formed.  The
 point clouds upstream computes for the temporal and tracker views and then discards are skipped on both paths.
 """
+import io
+import os
 import pathlib
+import zipfile
 from collections import defaultdict
 
 import numpy as np
@@ -34,6 +50,20 @@ from .static_aggregation import hwf_to_K
 ALL_SCENE_IDS_NVIDIA_DYN = ["Balloon1", "Balloon2", "Jumping", "Playground", "Skating", "Truck", "Umbrella", "dynamicFace"]
 N_CAMS = 12
 TGT_HEIGHT = 288
+ZOE_TYPES = ("n", "k", "nk")  # ZoeDepth checkpoints: NYU, KITTI, both
+ZOE_PRINCIPLES = ("me_med_share", "me_med_indiv", "me_trim_share", "me_trim_indiv")
+
+
+def make_zoe_k_dict():
+    """``use_zoe_depth`` key -> (model type, alignment principle), in upstream's order (:116-125)"""
+    return {f"{t}_{k}": (t, k) for t in ZOE_TYPES for k in ZOE_PRINCIPLES}
+
+
+def zoe_scale_shift_keys(principle):
+    """ZOE_DEPTH_PRINCIPLE_DICT (:39-50): ``m[a]e_<fit>_<scope>`` -> the .npz's disparity-domain scale and shift names"""
+    err, fit, scope = principle.split("_")
+    assert err in ("me", "mae") and fit in ("med", "trim") and scope in ("share", "indiv"), principle
+    return f"disp_{scope}_scale_{fit}", f"disp_{scope}_shift_{fit}"
 
 
 # ---------------------------------------------------------------------------- file formats
@@ -102,12 +132,16 @@ def ray_constants(K, c2w):
     return c32[:3, :3] @ np.linalg.inv(K32[:3, :3]).astype(np.float32), c32[:3, 3]
 
 
-def compute_pcl(h, w, K, c2w, depth):
-    """_compute_pcl (:840-847): fp32 rays through integer pixel centres times z-depth."""
+def compute_pcl(h, w, K, c2w, depth, f64_depth=False):
+    """_compute_pcl (:840-847): fp32 rays through integer pixel centres times z-depth.  ``f64_depth`` (the ZoeDepth
+    branch under NumPy 2): the float32 rays times a float64 depth promote, so the points are float64, multiply and add
+    rounded separately."""
     M, o = ray_constants(K, c2w)
     u, v = np.meshgrid(np.arange(w, dtype=np.float32), np.arange(h, dtype=np.float32))
     pix = np.stack([u.reshape(-1), v.reshape(-1), np.ones(h * w, np.float32)], 0)
     rays_d = (M @ pix).T
+    if f64_depth:
+        return o[None, :].astype(np.float64) + rays_d.astype(np.float64) * np.asarray(depth, np.float64).reshape(-1, 1)
     return o[None, :] + rays_d * np.asarray(depth, np.float32).reshape(-1, 1)
 
 
@@ -119,21 +153,31 @@ def depth_range_from_points(pcl_world, c2w_tgt):
     return np.array([max(1e-16, 0.8 * np.min(z)), max(2e-16, 1.2 * np.quantile(z, 0.9))])
 
 
-def spatial_depth_range(views, c2w_tgt, device=None, owner="NvidiaDynEvaluationDataset"):
-    """float32 depth_range[2] of the stacked spatial ``views`` (depth[V,H,W], K[V,4,4], c2w[V,4,4]) seen from ``c2w_tgt``:
-    depth_range_from_points over every view's compute_pcl with ``device=None``, else ``ops.nvidia_depth_range`` on that
-    device (bit-identical; no host points)"""
-    depths, Ks, c2ws = views["depth"], views["K"], views["c2w"]
-    h, w = depths.shape[1:3]
-    if device is None:
-        pcl = np.concatenate([compute_pcl(h, w, K, c2w, d) for K, c2w, d in zip(Ks, c2ws, depths)], axis=0)
-        return torch.from_numpy(np.ascontiguousarray(depth_range_from_points(pcl, c2w_tgt), dtype=np.float32))
+def _refuse_gpu_in_worker(owner):
     if torch.utils.data.get_worker_info() is not None:
         raise RuntimeError(f"{owner}(device=...) computes depth_range on the GPU, which forked DataLoader workers must not "
                            "touch: use n_dataloader_workers=0 (or device=None)")
+
+
+def ray_rows(Ks, c2ws):
+    """[V,12] float32: every view's ray_constants, M row-major then o, as the depth-range ops take them"""
+    return np.stack([np.concatenate([M.reshape(-1), o]) for M, o in (ray_constants(K, c2w) for K, c2w in zip(Ks, c2ws))])
+
+
+def spatial_depth_range(views, c2w_tgt, device=None, owner="NvidiaDynEvaluationDataset", f64_depth=False):
+    """float32 depth_range[2] of the stacked spatial ``views`` (depth[V,H,W], K[V,4,4], c2w[V,4,4]) seen from ``c2w_tgt``:
+    depth_range_from_points over every view's compute_pcl with ``device=None``, else ``ops.nvidia_depth_range`` on that
+    device (bit-identical; no host points).  ``f64_depth``: the ZoeDepth branch's float64 depths, always in numpy (its
+    device path is the fused ``ops.nvidia_zoe_depth``, which starts from the predictions)."""
+    depths, Ks, c2ws = views["depth"], views["K"], views["c2w"]
+    h, w = depths.shape[1:3]
+    if device is None or f64_depth:
+        pcl = np.concatenate([compute_pcl(h, w, K, c2w, d, f64_depth) for K, c2w, d in zip(Ks, c2ws, depths)], axis=0)
+        return torch.from_numpy(np.ascontiguousarray(depth_range_from_points(pcl, c2w_tgt), dtype=np.float32))
+    _refuse_gpu_in_worker(owner)
     from .. import ops
 
-    rays = np.stack([np.concatenate([M.reshape(-1), o]) for M, o in (ray_constants(K, c2w) for K, c2w in zip(Ks, c2ws))])
+    rays = ray_rows(Ks, c2ws)
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)  # noqa: E731
     return ops.nvidia_depth_range(T(depths), T(rays), np.linalg.inv(c2w_tgt)).cpu()
 
@@ -142,6 +186,51 @@ def _resize(arr, h, w, resample):
     if arr.shape[0] == h and arr.shape[1] == w:
         return arr
     return np.array(PIL.Image.fromarray(arr).resize((w, h), resample=resample))
+
+
+def _resize_nearest_f64(arr, h, w):
+    """_resize(..., NEAREST) of a float64 image (PIL has no such mode): the filter picks pixels, so resize their indices"""
+    if arr.shape[0] == h and arr.shape[1] == w:
+        return arr
+    idx = np.arange(arr.shape[0] * arr.shape[1], dtype=np.int32).reshape(arr.shape[:2])
+    return arr.reshape(-1)[_resize(idx, h, w, PIL.Image.Resampling.NEAREST)]
+
+
+# ---------------------------------------------------------------------------- ZoeDepth files
+def _load_zoe_npz(zoe_path, zip_obj, scene_id, zoe_type, frame_id):
+    """the frame's NpzFile of one model type: a file of the directory tree, or a member of the zip (:878-939)"""
+    rel = f"{scene_id}/dense/zoe_depths_{zoe_type}/{frame_id:05d}.npz"
+    if zip_obj is None:
+        return np.load(pathlib.Path(zoe_path) / rel)
+    return np.load(io.BytesIO(zip_obj.read(f"{pathlib.Path(zoe_path).stem}/{rel}")), allow_pickle=True)
+
+
+def select_zoe_pair(zoe_path, zip_obj, scene_id, frame_id, use_zoe_depth, zoe_k_dict=None):
+    """(model type, principle) of a frame: the key's entry of ``zoe_k_dict``, or for "moe" the pair whose stored mean error
+    is smallest in magnitude, the first in the dict's order among equals (upstream's stable sort, :874-911)"""
+    zoe_k_dict = make_zoe_k_dict() if zoe_k_dict is None else zoe_k_dict
+    if use_zoe_depth != "moe":
+        return zoe_k_dict[use_zoe_depth]
+    files = {t: _load_zoe_npz(zoe_path, zip_obj, scene_id, t, frame_id) for t in {t for t, _ in zoe_k_dict.values()}}
+    errs = [(t, k, float(files[t][k])) for t, k in zoe_k_dict.values()]
+    return sorted(errs, key=lambda e: abs(e[2]))[0][:2]
+
+
+def read_zoe_npz(zoe_path, zip_obj, scene_id, frame_id, use_zoe_depth, zoe_k_dict=None, pair=None):
+    """(depth_pred [H,W], scale, shift) of a frame as stored (the released files: float32, and 0-d float64 arrays) from
+    ``zoe_path`` (a directory, or the zip behind the open ``zip_obj``), for the pair ``select_zoe_pair`` picks"""
+    zoe_type, principle = pair or select_zoe_pair(zoe_path, zip_obj, scene_id, frame_id, use_zoe_depth, zoe_k_dict)
+    info = _load_zoe_npz(zoe_path, zip_obj, scene_id, zoe_type, frame_id)
+    k_scale, k_shift = zoe_scale_shift_keys(principle)
+    return info["depth_pred"], info[k_scale], info[k_shift]
+
+
+def zoe_align(depth_pred, scale, shift):
+    """upstream's three lines (:941-943) in the types they meet: float32 disparity; under NumPy 2 the 0-d float64 scale
+    and shift promote ``disp`` and the depth to float64"""
+    raw_disp = 1.0 / (depth_pred + 1e-16)
+    disp = scale * raw_disp + shift
+    return 1 / (disp + 1e-16)
 
 
 # ---------------------------------------------------------------------------- dataset
@@ -157,8 +246,15 @@ class NvidiaDynEvaluationDataset(Dataset):
         assert not use_aug
         assert mode in ["eval"], mode
         assert rgb_range == "0_1", rgb_range
-        if use_zoe_depth != "none":
-            raise NotImplementedError("ZoeDepth inputs are not mirrored; use the DynIBaR disparities (use_zoe_depth='none')")
+        self.zoe_k_dict = make_zoe_k_dict()
+        assert use_zoe_depth in ["none", "moe"] + list(self.zoe_k_dict), f"{use_zoe_depth}, {self.zoe_k_dict.keys()}"
+        self.use_zoe_depth = use_zoe_depth
+        if use_zoe_depth != "none":  # a directory or a .zip; whichever of the two forms exists (:131-147)
+            zp = pathlib.Path(data_root) / zoe_depth_data_path
+            if not zp.exists():
+                zp = zp.parent / zp.stem if zp.suffix in [".zip"] else zp.parent / f"{zp.name}.zip"
+            assert zp.exists(), zp
+            self.zoe_depth_data_path = zp
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
         self.n_src_views_spatial = n_src_views_spatial
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
@@ -190,6 +286,43 @@ class NvidiaDynEvaluationDataset(Dataset):
     def __len__(self):
         return len(self.valid_fs)
 
+    # ------------------------------------------------------------------ ZoeDepth
+    use_zoe_depth, zoe_depth_data_path = "none", None  # (subclasses that build themselves never read ZoeDepth)
+    _zoe_zip = None  # (pid, ZipFile): opened on the first item of every process, never pickled
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop("_zoe_zip", None)
+        return state
+
+    def _zoe_zip_obj(self):
+        if not self.zoe_depth_data_path.is_file():
+            return None
+        if self._zoe_zip is None or self._zoe_zip[0] != os.getpid():
+            self._zoe_zip = (os.getpid(), zipfile.ZipFile(self.zoe_depth_data_path))
+        return self._zoe_zip[1]
+
+    def _read_zoe(self, scene_id, frame_id):
+        """read_zoe_npz of a frame; the "moe" choice is a property of the files, so it is kept per (scene, frame)"""
+        zobj, cache = self._zoe_zip_obj(), self.__dict__.setdefault("_zoe_pairs", {})
+        if (scene_id, frame_id) not in cache:
+            cache[scene_id, frame_id] = select_zoe_pair(self.zoe_depth_data_path, zobj, scene_id, frame_id, self.use_zoe_depth,
+                                                        self.zoe_k_dict)
+        return read_zoe_npz(self.zoe_depth_data_path, zobj, scene_id, frame_id, self.use_zoe_depth, self.zoe_k_dict,
+                            pair=cache[scene_id, frame_id])
+
+    def _zoe_group_on_device(self, scene_id, frame_ids, tgt_shape):
+        """(depth_pred [V,H,W] float32, scale_shift [V,2] float64) when ``ops.nvidia_zoe_depth`` serves the group: a GPU
+        ``device`` and files of the target size in the released dtypes; else None (the numpy path)"""
+        if self.use_zoe_depth == "none" or self.depth_device is None:
+            return None
+        _refuse_gpu_in_worker(type(self).__name__)
+        read = [self._read_zoe(scene_id, f) for f in frame_ids]
+        if any(p.shape != tuple(tgt_shape) or p.dtype != np.float32 or a.dtype != np.float64 or b.dtype != np.float64
+               for p, a, b in read):
+            return None
+        return np.stack([p for p, _, _ in read]), np.array([[float(a), float(b)] for _, a, b in read], np.float64)
+
     # ------------------------------------------------------------------ readers
     def _read_cam(self, scene_id):
         if scene_id not in self._cam_cache:
@@ -204,6 +337,8 @@ class NvidiaDynEvaluationDataset(Dataset):
         return _resize(m, tgt_h, tgt_w, PIL.Image.Resampling.NEAREST)  # True = dynamic
 
     def _read_depth(self, scene_id, frame_id):
+        if self.use_zoe_depth != "none":
+            return zoe_align(*self._read_zoe(scene_id, frame_id))
         return 1 / (np.load(self.depth_data_dir / scene_id / "disp" / f"{frame_id:05d}.npy") + 1e-8)
 
     def _read_flow(self, scene_id, src_frame_id, tgt_frame_id, tgt_shape):
@@ -234,17 +369,21 @@ class NvidiaDynEvaluationDataset(Dataset):
 
     # ------------------------------------------------------------------ one source view
     def _aug_c2w(self, c2w):
-        """the camera-to-world of _compute_cam_info (:947-955); upstream's augment_cam("none") inverts twice, which this
-        loader's fixture does not see"""
+        """the camera-to-world of _compute_cam_info (:947-955); upstream's augment_cam("none") inverts twice, which the
+        disparity path's fixture does not see and that path leaves out.  The ZoeDepth fixture is compared bit for bit, so
+        that branch inverts twice like upstream (and like nvidia_vis)."""
+        if self.use_zoe_depth != "none":
+            return np.linalg.inv(np.linalg.inv(c2w))
         return c2w
 
     def _src_img_f(self, scene_id, frame_id):
         """Frame i of the monocular video is camera i % 12 of time step i (:647-653)."""
         return self.scene_img_dict[scene_id][frame_id][frame_id % N_CAMS]
 
-    def _source_view(self, scene_id, frame_id, c2w, hwf, tgt_shape, with_geometry=True, img_f=None):
+    def _source_view(self, scene_id, frame_id, c2w, hwf, tgt_shape, with_geometry=True, img_f=None, depth=None):
         """image, flat camera and (optionally) dynamic mask / depth / camera matrices of an input
-        frame (:728-838); spatial_depth_range makes the world points from depth, K and c2w."""
+        frame (:728-838); spatial_depth_range makes the world points from depth, K and c2w.
+        ``depth``: taken as the view's depth in place of the file's (the ZoeDepth device path)."""
         h, w = tgt_shape
         if img_f is None:
             img_f = self._src_img_f(scene_id, frame_id)
@@ -256,14 +395,33 @@ class NvidiaDynEvaluationDataset(Dataset):
         out = {"rgb": rgb, "flat_cam": flat_cam}
         if with_geometry:
             mask = self._read_mask(scene_id, frame_id, h, w).astype(np.float32)
-            depth = _resize(self._read_depth(scene_id, frame_id), h, w, PIL.Image.Resampling.NEAREST)
+            if depth is None:
+                depth = self._read_depth(scene_id, frame_id)
+                depth = (_resize_nearest_f64(depth, h, w) if depth.dtype == np.float64 and self.use_zoe_depth != "none" else
+                         _resize(depth, h, w, PIL.Image.Resampling.NEAREST))
             out.update(dyn_mask=mask, depth=depth, dyn_rgb=rgb * mask[..., None], static_rgb=rgb * (1 - mask[..., None]),
                        K=K, c2w=c2w)
         return out
 
-    def _stack_views(self, scene_id, frame_ids, all_c2w, all_hwf, tgt_shape):
-        views = [self._source_view(scene_id, f, all_c2w[f], all_hwf[f], tgt_shape) for f in frame_ids]
-        return {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
+    def _stack_views(self, scene_id, frame_ids, all_c2w, all_hwf, tgt_shape, range_c2w_tgt=None):
+        """the stacked views of ``frame_ids``.  ZoeDepth on a GPU ``device``: their depths come from one
+        ``ops.nvidia_zoe_depth`` call, with ``range_c2w_tgt`` fused with the group's ``depth_range`` (an extra key)."""
+        zoe = self._zoe_group_on_device(scene_id, frame_ids, tgt_shape)
+        preds = [None] * len(frame_ids) if zoe is None else zoe[0]
+        views = [self._source_view(scene_id, f, all_c2w[f], all_hwf[f], tgt_shape, depth=p) for f, p in zip(frame_ids, preds)]
+        out = {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
+        if zoe is not None:
+            from .. import ops
+
+            dev = self.depth_device
+            pred = torch.from_numpy(zoe[0]).to(dev)
+            if range_c2w_tgt is None:
+                out["depth"] = ops.nvidia_zoe_depth(pred, zoe[1]).cpu().numpy()
+            else:
+                rays = torch.from_numpy(ray_rows(out["K"], out["c2w"]).astype(np.float32)).to(dev)
+                depth, rng = ops.nvidia_zoe_depth(pred, zoe[1], rays, np.linalg.inv(range_c2w_tgt))
+                out["depth"], out["depth_range"] = depth.cpu().numpy(), rng.cpu()
+        return out
 
     # ------------------------------------------------------------------ item
     def _common_item(self, index):
@@ -307,13 +465,18 @@ class NvidiaDynEvaluationDataset(Dataset):
         F32, sel, scene_id = c["F32"], c["sel"], c["scene_id"]
         spatial_ids = select_spatial_frames(c["tgt_frame_id"], c["tgt_cam_id"], c["n_frames"], c["all_c2w"], self.n_src_views_spatial)
         assert self.n_src_views_spatial < N_CAMS * 2
-        spatial = self._stack_views(scene_id, spatial_ids, c["all_c2w"], c["all_hwf"], c["tgt_shape"])
+        c2w_tgt = c["all_c2w"][c["tgt_cam_id"]]
+        spatial = self._stack_views(scene_id, spatial_ids, c["all_c2w"], c["all_hwf"], c["tgt_shape"], range_c2w_tgt=c2w_tgt)
+        depth_range = spatial.get("depth_range")  # the fused ZoeDepth pass has it already
+        if depth_range is None:
+            depth_range = spatial_depth_range(spatial, c2w_tgt, self.depth_device, type(self).__name__,
+                                              f64_depth=self.use_zoe_depth != "none" and spatial["depth"].dtype == np.float64)
         item["seq_ids"] = torch.LongTensor(np.array([c["tgt_frame_id"], *spatial_ids, *sel["temporal"]]))
         item.update({
             "rgb_src_spatial": F32(spatial["rgb"]), "dyn_rgb_src_spatial": F32(spatial["dyn_rgb"]),
             "static_rgb_src_spatial": F32(spatial["static_rgb"]), "dyn_mask_src_spatial": F32(spatial["dyn_mask"])[..., None],
             "flat_cam_src_spatial": F32(spatial["flat_cam"]), "depth_src_spatial": F32(spatial["depth"])[..., None],
-            "depth_range": spatial_depth_range(spatial, c["all_c2w"][c["tgt_cam_id"]], self.depth_device, type(self).__name__),
+            "depth_range": depth_range,
         })
         for side, key in (("fwd2tgt", "n_actual_fwd2tgt"), ("bwd2tgt", "n_actual_bwd2tgt")):
             tr = self._stack_views(scene_id, sel[side], c["all_c2w"], c["all_hwf"], c["tgt_shape"])

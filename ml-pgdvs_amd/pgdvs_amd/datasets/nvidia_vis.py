@@ -47,7 +47,8 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         assert mode in ["vis"], mode
         assert rgb_range == "0_1", rgb_range
         if use_zoe_depth != "none":
-            raise NotImplementedError("ZoeDepth inputs are not mirrored; use the DynIBaR disparities (use_zoe_depth='none')")
+            raise NotImplementedError("ZoeDepth inputs are read by nvidia_eval only (upstream's visualisation loader never sets the path "
+                                      "it reads them from); use the DynIBaR disparities (use_zoe_depth='none')")
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
         self.n_src_views_spatial = n_src_views_spatial
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side

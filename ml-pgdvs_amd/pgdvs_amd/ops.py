@@ -779,6 +779,44 @@ def nvidia_depth_range(depth, rays, inv_c2w_tgt, near_far=None):
     return out
 
 
+def nvidia_zoe_depth(depth_pred, scale_shift, rays=None, inv_c2w_tgt=None, near_far=None):
+    """The NVIDIA evaluation loader's ZoeDepth alignment (``pgdvs_nvidia_zoe_depth_range``; include/pgdvs_hip.h):
+    depth_pred[V,H,W] float32 on the GPU and the numpy float64 ``scale_shift[V,2]`` (scale, shift per view) -> depth[V,H,W]
+    float32 on the GPU, bit-identical to ``datasets.nvidia_eval.zoe_align`` rounded to float32.  With ``rays[V,12]`` (float32
+    on the GPU, as in ``nvidia_depth_range``) and the target's float64 ``inv_c2w_tgt[4,4]`` it returns (depth, depth_range[2])
+    from the same pass, the range over the cloud unprojected with the float64 depth; ``near_far``: optional device float64[2]
+    for the pair before the cast.  One-pixel views are rejected on the range path only."""
+    d = _req(depth_pred, torch.float32, "depth_pred")
+    if d.ndim != 3:
+        raise ValueError(f"nvidia_zoe_depth: depth_pred [V,H,W] expected, got {tuple(d.shape)}")
+    V, H, W = (int(x) for x in d.shape)
+    ss = np.ascontiguousarray(np.asarray(scale_shift), dtype=np.float64)
+    if ss.shape != (V, 2):
+        raise ValueError(f"nvidia_zoe_depth: scale_shift {ss.shape}, expected {(V, 2)}")
+    if (rays is None) != (inv_c2w_tgt is None) or (near_far is not None and rays is None):
+        raise ValueError("nvidia_zoe_depth: rays and inv_c2w_tgt go together, near_far only with them")
+    ssv = (C.c_double * (2 * V))(*ss.reshape(-1).tolist()) if V else None
+    lib = _lib.load()
+    out = torch.empty((V, H, W), dtype=torch.float32, device=d.device)
+    if rays is None:
+        check(lib.pgdvs_nvidia_zoe_depth_range(_ptr(d), ssv, None, V, H, W, None, _ptr(out), None, None, None, 0, _stream()),
+              "pgdvs_nvidia_zoe_depth_range")
+        return out
+    r = _req(rays, torch.float32, "rays")
+    if tuple(r.shape) != (V, 12):
+        raise ValueError(f"nvidia_zoe_depth: shapes depth_pred {tuple(d.shape)}, rays {tuple(r.shape)}")
+    a = np.ascontiguousarray(np.asarray(inv_c2w_tgt), dtype=np.float64).reshape(-1)
+    assert a.size == 16, a.shape
+    mat = (C.c_double * 16)(*a.tolist())
+    if near_far is not None:
+        assert near_far.is_cuda and near_far.dtype == torch.float64 and near_far.numel() >= 2 and near_far.is_contiguous()
+    ws = _ws(lib.pgdvs_nvidia_zoe_depth_range_workspace_bytes(V, H, W), d.device)
+    rng = torch.empty((2,), dtype=torch.float32, device=d.device)
+    check(lib.pgdvs_nvidia_zoe_depth_range(_ptr(d), ssv, _ptr(r), V, H, W, mat, _ptr(out), _ptr(rng), _ptr(near_far), _ptr(ws),
+                                           ws.numel(), _stream()), "pgdvs_nvidia_zoe_depth_range")
+    return out, rng
+
+
 PNG_QUANT = {"save_image": 0, "truncate": 1}
 
 
