@@ -1,6 +1,6 @@
 // Exact order statistics of a device array of float / double keys, as numpy's partition orders them: an MSB-first radix
 // select over the keys' order-preserving bit patterns (11-bit digits: 3 passes for float, 6 for double; -0.0 counted as
-// +0.0), shared by the loaders' depth-range ops (dycheck_range.hip, nvidia_range.hip).
+// +0.0), shared by the loaders' depth-range ops (depth_range.hip).
 //
 // NR ranks run together: a histogram pass counts each key into the slot of the rank whose prefix it matches (ranks with
 // equal prefixes share a slot, distinct prefixes are disjoint, so one LDS atomic per key at most), a one-block pass of

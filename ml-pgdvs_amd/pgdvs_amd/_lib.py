@@ -74,7 +74,6 @@ SIGNATURES = {
 }
 
 
-
 class ViewGeoDesc(C.Structure):
     """``pgdvs_view_geo_desc`` (include/pgdvs_hip.h), field for field."""
     _fields_ = [

@@ -22,6 +22,9 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
+from ._common import (F32, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
+                      resize, stack_views, tracker_entries)
+
 ALL_SCENE_IDS_DYCHECK_IPHONE = ["apple", "block", "paper-windmill", "space-out", "spin", "teddy", "wheel"]
 
 
@@ -333,12 +336,6 @@ def depth_range_numpy(pcl_src_spatial, dyn_mask_src_spatial, raw_c2w_tgt, flat_c
     return depth_range.astype(np.float32)
 
 
-def _resize(arr, h, w, resample):
-    if arr.shape[0] == h and arr.shape[1] == w:
-        return arr
-    return np.array(PIL.Image.fromarray(arr).resize((w, h), resample=resample))
-
-
 # ---------------------------------------------------------------------------- dataset
 class DyCheckiPhoneEvaluationDataset(Dataset):
     dataset_name = "DyCheck iPhone Eval"
@@ -405,14 +402,14 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         cam = p.load_camera(time_id, cam_id)
         K, w2c = cam.intrin, cam.extrin
         h, w = tgt_shape
-        raw = _resize(raw, h, w, PIL.Image.Resampling.BOX)
+        raw = resize(raw, h, w, PIL.Image.Resampling.BOX)
         out = {}
         if with_geometry:
             name = p.get_frame_name(time_id, cam_id)
             m = np.array(PIL.Image.open(self.mask_data_dir / scene_id / f"masks/final/{name}_final.png"))  # True = dynamic
-            out["dyn_mask"] = _resize(m, h, w, PIL.Image.Resampling.NEAREST).astype(np.float32)
+            out["dyn_mask"] = resize(m, h, w, PIL.Image.Resampling.NEAREST).astype(np.float32)
             depth = p.load_depth(time_id, cam_id)[..., 0]
-            out["depth"] = _resize(depth, h, w, PIL.Image.Resampling.NEAREST)
+            out["depth"] = resize(depth, h, w, PIL.Image.Resampling.NEAREST)
         # base.augment_cam("none") inverts twice more: every inverse is LAPACK's float32 one, as upstream
         c2w = np.linalg.inv(np.linalg.inv(np.linalg.inv(w2c)))
         K4 = np.eye(4)
@@ -423,27 +420,20 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
             out["static_rgb"] = rgb * (1 - out["dyn_mask"][..., None])
             out["K"], out["c2w"] = K4, c2w
         out["rgb"] = rgb
-        out["flat_cam"] = np.concatenate(([rgb.shape[0], rgb.shape[1]], K4.flatten(), c2w.flatten())).astype(np.float32)
+        out["flat_cam"] = flat_cam(h, w, K4, c2w)
         return out
 
     def _stack_views(self, scene_id, time_ids, tgt_shape):
         cam_id = self.get_train_cam_id(scene_id)
-        views = [self._process_view(scene_id, t, cam_id, tgt_shape, True) for t in time_ids]
-        return {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
+        return stack_views([self._process_view(scene_id, t, cam_id, tgt_shape, True) for t in time_ids])
 
     def _read_flow(self, scene_id, src_time_id, tgt_time_id, tgt_shape):
         """:920-983 -- zeros for the placeholder pair; otherwise flows/interval_k/<a>_<b>.npz with the occlusion mask
         sum|coord_diff| > flow_consist_thres."""
-        if src_time_id == tgt_time_id:
-            return np.zeros(list(tgt_shape) + [2], np.float32), np.zeros(tgt_shape, np.float32)
         p, cam = self.parser_dict[scene_id], self.get_train_cam_id(scene_id)
         f = (self.flow_data_dir / f"{scene_id}" / f"flows/interval_{abs(tgt_time_id - src_time_id)}" /
              f"{p.get_frame_name(src_time_id, cam)}_{p.get_frame_name(tgt_time_id, cam)}.npz")
-        info = np.load(f)
-        flow = info["flow"]
-        occ = (np.sum(np.abs(info["coord_diff"]), axis=2) > self.flow_consist_thres).astype(np.float32)
-        assert flow.shape[0] == tgt_shape[0] and flow.shape[1] == tgt_shape[1], (flow.shape, tgt_shape)
-        return flow, occ
+        return read_flow_pair_or_zeros(f if src_time_id != tgt_time_id else None, tgt_shape, self.flow_consist_thres)
 
     def _depth_range(self, spatial, raw_c2w_tgt, flat_cam_tgt, near, far, tgt_shape):
         h, w = tgt_shape
@@ -451,15 +441,13 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         if self.device is None:
             pcl = np.concatenate([compute_pcl(h, w, M, o, d) for (M, o), d in zip(rays, spatial["depth"])], axis=0)
             return torch.from_numpy(depth_range_numpy(pcl, spatial["dyn_mask"], raw_c2w_tgt, flat_cam_tgt, near, far, h, w))
-        if torch.utils.data.get_worker_info() is not None:
-            raise RuntimeError("DyCheckiPhoneEvaluationDataset(device=...) computes depth_range on the GPU, which forked "
-                               "DataLoader workers must not touch: use n_dataloader_workers=0 (or device=None)")
+        refuse_gpu_in_worker(type(self).__name__)
         from .. import ops
 
         dev = self.device
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
         out = ops.dycheck_depth_range(
-            T(spatial["depth"]), T(spatial["dyn_mask"]), T(np.stack([np.concatenate([M.reshape(-1), o]) for M, o in rays])),
+            T(spatial["depth"]), T(spatial["dyn_mask"]), T(ray_rows(rays)),
             np.linalg.inv(raw_c2w_tgt), np.linalg.inv(flat_cam_tgt[18:34].reshape((4, 4))), flat_cam_tgt[2:18].reshape((4, 4))[:3, :3],
             near, far)
         return out.cpu()
@@ -482,32 +470,14 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         tgt = self._process_view(scene_id, tgt_time_id, tgt_cam_id, tgt_shape, False)
         spatial = self._stack_views(scene_id, spatial_ids, tgt_shape)
         depth_range = self._depth_range(spatial, raw_c2w_tgt, tgt["flat_cam"], p.near, p.far, tgt_shape)
-        temporal = self._stack_views(scene_id, sel["temporal"], tgt_shape)
-        fwd = self._stack_views(scene_id, sel["fwd2tgt"], tgt_shape)
-        bwd = self._stack_views(scene_id, sel["bwd2tgt"], tgt_shape)
-        flow_fwd, occ_fwd = self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape)
-        flow_bwd, occ_bwd = self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)
-        F = lambda a: torch.FloatTensor(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
-        ret = {"scene_id": scene_id, "seq_ids": torch.LongTensor(frame_ids), "rgb_tgt": F(tgt["rgb"])}
-        for sfx, v in (("spatial", spatial), ("temporal", temporal)):
-            ret.update({f"rgb_src_{sfx}": F(v["rgb"]), f"dyn_rgb_src_{sfx}": F(v["dyn_rgb"]), f"static_rgb_src_{sfx}": F(v["static_rgb"])})
-            if sfx == "spatial":
-                ret["n_actual_temporal"] = torch.LongTensor([sel["n_actual_temporal"]])
-        for side, v in (("fwd2tgt", fwd), ("bwd2tgt", bwd)):
-            s = f"src_temporal_track_{side}"
-            ret.update({f"n_actual_temporal_track_{side}": torch.LongTensor([sel[f"n_actual_{side}"]]), f"rgb_{s}": F(v["rgb"]),
-                        f"dyn_rgb_{s}": F(v["dyn_rgb"]), f"static_rgb_{s}": F(v["static_rgb"])})
-        for sfx, v in (("spatial", spatial), ("temporal", temporal), ("temporal_track_fwd2tgt", fwd), ("temporal_track_bwd2tgt", bwd)):
-            ret[f"dyn_mask_src_{sfx}"] = F(v["dyn_mask"])[..., None]
-        ret.update({"eval_mask": F(covis)[..., None], "flow_fwd": F(flow_fwd), "flow_fwd_occ_mask": F(occ_fwd)[..., None],
-                    "flow_bwd": F(flow_bwd), "flow_bwd_occ_mask": F(occ_bwd)[..., None], "flat_cam_tgt": F(tgt["flat_cam"])})
-        for sfx, v in (("spatial", spatial), ("temporal", temporal), ("temporal_track_fwd2tgt", fwd), ("temporal_track_bwd2tgt", bwd)):
-            ret[f"flat_cam_src_{sfx}"] = F(v["flat_cam"])
-        for sfx, v in (("spatial", spatial), ("temporal", temporal), ("temporal_track_fwd2tgt", fwd), ("temporal_track_bwd2tgt", bwd)):
-            ret[f"depth_src_{sfx}"] = F(v["depth"])[..., None]
-        ret.update({"depth_range": depth_range, "time_tgt": torch.FloatTensor([tgt_time_id]),
-                    "time_src_temporal": torch.FloatTensor(sel["temporal"]),
-                    "time_src_temporal_track_fwd2tgt": torch.FloatTensor(sel["fwd2tgt"]),
-                    "time_src_temporal_track_bwd2tgt": torch.FloatTensor(sel["bwd2tgt"]),
-                    "misc": {"scene_id": scene_id, "tgt_frame_id": tgt_time_id, "tgt_cam_id": tgt_cam_id, "tgt_frame_name": tgt_frame_name}})
+        stack = lambda ids: self._stack_views(scene_id, ids, tgt_shape)  # noqa: E731
+        ret = {"scene_id": scene_id, "seq_ids": torch.LongTensor(frame_ids), "rgb_tgt": F32(tgt["rgb"]),
+               "eval_mask": F32(covis)[..., None], "flat_cam_tgt": F32(tgt["flat_cam"]), "depth_range": depth_range,
+               "time_tgt": torch.FloatTensor([tgt_time_id]),
+               "misc": {"scene_id": scene_id, "tgt_frame_id": tgt_time_id, "tgt_cam_id": tgt_cam_id, "tgt_frame_name": tgt_frame_name}}
+        ret.update(group_entries("spatial", spatial))
+        ret.update(group_entries("temporal", stack(sel["temporal"]), sel["temporal"], sel["n_actual_temporal"]))
+        ret.update(flow_entries(self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape),
+                                self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)))
+        ret.update(tracker_entries(sel, stack))
         return ret

@@ -24,7 +24,8 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from .nvidia_eval import _resize, read_flow_npz, spatial_depth_range
+from ._common import F32, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views, tracker_entries
+from .nvidia_eval import spatial_depth_range
 
 N_BT_REPS = 8
 
@@ -140,26 +141,20 @@ class MonoVisualizationDataset(Dataset):
 
     def _source_view(self, scene_dir, img_f, c2w, K, tgt_shape):
         h, w = tgt_shape
-        rgb = _resize(np.array(PIL.Image.open(img_f)), h, w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0
+        rgb = resize(np.array(PIL.Image.open(img_f)), h, w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0
         name = pathlib.Path(img_f).stem
-        mask = _resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w,
+        mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w,
                        PIL.Image.Resampling.NEAREST).astype(np.float32)
-        depth = _resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
-        flat_cam = np.concatenate(([h, w], np.asarray(K).flatten(), np.asarray(c2w).flatten())).astype(np.float32)
-        return {"rgb": rgb, "flat_cam": flat_cam, "dyn_mask": mask, "depth": depth, "dyn_rgb": rgb * mask[..., None],
+        depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
+        return {"rgb": rgb, "flat_cam": flat_cam(h, w, K, c2w), "dyn_mask": mask, "depth": depth, "dyn_rgb": rgb * mask[..., None],
                 "static_rgb": rgb * (1 - mask[..., None]), "K": np.asarray(K), "c2w": np.asarray(c2w)}
 
     def _stack_views(self, scene_dir, img_fs, frame_ids, all_c2w, all_K, tgt_shape):
-        views = [self._source_view(scene_dir, img_fs[f], all_c2w[f], all_K[f], tgt_shape) for f in frame_ids]
-        return {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
+        return stack_views([self._source_view(scene_dir, img_fs[f], all_c2w[f], all_K[f], tgt_shape) for f in frame_ids])
 
     def _read_flow(self, scene_dir, img_fs, a, b, tgt_shape):
-        if a == b:
-            return np.zeros(list(tgt_shape) + [2], np.float32), np.zeros(tgt_shape, np.float32)
-        flow, occ = read_flow_npz(scene_dir / "flows" / f"interval_{abs(b - a)}" / f"{img_fs[a].stem}_{img_fs[b].stem}.npz",
-                                  self.flow_consist_thres)
-        assert flow.shape[:2] == tuple(tgt_shape), (flow.shape, tgt_shape)
-        return flow, occ
+        f = scene_dir / "flows" / f"interval_{abs(b - a)}" / f"{img_fs[a].stem}_{img_fs[b].stem}.npz"
+        return read_flow_pair_or_zeros(f if a != b else None, tgt_shape, self.flow_consist_thres)
 
     def __getitem__(self, index):
         scene_id, scene_dir, tgt_time, tgt_idx, tgt_c2w, _ = self.valid_fs[index]
@@ -173,36 +168,19 @@ class MonoVisualizationDataset(Dataset):
         spatial_ids = sorted(np.argsort(d)[: self.n_src_views_spatial].tolist())
         tgt_h, tgt_w = np.array(PIL.Image.open(img_fs[0])).shape[:2]
         shape = (tgt_h, tgt_w)
-        F32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
-        spatial = self._stack_views(scene_dir, img_fs, spatial_ids, all_c2w, all_K, shape)
-        temporal = self._stack_views(scene_dir, img_fs, sel["temporal"], all_c2w, all_K, shape)
-        flow_fwd, occ_fwd = self._read_flow(scene_dir, img_fs, sel["temporal"][0], sel["temporal"][1], shape)
-        flow_bwd, occ_bwd = self._read_flow(scene_dir, img_fs, sel["temporal"][1], sel["temporal"][0], shape)
+        stack = lambda ids: self._stack_views(scene_dir, img_fs, ids, all_c2w, all_K, shape)  # noqa: E731
+        spatial = stack(spatial_ids)
         item = {
             "scene_id": scene_id,
             "seq_ids": torch.LongTensor(np.array([tgt_time, *spatial_ids, *sel["temporal"]])),  # (time truncated, as upstream)
-            "rgb_src_spatial": F32(spatial["rgb"]), "dyn_rgb_src_spatial": F32(spatial["dyn_rgb"]),
-            "static_rgb_src_spatial": F32(spatial["static_rgb"]),
-            "n_actual_temporal": torch.LongTensor([sel["n_actual_temporal"]]),
-            "rgb_src_temporal": F32(temporal["rgb"]), "dyn_rgb_src_temporal": F32(temporal["dyn_rgb"]),
-            "static_rgb_src_temporal": F32(temporal["static_rgb"]),
-            "dyn_mask_src_spatial": F32(spatial["dyn_mask"])[..., None], "dyn_mask_src_temporal": F32(temporal["dyn_mask"])[..., None],
-            "flow_fwd": F32(flow_fwd), "flow_fwd_occ_mask": F32(occ_fwd)[..., None],
-            "flow_bwd": F32(flow_bwd), "flow_bwd_occ_mask": F32(occ_bwd)[..., None],
-            "flat_cam_tgt": F32(np.concatenate(([tgt_h, tgt_w], all_K[0].flatten(), tgt_c2w.flatten()))),
-            "flat_cam_src_spatial": F32(spatial["flat_cam"]), "flat_cam_src_temporal": F32(temporal["flat_cam"]),
-            "depth_src_temporal": F32(temporal["depth"])[..., None],
+            "flat_cam_tgt": F32(flat_cam(tgt_h, tgt_w, all_K[0], tgt_c2w)),
             "depth_range": spatial_depth_range(spatial, tgt_c2w, self.depth_device, type(self).__name__),
-            "time_tgt": torch.FloatTensor([tgt_time]), "time_src_temporal": torch.FloatTensor(sel["temporal"]),
+            "time_tgt": torch.FloatTensor([tgt_time]),
             "misc": {"scene_id": scene_id, "tgt_time": tgt_time, "tgt_idx": tgt_idx},
         }
-        for side, key in (("fwd2tgt", "n_actual_fwd2tgt"), ("bwd2tgt", "n_actual_bwd2tgt")):
-            tr = self._stack_views(scene_dir, img_fs, sel[side], all_c2w, all_K, shape)
-            sfx = f"src_temporal_track_{side}"
-            item.update({
-                f"n_actual_temporal_track_{side}": torch.LongTensor([sel[key]]),
-                f"rgb_{sfx}": F32(tr["rgb"]), f"dyn_rgb_{sfx}": F32(tr["dyn_rgb"]), f"static_rgb_{sfx}": F32(tr["static_rgb"]),
-                f"dyn_mask_{sfx}": F32(tr["dyn_mask"])[..., None], f"flat_cam_{sfx}": F32(tr["flat_cam"]),
-                f"depth_{sfx}": F32(tr["depth"])[..., None], f"time_{sfx}": torch.FloatTensor(sel[side]),
-            })
+        item.update(group_entries("spatial", spatial, depth=False))
+        item.update(group_entries("temporal", stack(sel["temporal"]), sel["temporal"], sel["n_actual_temporal"]))
+        item.update(flow_entries(self._read_flow(scene_dir, img_fs, sel["temporal"][0], sel["temporal"][1], shape),
+                                 self._read_flow(scene_dir, img_fs, sel["temporal"][1], sel["temporal"][0], shape)))
+        item.update(tracker_entries(sel, stack))
         return item

@@ -45,11 +45,13 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
+from ._common import (F32, TGT_HEIGHT, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
+                      read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
+from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
 from .static_aggregation import hwf_to_K
 
 ALL_SCENE_IDS_NVIDIA_DYN = ["Balloon1", "Balloon2", "Jumping", "Playground", "Skating", "Truck", "Umbrella", "dynamicFace"]
 N_CAMS = 12
-TGT_HEIGHT = 288
 ZOE_TYPES = ("n", "k", "nk")  # ZoeDepth checkpoints: NYU, KITTI, both
 ZOE_PRINCIPLES = ("me_med_share", "me_med_indiv", "me_trim_share", "me_trim_indiv")
 
@@ -81,15 +83,6 @@ def read_llff_cams(poses_bounds_path):
     c2w[:, 3, 3] = 1.0
     c2w[..., 1:3] *= -1.0
     return hwf, c2w
-
-
-def read_flow_npz(path, occ_thres=1.0):
-    """``flows/interval_k/<a>_<b>.npz`` {flow[H,W,2], coord_diff[H,W,2]} -> (flow, occlusion
-    mask = sum|coord_diff| > thres as float32) (:957-1011)."""
-    info = np.load(path)
-    flow = info["flow"]
-    occ = (np.sum(np.abs(info["coord_diff"]), axis=2) > occ_thres).astype(np.float32)
-    return flow, occ
 
 
 def select_temporal_frames(tgt_frame_id, tgt_cam_id, n_frames, n_track_one_side):
@@ -153,15 +146,9 @@ def depth_range_from_points(pcl_world, c2w_tgt):
     return np.array([max(1e-16, 0.8 * np.min(z)), max(2e-16, 1.2 * np.quantile(z, 0.9))])
 
 
-def _refuse_gpu_in_worker(owner):
-    if torch.utils.data.get_worker_info() is not None:
-        raise RuntimeError(f"{owner}(device=...) computes depth_range on the GPU, which forked DataLoader workers must not "
-                           "touch: use n_dataloader_workers=0 (or device=None)")
-
-
 def ray_rows(Ks, c2ws):
     """[V,12] float32: every view's ray_constants, M row-major then o, as the depth-range ops take them"""
-    return np.stack([np.concatenate([M.reshape(-1), o]) for M, o in (ray_constants(K, c2w) for K, c2w in zip(Ks, c2ws))])
+    return _ray_rows(ray_constants(K, c2w) for K, c2w in zip(Ks, c2ws))
 
 
 def spatial_depth_range(views, c2w_tgt, device=None, owner="NvidiaDynEvaluationDataset", f64_depth=False):
@@ -174,26 +161,10 @@ def spatial_depth_range(views, c2w_tgt, device=None, owner="NvidiaDynEvaluationD
     if device is None or f64_depth:
         pcl = np.concatenate([compute_pcl(h, w, K, c2w, d, f64_depth) for K, c2w, d in zip(Ks, c2ws, depths)], axis=0)
         return torch.from_numpy(np.ascontiguousarray(depth_range_from_points(pcl, c2w_tgt), dtype=np.float32))
-    _refuse_gpu_in_worker(owner)
+    refuse_gpu_in_worker(owner)
     from .. import ops
 
-    rays = ray_rows(Ks, c2ws)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)  # noqa: E731
-    return ops.nvidia_depth_range(T(depths), T(rays), np.linalg.inv(c2w_tgt)).cpu()
-
-
-def _resize(arr, h, w, resample):
-    if arr.shape[0] == h and arr.shape[1] == w:
-        return arr
-    return np.array(PIL.Image.fromarray(arr).resize((w, h), resample=resample))
-
-
-def _resize_nearest_f64(arr, h, w):
-    """_resize(..., NEAREST) of a float64 image (PIL has no such mode): the filter picks pixels, so resize their indices"""
-    if arr.shape[0] == h and arr.shape[1] == w:
-        return arr
-    idx = np.arange(arr.shape[0] * arr.shape[1], dtype=np.int32).reshape(arr.shape[:2])
-    return arr.reshape(-1)[_resize(idx, h, w, PIL.Image.Resampling.NEAREST)]
+    return ops.nvidia_depth_range(F32(depths).to(device), F32(ray_rows(Ks, c2ws)).to(device), np.linalg.inv(c2w_tgt)).cpu()
 
 
 # ---------------------------------------------------------------------------- ZoeDepth files
@@ -260,11 +231,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        root = pathlib.Path(data_root)
-        self.raw_data_dir, self.depth_data_dir = root / raw_data_dir, root / depth_data_dir
-        self.mask_data_dir, self.flow_data_dir = root / mask_data_dir, root / flow_data_dir
-        for d in (self.raw_data_dir, self.depth_data_dir, self.mask_data_dir, self.flow_data_dir):
-            assert d.exists(), d
+        self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
         # e.g. Balloon1/dense/mv_images/00000/cam01.jpg
@@ -282,6 +249,13 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.scene_img_dict = {k: dict(v) for k, v in self.scene_img_dict.items()}
         self.valid_fs = sorted(entries)  # same order on every worker / rank
         self._cam_cache = {}
+
+    def _set_dirs(self, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir):
+        root = pathlib.Path(data_root)
+        self.raw_data_dir, self.depth_data_dir = root / raw_data_dir, root / depth_data_dir
+        self.mask_data_dir, self.flow_data_dir = root / mask_data_dir, root / flow_data_dir
+        for d in (self.raw_data_dir, self.depth_data_dir, self.mask_data_dir, self.flow_data_dir):
+            assert d.exists(), d
 
     def __len__(self):
         return len(self.valid_fs)
@@ -316,7 +290,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         ``device`` and files of the target size in the released dtypes; else None (the numpy path)"""
         if self.use_zoe_depth == "none" or self.depth_device is None:
             return None
-        _refuse_gpu_in_worker(type(self).__name__)
+        refuse_gpu_in_worker(type(self).__name__)
         read = [self._read_zoe(scene_id, f) for f in frame_ids]
         if any(p.shape != tuple(tgt_shape) or p.dtype != np.float32 or a.dtype != np.float64 or b.dtype != np.float64
                for p, a, b in read):
@@ -342,13 +316,9 @@ class NvidiaDynEvaluationDataset(Dataset):
         return 1 / (np.load(self.depth_data_dir / scene_id / "disp" / f"{frame_id:05d}.npy") + 1e-8)
 
     def _read_flow(self, scene_id, src_frame_id, tgt_frame_id, tgt_shape):
-        if src_frame_id == tgt_frame_id:
-            return np.zeros(list(tgt_shape) + [2], np.float32), np.zeros(tgt_shape, np.float32)
         k = abs(tgt_frame_id - src_frame_id)
-        flow, occ = read_flow_npz(self.flow_data_dir / scene_id / "dense" / "flows" / f"interval_{k}" /
-                                  f"{src_frame_id:05d}_{tgt_frame_id:05d}.npz", self.flow_consist_thres)
-        assert flow.shape[:2] == tuple(tgt_shape), (flow.shape, tgt_shape)
-        return flow, occ
+        f = self.flow_data_dir / scene_id / "dense" / "flows" / f"interval_{k}" / f"{src_frame_id:05d}_{tgt_frame_id:05d}.npz"
+        return read_flow_pair_or_zeros(f if k else None, tgt_shape, self.flow_consist_thres)
 
     def _read_eval_mask(self, scene_id, frame_id, cam_id, h, w):
         f = self.raw_data_dir / scene_id / "dense" / "mv_masks" / f"{frame_id:05d}" / f"cam{cam_id + 1:02d}.png"
@@ -360,9 +330,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         video's size with LANCZOS as upstream (:367-380)"""
         raw = np.array(PIL.Image.open(img_f))
         if raw.shape[0] != TGT_HEIGHT:
-            mono = list(pathlib.Path(scene_dir).glob(f"images_*x{TGT_HEIGHT}"))
-            assert len(mono) == 1, mono
-            new_w, new_h = (int(x) for x in mono[0].name.split("images_")[1].split("x"))
+            new_h, new_w = mono_size(scene_dir)
             raw = np.array(PIL.Image.fromarray(raw).resize((new_w, new_h), resample=PIL.Image.Resampling.LANCZOS))
         assert raw.shape[0] == TGT_HEIGHT, raw.shape
         return raw
@@ -391,8 +359,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         K = np.eye(4)
         K[:3, :3] = hwf_to_K(*hwf, tgt_shape=tgt_shape)
         c2w = self._aug_c2w(np.asarray(c2w))
-        flat_cam = np.concatenate(([h, w], K.flatten(), np.asarray(c2w).flatten())).astype(np.float32)
-        out = {"rgb": rgb, "flat_cam": flat_cam}
+        out = {"rgb": rgb, "flat_cam": flat_cam(h, w, K, c2w)}
         if with_geometry:
             mask = self._read_mask(scene_id, frame_id, h, w).astype(np.float32)
             if depth is None:
@@ -409,7 +376,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         zoe = self._zoe_group_on_device(scene_id, frame_ids, tgt_shape)
         preds = [None] * len(frame_ids) if zoe is None else zoe[0]
         views = [self._source_view(scene_id, f, all_c2w[f], all_hwf[f], tgt_shape, depth=p) for f, p in zip(frame_ids, preds)]
-        out = {k: np.stack([v[k] for v in views], axis=0) for k in views[0]}
+        out = stack_views(views)
         if zoe is not None:
             from .. import ops
 
@@ -418,7 +385,7 @@ class NvidiaDynEvaluationDataset(Dataset):
             if range_c2w_tgt is None:
                 out["depth"] = ops.nvidia_zoe_depth(pred, zoe[1]).cpu().numpy()
             else:
-                rays = torch.from_numpy(ray_rows(out["K"], out["c2w"]).astype(np.float32)).to(dev)
+                rays = F32(ray_rows(out["K"], out["c2w"])).to(dev)
                 depth, rng = ops.nvidia_zoe_depth(pred, zoe[1], rays, np.linalg.inv(range_c2w_tgt))
                 out["depth"], out["depth_range"] = depth.cpu().numpy(), rng.cpu()
         return out
@@ -437,32 +404,24 @@ class NvidiaDynEvaluationDataset(Dataset):
         tgt = self._source_view(scene_id, tgt_frame_id, all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape,
                                 with_geometry=False, img_f=img_f)
         temporal = self._stack_views(scene_id, sel["temporal"], all_c2w, all_hwf, tgt_shape)
-        flow_fwd, occ_fwd = self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape)
-        flow_bwd, occ_bwd = self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)
-        T = torch.from_numpy
-        F32 = lambda a: T(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
         item = {
             "scene_id": scene_id,
             "rgb_tgt": F32(tgt["rgb"]),
-            "n_actual_temporal": torch.LongTensor([sel["n_actual_temporal"]]),
-            "rgb_src_temporal": F32(temporal["rgb"]), "dyn_rgb_src_temporal": F32(temporal["dyn_rgb"]),
-            "static_rgb_src_temporal": F32(temporal["static_rgb"]),
-            "dyn_mask_src_temporal": F32(temporal["dyn_mask"])[..., None],
             "eval_mask": F32(self._read_eval_mask(scene_id, tgt_frame_id, tgt_cam_id, raw_h, raw_w)),
-            "flow_fwd": F32(flow_fwd), "flow_fwd_occ_mask": F32(occ_fwd)[..., None],
-            "flow_bwd": F32(flow_bwd), "flow_bwd_occ_mask": F32(occ_bwd)[..., None],
-            "flat_cam_tgt": F32(tgt["flat_cam"]), "flat_cam_src_temporal": F32(temporal["flat_cam"]),
-            "depth_src_temporal": F32(temporal["depth"])[..., None],
-            "time_tgt": torch.FloatTensor([tgt_frame_id]), "time_src_temporal": torch.FloatTensor(sel["temporal"]),
+            "flat_cam_tgt": F32(tgt["flat_cam"]),
+            "time_tgt": torch.FloatTensor([tgt_frame_id]),
             "misc": {"scene_id": scene_id, "tgt_frame_id": tgt_frame_id, "tgt_cam_id": tgt_cam_id},
         }
+        item.update(group_entries("temporal", temporal, sel["temporal"], sel["n_actual_temporal"]))
+        item.update(flow_entries(self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape),
+                                 self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)))
         ctx = dict(scene_id=scene_id, tgt_frame_id=tgt_frame_id, tgt_cam_id=tgt_cam_id, all_hwf=all_hwf, all_c2w=all_c2w,
-                   n_frames=n_frames, sel=sel, tgt_shape=tgt_shape, F32=F32)
+                   n_frames=n_frames, sel=sel, tgt_shape=tgt_shape)
         return item, ctx
 
     def __getitem__(self, index):
         item, c = self._common_item(index)
-        F32, sel, scene_id = c["F32"], c["sel"], c["scene_id"]
+        sel, scene_id = c["sel"], c["scene_id"]
         spatial_ids = select_spatial_frames(c["tgt_frame_id"], c["tgt_cam_id"], c["n_frames"], c["all_c2w"], self.n_src_views_spatial)
         assert self.n_src_views_spatial < N_CAMS * 2
         c2w_tgt = c["all_c2w"][c["tgt_cam_id"]]
@@ -472,21 +431,8 @@ class NvidiaDynEvaluationDataset(Dataset):
             depth_range = spatial_depth_range(spatial, c2w_tgt, self.depth_device, type(self).__name__,
                                               f64_depth=self.use_zoe_depth != "none" and spatial["depth"].dtype == np.float64)
         item["seq_ids"] = torch.LongTensor(np.array([c["tgt_frame_id"], *spatial_ids, *sel["temporal"]]))
-        item.update({
-            "rgb_src_spatial": F32(spatial["rgb"]), "dyn_rgb_src_spatial": F32(spatial["dyn_rgb"]),
-            "static_rgb_src_spatial": F32(spatial["static_rgb"]), "dyn_mask_src_spatial": F32(spatial["dyn_mask"])[..., None],
-            "flat_cam_src_spatial": F32(spatial["flat_cam"]), "depth_src_spatial": F32(spatial["depth"])[..., None],
-            "depth_range": depth_range,
-        })
-        for side, key in (("fwd2tgt", "n_actual_fwd2tgt"), ("bwd2tgt", "n_actual_bwd2tgt")):
-            tr = self._stack_views(scene_id, sel[side], c["all_c2w"], c["all_hwf"], c["tgt_shape"])
-            sfx = f"src_temporal_track_{side}"
-            item.update({
-                f"n_actual_temporal_track_{side}": torch.LongTensor([sel[key]]),
-                f"rgb_{sfx}": F32(tr["rgb"]), f"dyn_rgb_{sfx}": F32(tr["dyn_rgb"]), f"static_rgb_{sfx}": F32(tr["static_rgb"]),
-                f"dyn_mask_{sfx}": F32(tr["dyn_mask"])[..., None], f"flat_cam_{sfx}": F32(tr["flat_cam"]),
-                f"depth_{sfx}": F32(tr["depth"])[..., None], f"time_{sfx}": torch.FloatTensor(sel[side]),
-            })
+        item.update(group_entries("spatial", spatial), depth_range=depth_range)
+        item.update(tracker_entries(sel, lambda ids: self._stack_views(scene_id, ids, c["all_c2w"], c["all_hwf"], c["tgt_shape"])))
         return item
 
 
@@ -509,13 +455,12 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
     def _load_mono_video(self, scene_id):
         """frames, depths, dynamic masks and cameras of the monocular video (:183-222)"""
         scene_dir = self.raw_data_dir / scene_id / "dense"
-        mono = list(scene_dir.glob(f"images_*x{TGT_HEIGHT}"))
-        assert len(mono) == 1, mono
-        tgt_w, tgt_h = (int(x) for x in mono[0].name.split("images_")[1].split("x"))
+        tgt_h, tgt_w = mono_size(scene_dir)
         all_hwf, all_c2w = self._read_cam(scene_id)
         all_hwf[:, 0], all_hwf[:, 1] = tgt_h, tgt_w
         n = all_hwf.shape[0]
-        imgs = np.stack([_resize(np.array(PIL.Image.open(mono[0] / f"{i:05d}.png")), tgt_h, tgt_w, PIL.Image.Resampling.LANCZOS)
+        mono = scene_dir / f"images_{tgt_w}x{tgt_h}"
+        imgs = np.stack([_resize(np.array(PIL.Image.open(mono / f"{i:05d}.png")), tgt_h, tgt_w, PIL.Image.Resampling.LANCZOS)
                          for i in range(n)]).astype(np.float32) / 255.0
         depths = np.stack([self._read_depth(scene_id, i) for i in range(n)]).astype(np.float32)
         masks = np.stack([self._read_mask(scene_id, i, tgt_h, tgt_w).astype(bool) for i in range(n)])

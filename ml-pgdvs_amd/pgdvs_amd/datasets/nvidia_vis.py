@@ -13,24 +13,14 @@ source images are ``mv_images/<frame>/cam<frame % 12 + 1>.jpg``; the target came
 ``nvidia_eval.spatial_depth_range``: numpy with ``device=None``, the HIP op on a GPU ``device``.  ZoeDepth inputs are not
 mirrored (upstream's own branch reads an attribute it never sets).
 """
-import pathlib
-
 import numpy as np
-import PIL.Image
 import torch
 
+from ._common import F32, flat_cam, flow_entries, group_entries, mono_size, tracker_entries
 from .mono_vis import render_path, select_frames_for_time
 from .nvidia_eval import (ALL_SCENE_IDS_NVIDIA_DYN, N_CAMS, TGT_HEIGHT, NvidiaDynEvaluationDataset, read_llff_cams,
                           spatial_depth_range)
 from .static_aggregation import hwf_to_K
-
-
-def _mono_size(scene_dir):
-    """(h, w) of the scene's ``images_<W>x288`` directory"""
-    mono = list(pathlib.Path(scene_dir).glob(f"images_*x{TGT_HEIGHT}"))
-    assert len(mono) == 1, mono
-    w, h = (int(x) for x in mono[0].name.split("images_")[1].split("x"))
-    return h, w
 
 
 class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
@@ -54,18 +44,14 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        root = pathlib.Path(data_root)
-        self.raw_data_dir, self.depth_data_dir = root / raw_data_dir, root / depth_data_dir
-        self.mask_data_dir, self.flow_data_dir = root / mask_data_dir, root / flow_data_dir
-        for d in (self.raw_data_dir, self.depth_data_dir, self.mask_data_dir, self.flow_data_dir):
-            assert d.exists(), d
+        self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         self.c2w_dict, self.hwf_dict, self.valid_fs = {}, {}, []
         for scene in scene_ids:  # (:158-260)
             scene_dir = self.raw_data_dir / scene / "dense"
             all_hwf, all_c2w = read_llff_cams(scene_dir / "poses_bounds_cvd.npy")
             bds = np.load(scene_dir / "poses_bounds_cvd.npy", allow_pickle=True)[:, -2:].astype(np.float32)
-            all_hwf[:, 0], all_hwf[:, 1] = _mono_size(scene_dir)  # the focal stays at the stored resolution
+            all_hwf[:, 0], all_hwf[:, 1] = mono_size(scene_dir)  # the focal stays at the stored resolution
             self.c2w_dict[scene], self.hwf_dict[scene] = all_c2w.copy(), all_hwf.copy()
             for t, i, c2w in render_path(all_hwf[0, 2], all_c2w, bds[:, 0], vis_center_time=vis_center_time,
                                          n_render_frames=n_render_frames, vis_time_interval=vis_time_interval,
@@ -89,44 +75,24 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         pool = list(range(max(0, sel["temporal"][0] - N_CAMS), min(n_frames, sel["temporal"][1] + N_CAMS)))
         d = np.linalg.norm(tgt_c2w[None, :3, 3] - all_c2w[pool, :3, 3], axis=1)  # sort_poses_wrt_ref(dist_method="dist")
         spatial_ids = sorted(pool[i] for i in np.argsort(d)[: self.n_src_views_spatial])
-        tgt_shape = _mono_size(scene_dir)
+        tgt_shape = mono_size(scene_dir)
         assert tgt_shape[0] == TGT_HEIGHT, tgt_shape
         aug_c2w = self._aug_c2w(tgt_c2w)
         aug_K = np.eye(4)
         aug_K[:3, :3] = hwf_to_K(*all_hwf[0], tgt_shape=tgt_shape)
-        flat_cam_tgt = np.concatenate(([tgt_shape[0], tgt_shape[1]], aug_K.flatten(), aug_c2w.flatten())).astype(np.float32)
         stack = lambda ids: self._stack_views(scene_id, ids, all_c2w, all_hwf, tgt_shape)  # noqa: E731
         spatial = stack(spatial_ids)
-        depth_range = spatial_depth_range(spatial, aug_c2w, self.depth_device, type(self).__name__)
-        temporal = stack(sel["temporal"])
-        flow_fwd, occ_fwd = self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape)
-        flow_bwd, occ_bwd = self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)
-        F32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
         item = {
             "scene_id": scene_id,
             "seq_ids": torch.LongTensor(np.array([tgt_time, *spatial_ids, *sel["temporal"]])),  # (time truncated, as upstream)
-            "rgb_src_spatial": F32(spatial["rgb"]), "dyn_rgb_src_spatial": F32(spatial["dyn_rgb"]),
-            "static_rgb_src_spatial": F32(spatial["static_rgb"]),
-            "n_actual_temporal": torch.LongTensor([sel["n_actual_temporal"]]),
-            "rgb_src_temporal": F32(temporal["rgb"]), "dyn_rgb_src_temporal": F32(temporal["dyn_rgb"]),
-            "static_rgb_src_temporal": F32(temporal["static_rgb"]),
-            "dyn_mask_src_spatial": F32(spatial["dyn_mask"])[..., None], "dyn_mask_src_temporal": F32(temporal["dyn_mask"])[..., None],
-            "flow_fwd": F32(flow_fwd), "flow_fwd_occ_mask": F32(occ_fwd)[..., None],
-            "flow_bwd": F32(flow_bwd), "flow_bwd_occ_mask": F32(occ_bwd)[..., None],
-            "flat_cam_tgt": F32(flat_cam_tgt),
-            "flat_cam_src_spatial": F32(spatial["flat_cam"]), "flat_cam_src_temporal": F32(temporal["flat_cam"]),
-            "depth_src_temporal": F32(temporal["depth"])[..., None],
-            "depth_range": depth_range,
-            "time_tgt": torch.FloatTensor([tgt_time]), "time_src_temporal": torch.FloatTensor(sel["temporal"]),
+            "flat_cam_tgt": F32(flat_cam(*tgt_shape, aug_K, aug_c2w)),
+            "depth_range": spatial_depth_range(spatial, aug_c2w, self.depth_device, type(self).__name__),
+            "time_tgt": torch.FloatTensor([tgt_time]),
             "misc": {"scene_id": scene_id, "tgt_time": tgt_time, "tgt_idx": tgt_idx},
         }
-        for side, key in (("fwd2tgt", "n_actual_fwd2tgt"), ("bwd2tgt", "n_actual_bwd2tgt")):
-            tr = stack(sel[side])
-            sfx = f"src_temporal_track_{side}"
-            item.update({
-                f"n_actual_temporal_track_{side}": torch.LongTensor([sel[key]]),
-                f"rgb_{sfx}": F32(tr["rgb"]), f"dyn_rgb_{sfx}": F32(tr["dyn_rgb"]), f"static_rgb_{sfx}": F32(tr["static_rgb"]),
-                f"dyn_mask_{sfx}": F32(tr["dyn_mask"])[..., None], f"flat_cam_{sfx}": F32(tr["flat_cam"]),
-                f"depth_{sfx}": F32(tr["depth"])[..., None], f"time_{sfx}": torch.FloatTensor(sel[side]),
-            })
+        item.update(group_entries("spatial", spatial, depth=False))
+        item.update(group_entries("temporal", stack(sel["temporal"]), sel["temporal"], sel["n_actual_temporal"]))
+        item.update(flow_entries(self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape),
+                                 self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)))
+        item.update(tracker_entries(sel, stack))
         return item

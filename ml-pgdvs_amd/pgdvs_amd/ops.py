@@ -723,6 +723,19 @@ def dycheck_lpips(pred_planar, gt_hwc, mask_hw1, weights):
                        _ptr(p), _ptr(g), _ptr(m), H, W, _ptr(cw), _ptr(cb), _ptr(lw))[0]
 
 
+def _mat64(a, n: int):
+    """``a`` as a contiguous float64 ``c_double * n`` array (host matrices travel by value)."""
+    a = np.ascontiguousarray(np.asarray(a), dtype=np.float64).reshape(-1)
+    assert a.size == n, a.shape
+    return (C.c_double * n)(*a.tolist())
+
+
+def _out64(t):
+    """The depth-range ops' optional output, a contiguous device float64 tensor of at least two elements: its pointer or None."""
+    assert t is None or (t.is_cuda and t.dtype == torch.float64 and t.numel() >= 2 and t.is_contiguous())
+    return _ptr(t)
+
+
 def dycheck_depth_range(depth, dyn_mask, rays, inv_raw_c2w_tgt, inv_c2w_tgt, K_tgt, near, far, quantiles=None):
     """The DyCheck loader's per-pixel depth range (``pgdvs_dycheck_depth_range``; include/pgdvs_hip.h): depth[V,H,W] float32
     or float64 and dyn_mask[V,H,W] on the GPU, rays[V,12] float32 on the GPU (per view ``M`` row-major and the origin, as
@@ -738,20 +751,13 @@ def dycheck_depth_range(depth, dyn_mask, rays, inv_raw_c2w_tgt, inv_c2w_tgt, K_t
         raise ValueError(f"dycheck_depth_range: shapes depth {tuple(d.shape)}, dyn_mask {tuple(m.shape)}, rays {tuple(r.shape)}")
     V, H, W = (int(x) for x in d.shape)
     f64 = int(d.dtype == torch.float64)
-    mats = []
-    for a, n in ((inv_raw_c2w_tgt, 16), (inv_c2w_tgt, 16), (K_tgt, 9)):
-        a = np.ascontiguousarray(np.asarray(a), dtype=np.float64).reshape(-1)
-        assert a.size == n, a.shape
-        mats.append((C.c_double * n)(*a.tolist()))
-    if quantiles is not None:
-        assert quantiles.is_cuda and quantiles.dtype == torch.float64 and quantiles.numel() >= 2 and quantiles.is_contiguous()
+    mats = [_mat64(inv_raw_c2w_tgt, 16), _mat64(inv_c2w_tgt, 16), _mat64(K_tgt, 9)]
     lib = _lib.load()
     ws = _ws(lib.pgdvs_dycheck_depth_range_workspace_bytes(V, H, W, f64), d.device)
     out = torch.empty((H, W, 2), dtype=torch.float32, device=d.device)
     check(lib.pgdvs_dycheck_depth_range(_ptr(d), f64, _ptr(m), _ptr(r), V, H, W, mats[0], mats[1], mats[2], float(near), float(far),
-                                        _ptr(out), _ptr(quantiles), _ptr(ws), ws.numel(), _stream()), "pgdvs_dycheck_depth_range")
+                                        _ptr(out), _out64(quantiles), _ptr(ws), ws.numel(), _stream()), "pgdvs_dycheck_depth_range")
     return out
-
 
 
 def nvidia_depth_range(depth, rays, inv_c2w_tgt, near_far=None):
@@ -766,15 +772,11 @@ def nvidia_depth_range(depth, rays, inv_c2w_tgt, near_far=None):
     if d.ndim != 3 or tuple(r.shape) != (d.shape[0], 12):
         raise ValueError(f"nvidia_depth_range: shapes depth {tuple(d.shape)}, rays {tuple(r.shape)}")
     V, H, W = (int(x) for x in d.shape)
-    a = np.ascontiguousarray(np.asarray(inv_c2w_tgt), dtype=np.float64).reshape(-1)
-    assert a.size == 16, a.shape
-    mat = (C.c_double * 16)(*a.tolist())
-    if near_far is not None:
-        assert near_far.is_cuda and near_far.dtype == torch.float64 and near_far.numel() >= 2 and near_far.is_contiguous()
+    mat = _mat64(inv_c2w_tgt, 16)
     lib = _lib.load()
     ws = _ws(lib.pgdvs_nvidia_depth_range_workspace_bytes(V, H, W), d.device)
     out = torch.empty((2,), dtype=torch.float32, device=d.device)
-    check(lib.pgdvs_nvidia_depth_range(_ptr(d), _ptr(r), V, H, W, mat, _ptr(out), _ptr(near_far), _ptr(ws), ws.numel(),
+    check(lib.pgdvs_nvidia_depth_range(_ptr(d), _ptr(r), V, H, W, mat, _ptr(out), _out64(near_far), _ptr(ws), ws.numel(),
                                        _stream()), "pgdvs_nvidia_depth_range")
     return out
 
@@ -795,7 +797,7 @@ def nvidia_zoe_depth(depth_pred, scale_shift, rays=None, inv_c2w_tgt=None, near_
         raise ValueError(f"nvidia_zoe_depth: scale_shift {ss.shape}, expected {(V, 2)}")
     if (rays is None) != (inv_c2w_tgt is None) or (near_far is not None and rays is None):
         raise ValueError("nvidia_zoe_depth: rays and inv_c2w_tgt go together, near_far only with them")
-    ssv = (C.c_double * (2 * V))(*ss.reshape(-1).tolist()) if V else None
+    ssv = _mat64(ss, 2 * V) if V else None
     lib = _lib.load()
     out = torch.empty((V, H, W), dtype=torch.float32, device=d.device)
     if rays is None:
@@ -805,14 +807,10 @@ def nvidia_zoe_depth(depth_pred, scale_shift, rays=None, inv_c2w_tgt=None, near_
     r = _req(rays, torch.float32, "rays")
     if tuple(r.shape) != (V, 12):
         raise ValueError(f"nvidia_zoe_depth: shapes depth_pred {tuple(d.shape)}, rays {tuple(r.shape)}")
-    a = np.ascontiguousarray(np.asarray(inv_c2w_tgt), dtype=np.float64).reshape(-1)
-    assert a.size == 16, a.shape
-    mat = (C.c_double * 16)(*a.tolist())
-    if near_far is not None:
-        assert near_far.is_cuda and near_far.dtype == torch.float64 and near_far.numel() >= 2 and near_far.is_contiguous()
+    mat = _mat64(inv_c2w_tgt, 16)
     ws = _ws(lib.pgdvs_nvidia_zoe_depth_range_workspace_bytes(V, H, W), d.device)
     rng = torch.empty((2,), dtype=torch.float32, device=d.device)
-    check(lib.pgdvs_nvidia_zoe_depth_range(_ptr(d), ssv, _ptr(r), V, H, W, mat, _ptr(out), _ptr(rng), _ptr(near_far), _ptr(ws),
+    check(lib.pgdvs_nvidia_zoe_depth_range(_ptr(d), ssv, _ptr(r), V, H, W, mat, _ptr(out), _ptr(rng), _out64(near_far), _ptr(ws),
                                            ws.numel(), _stream()), "pgdvs_nvidia_zoe_depth_range")
     return out, rng
 

@@ -1,4 +1,4 @@
-"""The DyCheck loader's depth range on the MI355X (csrc/dycheck_range.hip, DESIGN.md 8f-3 DyCheck): bit-identical to the
+"""The DyCheck loader's depth range on the MI355X (csrc/depth_range.hip, DESIGN.md 8f-3 DyCheck): bit-identical to the
 numpy path on every fixture item and on a 10 x 360 x 480 scene (many points per pixel, points behind the camera, hits on the
 last row / column), the quantile stage exact against np.quantile on adversarial sets, the loader's two paths key for key,
 and a DyCheck item through the HIP renderer (GNT static branch) and eval_step(quant_type="dycheck_iphone")."""

@@ -1,4 +1,4 @@
-"""The NVIDIA-family depth range on the MI355X (csrc/nvidia_range.hip, DESIGN.md 8f-3 NVIDIA): bit-identical to the numpy
+"""The NVIDIA-family depth range on the MI355X (csrc/depth_range.hip, DESIGN.md 8f-3 NVIDIA): bit-identical to the numpy
 path (float32 depth_range and float64 near / far) on the visualisation fixture tree, on 288 x 550 scenes of 10 and 24
 views and on adversarial inputs; the three loaders' device paths item for item against their numpy paths; and an
 nvidia_vis item through PGDVSRenderer.forward (GNT static renderer, softsplat dynamic branch)."""

@@ -1,4 +1,4 @@
-"""The ZoeDepth alignment fused into the NVIDIA depth range on the MI355X (csrc/nvidia_range.hip, DESIGN.md 8f-3 NVIDIA):
+"""The ZoeDepth alignment fused into the NVIDIA depth range on the MI355X (csrc/depth_range.hip, DESIGN.md 8f-3 NVIDIA):
 bit-identical to a numpy statement written here (upstream's three lines, then the float64 unprojection and
 depth_range_from_points) and to the reference's fixture, never compared with itself: the loader's device path item for
 item, the op on shapes that are no multiple of the block and span several, edge values in one small view, the

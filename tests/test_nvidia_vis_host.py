@@ -1,6 +1,6 @@
 """The NVIDIA visualisation loader (datasets/nvidia_vis.py) against the reference's own output on a synthetic tree
 (tests/golden/make_golden_nvidia_vis.py), its place in the config surface, its argument checks, and the host-side
-contract of the NVIDIA-family depth-range op (csrc/nvidia_range.hip): the library exports it, its workspace query rejects
+contract of the NVIDIA-family depth-range op (csrc/depth_range.hip): the library exports it, its workspace query rejects
 the documented shapes, and numpy's float32 unprojection at the NVIDIA size follows the order the op follows."""
 import pathlib
 import sys

@@ -22,6 +22,7 @@ for p in (str(ROOT), str(ROOT / "ml-pgdvs_amd"), str(ROOT / "tests"), str(ROOT /
         sys.path.insert(0, p)
 
 from eval_lpips_bench import event_median  # noqa: E402
+from pgdvs_amd.datasets._common import ray_rows  # noqa: E402
 
 
 def scene(V, H, W, seed):
@@ -42,7 +43,7 @@ def host_device(s, near, far, dev):
     from pgdvs_amd import ops
 
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    rays = np.stack([np.concatenate([M.reshape(-1), o]) for M, o in s["rays"]])
+    rays = ray_rows(s["rays"])
     out = ops.dycheck_depth_range(T(s["depth"]), T(s["dyn"]), T(rays), np.linalg.inv(s["raw_c2w_tgt"]),
                                   np.linalg.inv(s["flat_cam_tgt"][18:34].reshape(4, 4)), s["K3"], near, far)
     return out.cpu().numpy()
@@ -88,7 +89,7 @@ def main():
         want = host_numpy(s, near, far)
         got = host_device(s, near, far, dev)
         T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-        rays = T(np.stack([np.concatenate([M.reshape(-1), o]) for M, o in s["rays"]]))
+        rays = T(ray_rows(s["rays"]))
         d, m = T(s["depth"]), T(s["dyn"])
         A, B = np.linalg.inv(s["raw_c2w_tgt"]), np.linalg.inv(s["flat_cam_tgt"][18:34].reshape(4, 4))
         run = lambda: ops.dycheck_depth_range(d, m, rays, A, B, s["K3"], near, far)  # noqa: E731

@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from pgdvs_amd import _lib, ops
-    from pgdvs_amd.datasets.nvidia_eval import compute_pcl, ray_constants, spatial_depth_range
+    from pgdvs_amd.datasets.nvidia_eval import compute_pcl, ray_rows, spatial_depth_range
     from test_gpu_nvidia_vis import _scene
 
     dev = torch.device("cuda:0")
@@ -42,7 +42,7 @@ def main():
         views = {"depth": depths, "K": Ks, "c2w": c2ws}
         want = spatial_depth_range(views, tgt).numpy()
         got = spatial_depth_range(views, tgt, dev).numpy()
-        rays = np.stack([np.concatenate([M.reshape(-1), o]) for M, o in (ray_constants(K, c) for K, c in zip(Ks, c2ws))])
+        rays = ray_rows(Ks, c2ws)
         d, r = torch.from_numpy(depths).to(dev), torch.from_numpy(rays.astype(np.float32)).to(dev)
         inv = np.linalg.inv(tgt)
         run = lambda: ops.nvidia_depth_range(d, r, inv)  # noqa: E731
