@@ -715,6 +715,32 @@ int pgdvs_png_scanlines(const float *img_planar, int B, int H, int W, int quant,
 int pgdvs_eval_export_scanlines(const float *pred_planar, const float *gt_hwc, const float *static_planar, int H, int W,
                                 int adaptive, uint8_t *out, pgdvs_stream_t stream);
 
+/* ---- preprocessing ---------------------------------------------------------- */
+/* Forward-backward flow consistency, both directions in ONE launch (pgdvs/preprocess/common.py:211-233 bilinear_sampler /
+ * coords_grid, :314-325 compute_occlusion(return_raw=True); compute_flow.py:335-340, 351-358: the ``coord_diff`` of the
+ * flows/interval_k/<a>_<b>.npz files): flow12[H,W,2], flow21[H,W,2] float32 (x, y), the layout the .npz stores ->
+ * coord_diff_1[H,W,2] (flow12 checked against flow21) and coord_diff_2[H,W,2] (flow21 against flow12).  Per pixel p, in
+ * float32 and upstream's operation order, every operation rounded on its own: c1 = p + flow12(p); g = 2 c1 / (W - 1) - 1
+ * (rows: H - 1); grid_sample(align_corners=True, padding zeros) of flow21 at g: ix = ((g + 1) / 2) (W - 1), weights
+ * w = ix - floor(ix) and 1 - w, the products summed nw, ne, sw, se, a corner outside the image contributing zero (not a
+ * clamped texel); coord_diff = p - (c1 + sample).  No flow value is ever turned into an address before it is known to lie
+ * in the image.  NaN flows: undefined values, no fault.  No workspace.  Pointers 8-byte aligned.
+ * Shapes: H, W >= 2 (upstream divides by W - 1), H < 2^18 - 4, H W < 2^31, else PGDVS_ERR_INVALID. */
+int pgdvs_flow_consistency(const float *flow12, const float *flow21, int H, int W, float *coord_diff_1, float *coord_diff_2,
+                           pgdvs_stream_t stream);
+/* The flow_epi motion mask of one direction in ONE launch (pgdvs/preprocess/compute_mask.py:164-181
+ * compute_epipolar_distance, :196-215 read_optical_flow, :311-338 compute_mask_epipolar_flow): flow[H,W,2] and
+ * coord_diff[H,W,2] float32 on the device, F = HOST double[9], the row-major fundamental matrix with l_2 = F p_1 (by the
+ * convention of inv_c2w_tgt above) -> mask[H,W] uint8 (0 / 1) and, unless NULL, e_dist[H,W] double, already multiplied by
+ * the consistency mask.  Per pixel p = (x, y): p2 = p + flow in float32, widened; l = F (x, y, 1); d = |p2x l0 + p2y l1 +
+ * l2| / (sqrt(l0^2 + l1^2) + 1e-8) in double; consistent = |cd0| + |cd1| <= consist_thres in float32; e_dist = d
+ * consistent; raw = e_dist > threshold.  mask = skimage's binary_opening(raw, disk(1)): erosion with the 3 x 3 cross
+ * reading SET pixels outside the image, then dilation reading CLEAR ones.  Distance, threshold, erosion and dilation are
+ * one kernel over 64 x 16 tiles with a 2-pixel halo of recomputed raw bits in LDS.  No workspace.  flow, coord_diff and
+ * e_dist 8-byte aligned.  Shapes: H, W >= 2, H < 2^18 - 4, H W < 2^31, else PGDVS_ERR_INVALID. */
+int pgdvs_epipolar_mask(const float *flow, const float *coord_diff, int H, int W, const double *F, double consist_thres,
+                        double threshold, uint8_t *mask, double *e_dist, pgdvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -815,6 +815,42 @@ def nvidia_zoe_depth(depth_pred, scale_shift, rays=None, inv_c2w_tgt=None, near_
     return out, rng
 
 
+def _flow_pair(a, b, names, what):
+    """two float32 [H,W,2] GPU tensors of one shape, H, W >= 2 (the preprocessing ops' inputs)"""
+    a, b = _req(a, torch.float32, names[0]), _req(b, torch.float32, names[1])
+    if a.ndim != 3 or a.shape[2] != 2 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise ValueError(f"{what}: shapes {names[0]} {tuple(a.shape)}, {names[1]} {tuple(b.shape)} ([H,W,2] each, one device)")
+    if a.shape[0] < 2 or a.shape[1] < 2:
+        raise ValueError(f"{what}: H, W >= 2 expected, got {tuple(a.shape)}")
+    return a, b
+
+
+def flow_consistency(flow12, flow21):
+    """Forward-backward flow consistency (``pgdvs_flow_consistency``; include/pgdvs_hip.h): flow12[H,W,2] and flow21[H,W,2]
+    float32 on the GPU -> (coord_diff_1, coord_diff_2), float32 [H,W,2] on the GPU, the ``coord_diff`` entries of
+    ``<a>_<b>.npz`` and ``<b>_<a>.npz``; both directions in one launch."""
+    a, b = _flow_pair(flow12, flow21, ("flow12", "flow21"), "flow_consistency")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    cd1, cd2 = torch.empty_like(a), torch.empty_like(a)
+    check(_lib.load().pgdvs_flow_consistency(_ptr(a), _ptr(b), H, W, _ptr(cd1), _ptr(cd2), _stream()), "pgdvs_flow_consistency")
+    return cd1, cd2
+
+
+def epipolar_mask(flow, coord_diff, F, consist_thres=1.0, threshold=1.0, want_dist=False):
+    """The ``flow_epi`` motion mask of one direction (``pgdvs_epipolar_mask``; include/pgdvs_hip.h): flow[H,W,2] and
+    coord_diff[H,W,2] float32 on the GPU, the numpy float64 fundamental matrix ``F[3,3]`` (l_2 = F p_1) -> mask[H,W] uint8
+    on the GPU: (epipolar distance x consistency > threshold) opened with ``disk(1)``.  ``want_dist``: returns
+    (mask, e_dist[H,W] float64 on the GPU), the distance already multiplied by the consistency mask."""
+    f, cd = _flow_pair(flow, coord_diff, ("flow", "coord_diff"), "epipolar_mask")
+    H, W = int(f.shape[0]), int(f.shape[1])
+    mat = _mat64(F, 9)
+    mask = torch.empty((H, W), dtype=torch.uint8, device=f.device)
+    dist = torch.empty((H, W), dtype=torch.float64, device=f.device) if want_dist else None
+    check(_lib.load().pgdvs_epipolar_mask(_ptr(f), _ptr(cd), H, W, mat, float(consist_thres), float(threshold), _ptr(mask),
+                                          _ptr(dist), _stream()), "pgdvs_epipolar_mask")
+    return (mask, dist) if want_dist else mask
+
+
 PNG_QUANT = {"save_image": 0, "truncate": 1}
 
 
