@@ -124,6 +124,8 @@ def gather_rows(src: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor) -> torc
     width = s.shape[-1]
     cap = idx.numel()
     dst = torch.empty((cap, width), dtype=torch.float32, device=s.device)
+    if s.shape[0] == 0:  # nothing to gather from (an empty tensor has no pointer to pass): the count is 0
+        return dst
     check(_lib.load().pgdvs_gather_rows(_ptr(s), _ptr(idx), _ptr(cnt), cap, width, _ptr(dst), _stream()), "pgdvs_gather_rows")
     return dst
 
@@ -204,6 +206,8 @@ def track_points(tracks, visibles, frame_kind, times, time_tgt, rgbs, depths, ca
     valid = torch.empty(max(P, 1), dtype=torch.uint8, device=t.device)
     pcl = torch.empty((max(P, 1), 3), dtype=torch.float32, device=t.device)
     rgb = torch.empty((max(P, 1), 3), dtype=torch.float32, device=t.device)
+    if P == 0:  # no track (empty tensors have no pointer to pass; the entry point launches nothing for P = 0)
+        return valid[:0], pcl[:0], rgb[:0]
     check(_lib.load().pgdvs_track_points(_ptr(t), _ptr(v), P, N, C.cast(kind, C.c_void_p), _ptr(_req(times, torch.float32, "times")),
                                          _ptr(_req(time_tgt, torch.float32, "time_tgt")), _ptr(rg),
                                          _ptr(_req(depths, torch.float32, "depths")), H, W, _ptr(_req(cams, torch.float32, "cams")),
