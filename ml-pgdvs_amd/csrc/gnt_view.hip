@@ -305,6 +305,9 @@ gnt_view_layer_kernel(const float *__restrict__ W_arg, const float *__restrict__
     // bm = (A2's bias - reference logit m) in log2 units: the logits leave the second layer's MFMAs already
     // relative to the reference (no subtraction, no bias reload per view); m itself is never needed
     float bm[16], l[16], acc[16];
+    // sk / sk2: running mean of k over the valid views and the sum of squares about it (Welford's update: one pass,
+    // and nothing lost to cancellation when the views' spread is small against their values -- sum k^2 - n mean^2 left
+    // 1e-5 of noise on the std, 1e-4 on identical views, where this form gives exactly 0)
     float sk[16], sk2[16], sabs[16], ue[16];
     load_row16(sA2b, bm, hq);
 #pragma unroll
@@ -371,10 +374,14 @@ gnt_view_layer_kernel(const float *__restrict__ W_arg, const float *__restrict__
         pack_hidden(hid, hk);
       }
       if (STATS && ok) {
+        // 1 / n to an ulp is enough: an inexact step only moves the centre the squares are summed about, by 1e-7 of d
+        // (an error of the second order in sk2), and d = 0 -- identical views -- stays exact
+        const float rn = __builtin_amdgcn_rcpf((float)(nvalid + 1));
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-          sk[t] += k[t];
-          sk2[t] = __builtin_fmaf(k[t], k[t], sk2[t]);
+          const float d = k[t] - sk[t];
+          sk[t] = __builtin_fmaf(d, rn, sk[t]);
+          sk2[t] = __builtin_fmaf(d, k[t] - sk[t], sk2[t]);
           sabs[t] += fabsf(k[t]);
         }
       }
@@ -476,8 +483,7 @@ gnt_view_layer_kernel(const float *__restrict__ W_arg, const float *__restrict__
         const float n = (float)nvalid;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-          const float mean = sk[t] / n;
-          const float var = (sk2[t] - n * mean * mean) / (n - 1.0f);
+          const float var = sk2[t] / (n - 1.0f);
           const float sdev = sqrtf(fmaxf(var, 0.0f));
           sd += sdev;
           sdn += sdev / (sabs[t] / n + 1e-6f);
