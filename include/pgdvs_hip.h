@@ -740,6 +740,45 @@ int pgdvs_flow_consistency(const float *flow12, const float *flow21, int H, int 
  * e_dist 8-byte aligned.  Shapes: H, W >= 2, H < 2^18 - 4, H W < 2^31, else PGDVS_ERR_INVALID. */
 int pgdvs_epipolar_mask(const float *flow, const float *coord_diff, int H, int W, const double *F, double consist_thres,
                         double threshold, uint8_t *mask, double *e_dist, pgdvs_stream_t stream);
+/* The ZoeDepth stage's look-ups for one frame (pgdvs/preprocess/compute_zoedepth.py:262-294; csrc/zoe_align.hip):
+ * pred_depth[H,W] and mask[H,W] float32 and pts3d[P,3] float32 on the device, w2c = HOST double[16] and K = HOST double[9],
+ * row-major -> the kept points, in ascending point order: proj_pcl[3,P] double (rows x, y, 1; the first *count entries of
+ * each row), pcl_depth_mvs[P] double, pcl_depth_pred[P] float32, index[P] int64 and the device int32 *count.  Float64
+ * throughout.  Per point: out = w2c [X,1], im = K out[:3], depth = im[2], (x, y) = im[:2] / im[2]; kept when
+ * 0 <= x < W and 0 <= y < H (:272-277), then spline(mask)(y, x) < 0.1 (:282-283), then depth > 1e-3 (:286), upstream's
+ * order, each test on the float coordinate; pcl_depth_pred = spline(pred_depth)(y, x) (:290).  spline is
+ * scipy.ndimage.map_coordinates(order=3, mode="constant") with float32 output: cubic B-spline coefficients of the whole
+ * image in double (per axis, axis 0 first: gain (1 - z)(1 - 1/z), z = sqrt(3) - 2, causal start
+ * c0 = (c0 + sum z^i (c_i + z^(n-1) c_(n-1-i))) / (1 - z^(2n-2)), anticausal start
+ * c_(n-1) = (z c_(n-2) + c_(n-1)) z / (z^2 - 1)), then 0 for a coordinate outside [0, H-1] x [0, W-1] (so also in the last
+ * fractional row and column, which pass the first test: upstream's quirk, kept), else the 4 x 4 taps with mirrored tap
+ * indices, rounded to float32 once.  The row pass works on 128-column chunks with a 40-column warm-up on either side and the
+ * start sum stops after 64 terms: both below 1e-22 of the image's scale.  No coordinate becomes an index before it is known
+ * to lie in the image; NaN coordinates are dropped.  workspace: pgdvs_zoe_sample_workspace_bytes(H, W, P) bytes, 256-byte
+ * aligned.  Shapes: H, W >= 2, H W < 2^30, 1 <= P < 2^31, else PGDVS_ERR_INVALID. */
+int64_t pgdvs_zoe_sample_workspace_bytes(int H, int W, int64_t P);
+int pgdvs_zoe_sample(const float *pred_depth, const float *mask, int H, int W, const float *pts3d, int64_t P, const double *w2c,
+                     const double *K, double *proj_pcl, double *pcl_depth_mvs, float *pcl_depth_pred, int64_t *index,
+                     int32_t *count, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+/* The scale and shift that align one frame's predicted depths with its COLMAP depths in disparity
+ * (compute_zoedepth.py:309-388): pcl_depth_pred[n] float32 and pcl_depth_mvs[n] double on the device ->
+ * fit[4] double on the device (disp_indiv_scale_med, disp_indiv_shift_med, disp_indiv_scale_trim, disp_indiv_shift_trim),
+ * flag_trim[n] uint8 (0 / 1) and the device int32 *status: bit 0 a sampled prediction < 0 or NaN, bit 1 a COLMAP depth < 0
+ * or NaN (upstream's assertions, :313-319; the outputs are then undefined).  Upstream's types under NumPy 2: nn_disp =
+ * 1 / (pred + 1e-16) and its median in float32 with 1e-16 added in float32, mvs_disp, the ratios and everything after them
+ * in double; np.median of an even count is (a + b) / 2 in the array's type; a negative scale becomes 0; np.quantile(., 0.8)
+ * by numpy's linear rule; flag_trim = diff <= threshold.  Medians and the quantile's neighbours are exact order statistics
+ * (radix select), the two means float64 tree sums of one workgroup.  workspace: pgdvs_zoe_fit_workspace_bytes(n) bytes,
+ * 256-byte aligned.  1 <= n < 2^31, else PGDVS_ERR_INVALID. */
+int64_t pgdvs_zoe_fit_workspace_bytes(int64_t n);
+int pgdvs_zoe_fit(const float *pcl_depth_pred, const double *pcl_depth_mvs, int64_t n, double *fit, uint8_t *flag_trim,
+                  int32_t *status, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+/* The error table of one frame (compute_zoedepth.py:424-465): over the samples of flag_trim[n], diff = pcl_depth_mvs -
+ * 1 / (nn_disp scale + shift) in double, nn_disp as above, for scale_shift = HOST double[4][2], the (scale, shift) of
+ * med_share, med_indiv, trim_share, trim_indiv -> errors[8] double on the device: mean |diff| of the four pairs, then mean
+ * diff of the four.  One workgroup, float64 tree sums.  No workspace.  1 <= n < 2^31, else PGDVS_ERR_INVALID. */
+int pgdvs_zoe_errors(const float *pcl_depth_pred, const double *pcl_depth_mvs, const uint8_t *flag_trim, int64_t n,
+                     const double *scale_shift, double *errors, pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

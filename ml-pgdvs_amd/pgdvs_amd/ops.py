@@ -855,6 +855,71 @@ def epipolar_mask(flow, coord_diff, F, consist_thres=1.0, threshold=1.0, want_di
     return (mask, dist) if want_dist else mask
 
 
+def zoe_sample(pred_depth, mask, pts3d, w2c, K):
+    """The ZoeDepth stage's look-ups for one frame (``pgdvs_zoe_sample``; include/pgdvs_hip.h): pred_depth[H,W], mask[H,W]
+    and pts3d[P,3] float32 on the GPU, the numpy float64 ``w2c[4,4]`` and ``K[3,3]`` -> (proj_pcl[3,n] float64,
+    pcl_depth_mvs[n] float64, pcl_depth_pred[n] float32, index[n] int64) on the GPU, the kept points in ascending order.
+    Reads the count back (one synchronisation)."""
+    d = _req(pred_depth, torch.float32, "pred_depth")
+    m = _req(mask, torch.float32, "mask")
+    p = _req(pts3d, torch.float32, "pts3d")
+    if d.ndim != 2 or tuple(m.shape) != tuple(d.shape) or p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+        raise ValueError(f"zoe_sample: shapes pred_depth {tuple(d.shape)}, mask {tuple(m.shape)}, pts3d {tuple(p.shape)}")
+    if d.shape[0] < 2 or d.shape[1] < 2:
+        raise ValueError(f"zoe_sample: H, W >= 2 expected, got {tuple(d.shape)}")
+    H, W, P = int(d.shape[0]), int(d.shape[1]), int(p.shape[0])
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_zoe_sample_workspace_bytes(H, W, P), d.device)
+    proj = torch.empty((3, P), dtype=torch.float64, device=d.device)
+    mvs = torch.empty((P,), dtype=torch.float64, device=d.device)
+    pred = torch.empty((P,), dtype=torch.float32, device=d.device)
+    index = torch.empty((P,), dtype=torch.int64, device=d.device)
+    cnt = torch.empty((1,), dtype=torch.int32, device=d.device)
+    check(lib.pgdvs_zoe_sample(_ptr(d), _ptr(m), H, W, _ptr(p), P, _mat64(w2c, 16), _mat64(K, 9), _ptr(proj), _ptr(mvs), _ptr(pred),
+                               _ptr(index), _ptr(cnt), _ptr(ws), ws.numel(), _stream()), "pgdvs_zoe_sample")
+    n = checked_count(cnt, "pgdvs_zoe_sample")
+    return proj[:, :n], mvs[:n], pred[:n], index[:n]
+
+
+def _zoe_samples(pcl_depth_pred, pcl_depth_mvs, what):
+    a, b = _req(pcl_depth_pred, torch.float32, "pcl_depth_pred").reshape(-1), _req(pcl_depth_mvs, torch.float64, "pcl_depth_mvs").reshape(-1)
+    if a.numel() != b.numel() or a.numel() < 1:
+        raise ValueError(f"{what}: {a.numel()} predicted and {b.numel()} MVS depths (one each per sample, at least one)")
+    return a, b
+
+
+def zoe_fit(pcl_depth_pred, pcl_depth_mvs):
+    """The disparity-domain scale and shift of one frame (``pgdvs_zoe_fit``; include/pgdvs_hip.h): pcl_depth_pred[n]
+    float32 and pcl_depth_mvs[n] float64 on the GPU -> (fit[4] float64: scale_med, shift_med, scale_trim, shift_trim;
+    flag_trim[n] bool; status[1] int32: bit 0 a negative prediction, bit 1 a negative MVS depth), all on the GPU."""
+    a, b = _zoe_samples(pcl_depth_pred, pcl_depth_mvs, "zoe_fit")
+    n = a.numel()
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_zoe_fit_workspace_bytes(n), a.device)
+    fit = torch.empty((4,), dtype=torch.float64, device=a.device)
+    flag = torch.empty((n,), dtype=torch.uint8, device=a.device)
+    status = torch.empty((1,), dtype=torch.int32, device=a.device)
+    check(lib.pgdvs_zoe_fit(_ptr(a), _ptr(b), n, _ptr(fit), _ptr(flag), _ptr(status), _ptr(ws), ws.numel(), _stream()), "pgdvs_zoe_fit")
+    return fit, flag.view(torch.bool), status
+
+
+def zoe_errors(pcl_depth_pred, pcl_depth_mvs, flag_trim, scale_shift):
+    """The error table of one frame (``pgdvs_zoe_errors``; include/pgdvs_hip.h): the samples and flag_trim[n] (bool or
+    uint8) on the GPU, the numpy float64 ``scale_shift[4,2]`` of med_share, med_indiv, trim_share, trim_indiv ->
+    errors[8] float64 on the GPU: the four mean absolute errors, then the four mean errors."""
+    a, b = _zoe_samples(pcl_depth_pred, pcl_depth_mvs, "zoe_errors")
+    if not isinstance(flag_trim, torch.Tensor) or not flag_trim.is_cuda:
+        raise PgdvsHipError("flag_trim: expected a GPU tensor (no CPU fallback)")
+    f = flag_trim.reshape(-1).contiguous()
+    f = f.view(torch.uint8) if f.dtype == torch.bool else _req(f, torch.uint8, "flag_trim")
+    if f.numel() != a.numel():
+        raise ValueError(f"zoe_errors: flag_trim has {f.numel()} entries for {a.numel()} samples")
+    out = torch.empty((8,), dtype=torch.float64, device=a.device)
+    check(_lib.load().pgdvs_zoe_errors(_ptr(a), _ptr(b), _ptr(f), a.numel(), _mat64(scale_shift, 8), _ptr(out), _stream()),
+          "pgdvs_zoe_errors")
+    return out
+
+
 PNG_QUANT = {"save_image": 0, "truncate": 1}
 
 
