@@ -97,6 +97,21 @@ inline hipError_t fill_async(void *ptr, unsigned char byte, size_t nbytes, hipSt
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t align_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 
+// Carves a workspace into its regions, one statement per region: take<T>(bytes) returns the current position and advances
+// by `bytes` rounded up to `align`.  A zero-byte region takes nothing: the next one starts at the same address (every layout
+// counts it so; a region that must exist clamps its own size).  base == nullptr serves the *_workspace_bytes queries: only
+// `off` means anything then.
+struct Carver {
+  char *base;
+  int64_t off = 0;
+  template <class T>
+  T *take(int64_t bytes, int64_t align = 256) {
+    T *p = reinterpret_cast<T *>(base + off);
+    off += align_up(bytes, align);
+    return p;
+  }
+};
+
 // Camera block kept in registers/SGPRs: loaded through a uniform pointer so the
 // compiler can use scalar loads.
 struct CamBlock {

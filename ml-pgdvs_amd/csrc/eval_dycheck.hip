@@ -326,13 +326,13 @@ static bool dycheck_lpips_plan(int H, int W, DlPlan &pl) {
   for (int k = 0; k < kLpLayers; ++k) {
     const int64_t hw = (int64_t)pl.net.h[k] * pl.net.w[k];
     pl.off_map[k] = o;
-    o += lpips_align256(2 * hw * 4);
+    o += align_up(2 * hw * 4, 256);
     pl.head_block0[k] = nb;
     nb += (int)((2 * hw + kDlThreads - 1) / kDlThreads);
   }
   pl.head_block0[kLpLayers] = nb;
   pl.off_part = o;
-  o += lpips_align256((int64_t)kDlFinalBlocks * kDlSums * 8);
+  o += align_up((int64_t)kDlFinalBlocks * kDlSums * 8, 256);
   pl.total = o;
   return true;
 }

@@ -1283,9 +1283,6 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
 #pragma unroll
   for (int u = 0; u < kTpqQueue; ++u) qd[u] = __builtin_inff();
   int qc = 0;
-#ifdef PGDVS_AB_TPQ_STATS
-  int dbg_acc = 0, dbg_cand = 0, dbg_flush = 0, dbg_steps = 0;
-#endif
   int k = -1;
   // the lane's current run as BYTE offsets into `sorted` (16 bytes per point; the host takes this pass only below
   // 2^27 points): the load then takes scalar base + 32-bit vector offset as it stands -- no sign extension, no
@@ -1318,13 +1315,7 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
         for (int u = kTpqQueue - 1; u > 0; --u) qd[u] = qd[u - 1];
         qd[0] = d;
         ++qc;
-#ifdef PGDVS_AB_TPQ_STATS
-        ++dbg_acc;
-#endif
       }
-#ifdef PGDVS_AB_TPQ_STATS
-      ++dbg_cand;
-#endif
     }
     if (__builtin_amdgcn_ballot_w64(qc == kTpqQueue) != 0) {
 #pragma unroll
@@ -1335,13 +1326,7 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
       }
       qc = 0;
       mx = a[KK - 1];
-#ifdef PGDVS_AB_TPQ_STATS
-      ++dbg_flush;
-#endif
     }
-#ifdef PGDVS_AB_TPQ_STATS
-    ++dbg_steps;
-#endif
     return __builtin_amdgcn_ballot_w64(v_issue || k < 9) != 0;  // anything requested or left to visit?
   };
   for (;;) {
@@ -1354,25 +1339,6 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
     __builtin_amdgcn_sched_barrier(0);
   }
   mx = a[KK - 1];
-#ifdef PGDVS_AB_TPQ_STATS
-  {  // [1] accepted candidates (all lanes), [2] candidates evaluated, [3] flushes x 64, [4] half-steps x 64, [5] max accepted per wave, summed
-    int32_t *st = open_count - 18;
-    int acc = dbg_acc, cand = dbg_cand, mxa = dbg_acc;
-    for (int off = 32; off > 0; off >>= 1) {
-      acc += __shfl_xor(acc, off, 64);
-      cand += __shfl_xor(cand, off, 64);
-      const int o = __shfl_xor(mxa, off, 64);
-      mxa = o > mxa ? o : mxa;
-    }
-    if ((tid & 63) == 0) {
-      atomicAdd(&st[1], acc);
-      atomicAdd(&st[2], cand);
-      atomicAdd(&st[3], dbg_flush);
-      atomicAdd(&st[4], dbg_steps);
-      atomicAdd(&st[5], mxa);
-    }
-  }
-#endif
   cut = mx < __builtin_inff() && mx == s_thr[tid];  // the threshold left the list short
   const float safe2 = s_safe[tid];
   const bool retry = cut && live && mx < safe2;  // (a list cut at the block's own bound is not complete anyway)
@@ -1515,7 +1481,7 @@ grid_fallback_finish_kernel(const GridParams *__restrict__ gp, const float4 *__r
 struct GridWs {
   unsigned *bbox;
   GridParams *gp;
-  int32_t *block_sums, *cell_of;
+  int32_t *cell_of;
   float4 *samples;         // [sample_blocks][kSampleSlots]: the thinned cloud behind the cell size (grid_sample_kernel)
   int32_t *sample_count;   // [sample_blocks]
   float *sample_d1;        // [kSampleMaxQueries]
@@ -1534,7 +1500,7 @@ struct GridWs {
   int32_t *stats;  // [16] ring histogram, filled only when PGDVS_KNN_STATS=1 (diagnostics)
   // second level
   GridParams *gp2;
-  int32_t *cell_count2, *cell_start2, *block_sums2;
+  int32_t *cell_count2, *cell_start2;
   float4 *sorted2;
   int32_t *fb2_count, *fb2_list;
   float *fb2_bound;
@@ -1551,77 +1517,50 @@ constexpr float kCoarseScale = 8.0f, kCoarseScaleMany = 4.0f;
 
 static GridWs grid_ws_layout(void *base, int64_t capacity, int64_t qcapacity) {
   GridWs w;
-  char *p = reinterpret_cast<char *>(base);
-  int64_t off = 0;
+  const int64_t points = capacity > 0 ? capacity : 1;
+  const int64_t cells = points < kGridMaxCells ? points : (int64_t)kGridMaxCells;  // occupied cells <= min(points, cells)
+  const int64_t occ_words = (cells + 2) * kSub;
+  const int64_t queries = qcapacity > points ? qcapacity : points;  // queries that may fall back
+  Carver c{reinterpret_cast<char *>(base)};
   // one 256-byte state block, zeroed by one memset per call: complemented bbox min, bbox max,
   // the ring histogram and the open-query counters of both levels
-  w.bbox = reinterpret_cast<unsigned *>(p + off);
-  w.stats = reinterpret_cast<int32_t *>(p + off + 128);
-  w.fb_count = reinterpret_cast<int32_t *>(p + off + 192);
-  w.fb2_count = reinterpret_cast<int32_t *>(p + off + 196);
-  w.open_count = reinterpret_cast<int32_t *>(p + off + 200);
-  w.nocc = reinterpret_cast<int32_t *>(p + off + 204);  // [2]: occupied cells, kSub x that
-  w.scan_ticket = reinterpret_cast<int32_t *>(p + off + 216);  // [2]: tile tickets of the two scans (grid_scan_kernel)
-  w.scan_error = reinterpret_cast<int32_t *>(p + off + 224);   // a look-back spin gave up: results are poisoned (NaN)
-  off += 256;
+  char *const state = c.take<char>(256);
+  w.bbox = reinterpret_cast<unsigned *>(state);
+  w.stats = reinterpret_cast<int32_t *>(state + 128);
+  w.fb_count = reinterpret_cast<int32_t *>(state + 192);
+  w.fb2_count = reinterpret_cast<int32_t *>(state + 196);
+  w.open_count = reinterpret_cast<int32_t *>(state + 200);
+  w.nocc = reinterpret_cast<int32_t *>(state + 204);  // [2]: occupied cells, kSub x that
+  w.scan_ticket = reinterpret_cast<int32_t *>(state + 216);  // [2]: tile tickets of the two scans (grid_scan_kernel)
+  w.scan_error = reinterpret_cast<int32_t *>(state + 224);   // a look-back spin gave up: results are poisoned (NaN)
   // ... and the look-back words of the two scans (grid_scan_kernel), one per tile that can occur
-  w.scan_state = reinterpret_cast<unsigned long long *>(p + off);
-  w.scan_tiles = (int)((((capacity < kGridMaxCells ? (capacity > 0 ? capacity : 1) : (int64_t)kGridMaxCells) + 2) * kSub) / kScanTile + 1);
-  off += (int64_t)w.scan_tiles * 8;
-  w.scan_state2 = reinterpret_cast<unsigned long long *>(p + off);
-  off += (int64_t)(kCoarseMaxCells / kScanTile + 2) * 8;
-  w.rank_state = reinterpret_cast<unsigned long long *>(p + off);  // [kRankBlocksMax] tagged bit counts + the ticket word
-  off += (int64_t)(kRankBlocksMax + 1) * 8;
-  off = align_up(off, 256);
-  w.state_bytes = off;
-  w.gp = reinterpret_cast<GridParams *>(p + off);
-  off += 256;
-  w.sample_blocks = (int)(((capacity > 0 ? capacity : 1) + kSampleBlock - 1) / kSampleBlock);
-  w.samples = reinterpret_cast<float4 *>(p + off);
-  off += align_up((int64_t)w.sample_blocks * kSampleSlots * 16, 256);
-  w.sample_count = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((int64_t)w.sample_blocks * 4, 256);
-  w.sample_d1 = reinterpret_cast<float *>(p + off);
-  off += align_up((int64_t)kSampleMaxQueries * 4, 256);
-  w.tab = reinterpret_cast<uint4 *>(p + off);
-  off += align_up((int64_t)kTabWords * 16, 256);
-  {  // occupied cells <= min(points, cells)
-    const int64_t occ_cap = ((capacity < kGridMaxCells ? (capacity > 0 ? capacity : 1) : (int64_t)kGridMaxCells) + 2) * kSub;
-    w.occ_count = reinterpret_cast<int32_t *>(p + off);
-    off += align_up(occ_cap * 4, 256);
-    w.occ_start = reinterpret_cast<int32_t *>(p + off);
-    off += align_up(occ_cap * 4, 256);
-  }
-  w.block_sums = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((int64_t)(kGridMaxCells / kScanTile) * 4, 256);
-  w.cell_of = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((capacity > 0 ? capacity : 1) * 4, 256);
-  w.sorted = reinterpret_cast<float4 *>(p + off);
-  off += align_up((capacity > 0 ? capacity : 1) * 16, 256);
-  const int64_t qcap = qcapacity > capacity ? qcapacity : capacity;  // queries that may fall back
-  w.fb_list = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((qcap > 0 ? qcap : 1) * 4, 256);
-  w.fb_bound = reinterpret_cast<float *>(p + off);
-  off += align_up((qcap > 0 ? qcap : 1) * 4, 256);
-  w.open_list = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((capacity > 0 ? capacity : 1) * 4, 256);
-  w.fb_partial = reinterpret_cast<float *>(p + off);
-  off += align_up((int64_t)kFbMaxSliced * kFbSlices * 64 * 4, 256);
-  w.gp2 = reinterpret_cast<GridParams *>(p + off);
-  off += 256;
-  w.cell_count2 = reinterpret_cast<int32_t *>(p + off);
-  off += align_up(((int64_t)kCoarseMaxCells + 1) * 4, 256);
-  w.cell_start2 = reinterpret_cast<int32_t *>(p + off);
-  off += align_up(((int64_t)kCoarseMaxCells + 1) * 4, 256);
-  w.block_sums2 = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((int64_t)(kGridMaxCells / kScanTile) * 4, 256);
-  w.sorted2 = reinterpret_cast<float4 *>(p + off);
-  off += align_up((capacity > 0 ? capacity : 1) * 16, 256);
-  w.fb2_list = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((qcap > 0 ? qcap : 1) * 4, 256);
-  w.fb2_bound = reinterpret_cast<float *>(p + off);
-  off += align_up((qcap > 0 ? qcap : 1) * 4, 256);
-  w.total_bytes = off;
+  w.scan_tiles = (int)(occ_words / kScanTile + 1);
+  w.scan_state = c.take<unsigned long long>((int64_t)w.scan_tiles * 8, 8);
+  w.scan_state2 = c.take<unsigned long long>((int64_t)(kCoarseMaxCells / kScanTile + 2) * 8, 8);
+  w.rank_state = c.take<unsigned long long>((int64_t)(kRankBlocksMax + 1) * 8, 8);  // [kRankBlocksMax] tagged bit counts + the ticket word
+  c.off = align_up(c.off, 256);
+  w.state_bytes = c.off;
+  w.gp = c.take<GridParams>(256);
+  w.sample_blocks = (int)cdiv(points, kSampleBlock);
+  w.samples = c.take<float4>((int64_t)w.sample_blocks * kSampleSlots * 16);
+  w.sample_count = c.take<int32_t>((int64_t)w.sample_blocks * 4);
+  w.sample_d1 = c.take<float>((int64_t)kSampleMaxQueries * 4);
+  w.tab = c.take<uint4>((int64_t)kTabWords * 16);
+  w.occ_count = c.take<int32_t>(occ_words * 4);
+  w.occ_start = c.take<int32_t>(occ_words * 4);
+  w.cell_of = c.take<int32_t>(points * 4);
+  w.sorted = c.take<float4>(points * 16);
+  w.fb_list = c.take<int32_t>(queries * 4);
+  w.fb_bound = c.take<float>(queries * 4);
+  w.open_list = c.take<int32_t>(points * 4);
+  w.fb_partial = c.take<float>((int64_t)kFbMaxSliced * kFbSlices * 64 * 4);
+  w.gp2 = c.take<GridParams>(256);
+  w.cell_count2 = c.take<int32_t>(((int64_t)kCoarseMaxCells + 1) * 4);
+  w.cell_start2 = c.take<int32_t>(((int64_t)kCoarseMaxCells + 1) * 4);
+  w.sorted2 = c.take<float4>(points * 16);
+  w.fb2_list = c.take<int32_t>(queries * 4);
+  w.fb2_bound = c.take<float>(queries * 4);
+  w.total_bytes = c.off;
   return w;
 }
 
@@ -1721,9 +1660,6 @@ static int knn_grid_search(const float *pts, const int32_t *count, int64_t capac
                reinterpret_cast<int32_t *>(ws.rank_state + kRankBlocksMax), ws.scan_error, ws.nocc);
   PGDVS_LAUNCH("grid_occ_count", grid_occ_count_kernel, dim3(gpts), dim3(256), 0, st, ws.gp, ws.cell_of,
                (const uint4 *)ws.tab, ws.occ_count);
-  const int64_t occ_cap = capacity < kGridMaxCells ? capacity : (int64_t)kGridMaxCells;
-  const int nb = (int)cdiv(occ_cap + 1, kScanTile);  // (<= kGridMaxCells / kScanTile = 1024: one pass over the block sums)
-  (void)nb;
   PGDVS_LAUNCH("grid_scan", grid_scan_kernel, dim3((unsigned)(ws.scan_tiles < kScanMaxBlocks ? ws.scan_tiles : kScanMaxBlocks)), dim3(1024), 0, st,
                ws.occ_count, (const int32_t *)(ws.nocc + 1), ws.occ_start, ws.scan_state, ws.scan_ticket, ws.scan_error);
   PGDVS_LAUNCH("grid_fill", grid_fill_kernel, dim3(gpts), dim3(256), 0, st, pts, ws.gp, ws.cell_of,
@@ -1731,11 +1667,7 @@ static int knn_grid_search(const float *pts, const int32_t *count, int64_t capac
   CellIndex ci;
   ci.start = ws.occ_start;
   ci.tab = ws.tab;
-  const bool want_stats = option_int(options().knn_stats) != 0;
-  int32_t *stats = want_stats ? ws.stats : nullptr;
-#ifdef PGDVS_AB_TPQ_STATS
-  stats = nullptr;
-#endif
+  int32_t *const stats = option_int(options().knn_stats) != 0 ? ws.stats : nullptr;
   const unsigned gq = (unsigned)(cdiv(nq_cap, 4) < 256 * 8 ? (cdiv(nq_cap, 4) > 0 ? cdiv(nq_cap, 4) : 1) : 256 * 8);
   // (option knn_no_tpq: diagnostics and tests, the wavefront-per-query search for every query)
   bool tpq = qpts == nullptr && option_int(options().knn_no_tpq) == 0 && capacity < (1ll << 27);  // (32-bit byte offsets)
@@ -1761,24 +1693,21 @@ static int knn_grid_search(const float *pts, const int32_t *count, int64_t capac
         tpq = false;
     }
   }
-  const int ring_cap_after_tpq = kRingCapAfterTpq;
   QuerySrc qs1 = qs;
   if (tpq) {  // the ring search only sees what the first pass left open
     qs1.list = ws.open_list;
     qs1.list_count = ws.open_count;
   }
   PGDVS_LAUNCH("grid_query", grid_query_kernel, dim3(gq), dim3(256), 0, st, ws.gp,
-               ws.sorted, ci, KK, qs1, avg_out, stats, tpq ? ring_cap_after_tpq : kRingCap, ws.fb_count, ws.fb_list,
+               ws.sorted, ci, KK, qs1, avg_out, stats, tpq ? kRingCapAfterTpq : kRingCap, ws.fb_count, ws.fb_list,
                ws.fb_bound);
   // Second level: the queries still open after kRingCap rings (isolated points, far from
   // everything in units of the cell size) repeat the ring search on a grid with
   // kCoarseScale-times larger cells before anything is scanned exhaustively.  All of it is
   // gated on the device-side count of open queries.
-  const int nb2 = kCoarseMaxCells / kScanTile;
   PGDVS_LAUNCH("grid2_count", grid_coarse_count_kernel, dim3(gpts), dim3(256), 0, st, pts, ws.gp, ws.bbox, ws.gp2, kCoarseScale,
                kCoarseScaleMany, (const int32_t *)ws.fb_count, qpts ? qcount : (const int32_t *)nullptr, kCoarseMaxCells, ws.cell_of,
                ws.cell_count2);
-  (void)nb2;
   PGDVS_LAUNCH("grid2_scan", grid_scan_kernel, dim3(kCoarseMaxCells / kScanTile + 1), dim3(1024), 0, st, ws.cell_count2,
                (const int32_t *)&ws.gp2->ncells, ws.cell_start2, ws.scan_state2, ws.scan_ticket + 1, ws.scan_error);
   PGDVS_LAUNCH("grid2_fill", grid_fill_kernel, dim3(gpts), dim3(256), 0, st, pts, ws.gp2, ws.cell_of,
@@ -1798,9 +1727,6 @@ static int knn_grid_search(const float *pts, const int32_t *count, int64_t capac
                qs, ws.fb2_count, ws.fb2_list, ws.fb2_bound, ws.fb_partial);
   PGDVS_LAUNCH("grid_fallback_finish", grid_fallback_finish_kernel, dim3(256), dim3(1024), 0, st, ws.gp, ws.sorted, KK, qs,
                ws.fb2_count, ws.fb2_list, ws.fb2_bound, ws.fb_partial, avg_out, (const int32_t *)ws.scan_error);
-#ifdef PGDVS_AB_TPQ_STATS
-  if (want_stats) stats = ws.stats;
-#endif
   if (stats) {  // diagnostics only (PGDVS_KNN_STATS=1): synchronises and prints the ring histogram
     int32_t hst[16], nfb = 0, nfb2 = 0;
     GridParams g1, g2;

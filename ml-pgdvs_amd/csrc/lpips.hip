@@ -271,13 +271,13 @@ bool lpips_net_plan(int H, int W, int n_img, LpipsNetPlan &pl) {
   if (pl.h[4] < 1 || pl.w[4] < 1) return false;
   int64_t o = 0;
   pl.off_x = o;
-  o += lpips_align256((int64_t)n_img * 3 * H * W * 4);
+  o += align_up((int64_t)n_img * 3 * H * W * 4, 256);
   for (int k = 0; k < kLpLayers; ++k) {
     pl.off_relu[k] = o;
-    o += lpips_align256((int64_t)n_img * kLpCout[k] * pl.h[k] * pl.w[k] * 4);
+    o += align_up((int64_t)n_img * kLpCout[k] * pl.h[k] * pl.w[k] * 4, 256);
     if (k < 2) {
       pl.off_pool[k] = o;
-      o += lpips_align256((int64_t)n_img * kLpCout[k] * pl.ph[k] * pl.pw[k] * 4);
+      o += align_up((int64_t)n_img * kLpCout[k] * pl.ph[k] * pl.pw[k] * 4, 256);
     }
   }
   pl.end = o;
@@ -294,7 +294,7 @@ static bool lpips_plan(int H, int W, LpipsPlan &pl) {
     nb += (pl.net.h[k] * pl.net.w[k] + kHdThreads - 1) / kHdThreads;
   }
   pl.head_block0[kLpLayers] = nb;
-  o += lpips_align256((int64_t)nb * kHdSums * 8);
+  o += align_up((int64_t)nb * kHdSums * 8, 256);
   pl.total = o;
   return true;
 }

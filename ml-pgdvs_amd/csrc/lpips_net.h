@@ -20,8 +20,6 @@ struct LpipsNetPlan {
   int64_t off_x, off_relu[kLpLayers], off_pool[2], end;
 };
 
-inline int64_t lpips_align256(int64_t b) { return (b + 255) / 256 * 256; }
-
 // false: the image is too small for the backbone (an empty relu5 map) or too large for the 32-bit pixel indices
 bool lpips_net_plan(int H, int W, int n_img, LpipsNetPlan &pl);
 

@@ -172,13 +172,29 @@ mesh_shade_kernel(int H, int W, const float4 *__restrict__ ndc, const int32_t *_
   if (face_out) face_out[t] = fid;
 }
 
+struct MeshWs {
+  int32_t *first;            // the first kept vertex (one word in a 256-byte block)
+  float4 *ndc;               // [P]
+  unsigned long long *zkey;  // [P]
+  int64_t total_bytes;
+};
+
+static MeshWs mesh_ws_layout(void *base, int64_t P) {
+  MeshWs w;
+  Carver c{reinterpret_cast<char *>(base)};
+  w.first = c.take<int32_t>(256);
+  w.ndc = c.take<float4>(P * 16);
+  w.zkey = c.take<unsigned long long>(P * 8);
+  w.total_bytes = c.off;
+  return w;
+}
+
 }  // namespace pgdvs
 
 using namespace pgdvs;
 
 PGDVS_API int64_t pgdvs_mesh_render_workspace_bytes(int H, int W) {
-  const int64_t P = (int64_t)H * W;
-  return 256 + align_up(P * 16, 256) + align_up(P * 8, 256);
+  return mesh_ws_layout(nullptr, (int64_t)H * W).total_bytes;
 }
 
 PGDVS_API int pgdvs_mesh_render(const float *cam_tgt, int H, int W, const uint8_t *keep, const float *pcl,
@@ -186,28 +202,25 @@ PGDVS_API int pgdvs_mesh_render(const float *cam_tgt, int H, int W, const uint8_
                                 void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
   PGDVS_REQUIRE(cam_tgt && keep && pcl && rgb && img_planar && mask, "pgdvs_mesh_render: null pointer");
   PGDVS_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < (1ll << 30), "pgdvs_mesh_render: bad shape");
-  if (!workspace || workspace_bytes < pgdvs_mesh_render_workspace_bytes(H, W)) {
+  const int64_t P = (int64_t)H * W;
+  const MeshWs ws = mesh_ws_layout(workspace, P);
+  if (!workspace || workspace_bytes < ws.total_bytes) {
     set_error("pgdvs_mesh_render: workspace too small");
     return PGDVS_ERR_WORKSPACE;
   }
   hipStream_t st = as_stream(stream);
-  const int64_t P = (int64_t)H * W;
-  char *p = reinterpret_cast<char *>(workspace);
-  int32_t *first = reinterpret_cast<int32_t *>(p);
-  float4 *ndc = reinterpret_cast<float4 *>(p + 256);
-  unsigned long long *zkey = reinterpret_cast<unsigned long long *>(p + 256 + align_up(P * 16, 256));
-  hipError_t e = hipMemsetAsync(first, 0x7f, 4, st);
-  if (e == hipSuccess) e = fill_async(zkey, 0xff, (size_t)P * 8, st);
+  hipError_t e = hipMemsetAsync(ws.first, 0x7f, 4, st);
+  if (e == hipSuccess) e = fill_async(ws.zkey, 0xff, (size_t)P * 8, st);
   if (e != hipSuccess) {
     set_error("mesh_render memset: %s", hipGetErrorString(e));
     return PGDVS_ERR_LAUNCH;
   }
   unsigned gv = (unsigned)(cdiv(P, 256) < 2048 ? cdiv(P, 256) : 2048);
-  PGDVS_LAUNCH("mesh_verts", mesh_verts_kernel, dim3(gv), dim3(256), 0, st, cam_tgt, H, W, keep, pcl, ndc, first);
+  PGDVS_LAUNCH("mesh_verts", mesh_verts_kernel, dim3(gv), dim3(256), 0, st, cam_tgt, H, W, keep, pcl, ws.ndc, ws.first);
   PGDVS_LAUNCH("mesh_faces", mesh_faces_kernel, dim3((unsigned)cdiv(2 * P, 256)), dim3(256), 0, st, H, W,
-               (const float4 *)ndc, (const int32_t *)first, zkey);
+               (const float4 *)ws.ndc, (const int32_t *)ws.first, ws.zkey);
   PGDVS_LAUNCH("mesh_shade", mesh_shade_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, st, H, W,
-               (const float4 *)ndc, (const int32_t *)first, (const unsigned long long *)zkey, rgb, img_planar, mask,
+               (const float4 *)ws.ndc, (const int32_t *)ws.first, (const unsigned long long *)ws.zkey, rgb, img_planar, mask,
                face_out);
   return check_launch("mesh_render");
 }

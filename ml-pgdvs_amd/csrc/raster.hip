@@ -54,17 +54,12 @@ __device__ __forceinline__ TileBox tile_box(const RasterCam &rc, float3 p, float
   // |i - xc| < radius in pixels, i.e. the integers of [ceil(xc - r), floor(xc + r)].  The margin only has to cover the
   // rounding of this inversion against the forward pix_to_ndc used by the tile kernel (~1e-3 px at 4k).  (A margin of
   // 1.5 px put 24 % more entries into the tile lists; until round 5 the interval was [floor(xc - r), ceil(xc + r)], one
-  // pixel more on either side: PGDVS_AB_BOX_WIDE builds.)
+  // pixel more on either side.)
   float rpx = radius * (float)W / rc.range_x + 0.0625f;
   float rpy = radius * (float)H / rc.range_y + 0.0625f;
-#ifdef PGDVS_AB_BOX_WIDE
-  float x0 = floorf(xc - rpx), x1 = ceilf(xc + rpx);
-  float y0 = floorf(yc - rpy), y1 = ceilf(yc + rpy);
-#else
   float x0 = ceilf(xc - rpx), x1 = floorf(xc + rpx);
   float y0 = ceilf(yc - rpy), y1 = floorf(yc + rpy);
   if (x1 < x0 || y1 < y0) return b;  // (a disc smaller than a pixel between two pixel centres)
-#endif
   if (x1 < 0.0f || y1 < 0.0f || x0 > (float)(W - 1) || y0 > (float)(H - 1)) return b;
   int ix0 = x0 < 0.0f ? 0 : (int)x0, iy0 = y0 < 0.0f ? 0 : (int)y0;
   int ix1 = x1 > (float)(W - 1) ? W - 1 : (int)x1, iy1 = y1 > (float)(H - 1) ? H - 1 : (int)y1;
@@ -1068,25 +1063,16 @@ struct RasterWs {
 static RasterWs raster_ws_layout(void *base, int64_t n, int H, int W, float radius) {
   RasterWs w;
   int64_t ntiles = cdiv(W, kTile) * cdiv(H, kTile);
-  char *p = reinterpret_cast<char *>(base);
-  int64_t off = 0;
-  w.tile_count = reinterpret_cast<int32_t *>(p + off);
-  off += align_up(ntiles * 4, 256);
-  w.cursor = reinterpret_cast<int32_t *>(p + off);
-  off += align_up(ntiles * 4, 256);
-  w.seg_cursor = reinterpret_cast<int32_t *>(p + off);
-  off += align_up(ntiles * 4, 256);
-  w.stats = reinterpret_cast<int32_t *>(p + off);
-  off += 256;
-  w.offsets = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((ntiles + 1) * 4, 256);
-  w.tile_bound = reinterpret_cast<float *>(p + off);
-  off += align_up(ntiles * 4, 256);
-  w.zmin = reinterpret_cast<unsigned *>(p + off);
-  off += align_up((int64_t)H * W * 4, 256);
+  Carver c{reinterpret_cast<char *>(base)};
+  w.tile_count = c.take<int32_t>(ntiles * 4);
+  w.cursor = c.take<int32_t>(ntiles * 4);
+  w.seg_cursor = c.take<int32_t>(ntiles * 4);
+  w.stats = c.take<int32_t>(256);
+  w.offsets = c.take<int32_t>((ntiles + 1) * 4);
+  w.tile_bound = c.take<float>(ntiles * 4);
+  w.zmin = c.take<unsigned>((int64_t)H * W * 4);
   w.list_capacity = (n > 0 ? n : 1) * max_tiles_per_point(radius, H, W);
-  w.lists = reinterpret_cast<float4 *>(p + off);
-  off += align_up(w.list_capacity * 16, 256);
+  w.lists = c.take<float4>(w.list_capacity * 16);
   // the direct pass's segments: only where a segment is worth more than the average list can need (images of at least a
   // few tiles; tiny test images keep the exact passes alone) and the block stays below 2 GB
   // ... and clouds the direct pass can take at all: below kSegLayoutDensity rows per pixel (the default of the runtime gate,
@@ -1100,11 +1086,10 @@ static RasterWs raster_ws_layout(void *base, int64_t n, int H, int W, float radi
     se = se < 256 ? 256 : (se > kSegEntries ? kSegEntries : se);
     if (ntiles * se * 16 <= (2ll << 30)) {
       w.seg_entries = (int)se;
-      w.seg_lists = reinterpret_cast<float4 *>(p + off);
-      off += align_up(ntiles * se * 16, 256);
+      w.seg_lists = c.take<float4>(ntiles * se * 16);
     }
   }
-  w.total_bytes = off;
+  w.total_bytes = c.off;
   return w;
 }
 

@@ -34,8 +34,6 @@
 //            with correctly rounded divisions.
 // No host synchronisation: the running point counts live on the device.
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -140,24 +138,11 @@ struct ByteStamp {  // one occupancy byte per (frame, pixel): frame 0's chip-fil
   // [1 .. 64] points whose projections the fp32 form left to the fp64 queue -- summed per workgroup in LDS and added once per
   // workgroup and frame group to word 1 + (workgroup & 63): one hot word cost every link of the chain 4 us
   unsigned *stat;
-#ifdef PGDVS_AB_CHAIN  // tools/r05_chain_cost.sh: a duplicate chain that computes everything and stores nothing
-  __device__ __forceinline__ void operator()(int f, int q) const { if (occ_all) occ_all[(int64_t)f * P + q] = 1; }
-#else
   // (frame base on the scalar unit, the pixel as an unsigned 32-bit offset: the store takes them as they are -- a 64-bit
   // f * P + q per lane cost three vector instructions per stamp)
   __device__ __forceinline__ void operator()(int f, int q) const { (occ_all + (int64_t)f * P)[(unsigned)q] = 1; }
-#endif
-};
-// (experiment, tools/r06_ab.sh with EXTRA=-DPGDVS_AB_TBS: the chain's links look at the byte before they set it -- 70 % of
-// their stamps hit bytes that frame 0's push or an earlier link has set already)
-struct ByteStampTest {
-  uint8_t *occ_all;
-  int64_t P;
-  unsigned *stat;
-  __device__ __forceinline__ void operator()(int f, int q) const {
-    uint8_t *p = occ_all + (int64_t)f * P;
-    if (p[(unsigned)q] == 0) p[(unsigned)q] = 1;
-  }
+  // (measured and dropped, round 6: links that look at the byte before they set it -- 70 % of their stamps hit bytes that
+  // frame 0's push or an earlier link has set already; docs/DESIGN_HISTORY.md)
 };
 template <class Stamp>
 __device__ __attribute__((noinline)) void mark_reference_order(const ProjF64 *__restrict__ pj, double x, double y,
@@ -782,9 +767,6 @@ agg_step_kernel(SelArgs a, uint8_t *__restrict__ occ_all, uint16_t *__restrict__
     // zeroed per call with the maps): 2-byte stores from every thread were partial writes of ~130 k cache lines per link
     const uint32_t pair = bits | ((uint32_t)__shfl_down((int)bits, 1, 8) << 16);
     const uint32_t p1 = (uint32_t)__shfl_down((int)pair, 2, 8), p2 = (uint32_t)__shfl_down((int)pair, 4, 8), p3 = (uint32_t)__shfl_down((int)pair, 6, 8);
-#ifdef PGDVS_AB_CHAIN
-    if (sel16 != nullptr)
-#endif
     if (blockIdx.y == 0 && (tid & 7) == 0 && base < Wd * 32 && (pair | p1 | p2 | p3) != 0u)
       *reinterpret_cast<uint4 *>(sel16 + (((int64_t)src * Wd * 32 + base) >> 4)) = make_uint4(pair, p1, p2, p3);
   }
@@ -803,11 +785,7 @@ agg_step_kernel(SelArgs a, uint8_t *__restrict__ occ_all, uint16_t *__restrict__
   for (uint32_t m = bits; m; m &= m - 1) s_list[slot++] = (uint16_t)((tid << 4) | __builtin_ctz(m));
   if (tid == 0) s_qn[0] = s_qn[1] = 0;
   __syncthreads();
-#ifdef PGDVS_AB_TBS
-  const ByteStampTest stamp{occ_all, (int64_t)H * W, stat};
-#else
   const ByteStamp stamp{occ_all, (int64_t)H * W, stat};
-#endif
   const float wm1 = (float)(W - 1), hm1 = (float)(H - 1);
   // Round 6: a workgroup lists ~120 pixels (60 k per link over 512 workgroups), so with one thread per listed pixel two of its
   // four wavefronts had nothing to screen -- and ran the whole frame loop on NaNs beside the other two, which walked all the
@@ -946,11 +924,6 @@ agg_rows_kernel(const uint32_t *__restrict__ sel, int64_t Wd, int tiles, const i
   }
 }
 
-#ifdef PGDVS_AB_CHAIN
-__global__ void agg_empty_kernel(int *p) {
-  if (p != nullptr && threadIdx.x == 12345) *p = 0;
-}
-#endif
 struct CamChunk {
   CamBlock c[12];
 };
@@ -1001,53 +974,38 @@ static AggWs agg_ws_layout(void *base, int S, int H, int W, int64_t capacity) {
   const int64_t P = (int64_t)H * W;
   const int64_t tiles = cdiv(P, kSelTile);
   const int64_t tiles0 = tiles;  // one look-back granule per selection tile
-  char *p = reinterpret_cast<char *>(base);
-  int64_t off = 0;
-  w.tile_cnt = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((int64_t)S * tiles * 4, 256);
+  Carver c{reinterpret_cast<char *>(base)};
+  w.tile_cnt = c.take<int32_t>((int64_t)S * tiles * 4);
   // the state block and, right behind it, the occupancy maps of frames 1 .. S-1 (frame 0 has none): ONE fill per call
   // clears both
-  w.state = p + off;
-  w.cnts = reinterpret_cast<int64_t *>(p + off);
-  off += align_up((int64_t)(S + 1) * 8, 16);
-  w.ticket = reinterpret_cast<int32_t *>(p + off);
-  off += align_up((int64_t)S * 4, 16);
-  w.error = reinterpret_cast<int32_t *>(p + off);
-  off += 16;
-  w.stat = reinterpret_cast<unsigned *>(p + off);
-  off += align_up((int64_t)kAggStatWords * 4, 16);
-  w.desc = reinterpret_cast<unsigned long long *>(p + off);
-  off += align_up(tiles0 * 8, 16);
-  off = align_up(off, 256);
-  w.state_bytes = (p + off) - w.state;
+  w.cnts = c.take<int64_t>((int64_t)(S + 1) * 8, 16);
+  w.state = reinterpret_cast<char *>(w.cnts);
+  w.ticket = c.take<int32_t>((int64_t)S * 4, 16);
+  w.error = c.take<int32_t>(16, 16);
+  w.stat = c.take<unsigned>((int64_t)kAggStatWords * 4, 16);
+  w.desc = c.take<unsigned long long>(tiles0 * 8, 16);
+  c.off = align_up(c.off, 256);
+  w.state_bytes = (c.base + c.off) - w.state;
   // occ[f][q] lives at occ + f * P + q for f >= 1; the pointer itself lies P bytes before the first map and is never
   // dereferenced for frame 0
-  w.occ = reinterpret_cast<uint8_t *>(p + off) - P;
-  off += align_up((int64_t)(S - 1) * P + 32, 256);
+  w.occ = c.take<uint8_t>((int64_t)(S - 1) * P + 32) - P;
   w.Wd = tiles * kBitTileWords;
-  w.sel = reinterpret_cast<uint32_t *>(p + off);
-  off += align_up((int64_t)S * w.Wd * 4, 256);
+  w.sel = c.take<uint32_t>((int64_t)S * w.Wd * 4);
   // (very long videos do without the staging block -- agg_rows then gathers depths and colours itself)
   w.stage_rows = nullptr;
   w.stage_cst = nullptr;
   w.step_gx = (int)align_up(cdiv(w.Wd * 32 / kStepChunkPx, kStepChunks), 8);
-  if ((int64_t)S * w.step_gx * (kStepThreads * kStepPx) * 16 <= (4ll << 30)) {
-    w.stage_rows = reinterpret_cast<float *>(p + off);
-    off += align_up((int64_t)S * w.step_gx * (kStepThreads * kStepPx) * 16, 256);
-    w.stage_cst = reinterpret_cast<uint16_t *>(p + off);
-    off += align_up((int64_t)S * w.step_gx * kStepChunks * 2, 256);
+  const int64_t stage_rows_bytes = (int64_t)S * w.step_gx * (kStepThreads * kStepPx) * 16;
+  if (stage_rows_bytes <= (4ll << 30)) {
+    w.stage_rows = c.take<float>(stage_rows_bytes);
+    w.stage_cst = c.take<uint16_t>((int64_t)S * w.step_gx * kStepChunks * 2);
   }
-  w.xyz = reinterpret_cast<float *>(p + off);
-  off += align_up((capacity > 0 ? capacity : 1) * 12, 256);
-  w.sel_pix = reinterpret_cast<int32_t *>(p + off);
-  off += align_up(P * 4, 256);
-  w.proj = reinterpret_cast<ProjF64 *>(p + off);
-  off += align_up((int64_t)S * (int64_t)sizeof(ProjF64), 256);
-  w.pc32 = reinterpret_cast<PushConsts *>(p + off);
-  off += align_up((int64_t)(S + 2) * (int64_t)sizeof(PushConsts), 256);
-  w.cams = reinterpret_cast<CamBlock *>(p + off);
-  off += align_up((int64_t)S * (int64_t)sizeof(CamBlock), 256);
-  w.total_bytes = off;
+  w.xyz = c.take<float>((capacity > 0 ? capacity : 1) * 12);
+  w.sel_pix = c.take<int32_t>(P * 4);
+  w.proj = c.take<ProjF64>((int64_t)S * (int64_t)sizeof(ProjF64));
+  w.pc32 = c.take<PushConsts>((int64_t)(S + 2) * (int64_t)sizeof(PushConsts));
+  w.cams = c.take<CamBlock>((int64_t)S * (int64_t)sizeof(CamBlock));
+  w.total_bytes = c.off;
   return w;
 }
 
@@ -1302,13 +1260,6 @@ static int static_aggregate_impl(const float *rgbs, const float *depths, const u
     // in flight the throughput is the other way round: 1037 frames/s with 6, 1048 with 8, 1055 with 16, 1058 with 24-32 -- one
     // row whenever the later frames fit a queue entry's mask
     const int sfpg = kPushMaxFpg;
-#ifdef PGDVS_AB_CHAIN
-    // tools/r05_chain_cost.sh: what the chain costs the throughput, by ADDING copies of it behind the real one (a link is
-    // idempotent: its own map is complete before it runs, so a second run selects, stamps and stages exactly the same)
-    const char *dbg = getenv("PGDVS_DBG_CHAIN");
-    const int dbg_mode = !dbg ? 0 : !strcmp(dbg, "dup") ? 1 : !strcmp(dbg, "dup_dry") ? 2 : !strcmp(dbg, "dup_empty") ? 3 : !strcmp(dbg, "dup_small") ? 4 : 0;
-    for (int pass = 0; pass < (dbg_mode ? 2 : 1); ++pass)
-#endif
     for (int i = 1; i < S; ++i) {
       SelArgs a;
       a.dyn_mask = dyn_masks + (size_t)i * P;
@@ -1317,26 +1268,6 @@ static int static_aggregate_impl(const float *rgbs, const float *depths, const u
       a.P = (int)P;
       a.W = W;
       const unsigned gy = i + 1 < S ? (unsigned)cdiv(S - 1 - i, sfpg) : 1u;
-#ifdef PGDVS_AB_CHAIN
-      if (pass == 1 && dbg_mode == 3) {
-        PGDVS_LAUNCH("agg_empty", agg_empty_kernel, dim3(1), dim3(64), 0, st, (int *)nullptr);
-        continue;
-      }
-      if (pass == 1 && dbg_mode == 4) {  // launch boundaries + the workgroups, which leave at once (frame index beyond the video)
-        PGDVS_LAUNCH("agg_empty", agg_empty_kernel, dim3(gx), dim3(kStepThreads), 0, st, (int *)nullptr);
-        continue;
-      }
-      if (pass == 1 && dbg_mode == 2) {
-        RowStage none;
-        none.rows = nullptr;
-        none.cst = stage.cst;
-        none.gx = stage.gx;
-        PGDVS_LAUNCH("agg_step_dry", agg_step_kernel<kPushQueueSmall>, dim3(gx, gy), dim3(kStepThreads), 0, st, a, (uint8_t *)nullptr,
-                     (uint16_t *)nullptr, ws.Wd, i, (const ProjF64 *)ws.proj, (const PushConsts *)ws.pc32, S, sfpg, H, W,
-                     frame_src(i), cams[(size_t)i], ws.stat, none);
-        continue;
-      }
-#endif
       PGDVS_LAUNCH("agg_step", agg_step_kernel<kPushQueueSmall>, dim3(gx, gy), dim3(kStepThreads), 0, st, a, ws.occ,
                    reinterpret_cast<uint16_t *>(ws.sel), ws.Wd, i, (const ProjF64 *)ws.proj, (const PushConsts *)ws.pc32, S, sfpg, H, W,
                    frame_src(i), cams[(size_t)i], ws.stat, stage);

@@ -86,17 +86,6 @@ struct ViewWs {
   int64_t total_bytes;
 };
 
-struct Carver {
-  char *base;
-  int64_t off = 0;
-  template <class T>
-  T *take(int64_t bytes) {
-    T *p = reinterpret_cast<T *>(base + off);
-    off += align_up(bytes > 0 ? bytes : 1, 256);
-    return p;
-  }
-};
-
 int view_layout(const pgdvs_view_geo_desc &d, void *base, ViewWs &w) {
   if (d.H <= 0 || d.W <= 0 || (int64_t)d.H * d.W >= (1ll << 31)) {
     set_error("pgdvs_view_geo: bad H/W");
