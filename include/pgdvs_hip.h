@@ -779,6 +779,47 @@ int pgdvs_zoe_fit(const float *pcl_depth_pred, const double *pcl_depth_mvs, int6
  * diff of the four.  One workgroup, float64 tree sums.  No workspace.  1 <= n < 2^31, else PGDVS_ERR_INVALID. */
 int pgdvs_zoe_errors(const float *pcl_depth_pred, const double *pcl_depth_mvs, const uint8_t *flag_trim, int64_t n,
                      const double *scale_shift, double *errors, pgdvs_stream_t stream);
+/* The final motion mask of one frame (pgdvs/preprocess/compute_mask.py:341-471 combine_masks, :184-193 warp_flow, :827-829;
+ * csrc/mask_combine.hip), ONE call per frame, no host synchronisation.  On the device: raw_no_warp[H,W] uint8 (the frame's
+ * flow_epi or semantic mask), sam[n_seg,H,W] uint8 or bool (any non-zero byte is set; NULL when n_seg = 0) and, from the
+ * second frame on, prev_mask[H,W] uint8 (the previous call's next_prev), prev_cnt[H,W] float32 (its dyn_cnt),
+ * bwd_flow[H,W,2] and bwd_coord_diff[H,W,2] float32 of <frame>_<previous>.npz; all four NULL on the first frame.
+ * cubic_table = HOST float[32][4], the warp's weights (below); may be NULL on the first frame.  img_idx is upstream's frame
+ * number.  Outputs, uint8 0 / 1 unless said: warp_prev, dyn_track (untouched on the first frame, may be NULL there),
+ * dyn_cnt float32, raw, raw_eroded, final_raw, final_mask, next_prev and, unless NULL, seg_counts[n_seg,2] int32 (n_pix,
+ * n_overlap) and seg_selected[n_seg].  dyn_cnt may not alias prev_cnt, nor next_prev prev_mask.
+ *   first frame: raw = raw_no_warp; dyn_cnt = raw_no_warp as float (:420).
+ *   later frames: bwd_mask = |cd0| + |cd1| <= 1 in float32 (:213); warp_prev = warp(prev_mask) >= 0.5 and bwd_mask (:401,
+ *     see the warp); dyn_track = (warp(prev_cnt) / float32(img_idx + 1) * bwd_mask) > float32(dyn_track_thres), the
+ *     division correctly rounded (:407); raw = raw_no_warp | erode(warp_prev & dyn_track) (:411-418);
+ *     dyn_cnt = warp(prev_cnt) + final_raw, without bwd_mask (:446).
+ *   raw_eroded = erode(raw) (:427).  Per segment n_pix and n_overlap = |segment & raw_eroded|, exact integers; selected when
+ *     n_overlap > 0 and double(n_overlap) > sam_overlap_thres * double(n_pix), strictly (:437-439); final_raw = raw_eroded |
+ *     every selected segment (:441); final_mask = dilate(final_raw) (:449); next_prev = erode(final_raw) (:827).
+ *   erode / dilate: skimage's binary_erosion / binary_dilation with disk(2), the 13 pixels with dx^2 + dy^2 <= 4; the
+ *     erosion reads SET pixels outside the image, the dilation CLEAR ones.
+ *   warp(img)(p): this project's statement of cv2.remap(INTER_CUBIC, BORDER_CONSTANT 0), float32, every operation rounded
+ *     on its own: x = flow_x + col clamped to [-8, W + 8] (a NaN becomes -8; y alike); s = rint(32 x), half to even;
+ *     ix = s >> 5, k = s & 31; cx = cubic_table[k]; the 4 x 4 taps at ix - 1 .. ix + 2, iy - 1 .. iy + 2, a tap outside
+ *     the image 0; w[j][i] = cy[j] cx[i]; each row ((v0 w0 + v1 w1) + v2 w2) + v3 w3, the rows added top to bottom.  The
+ *     mask is warped as 0.0 / 1.0.  No flow value becomes an address before it is known to lie in the image; NaN flows:
+ *     undefined values, no fault.
+ * workspace: pgdvs_mask_combine_workspace_bytes(H, W, n_seg) bytes, 256-byte aligned.  bwd_flow and bwd_coord_diff 8-byte
+ * aligned.  Shapes: H, W >= 1, each < 2^20 (tile rows ride grid.y), H W < 2^31 (the counts are int32), 0 <= n_seg < 65536
+ * (segments ride grid.y), 0 <= img_idx < 2^24, else PGDVS_ERR_INVALID (the workspace query too) and nothing is launched. */
+int64_t pgdvs_mask_combine_workspace_bytes(int H, int W, int n_seg);
+int pgdvs_mask_combine(const uint8_t *raw_no_warp, const uint8_t *sam, int n_seg, int H, int W, const uint8_t *prev_mask,
+                       const float *prev_cnt, const float *bwd_flow, const float *bwd_coord_diff, const float *cubic_table,
+                       int img_idx, double dyn_track_thres, double sam_overlap_thres, uint8_t *warp_prev, uint8_t *dyn_track,
+                       float *dyn_cnt, uint8_t *raw, uint8_t *raw_eroded, uint8_t *final_raw, uint8_t *final_mask,
+                       uint8_t *next_prev, int32_t *seg_counts, uint8_t *seg_selected, void *workspace, int64_t workspace_bytes,
+                       pgdvs_stream_t stream);
+/* The semantic raw mask (compute_mask.py:367-380): sem_ade20k[H,W] and sem_coco[H,W] int64 class ids on the device, counted
+ * from 0, -1 for "no class"; ids_ade20k[n_ade20k] and ids_coco[n_coco] = HOST int32 lists of the dynamic classes, counted
+ * from 1 (1 <= id <= 512) -> ade20k, coco and sem = ade20k | coco, uint8 [H,W] 0 / 1: a pixel is set when its id + 1 is
+ * listed.  One launch, no workspace.  Shapes: H, W >= 1, each < 2^20, H W < 2^31, else PGDVS_ERR_INVALID. */
+int pgdvs_semantic_mask(const int64_t *sem_ade20k, const int64_t *sem_coco, int H, int W, const int32_t *ids_ade20k, int n_ade20k,
+                        const int32_t *ids_coco, int n_coco, uint8_t *ade20k, uint8_t *coco, uint8_t *sem, pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

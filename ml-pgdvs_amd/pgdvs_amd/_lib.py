@@ -120,6 +120,10 @@ SIGNATURES.update({
     "pgdvs_zoe_fit_workspace_bytes": (_i64, [_i64]),
     "pgdvs_zoe_fit": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_zoe_errors": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "pgdvs_mask_combine_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pgdvs_mask_combine": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "pgdvs_semantic_mask": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

@@ -920,6 +920,82 @@ def zoe_errors(pcl_depth_pred, pcl_depth_mvs, flag_trim, scale_shift):
     return out
 
 
+def _mask8(t, name):
+    """a bool or uint8 GPU tensor as contiguous uint8 (bool reinterpreted, not copied)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PgdvsHipError(f"{name}: expected a GPU tensor (no CPU fallback)")
+    t = t.contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else _req(t, torch.uint8, name)
+
+
+def semantic_mask(sem_ade20k, sem_coco, ids_ade20k, ids_coco):
+    """The semantic raw mask (``pgdvs_semantic_mask``; include/pgdvs_hip.h): the two int64 class-id maps [H,W] on the GPU
+    (ids counted from 0, -1 for none) and the two Python lists of dynamic classes counted from 1 -> (ade20k, coco, sem)
+    uint8 [H,W] on the GPU."""
+    a, b = _req(sem_ade20k, torch.int64, "sem_ade20k"), _req(sem_coco, torch.int64, "sem_coco")
+    if a.ndim != 2 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise ValueError(f"semantic_mask: shapes sem_ade20k {tuple(a.shape)}, sem_coco {tuple(b.shape)} ([H,W] each, one device)")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    la, lb = [int(v) for v in ids_ade20k], [int(v) for v in ids_coco]
+    out = [torch.empty((H, W), dtype=torch.uint8, device=a.device) for _ in range(3)]
+    check(_lib.load().pgdvs_semantic_mask(_ptr(a), _ptr(b), H, W, (C.c_int32 * len(la))(*la), len(la), (C.c_int32 * len(lb))(*lb),
+                                          len(lb), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()), "pgdvs_semantic_mask")
+    return tuple(out)
+
+
+def mask_combine(raw_no_warp, sam, prev_mask=None, prev_cnt=None, bwd_flow=None, bwd_coord_diff=None, *, img_idx,
+                 dyn_track_thres=0.5, sam_overlap_thres=0.1, table=None, want_segments=False):
+    """The final motion mask of one frame (``pgdvs_mask_combine``; include/pgdvs_hip.h): raw_no_warp[H,W] and
+    sam[n_seg,H,W] (bool or uint8, n_seg >= 0) on the GPU and, from the second frame on, the previous call's ``next_prev``
+    and ``dyn_cnt`` with bwd_flow[H,W,2] and bwd_coord_diff[H,W,2] float32 -> a dict of GPU tensors: warp_prev, dyn_track
+    (None on the first frame), raw_no_warp, raw, raw_eroded, final_raw, final, next_prev as uint8 0 / 1 and dyn_cnt float32;
+    with ``want_segments`` also seg_counts[n_seg,2] int32 (n_pix, n_overlap) and seg_selected[n_seg] uint8.  ``table``: the
+    warp's float32 [32,4] weights, ``preprocess.final_mask.cubic_table()`` by default.  One C call, nothing read back."""
+    r = _mask8(raw_no_warp, "raw_no_warp")
+    s = _mask8(sam, "sam")
+    if r.ndim != 2 or s.ndim != 3 or tuple(s.shape[1:]) != tuple(r.shape) or s.device != r.device:
+        raise ValueError(f"mask_combine: shapes raw_no_warp {tuple(r.shape)}, sam {tuple(s.shape)} ([H,W] and [n_seg,H,W], one device)")
+    H, W, n_seg = int(r.shape[0]), int(r.shape[1]), int(s.shape[0])
+    prev = (prev_mask, prev_cnt, bwd_flow, bwd_coord_diff)
+    has_prev = prev_mask is not None
+    if any((t is not None) != has_prev for t in prev):
+        raise ValueError("mask_combine: prev_mask, prev_cnt, bwd_flow and bwd_coord_diff go together")
+    tab = None
+    if has_prev:
+        pm, pc = _mask8(prev_mask, "prev_mask"), _req(prev_cnt, torch.float32, "prev_cnt")
+        fl, cd = _req(bwd_flow, torch.float32, "bwd_flow"), _req(bwd_coord_diff, torch.float32, "bwd_coord_diff")
+        if tuple(pm.shape) != (H, W) or tuple(pc.shape) != (H, W) or tuple(fl.shape) != (H, W, 2) or tuple(cd.shape) != (H, W, 2):
+            raise ValueError(f"mask_combine: shapes prev_mask {tuple(pm.shape)}, prev_cnt {tuple(pc.shape)}, bwd_flow {tuple(fl.shape)}, "
+                             f"bwd_coord_diff {tuple(cd.shape)} for a {(H, W)} frame")
+        if table is None:
+            from .preprocess.final_mask import cubic_table
+
+            table = cubic_table()
+        table = np.ascontiguousarray(table, dtype=np.float32)
+        if table.shape != (32, 4):
+            raise ValueError(f"mask_combine: table {table.shape}, expected (32, 4)")
+        tab = (C.c_float * 128)(*table.reshape(-1).tolist())
+    else:
+        pm = pc = fl = cd = None
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_mask_combine_workspace_bytes(H, W, n_seg), r.device)
+    u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=r.device)  # noqa: E731
+    out = dict(warp_prev=u8() if has_prev else None, dyn_track=u8() if has_prev else None,
+               dyn_cnt=torch.empty((H, W), dtype=torch.float32, device=r.device), raw_no_warp=r, raw=u8(), raw_eroded=u8(),
+               final_raw=u8(), final=u8(), next_prev=u8())
+    counts = torch.empty((n_seg, 2), dtype=torch.int32, device=r.device) if want_segments else None
+    selected = torch.empty((n_seg,), dtype=torch.uint8, device=r.device) if want_segments else None
+    check(lib.pgdvs_mask_combine(_ptr(r), _ptr(s) if n_seg else None, n_seg, H, W, _ptr(pm), _ptr(pc), _ptr(fl), _ptr(cd), tab,
+                                 int(img_idx), float(dyn_track_thres), float(sam_overlap_thres), _ptr(out["warp_prev"]),
+                                 _ptr(out["dyn_track"]), _ptr(out["dyn_cnt"]), _ptr(out["raw"]), _ptr(out["raw_eroded"]),
+                                 _ptr(out["final_raw"]), _ptr(out["final"]), _ptr(out["next_prev"]),
+                                 _ptr(counts) if n_seg else None, _ptr(selected) if n_seg else None, _ptr(ws), ws.numel(), _stream()),
+          "pgdvs_mask_combine")
+    if want_segments:
+        out.update(seg_counts=counts, seg_selected=selected)
+    return out
+
+
 PNG_QUANT = {"save_image": 0, "truncate": 1}
 
 

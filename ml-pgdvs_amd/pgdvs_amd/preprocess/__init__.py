@@ -1,4 +1,4 @@
-"""The three stages of upstream's ``pgdvs/preprocess/`` that are its own arithmetic, not a third-party network:
+"""The four stages of upstream's ``pgdvs/preprocess/`` that are its own arithmetic, not a third-party network:
 
 ``flow``      forward-backward flow consistency (``coord_diff``) and the ``flows/interval_<k>/<a>_<b>.npz`` files every
               loader reads (``datasets._common.read_flow_npz``), around a plug-in optical-flow model.
@@ -8,12 +8,16 @@
               look-ups of the motion mask and the prediction, the median and trimmed-median scale and shift in disparity,
               the error table, and the ``zoe_depths_<type>/<frame>.npz`` files ``datasets.nvidia_eval`` reads, around a
               plug-in depth model.
+``final_mask`` upstream's ``combine_masks``: the ``flow_epi`` (or semantic) mask of a frame, the previous frame's result and
+              a "how often dynamic" count warped along the backward flow, eroded, grown to whole segments of a plug-in
+              segmenter and dilated; and ``run_masks``, the writer of the ``masks/final/<frame>_final.png`` files the
+              loaders and ``run_zoedepth`` read.
 
-Each runs in numpy (and scipy) on the host (``device=None``) or in HIP (csrc/preprocess.hip, csrc/zoe_align.hip).  The
-``flow_epi`` mask is an INPUT of upstream's ``combine_masks`` (compute_mask.py:341-471), which merges it with the semantic
-segmentations and propagates it in time; it is not the ``masks/final`` mask the loaders and ``run_zoedepth`` read.
-``combine_masks``, the ``masks/final`` writer and every network (RAFT, FlowFormer, OneFormer, SAM, ZoeDepth) are outside
-this package."""
+Each runs in numpy (and scipy) on the host (``device=None``) or in HIP (csrc/preprocess.hip, csrc/zoe_align.hip,
+csrc/mask_combine.hip).  ``run_flow`` -> ``run_masks`` -> ``run_zoedepth`` takes a directory of frames to the tree the
+loaders read.  Every network (RAFT, FlowFormer, OneFormer, SAM, ZoeDepth) is outside this package."""
+from .final_mask import (DYNAMIC_IDS_ADE20K, DYNAMIC_IDS_COCO, combine_masks, cubic_table, run_masks, semantic_mask,  # noqa: F401
+                         warp_flow_numpy)
 from .flow import flow_consistency, run_flow, write_flow_pair  # noqa: F401
 from .mask import epipolar_motion_mask, fundamental_matrix  # noqa: F401
 from .zoedepth import fit_frame, frame_errors, run_zoedepth, sample_frame  # noqa: F401
