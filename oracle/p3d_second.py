@@ -1,4 +1,5 @@
-"""SECOND, independent restatement of the pytorch3d 0.7.4 boundary of row A9 (test infrastructure only).
+"""SECOND, independent restatement of the pytorch3d 0.7.4 boundary of rows A9 (points; below) and A10 (mesh; the last
+section of this file, which says what it pins and what it cannot) -- test infrastructure only.
 
 pytorch3d is an un-vendored dependency of the reference (README.md:38, `conda install pytorch3d=0.7.4`)
 and cannot be obtained in the build container (no wheel, no source, no network), so neither
@@ -221,3 +222,149 @@ def norm_weighted_composite(idx, dist, radius, feat):
                 w = F(F(1) - F(dist[yi, xi, k] / r2))
                 out[yi, xi] = (out[yi, xi] + (w * feat[n]).astype(F) / t).astype(F)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Row A10 (dyn_render_type = "mesh"): the second statement of the mesh path.
+#
+# pytorch3d's source cannot be obtained here, so the in-face formulas below (the bounding-box test, the
+# +-1e-8 zero-area band, the 1e-8 added to the area, the perspective correction with its 1e-8 clamp and the
+# strict ``bary > 0`` test) necessarily come from the same reading of ``CheckPixelInsideFace``
+# (rasterize_meshes.cu) and geometry_utils.cuh as oracle/pgdvs_oracle.c's: if that reading is wrong, both
+# are wrong, and **parity of the in-face arithmetic with pytorch3d stays UNPINNED**.  What is independent of
+# the oracle and of csrc/mesh.hip is everything around those formulas:
+#   * structure -- every pixel is tested against every face, in face order, as the naive rasteriser does;
+#     there is no candidate pixel range (``ndc_to_pix_range`` is this project's invention) and no packed
+#     64-bit key: the winner is the minimum of (z, face index);
+#   * the explicit face list -- faces are rows of vertex ranks built the way render_dyn_mesh builds them
+#     (pgdvs_renderer_dyn.py:550-604: two stacks of candidates concatenated, the in-bounds filter, then the
+#     ``> 0`` filter), pinned to the reference's own output by tests/golden/mesh_edges.npz; the oracle and the
+#     kernel derive faces implicitly as (source pixel, kind);
+#   * the precision -- ``dtype=np.float32`` rounds every operation on its own (the "seq" flavour above, the
+#     oracle's operation order), ``dtype=np.float64`` is the high-precision reference on the same float32
+#     vertices.
+# ---------------------------------------------------------------------------------------------------
+MESH_EPS = 1e-8
+
+
+def mesh_faces_from_keep(keep):
+    """keep[H,W] (non-zero = a vertex) -> faces[#face,3] int64 of vertex ranks, in the reference's order."""
+    keep = np.asarray(keep) != 0
+    h, w = keep.shape
+    rows, cols = np.nonzero(keep)  # row-major, as torch.nonzero
+    vert_idxs_img = np.full((h, w), -1, np.int64)
+    vert_idxs_img[rows, cols] = np.arange(rows.shape[0])
+    # (row, col) -> (row, col), (row + 1, col), (row + 1, col + 1)  and  (row, col), (row + 1, col + 1), (row, col + 1)
+    cand_1 = np.stack([np.stack([rows, cols], 1), np.stack([rows + 1, cols], 1), np.stack([rows + 1, cols + 1], 1)], 1)
+    cand_2 = np.stack([np.stack([rows, cols], 1), np.stack([rows + 1, cols + 1], 1), np.stack([rows, cols + 1], 1)], 1)
+    cand = np.concatenate([cand_1, cand_2], 0).reshape(-1, 3, 2)  # [#cand, 3, 2]
+    in_bound = np.all((cand[..., 0] >= 0) & (cand[..., 0] < h) & (cand[..., 1] >= 0) & (cand[..., 1] < w), axis=1)
+    cand = cand[in_bound]
+    face_v = vert_idxs_img[cand[..., 0], cand[..., 1]].reshape(-1, 3)
+    return face_v[np.all(face_v > 0, axis=1)].astype(np.int64)  # sic: vertex 0 counts as "no vertex"
+
+
+def _edge(px, py, ax, ay, bx, by):
+    return (px - ax) * (by - ay) - (py - ay) * (bx - ax)
+
+
+def _pixel_centres(H, W, dtype):
+    """pixel centres in NDC, [H*W] each (PixToNonSquareNdc with reversed indices)"""
+    if dtype == np.float32:
+        xs = np.array([pix_to_non_square_ndc(W - 1 - xi, W, H) for xi in range(W)], F)
+        ys = np.array([pix_to_non_square_ndc(H - 1 - yi, H, W) for yi in range(H)], F)
+    else:
+        def centre(i, S1, S2):
+            rng = 2.0 * S1 / S2 if S1 > S2 else 2.0
+            return -rng / 2.0 + (rng * i + rng / 2.0) / S1
+
+        xs = np.array([centre(W - 1 - xi, W, H) for xi in range(W)], np.float64)
+        ys = np.array([centre(H - 1 - yi, H, W) for yi in range(H)], np.float64)
+    return np.tile(xs, H), np.repeat(ys, W)
+
+
+def _face_terms(px, py, v0, v1, v2, eps):
+    """CheckPixelInsideFace's arithmetic for one face at the pixel centres (px, py): the bounding-box flag, the
+    perspective-corrected barycentrics and z, unfiltered"""
+    (x0, y0, z0), (x1, y1, z1), (x2, y2, z2) = v0, v1, v2
+    xmin, xmax = np.fmin(np.fmin(x0, x1), x2), np.fmax(np.fmax(x0, x1), x2)
+    ymin, ymax = np.fmin(np.fmin(y0, y1), y2), np.fmax(np.fmax(y0, y1), y2)
+    outside = (px > xmax) | (px < xmin) | (py > ymax) | (py < ymin)
+    area = _edge(x2, y2, x0, y0, x1, y1) + eps
+    b0 = _edge(px, py, x1, y1, x2, y2) / area
+    b1 = _edge(px, py, x2, y2, x0, y0) / area
+    b2 = _edge(px, py, x0, y0, x1, y1) / area
+    t0 = b0 * z1 * z2
+    t1 = z0 * b1 * z2
+    t2 = z0 * z1 * b2
+    den = np.fmax(t0 + t1 + t2, eps)
+    w0, w1, w2 = t0 / den, t1 / den, t2 / den
+    z = w0 * z0 + w1 * z1 + w2 * z2
+    return outside, w0, w1, w2, z
+
+
+def rasterize_meshes_naive(ndc, faces, H, W, dtype=np.float32):
+    """RasterizeMeshesNaive for blur_radius 0, faces_per_pixel 1, perspective-correct, no clipping, no culling:
+    every pixel against every face of ``faces[#face,3]`` (indices into ``ndc[#vert,3]``), in face order.
+    -> face index [H,W] int64 (-1 = none), z [H,W], barycentrics [H,W,3], all in ``dtype``."""
+    dt = np.dtype(dtype).type
+    v = np.asarray(ndc, F).astype(dt)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    px, py = _pixel_centres(H, W, dt)
+    eps, zero = dt(F(MESH_EPS)), dt(0)
+    P = H * W
+    best = np.full(P, -1, np.int64)
+    zbuf = np.zeros(P, dt)
+    bary = np.zeros((P, 3), dt)
+    with np.errstate(all="ignore"):
+        for f, (i0, i1, i2) in enumerate(faces):
+            v0, v1, v2 = v[i0], v[i1], v[i2]
+            zmax = np.fmax(np.fmax(v0[2], v1[2]), v2[2])
+            face_area = _edge(v0[0], v0[1], v1[0], v1[1], v2[0], v2[1])
+            if zmax < zero or (face_area <= eps and face_area >= -eps):
+                continue
+            outside, w0, w1, w2, z = _face_terms(px, py, v0, v1, v2, eps)
+            inside = ~outside & ~(z < zero) & (w0 > zero) & (w1 > zero) & (w2 > zero)
+            win = inside & ((best < 0) | (z < zbuf))  # strict: among equal z the earlier face stays
+            best[win], zbuf[win] = f, z[win]
+            bary[win, 0], bary[win, 1], bary[win, 2] = w0[win], w1[win], w2[win]
+    return best.reshape(H, W), zbuf.reshape(H, W), bary.reshape(H, W, 3)
+
+
+def face_at_pixel(ndc, tri, H, W, yi, xi, dtype=np.float64):
+    """one face at one pixel, unfiltered: (smallest |barycentric|, z) -- how close the pixel is to the face's border"""
+    dt = np.dtype(dtype).type
+    v = np.asarray(ndc, F).astype(dt)
+    px, py = _pixel_centres(H, W, dt)
+    k = yi * W + xi
+    with np.errstate(all="ignore"):
+        _, w0, w1, w2, z = _face_terms(px[k:k + 1], py[k:k + 1], v[tri[0]], v[tri[1]], v[tri[2]], dt(F(MESH_EPS)))
+    return float(min(abs(w0[0]), abs(w1[0]), abs(w2[0]))), float(z[0])
+
+
+def interpolate_vertex_colors(face_idx, bary, faces, feat):
+    """TexturesVertex.sample_textures (interpolate_face_attributes: sum over the three corners in order) followed
+    by hard_rgb_blend on a black background -> img[H,W,C] in bary's dtype"""
+    dt = bary.dtype.type
+    feat = np.asarray(feat, F).astype(dt)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    H, W = face_idx.shape
+    img = np.zeros((H, W, feat.shape[1]), dt)
+    hit = face_idx >= 0
+    if hit.any():
+        fv = faces[face_idx[hit]]  # [n, 3]
+        b = bary[hit]
+        a = b[:, 0:1] * feat[fv[:, 0]]
+        a = a + b[:, 1:2] * feat[fv[:, 1]]
+        a = a + b[:, 2:3] * feat[fv[:, 2]]
+        img[hit] = a
+    return img
+
+
+def render_mesh(ndc, faces, feat, H, W, dtype=np.float32):
+    """render_dyn_mesh's two renders (pgdvs_renderer_dyn.py:646-658): the colour image, and the mask as
+    ``(render of ones) > 0`` -> img[H,W,3], mask[H,W] (float32 0/1), face index[H,W], z[H,W]"""
+    idx, z, bary = rasterize_meshes_naive(ndc, faces, H, W, dtype)
+    img = interpolate_vertex_colors(idx, bary, faces, feat)
+    ones = interpolate_vertex_colors(idx, bary, faces, np.ones((np.asarray(ndc).shape[0], 1), F))
+    return img, (ones[..., 0] > 0).astype(F), idx, z

@@ -1032,9 +1032,19 @@ ORC_API void orc_track_points(int64_t P, int N, int H, int W, const float *track
 /* barycentrics (PerspectiveCameras), no z clipping (znear is None),     */
 /* no back-face culling; shader = TexturesVertex interpolation +         */
 /* hard_rgb_blend on black (pgdvs/utils/pytorch3d_utils.py:50-67).       */
-/* pytorch3d is not installable here: parity UNPINNED, restated from     */
+/* pytorch3d is not installable here: the rasteriser is restated from    */
 /* pytorch3d/csrc/rasterize_meshes/rasterize_meshes.cu                   */
 /* (CheckPixelInsideFace) and csrc/utils/geometry_utils.cuh.             */
+/* PINNED: the topology -- which (pixel, kind) faces exist and their     */
+/* order -- to the face lists the reference itself builds                */
+/* (tests/golden/mesh_edges.npz), and the vertices / colours the whole   */
+/* path hands over; the candidate range, the z-buffer and the face order */
+/* to the naive every-pixel-against-every-face statement of              */
+/* oracle/p3d_second.py; vertex / edge / diagonal holes, exact depth     */
+/* ties and the closed area band to integer arithmetic                   */
+/* (tests/mesh_cases.py, tests/test_mesh_edges_host.py).                 */
+/* UNPINNED: the in-face formulas of mesh_pixel_in_face against          */
+/* pytorch3d itself -- both statements share this one reading of them.   */
 /*   keep[P] u8, pcl[P,3], rgb[P,3] dense over the source frame;         */
 /*   out: img[H,W,3], mask[H,W], face[H,W] (kind*P + pixel, -1 = none).  */
 /* ------------------------------------------------------------------ */
