@@ -241,54 +241,4 @@ __device__ __forceinline__ void project_point(const float *P, float x, float y, 
   v = clampf(p[1] / zz, -1e6f, 1e6f);
 }
 
-// Wave-aggregated tile counter update.  Clouds arrive in the raster order of their source
-// frames, so consecutive lanes of a wavefront mostly hit the same tile: lanes form RUNS of
-// equal tile id, the first lane of each run adds the run length for all of them, and every
-// run leader is active in ONE atomic wave-instruction (the atomic units are paced per
-// instruction, not per lane).  Any order is correct -- less coherent input only means
-// shorter runs.  Returns the slot reserved for this lane (fill) or nothing (count).
-struct RunInfo {
-  int leader;   // lane index of this lane's run leader
-  int length;   // run length (valid on the leader)
-  bool is_leader;
-};
-
-// PRECONDITION: all 64 lanes of the wavefront call it together (callers pad their loops to whole wavefronts and pass
-// t < 0 for lanes without work).  An inactive left neighbour leaves the DPP read at the lane's own value; the ballot of
-// active lanes below makes such a lane a leader anyway, so a partial wavefront still gets correct (shorter) runs.
-__device__ __forceinline__ RunInfo wave_runs(int t) {
-  const int lane = threadIdx.x & 63;
-  // wave_shr:1 -- lane i reads lane i-1 through the DPP path (no LDS round trip); lane 0 is a leader anyway
-  int prev = __builtin_amdgcn_update_dpp(t, t, 0x138, 0xf, 0xf, false);
-  const unsigned long long act = __ballot(1);
-  bool lead = lane == 0 || prev != t || !((act >> (lane ? lane - 1 : 0)) & 1ull);
-  unsigned long long L = __ballot(lead);
-  RunInfo r;
-  r.is_leader = lead;
-  unsigned long long below = L & ((lane == 63) ? ~0ull : ((2ull << lane) - 1ull));  // leaders at or below this lane
-  r.leader = 63 - __builtin_clzll(below);
-  unsigned long long above = lane == 63 ? 0ull : (L >> (lane + 1));  // leaders after this lane
-  r.length = above ? (int)__builtin_ctzll(above) + 1 : 64 - lane;
-  return r;
-}
-
-__device__ __forceinline__ void wave_tile_count(int32_t *__restrict__ counter, int t) {
-  RunInfo r = wave_runs(t);
-  if (r.is_leader && t >= 0)
-    __hip_atomic_fetch_add(&counter[t], r.length, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int wave_tile_reserve(int32_t *__restrict__ counter, int t) {
-  const int lane = threadIdx.x & 63;
-  RunInfo r = wave_runs(t);
-  int base = 0;
-  if (r.is_leader && t >= 0) base = atomicAdd(&counter[t], r.length);
-  base = __shfl(base, r.leader, 64);
-  return base + (lane - r.leader);
-}
-
-
-// wave-level inclusive/exclusive helpers (64-wide wavefront)
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
 }  // namespace pgdvs

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -27,6 +28,7 @@ __device__ __forceinline__ void block_partials(int tid, const double (&v)[kSums]
 #pragma unroll
   for (int k = 0; k < kSums; ++k) {
     double s = v[k];
+    // (wave_sum_down's tree, spelled out: through the helper eval_partials and dycheck_lpips_upsample allocate more registers)
     for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_down(s, off, kWave);
     if (lane == 0) red[wave][k] = s;
   }
@@ -43,8 +45,7 @@ __device__ __forceinline__ void block_partials(int tid, const double (&v)[kSums]
 __device__ __forceinline__ double ordered_block_sum(const double *__restrict__ p, int b0, int b1, int stride) {
   double v = 0.0;
   for (int b = b0 + (int)(threadIdx.x & (kWave - 1)); b < b1; b += kWave) v += p[(size_t)b * stride];
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;
+  return wave_sum_down(v);
 }
 
 }  // namespace pgdvs

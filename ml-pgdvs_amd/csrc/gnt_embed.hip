@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "gnt_mfma.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -301,9 +302,7 @@ gnt_head_kernel(const float *__restrict__ W, const float *__restrict__ q, int R,
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int f = 0; f < 64; ++f) {
-    float v = acc[f];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    const float v = wave_sum_all(acc[f]);
     if (lane == f) s_part[wave][f] = v;
   }
   __syncthreads();

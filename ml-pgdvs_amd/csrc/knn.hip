@@ -14,6 +14,7 @@
 // registers, so the common case per candidate is sub/mul/add/compare only.
 #include "common.h"
 #include "fused.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -163,7 +164,7 @@ __device__ __forceinline__ void stat_select_block(const int n, const int pass, c
   const double m2_in = in.m2;
   // sum of the per-block partials (nblocks <= 256), fixed shuffle tree
   double t = (pass < 2 && tid < nblocks) ? partials[tid] : 0.0;
-  for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+  t = wave_sum_down(t);
   if (lane == 0) dsum[wave] = t;
   // 2048 bins, 8 per thread: find the bin where the running count passes rank
   const unsigned *h = ghist + pass * kStatBins;
@@ -174,11 +175,7 @@ __device__ __forceinline__ void stat_select_block(const int n, const int pass, c
     loc[k] = tid * 8 + k < nb ? h[tid * 8 + k] : 0;
     s += loc[k];
   }
-  unsigned x = s;
-  for (int off = 1; off < 64; off <<= 1) {
-    unsigned y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
+  const unsigned x = wave_incl_scan(s);
   if (lane == 63) wtot[wave] = x;
   __syncthreads();
   unsigned before = x - s;  // counts in the bins of the threads before this one
@@ -272,7 +269,7 @@ stat_pass_kernel(const float *__restrict__ avg, const int32_t *__restrict__ coun
     }
   }
   if (pass < 2) {
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_sum_down(acc);
     if ((tid & 63) == 0) wsum[tid >> 6] = acc;
   }
   __syncthreads();

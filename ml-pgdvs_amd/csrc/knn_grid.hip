@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "fused.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -74,10 +75,8 @@ grid_bbox_kernel(const float *__restrict__ pts, const int32_t *__restrict__ coun
   }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    for (int off = 32; off > 0; off >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_down(mn[a], off, 64));
-      mx[a] = fmaxf(mx[a], __shfl_down(mx[a], off, 64));
-    }
+    mn[a] = wave_reduce_down<OpFmin>(mn[a]);
+    mx[a] = wave_reduce_down<OpFmax>(mx[a]);
     if ((threadIdx.x & 63) == 0) {
       s_mn[threadIdx.x >> 6][a] = mn[a];
       s_mx[threadIdx.x >> 6][a] = mx[a];
@@ -148,12 +147,8 @@ grid_sample_kernel(const float *__restrict__ pts, const int32_t *__restrict__ co
     }
   }
   const int mine = __popc(hit);
-  int incl = mine;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += y;
-  }
+  const int incl = wave_incl_scan(mine);
   if (lane == 63) s_w[wave] = incl;
   __syncthreads();
   int at = incl - mine;
@@ -216,7 +211,7 @@ grid_sample_nn_kernel(const int32_t *__restrict__ count, const float4 *__restric
       best = (k != self && k < nslots && d < best) ? d : best;
     }
   }
-  for (int off = 32; off > 0; off >>= 1) best = fminf(best, __shfl_xor(best, off, 64));
+  best = wave_reduce_all<OpFmin>(best);
   if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = best;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -265,18 +260,8 @@ grid_params_kernel(const unsigned *__restrict__ bbox, const int32_t *__restrict_
     {
       // bin tid: entries below it (scan over the 1024 bins: wavefront scan + the 16 wavefront totals)
       const int mine = s_hist[tid];
-      int incl = mine;
-      for (int off = 1; off < 64; off <<= 1) {
-        const int y = __shfl_up(incl, off, 64);
-        if ((tid & 63) >= off) incl += y;
-      }
-      if ((tid & 63) == 63) s_wtot[tid >> 6] = incl;
-      __syncthreads();
-      int ex = incl - mine, all = 0;
-      for (int w = 0; w < 16; ++w) {
-        ex += w < (tid >> 6) ? s_wtot[w] : 0;
-        all += s_wtot[w];
-      }
+      int all;
+      const int ex = block_excl_scan<16>(mine, s_wtot, all);
       if (level == 0 && tid == 0) {
         s_sel[2] = all;
         s_sel[1] = 0;
@@ -544,11 +529,7 @@ grid_rank_kernel(const GridParams *__restrict__ gp, uint4 *__restrict__ tab, uns
     c[k] = w < nw ? tab_word_bits(tab, w) : 0;
     s += c[k];
   }
-  int x = s;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
+  const int x = wave_incl_scan(s);
   if (lane == 63) ws[wave] = x;
   __syncthreads();
   if (wave == 0) {
@@ -572,7 +553,7 @@ grid_rank_kernel(const GridParams *__restrict__ gp, uint4 *__restrict__ tab, uns
       }
       pre += (int)(unsigned)v;
     }
-    for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
+    pre = wave_sum_all(pre);
     if (lane == 0) s_pre = pre;
   }
   __syncthreads();
@@ -656,11 +637,7 @@ grid_scan_kernel(const int32_t *__restrict__ in, const int32_t *__restrict__ n_p
   }
 #pragma unroll
   for (int k = 0; k < kScanVec; ++k) {
-    int t = v[k].x + v[k].y + v[k].z + v[k].w;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(t, off, 64);
-      if (lane >= off) t += y;
-    }
+    const int t = wave_incl_scan(v[k].x + v[k].y + v[k].z + v[k].w);
     x[k] = t;  // inclusive over the wavefront's groups of sub-tile k
     if (lane == 63) s_tot[k * 16 + wave] = t;
   }
@@ -668,11 +645,7 @@ grid_scan_kernel(const int32_t *__restrict__ in, const int32_t *__restrict__ n_p
   if (wave == 0) {
     // exclusive scan of the kScanVec * 16 totals in (sub-tile, wavefront) order, one per lane
     const int own = lane < kScanVec * 16 ? s_tot[lane] : 0;
-    int t = own;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(t, off, 64);
-      if (lane >= off) t += y;
-    }
+    const int t = wave_incl_scan(own);
     if (lane < kScanVec * 16) s_tot[lane] = t - own;
     const int sum = __shfl(t, 63, 64);  // the tile's sum
     // look-back: 64 earlier tiles at a time
@@ -699,8 +672,7 @@ grid_scan_kernel(const int32_t *__restrict__ in, const int32_t *__restrict__ n_p
         const unsigned long long whole = __ballot((w >> 32) == 2ull);
         const int stop = whole ? __builtin_ctzll(whole) : 63;  // nearest tile with a whole prefix
         int c = (lane <= stop && i >= 0) ? (int)(unsigned)w : 0;
-        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-        carry += c;
+        carry += wave_sum_all(c);
         if (whole) break;
       }
     }
@@ -935,8 +907,7 @@ __device__ __forceinline__ float4 load_query(const QuerySrc &qs, const float4 *_
 __device__ __forceinline__ void knn_finish(float best, int KK, int first_col, int n, int lane, int orig,
                                            float *__restrict__ avg_out) {
   float s = (lane >= first_col && lane < KK && lane < n) ? best : 0.0f;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s = s + __shfl_down(s, off, 64);
+  s = wave_sum_down(s);
   if (lane == 0) avg_out[orig] = s / (float)(KK - first_col);
 }
 

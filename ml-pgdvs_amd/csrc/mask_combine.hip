@@ -21,6 +21,7 @@
 // close   one workgroup per tile: final = dilate(final_raw), reading clear pixels outside the image, and next_prev =
 //         erode(final_raw), reading set ones, from one staged tile with a 2-pixel halo.
 #include "common.h"
+#include "wave.h"
 
 namespace pgdvs {
 namespace {
@@ -226,11 +227,8 @@ __global__ void __launch_bounds__(kBlock) seg_count_kernel(CountParams p) {
       n_overlap += (int)((p.bits[i >> 6] >> (i & 63)) & 1ull);
     }
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    n_pix += __shfl_xor(n_pix, d, 64);
-    n_overlap += __shfl_xor(n_overlap, d, 64);
-  }
+  n_pix = wave_sum_all(n_pix);
+  n_overlap = wave_sum_all(n_overlap);
   if ((threadIdx.x & 63) == 0) {
     part[0][threadIdx.x >> 6] = n_pix;
     part[1][threadIdx.x >> 6] = n_overlap;

@@ -12,6 +12,7 @@
 // (z bits << 32 | face order id) -- the total order (z, face id) pytorch3d's queue uses, so
 // the winner does not depend on scheduling.  A second pass shades the winners.
 #include "raster_cam.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -80,10 +81,7 @@ mesh_verts_kernel(const float *__restrict__ cam, int H, int W, const uint8_t *__
     }
     ndc[p] = o;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    int other = __shfl_down(mine, off, 64);
-    mine = other < mine ? other : mine;
-  }
+  mine = wave_reduce_down<OpMin>(mine);
   if ((threadIdx.x & 63) == 0 && mine != 0x7fffffff) atomicMin(first, mine);
 }
 

@@ -26,6 +26,7 @@
 // (stage_row<kHwc>) instead of three plane reads; everything behind the staging is scanline_row, shared with the
 // visualiser's kernel.
 #include "common.h"
+#include "wave.h"
 
 namespace pgdvs {
 namespace {
@@ -248,9 +249,7 @@ __device__ __forceinline__ void scanline_row(const Params &p, const float *__res
     // a thread's sum is at most 128 * 4 * ceil(groups / 256) < 2^31; the block's needs 64 bits for very wide rows
 #pragma unroll
     for (int f = 0; f < 5; ++f) {
-      unsigned long long v = cost[f];
-#pragma unroll
-      for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_down(v, d, kWave);
+      const unsigned long long v = wave_sum_down((unsigned long long)cost[f]);
       if ((threadIdx.x & (kWave - 1)) == 0) s_cost[threadIdx.x / kWave][f] = v;
     }
     __syncthreads();

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "wave.h"
 
 namespace pgdvs {
 namespace radix {
@@ -107,11 +108,7 @@ template <typename T, int NR> __device__ void select_digits(int pass, Sel<NR> *s
   constexpr int kPer = kBins / 64;
   uint32_t c = 0;
   for (int b = 0; b < kPer; ++b) c += h[lane * kPer + b];
-  uint32_t incl = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
+  const uint32_t incl = wave_incl_scan(c);
   const uint32_t excl = incl - c;
   const unsigned long long hit = __ballot(excl <= rem && rem < incl);
   const int L = hit ? __builtin_ctzll(hit) : 63;  // always hit: rem < n = total count of the slot

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "raster_cam.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -72,25 +73,6 @@ __device__ __forceinline__ TileBox tile_box(const RasterCam &rc, float3 p, float
   return b;
 }
 
-
-// maximum over the wavefront as a scalar: DPP butterflies inside each row of 16 lanes, row
-// broadcasts across rows (the total lands in lane 63), no LDS round trips
-__device__ __forceinline__ int wave_max_i32_scalar(int v) {
-  int t;
-  t = __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-  v = t > v ? t : v;
-  t = __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-  v = t > v ? t : v;
-  t = __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
-  v = t > v ? t : v;
-  t = __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false);  // row_mirror
-  v = t > v ? t : v;
-  t = __builtin_amdgcn_update_dpp(v, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
-  v = t > v ? t : v;
-  t = __builtin_amdgcn_update_dpp(v, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
-  v = t > v ? t : v;
-  return __builtin_amdgcn_readlane(v, 63);
-}
 
 // the tile box of every point spans at most 2 x 2 tiles: disc diameter + the margins of tile_box within one tile side
 __device__ __forceinline__ bool tile_box_within_2x2(const RasterCam &rc, float radius, int H, int W) {
@@ -303,11 +285,7 @@ raster_scan_kernel(const int32_t *__restrict__ counts, int n, int32_t *__restric
       v[k] = i0 + k < n ? counts[i0 + k] : 0;
       s += v[k];
     }
-    int x = s;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int y = __shfl_up(x, off, 64);
-      if (lane >= off) x += y;
-    }
+    const int x = wave_incl_scan(s);
     if (lane == 63) wave_sums[wave] = x;
     __syncthreads();
     int run = carry + x - s, total = 0;
@@ -720,12 +698,8 @@ raster_tile_kernel(const float4 *__restrict__ lists, const int32_t *__restrict__
       zmn = zb < zmn ? zb : zmn;
       zmx = zb > zmx ? zb : zmx;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned a = __shfl_xor(zmn, off, 64), b = __shfl_xor(zmx, off, 64);
-      zmn = a < zmn ? a : zmn;
-      zmx = b > zmx ? b : zmx;
-    }
+    zmn = wave_reduce_all<OpMin>(zmn);
+    zmx = wave_reduce_all<OpMax>(zmx);
     if (lane == 0) {
       s_red[wave] = zmn;
       s_red[4 + wave] = zmx;
@@ -768,12 +742,7 @@ raster_tile_kernel(const float4 *__restrict__ lists, const int32_t *__restrict__
         tot += c[j];
       }
       if (mx > (unsigned)kSortMaxBucket) s_flag = 1;
-      unsigned incl = tot;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += y;
-      }
+      const unsigned incl = wave_incl_scan(tot);
       if (lane == 63) s_red[8 + wave] = incl;
       __syncthreads();
       unsigned base = incl - tot;
@@ -1110,12 +1079,9 @@ __global__ void __launch_bounds__(1024) raster_counters_kernel(const int32_t *__
     mx = n > mx ? n : mx;
     nlong += n > kSortCap ? 1 : 0;
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    const int a = __shfl_xor(mx, off, 64);
-    mx = a > mx ? a : mx;
-    nlong += __shfl_xor(nlong, off, 64);
-    tot += __shfl_xor(tot, off, 64);
-  }
+  mx = wave_reduce_all<OpMax>(mx);
+  nlong = wave_sum_all(nlong);
+  tot = wave_sum_all(tot);
   if ((threadIdx.x & 63) == 0) {
     s_max[threadIdx.x >> 6] = mx;
     s_long[threadIdx.x >> 6] = nlong;

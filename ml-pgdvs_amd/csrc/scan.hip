@@ -7,6 +7,7 @@
 #include "scan.h"
 
 #include "fused.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -27,8 +28,7 @@ compact_count_kernel(const uint8_t *__restrict__ flags, int64_t n, int32_t *__re
     for (int k = 0; k < kCompactItems; ++k)
       if (base + k < n) c += flags[base + k] != 0;
   }
-  // wave reduce
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  c = wave_sum_down(c);
   int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) wave_sums[wave] = c;
   __syncthreads();
@@ -49,11 +49,7 @@ compact_scan_kernel(int32_t *__restrict__ block_counts, int nb, int32_t *__restr
   for (int start = 0; start < nb; start += 1024) {
     int i = start + threadIdx.x;
     int v = i < nb ? block_counts[i] : 0;
-    int x = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      int y = __shfl_up(x, off, 64);
-      if ((threadIdx.x & 63) >= off) x += y;
-    }
+    const int x = wave_incl_scan(v);
     int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 63) wave_sums[wave] = x;
     __syncthreads();
@@ -80,11 +76,7 @@ compact_scatter_kernel(const uint8_t *__restrict__ flags, int64_t n,
     f[k] = (base + k < n) && flags[base + k] != 0;
     c += f[k];
   }
-  int x = c;
-  for (int off = 1; off < 64; off <<= 1) {
-    int y = __shfl_up(x, off, 64);
-    if ((threadIdx.x & 63) >= off) x += y;
-  }
+  const int x = wave_incl_scan(c);
   int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 63) wave_sums[wave] = x;
   __syncthreads();
@@ -117,7 +109,7 @@ compact_gather_bbox_kernel(const uint8_t *__restrict__ flags, int64_t n, const i
   const int chunks_before = (int)blockIdx.x * (kCompactTile / 256);
   int pre = 0;
   for (int c = tid; c < chunks_before; c += kCompactBlock) pre += chunk_cnt[c];
-  for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
+  pre = wave_sum_all(pre);
   if (lane == 0) pre_sums[wave] = pre;
   const int64_t base = (int64_t)blockIdx.x * kCompactTile + (int64_t)tid * kCompactItems;
   bool f[kCompactItems];
@@ -127,11 +119,7 @@ compact_gather_bbox_kernel(const uint8_t *__restrict__ flags, int64_t n, const i
     f[k] = (base + k < n) && flags[base + k] != 0;
     c += f[k];
   }
-  int x = c;
-  for (int off = 1; off < 64; off <<= 1) {
-    int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
+  const int x = wave_incl_scan(c);
   if (lane == 63) wave_sums[wave] = x;
   __syncthreads();
   int tile_off = 0, wave_off = 0, total = 0;
@@ -168,10 +156,8 @@ compact_gather_bbox_kernel(const uint8_t *__restrict__ flags, int64_t n, const i
     }
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    for (int off = 32; off > 0; off >>= 1) {
-      mn[a] = fminf(mn[a], __shfl_xor(mn[a], off, 64));
-      mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], off, 64));
-    }
+    mn[a] = wave_reduce_all<OpFmin>(mn[a]);
+    mx[a] = wave_reduce_all<OpFmax>(mx[a]);
     if (lane == 0) {
       s_mn[wave][a] = mn[a];
       s_mx[wave][a] = mx[a];

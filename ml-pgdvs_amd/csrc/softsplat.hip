@@ -13,6 +13,7 @@
 // majority costs one atomic per channel instead of four.
 #include "common.h"
 #include "fused.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -328,11 +329,8 @@ dyn_splat_scatter_kernel(int H, int W, const float *__restrict__ rgb1,
   {  // window origin: the smallest in-image target coordinates of the tile (one LDS atomic per wavefront, not per lane:
      // 64 lanes on one LDS word are served one after the other)
     int mx = part ? (c.x0 < 0 ? 0 : c.x0) : 0x7fffffff, my = part ? (c.y0 < 0 ? 0 : c.y0) : 0x7fffffff;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      mx = min(mx, __shfl_xor(mx, d));
-      my = min(my, __shfl_xor(my, d));
-    }
+    mx = wave_reduce_all<OpMin>(mx);
+    my = wave_reduce_all<OpMin>(my);
     if ((threadIdx.x & 63) == 0 && mx != 0x7fffffff) {
       atomicMin(&s_org[0], mx);
       atomicMin(&s_org[1], my);

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "common.h"
+#include "wave.h"
 
 namespace pgdvs {
 
@@ -503,26 +504,6 @@ __device__ __forceinline__ void step_owner_of(const int64_t g, const int gx, int
   b = (j - r * L) * 8 + xcd;
 }
 
-// block-wide exclusive offset of `c` (256 threads) and the block total
-__device__ __forceinline__ int block_excl_256(const int c, int *s_wsum, int &total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = c;
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) s_wsum[wave] = x;
-  __syncthreads();
-  int wave_off = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w < wave) wave_off += s_wsum[w];
-    total += s_wsum[w];
-  }
-  return wave_off + x - c;
-}
-
 constexpr unsigned kSelSpinLimit = 1u << 22;
 
 // tile count granule: [63:48] frame tag, [47:46] status (unused, 1), [45:0] value
@@ -608,19 +589,8 @@ __global__ void __launch_bounds__(kSelThreads) agg_select_kernel(SelArgs a, CamB
   const int base = tile * kSelTile + tid * kSelItems;
   const unsigned flags = base < a.P ? sel_flags16(a, base) : 0u;
   const int c = __popc(flags);
-  int x = c;
-  for (int off = 1; off < 64; off <<= 1) {
-    int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) wave_sums[wave] = x;
-  __syncthreads();
-  int wave_off = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < kSelThreads / kWave; ++w) {
-    if (w < wave) wave_off += wave_sums[w];
-    total += wave_sums[w];
-  }
+  int total;
+  const int excl = block_excl_scan<kSelThreads / kWave>(c, wave_sums, total);
   // Ordered offsets without a second launch: every tile publishes its count as one tagged
   // 8-byte granule, then sums the granules of ALL its predecessors (each thread polls its own
   // few words, one visibility round trip in total -- every tile of a frame is resident at the
@@ -647,7 +617,7 @@ __global__ void __launch_bounds__(kSelThreads) agg_select_kernel(SelArgs a, CamB
     }
     part += (long long)(d & ((1ull << 46) - 1));
   }
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+  part = wave_sum_down(part);
   __shared__ long long wave_part[kSelThreads / kWave];
   if (lane == 0) wave_part[wave] = part;
   __syncthreads();
@@ -670,7 +640,7 @@ __global__ void __launch_bounds__(kSelThreads) agg_select_kernel(SelArgs a, CamB
   // several independent loads in flight, however the selected pixels cluster.
   if (total == 0) return;
   {
-    int slot = wave_off + x - c;
+    int slot = excl;
     unsigned f = flags;
     while (f) {
       const int k = __builtin_ctz(f);
@@ -774,7 +744,7 @@ agg_step_kernel(SelArgs a, uint8_t *__restrict__ occ_all, uint16_t *__restrict__
   if (rec_mine) reinterpret_cast<float4 *>(s_pc)[tid] = rec4;
   const int fb = fa + fpg < f_hi ? fa + fpg : f_hi;
   int n;
-  int slot = block_excl_256(__popc(bits), s_wsum, n);
+  int slot = block_excl_scan<4>(__popc(bits), s_wsum, n);
   if (n == 0) return;
   const bool staged = blockIdx.y == 0 && stage.rows != nullptr;
   const int64_t wg_slot = (int64_t)src * stage.gx + blockIdx.x;  // this workgroup's block of staged rows / chunk starts
@@ -836,7 +806,7 @@ __global__ void __launch_bounds__(kBitTileWords) agg_count_kernel(const uint32_t
   __shared__ int s_wsum[4];
   const int f = 1 + (int)blockIdx.y;
   int total;
-  block_excl_256(__popc(sel[(int64_t)f * Wd + (int64_t)blockIdx.x * kBitTileWords + threadIdx.x]), s_wsum, total);
+  block_excl_scan<4>(__popc(sel[(int64_t)f * Wd + (int64_t)blockIdx.x * kBitTileWords + threadIdx.x]), s_wsum, total);
   if (threadIdx.x == 0) tile_cnt[(int64_t)f * tiles + blockIdx.x] = total;
 }
 
@@ -869,7 +839,7 @@ agg_rows_kernel(const uint32_t *__restrict__ sel, int64_t Wd, int tiles, const i
   const int f = 1 + (int)blockIdx.y, t = (int)blockIdx.x;
   const uint32_t bits = sel[(int64_t)f * Wd + (int64_t)t * kBitTileWords + tid];
   int total;
-  int slot = block_excl_256(__popc(bits), s_wsum, total);
+  int slot = block_excl_scan<4>(__popc(bits), s_wsum, total);
   // (the last workgroup stays to leave the cloud's size)
   const bool last_wg = blockIdx.y == gridDim.y - 1 && blockIdx.x == gridDim.x - 1;
   if (total == 0 && !last_wg) return;
@@ -881,7 +851,7 @@ agg_rows_kernel(const uint32_t *__restrict__ sel, int64_t Wd, int tiles, const i
   // nothing have left by now.
   long long before = 0;
   for (int64_t u = (int64_t)tiles + tid; u < (int64_t)f * tiles + t; u += kBitTileWords) before += tile_cnt[u];
-  for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off, 64);
+  before = wave_sum_all(before);
   if ((tid & 63) == 0) s_before[tid >> 6] = before;
   __syncthreads();
   before = (s_before[0] + s_before[1]) + (s_before[2] + s_before[3]);

@@ -35,6 +35,7 @@
 #include "common.h"
 #include "radix_select.h"
 #include "scan.h"
+#include "wave.h"
 
 namespace pgdvs {
 namespace {
@@ -355,7 +356,7 @@ struct FinThreshold {
 };
 
 __device__ __forceinline__ double block_sum(double v, double *sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = wave_sum_down(v);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
   double s = 0.0;

@@ -61,7 +61,10 @@ def test_rays(golden_dir, name):
 
 
 # ---------------------------------------------------------------- compaction
-@pytest.mark.parametrize("n", [0, 1, 63, 4096, 4097, 100003, 2073600])
+# (wavefront = 64 flags' threads, tile = 4096 flags; compact_scan_kernel scans 1024 tile counts per round and carries the
+# running sum into the next: 4096 * 1024 flags fill one round exactly, one flag more opens a second)
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 100003, 2073600,
+                               4096 * 1024, 4096 * 1024 + 1, 4096 * 1025 + 5])
 def test_compact(n):
     rng = np.random.default_rng(n)
     flags = (rng.random(n) < 0.3).astype(np.uint8) * rng.integers(1, 255, n).astype(np.uint8)
