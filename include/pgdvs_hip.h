@@ -740,6 +740,46 @@ int pgdvs_flow_consistency(const float *flow12, const float *flow21, int H, int 
  * e_dist 8-byte aligned.  Shapes: H, W >= 2, H < 2^18 - 4, H W < 2^31, else PGDVS_ERR_INVALID. */
 int pgdvs_epipolar_mask(const float *flow, const float *coord_diff, int H, int W, const double *F, double consist_thres,
                         double threshold, uint8_t *mask, double *e_dist, pgdvs_stream_t stream);
+/* FlowFormer's tiled inference after the network (pgdvs/preprocess/compute_flow.py:138-165 compute_weight, :182-209, the tile
+ * branch of compute_flow_flowformer; csrc/flow_export.hip): tiles[n,2,ph,pw] float32 on the device, planar, as the network
+ * returns them; origins = HOST int32[n][2], (h, w) per tile in upstream's order (:61-82 compute_grid_indices); weight[ph,pw]
+ * float32 on the device -> flow[H,W,2] float32, the layout the .npz stores.  Per pixel and component, in float32: acc = +0,
+ * cnt = +0; over the tiles in index order that cover the pixel acc = acc + tile w and cnt = cnt + w, product and sum rounded
+ * separately; flow = acc / cnt, correctly rounded.  That is upstream's flows += F.pad(flow_pre * weights[idx]),
+ * flow_count += F.pad(weights[idx]), flows / flow_count: a tile that does not cover the pixel adds +0 there.  Denormal
+ * weights (the rim of a tile at sigma 0.05) are kept, nothing is flushed.  Origins may be unsorted and overlap in any way.
+ * One launch, no workspace.  tiles and weight 4-byte aligned, flow 8-byte.  PGDVS_ERR_INVALID unless 1 <= n <= 128,
+ * 1 <= ph <= H, 1 <= pw <= W, 0 <= h <= H - ph and 0 <= w <= W - pw for every origin, the tiles cover every pixel (else a
+ * pixel were 0 / 0), H < 2^18 - 4 and H W < 2^31. */
+int pgdvs_flow_tile_blend(const float *tiles, const int32_t *origins, int n, int ph, int pw, const float *weight, int H, int W,
+                          float *flow, pgdvs_stream_t stream);
+/* Everything upstream's flow stage derives from a pair's flows, in TWO launches (compute_flow.py:335-340 compute_occlusion,
+ * :351-361 the two .npz and the two flow_to_image PNGs; preprocess/common.py:93-205 make_colorwheel, flow_uv_to_colors,
+ * flow_to_image; csrc/flow_export.hip, csrc/png.hip): flow12[H,W,2], flow21[H,W,2] float32 on the device ->
+ *   coord_diff_1, coord_diff_2 [H,W,2]  exactly pgdvs_flow_consistency's values (the same per-pixel statement); both NULL:
+ *                                       the pictures alone, and then H, W >= 1 suffice and flow21 may be NULL as well:
+ *                                       ONE picture, rad_max[1] and out[1,H,1+3W]
+ *   rad_max[2] float32                  per flow the maximum over the frame of rad = sqrt(u u + v v), float32, square, sum
+ *                                       and root rounded on their own; NaN if any radius is NaN, as np.max
+ *   out[2,H,1+3W] uint8                 the PNG scanlines of flow_to_image(flow12) and flow_to_image(flow21), filtered as
+ *                                       pgdvs_png_scanlines filters (adaptive 0 / 1); out needs no alignment
+ * The colour of a pixel, upstream's types under NumPy 2: u, v divided by float32(rad_max + float32(1e-5)); rad again from the
+ * normalised pair; a = atan2f(-v, -u) / float32(pi); fk = (a + 1) / 2 * 54; k0 = floor(fk), k1 = k0 + 1 wrapped to 0 at 55,
+ * f = fk - k0, all float32; then in double col = (1 - f) wheel[k0] / 255 + f wheel[k1] / 255, col = 1 - rad (1 - col) where
+ * rad <= 1, else 0.75 col, and the byte floor(255 col).  wheel is the 55 x 3 Middlebury table (segments 15, 6, 4, 11, 13, 6).
+ * rad_max and the normalised u, v are correctly rounded IEEE and equal numpy's bit for bit; atan2f is the device library's,
+ * so a byte may differ by one level from a given machine's numpy where 255 col lies next to an integer.  A pixel whose
+ * normalised u or v is NaN gives 0 0 0 (upstream's NaN-to-integer cast is undefined); k0 is clamped before it indexes the
+ * table.  An infinite flow makes rad_max inf: finite pixels normalise to 0 and come out white, infinite ones are NaN.
+ * First launch: coord_diff and the radius maximum, one key per workgroup, grid-strided; second launch: one workgroup per
+ * row of either picture reduces the keys, colours the row and the row above it into LDS and filters (each flow is read from
+ * memory twice, the second time as "the row above" from the cache).  No atomics.  workspace:
+ * pgdvs_flow_pair_export_workspace_bytes(H, W) bytes, 256-byte aligned.  Flows and coord_diffs 8-byte aligned.  Shapes:
+ * H, W >= 2 (>= 1 without coord_diff), H W < 2^31, 2 H (1 + 3 W) < 2^31, else PGDVS_ERR_INVALID. */
+int64_t pgdvs_flow_pair_export_workspace_bytes(int H, int W);
+int pgdvs_flow_pair_export(const float *flow12, const float *flow21, int H, int W, int adaptive, float *coord_diff_1,
+                           float *coord_diff_2, float *rad_max, uint8_t *out, void *workspace, int64_t workspace_bytes,
+                           pgdvs_stream_t stream);
 /* The ZoeDepth stage's look-ups for one frame (pgdvs/preprocess/compute_zoedepth.py:262-294; csrc/zoe_align.hip):
  * pred_depth[H,W] and mask[H,W] float32 and pts3d[P,3] float32 on the device, w2c = HOST double[16] and K = HOST double[9],
  * row-major -> the kept points, in ascending point order: proj_pcl[3,P] double (rows x, y, 1; the first *count entries of

@@ -25,7 +25,13 @@
 // ground truth is channel-last: a row of it is already in PNG byte order, so it is staged with contiguous 16-byte loads
 // (stage_row<kHwc>) instead of three plane reads; everything behind the staging is scanline_row, shared with the
 // visualiser's kernel.
+//
+// Flow pictures (pgdvs/preprocess/common.py:93-205 flow_to_image, called at compute_flow.py:354-361): a third staging,
+// stage_row<kFlow>, computes a row's Middlebury colour-wheel bytes from the flow itself instead of quantising an image; the
+// scanlines of both pictures of a pair leave in one launch (flow_pictures_kernel, the second pass of
+// pgdvs_flow_pair_export; the first, in flow_export.hip, left the radius maximum as per-block keys).
 #include "common.h"
+#include "flow_pixel.h"
 #include "wave.h"
 
 namespace pgdvs {
@@ -38,6 +44,7 @@ constexpr int kWords = (kLead + 3 * kChunk + 8) / 4;  // + 8 bytes behind the la
 
 constexpr int kPlanar = 0;  // [3,H,W]: a row is three plane rows of W floats
 constexpr int kHwc = 1;     // [H,W,3]: a row is 3 W contiguous floats, already in PNG byte order
+constexpr int kFlow = 2;    // flow[H,W,2]: a row is W (u, v) pairs, coloured by flow_colour
 
 struct Params {
   const float *img;  // [B,3,H,W] (kPlanar) or [H,W,3] (kHwc)
@@ -45,7 +52,57 @@ struct Params {
   int H, W;
   int quant, adaptive;
   int vec4;          // W % 4 == 0 and img 16-byte aligned: float4 loads
+  float denom;       // kFlow: float32(rad_max + float32(1e-5)), what upstream divides u and v by
 };
+
+// The Middlebury colour wheel (Baker et al., "A Database and Evaluation Methodology for Optical Flow", ICCV 2007): six
+// segments of 15, 6, 4, 11, 13 and 6 entries, red -> yellow -> green -> cyan -> blue -> magenta -> red; along a segment one
+// channel ramps by floor(255 j / length), up or down, one stays 255 and one 0.  Held as entry / 255 in double, the value
+// upstream's tmp[k] / 255.0 has (one correctly rounded division either way).
+constexpr int kWheelN = 55;
+struct Wheel {
+  double v[kWheelN][3];
+};
+constexpr Wheel make_wheel() {
+  constexpr int len[6] = {15, 6, 4, 11, 13, 6};
+  constexpr int full[6] = {0, 1, 1, 2, 2, 0};  // the channel at 255
+  constexpr int ramp[6] = {1, 0, 2, 1, 0, 2};  // the channel that ramps, up in the even segments and down in the odd ones
+  Wheel w{};
+  int k = 0;
+  for (int s = 0; s < 6; ++s)
+    for (int j = 0; j < len[s]; ++j, ++k) {
+      const int r = 255 * j / len[s];
+      for (int c = 0; c < 3; ++c) w.v[k][c] = 0.0;
+      w.v[k][full[s]] = 255.0 / 255.0;
+      w.v[k][ramp[s]] = (double)(s % 2 == 0 ? r : 255 - r) / 255.0;
+    }
+  return w;
+}
+__device__ const Wheel kWheel = make_wheel();
+
+// One pixel of flow_to_image as R | G << 8 | B << 16, upstream's types under NumPy 2: the normalisation, the radius, the angle
+// and fk in float32, every operation rounded on its own; from the interpolation on in double (the wheel table is float64).
+// A NaN in the normalised u or v gives 0 0 0; the table index is clamped, so no flow value becomes an address.
+__device__ __forceinline__ uint32_t flow_colour(float2 f, float denom) {
+  const float u = f.x / denom, v = f.y / denom;
+  if (!(u == u) || !(v == v)) return 0u;
+  const float rad = sqrtf(u * u + v * v);
+  const float a = atan2f(-v, -u) / 3.14159274101257324f;
+  const float fk = (a + 1.0f) / 2.0f * (float)(kWheelN - 1);
+  const float k0f = floorf(fk);
+  const int k0 = k0f >= 0.0f ? (k0f <= (float)(kWheelN - 1) ? (int)k0f : kWheelN - 1) : 0;  // (a NaN lands on 0)
+  const int k1 = k0 + 1 == kWheelN ? 0 : k0 + 1;
+  const double fr = (double)fk - (double)k0;
+  uint32_t rgb = 0u;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double col = (1.0 - fr) * kWheel.v[k0][c] + fr * kWheel.v[k1][c];
+    col = rad <= 1.0f ? 1.0 - (double)rad * (1.0 - col) : col * 0.75;
+    const double b = floor(255.0 * col);
+    rgb |= (uint32_t)(int)fmin(fmax(b, 0.0), 255.0) << (8 * c);
+  }
+  return rgb;
+}
 
 __device__ __forceinline__ uint32_t quantise(float x, int quant) {
   if (!(x == x)) return 0u;
@@ -55,7 +112,7 @@ __device__ __forceinline__ uint32_t quantise(float x, int quant) {
   return (uint32_t)(int)v;
 }
 
-// Stage pixels [c0, c0 + n) of an image row (kPlanar: plane 0 of it at `src`; kHwc: its first float at `src`) into `dst`: pixel
+// Stage pixels [c0, c0 + n) of an image row (kPlanar: plane 0 of it at `src`; kHwc, kFlow: its first float at `src`) into `dst`: pixel
 // c0 + i at bytes kLead + 3 i, the pixel to the left of c0 (zero for c0 = 0) at bytes 5..7.  zero: the row above row 0.
 template <int L>
 __device__ void stage_row(const Params &p, const float *__restrict__ src, bool zero, int c0, int n, uint32_t *__restrict__ dst) {
@@ -90,8 +147,26 @@ __device__ void stage_row(const Params &p, const float *__restrict__ src, bool z
     }
     return;
   }
-  const size_t plane = (size_t)p.H * p.W;
   const int quads = (n + 3) >> 2;
+  if (L == kFlow) {
+    // four pixels, twelve bytes, three LDS words per thread and step, as the planar staging below
+    const float2 *__restrict__ row = reinterpret_cast<const float2 *>(src) + c0;
+    for (int q = threadIdx.x; q < quads; q += kBlock) {
+      uint32_t c[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c[i] = (!zero && 4 * q + i < n) ? flow_colour(row[4 * q + i], p.denom) : 0u;
+      uint32_t *w = dst + kLead / 4 + 3 * q;
+      w[0] = c[0] | (c[1] << 24);
+      w[1] = (c[1] >> 8) | (c[2] << 16);
+      w[2] = (c[2] >> 16) | (c[3] << 8);
+    }
+    if (threadIdx.x == kBlock - 1) {
+      dst[0] = 0u;
+      dst[1] = (!zero && c0 > 0) ? flow_colour(row[-1], p.denom) << 8 : 0u;
+    }
+    return;
+  }
+  const size_t plane = (size_t)p.H * p.W;
   for (int q = threadIdx.x; q < quads; q += kBlock) {
     uint32_t v[12];
     if (zero) {
@@ -218,7 +293,7 @@ __shared__ int s_type;
 template <int L>
 __device__ __forceinline__ void scanline_row(const Params &p, const float *__restrict__ cur, int y, uint8_t *__restrict__ out_row) {
   const int W = p.W;
-  const float *up = y > 0 ? cur - (L == kHwc ? 3 * W : W) : cur;  // (row 0 has zeros above it: stage_row's `zero`)
+  const float *up = y > 0 ? cur - (L == kHwc ? 3 * W : L == kFlow ? 2 * W : W) : cur;  // (row 0 has zeros above it: stage_row's `zero`)
   const int n_chunks = (W + kChunk - 1) / kChunk;
   int type = 0;
 
@@ -335,7 +410,60 @@ __global__ void __launch_bounds__(kBlock) eval_export_scanlines_kernel(ExportPar
   }
 }
 
+struct FlowPicParams {
+  const float *flow[2];  // [H,W,2] each (one or two pictures: the grid says)
+  const uint32_t *keys;  // [n_img][n_keys] radius keys of the first pass (flow_pixel.h)
+  float *rad_max;        // [n_img]
+  uint8_t *out;          // [n_img,H,1+3W]
+  int n_keys, H, W, adaptive;
+};
+
+// picture = blockIdx.x / H.  Every row's workgroup reduces the picture's keys itself (a few KB from the cache) rather than
+// wait for a launch that would do it once; integer maxima, so every workgroup holds the same bits.
+__global__ void __launch_bounds__(kBlock) flow_pictures_kernel(FlowPicParams e) {
+  __shared__ uint32_t s_key[kBlock / kWave];
+  const int H = e.H, W = e.W;
+  const int img = blockIdx.x / H, y = blockIdx.x - img * H;
+  uint32_t key = 0u;
+  for (int i = threadIdx.x; i < e.n_keys; i += kBlock) key = max(key, e.keys[(size_t)img * e.n_keys + i]);
+  key = wave_reduce_all<OpMax>(key);
+  if ((threadIdx.x & (kWave - 1)) == 0) s_key[threadIdx.x / kWave] = key;
+  __syncthreads();
+  key = s_key[0];
+#pragma unroll
+  for (int w = 1; w < kBlock / kWave; ++w) key = max(key, s_key[w]);
+  const float rad_max = rad_of_key(key);
+  if (y == 0 && threadIdx.x == 0) e.rad_max[img] = rad_max;
+  Params p;
+  p.img = e.flow[img];
+  p.out = e.out;
+  p.H = H;
+  p.W = W;
+  p.quant = 0;
+  p.adaptive = e.adaptive;
+  p.vec4 = 0;
+  p.denom = rad_max + 1e-5f;
+  scanline_row<kFlow>(p, p.img + (size_t)y * 2 * W, y, e.out + (size_t)blockIdx.x * (1 + 3 * (size_t)W));
+}
+
 }  // namespace
+
+int launch_flow_pictures(const float *flow12, const float *flow21, int n_img, int H, int W, int adaptive, const uint32_t *keys, int n_keys,
+                         float *rad_max, uint8_t *out, hipStream_t stream) {
+  FlowPicParams e;
+  e.flow[0] = flow12;
+  e.flow[1] = flow21;
+  e.keys = keys;
+  e.rad_max = rad_max;
+  e.out = out;
+  e.n_keys = n_keys;
+  e.H = H;
+  e.W = W;
+  e.adaptive = adaptive;
+  PGDVS_LAUNCH("flow_pictures", flow_pictures_kernel, dim3((unsigned)(n_img * H)), dim3(kBlock), 0, stream, e);
+  return check_launch("pgdvs_flow_pair_export");
+}
+
 }  // namespace pgdvs
 
 using namespace pgdvs;
@@ -356,6 +484,7 @@ PGDVS_API int pgdvs_png_scanlines(const float *img_planar, int B, int H, int W, 
   p.quant = quant;
   p.adaptive = adaptive;
   p.vec4 = (W % 4 == 0) && (reinterpret_cast<uintptr_t>(img_planar) & 15) == 0;
+  p.denom = 0.0f;
   PGDVS_LAUNCH("png_scanlines", png_scanlines_kernel, dim3((unsigned)(B * H)), dim3(kBlock), 0, as_stream(stream), p);
   return check_launch("pgdvs_png_scanlines");
 }

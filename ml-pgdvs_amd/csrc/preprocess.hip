@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "flow_pixel.h"
 
 namespace pgdvs {
 namespace {
@@ -31,12 +32,6 @@ struct FcParams {
   int H, W;
 };
 
-// img[y][x] when (x, y), float integers, lies in the image, else zero (grid_sample's padding_mode="zeros")
-__device__ __forceinline__ float2 texel_or_zero(const float2 *__restrict__ img, float x, float y, int H, int W) {
-  if (x >= 0.0f && x <= (float)(W - 1) && y >= 0.0f && y <= (float)(H - 1)) return img[(size_t)(int)y * W + (int)x];
-  return make_float2(0.0f, 0.0f);
-}
-
 __global__ void __launch_bounds__(kFcBlockX *kFcBlockY) flow_consistency_kernel(FcParams p) {
   const int x = blockIdx.x * kFcBlockX + threadIdx.x, y = blockIdx.y * kFcBlockY + threadIdx.y;
   if (x >= p.W || y >= p.H) return;
@@ -44,21 +39,7 @@ __global__ void __launch_bounds__(kFcBlockX *kFcBlockY) flow_consistency_kernel(
   const float2 *__restrict__ mine = p.flow[dir];
   const float2 *__restrict__ other = p.flow[1 - dir];
   const size_t i = (size_t)y * p.W + x;
-  const float2 f = mine[i];
-  const float px = (float)x, py = (float)y;
-  const float wm1 = (float)(p.W - 1), hm1 = (float)(p.H - 1);
-  const float c1x = px + f.x, c1y = py + f.y;
-  const float gx = 2.0f * c1x / wm1 - 1.0f, gy = 2.0f * c1y / hm1 - 1.0f;
-  const float ix = ((gx + 1.0f) / 2.0f) * wm1, iy = ((gy + 1.0f) / 2.0f) * hm1;
-  const float x0 = floorf(ix), y0 = floorf(iy);
-  const float w = ix - x0, n = iy - y0;
-  const float e = 1.0f - w, s = 1.0f - n;
-  const float2 nw = texel_or_zero(other, x0, y0, p.H, p.W), ne = texel_or_zero(other, x0 + 1.0f, y0, p.H, p.W);
-  const float2 sw = texel_or_zero(other, x0, y0 + 1.0f, p.H, p.W), se = texel_or_zero(other, x0 + 1.0f, y0 + 1.0f, p.H, p.W);
-  const float wnw = e * s, wne = w * s, wsw = e * n, wse = w * n;
-  const float sx = ((nw.x * wnw + ne.x * wne) + sw.x * wsw) + se.x * wse;
-  const float sy = ((nw.y * wnw + ne.y * wne) + sw.y * wsw) + se.y * wse;
-  p.out[dir][i] = make_float2(px - (c1x + sx), py - (c1y + sy));
+  p.out[dir][i] = coord_diff_pixel(mine[i], other, x, y, p.H, p.W);
 }
 
 // ---- epipolar mask ----

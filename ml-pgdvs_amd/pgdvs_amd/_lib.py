@@ -115,6 +115,9 @@ SIGNATURES.update({
     "pgdvs_eval_export_scanlines": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "pgdvs_flow_consistency": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "pgdvs_epipolar_mask": (_i, [_vp, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "pgdvs_flow_tile_blend": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "pgdvs_flow_pair_export_workspace_bytes": (_i64, [_i, _i]),
+    "pgdvs_flow_pair_export": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_zoe_sample_workspace_bytes": (_i64, [_i, _i, _i64]),
     "pgdvs_zoe_sample": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_zoe_fit_workspace_bytes": (_i64, [_i64]),

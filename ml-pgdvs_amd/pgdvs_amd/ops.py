@@ -840,6 +840,64 @@ def flow_consistency(flow12, flow21):
     return cd1, cd2
 
 
+def flow_tile_blend(tiles, origins, weight, H, W):
+    """FlowFormer's tiled inference after the network (``pgdvs_flow_tile_blend``; include/pgdvs_hip.h): tiles[n,2,ph,pw]
+    float32 on the GPU, planar as the network returns them, ``origins`` the n host pairs (h, w) in upstream's order,
+    weight[ph,pw] float32 on the GPU -> flow[H,W,2] float32 on the GPU: per pixel the weighted mean of the tiles that cover
+    it, accumulated in tile order.  One launch."""
+    t, w = _req(tiles, torch.float32, "tiles"), _req(weight, torch.float32, "weight")
+    org = np.ascontiguousarray(np.asarray(origins), dtype=np.int32)
+    if t.ndim != 4 or t.shape[1] != 2 or tuple(w.shape) != tuple(t.shape[2:]) or org.shape != (t.shape[0], 2) or t.device != w.device:
+        raise ValueError(f"flow_tile_blend: shapes tiles {tuple(t.shape)}, weight {tuple(w.shape)}, origins {org.shape} "
+                         "([n,2,ph,pw], [ph,pw] and [n,2], one device)")
+    n, _, ph, pw = (int(v) for v in t.shape)
+    H, W = int(H), int(W)
+    out = torch.empty((max(H, 0), max(W, 0), 2), dtype=torch.float32, device=t.device)
+    check(_lib.load().pgdvs_flow_tile_blend(_ptr(t), org.ctypes.data_as(C.c_void_p), n, ph, pw, _ptr(w), H, W, _ptr(out), _stream()),
+          "pgdvs_flow_tile_blend")
+    return out
+
+
+def _flow_export(a, b, H, W, adaptive, cd1, cd2, out, what):
+    shape = (1 if b is None else 2, H, 1 + 3 * W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=a.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == a.device and out.dtype == torch.uint8
+              and out.is_contiguous() and out.numel() == shape[0] * shape[1] * shape[2]):
+        raise ValueError(f"{what}: out must be a contiguous uint8 tensor of {shape} on {a.device}")
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_flow_pair_export_workspace_bytes(H, W), a.device)
+    rad_max = torch.empty((shape[0],), dtype=torch.float32, device=a.device)
+    check(lib.pgdvs_flow_pair_export(_ptr(a), _ptr(b), H, W, 1 if adaptive else 0, _ptr(cd1), _ptr(cd2), _ptr(rad_max), _ptr(out),
+                                     _ptr(ws), ws.numel(), _stream()), "pgdvs_flow_pair_export")
+    return rad_max, out.view(shape)
+
+
+def flow_pair_export(flow12, flow21, adaptive=True, out=None):
+    """Everything the flow stage derives from a pair's flows (``pgdvs_flow_pair_export``; include/pgdvs_hip.h): flow12[H,W,2]
+    and flow21[H,W,2] float32 on the GPU -> (coord_diff_1, coord_diff_2, rad_max[2], scanlines[2,H,1+3W] uint8), all on the
+    GPU: ``flow_consistency``'s values, the largest flow radius of each frame, and the PNG scanlines of the two colour-wheel
+    pictures (``adaptive`` as in ``png_scanlines``), ready for ``png.PngWriter``.  Two launches.  ``out``: a contiguous uint8
+    GPU tensor of 2 H (1 + 3 W) elements to fill in place (any alignment)."""
+    a, b = _flow_pair(flow12, flow21, ("flow12", "flow21"), "flow_pair_export")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    cd1, cd2 = torch.empty_like(a), torch.empty_like(a)
+    rad_max, out = _flow_export(a, b, H, W, adaptive, cd1, cd2, out, "flow_pair_export")
+    return cd1, cd2, rad_max, out
+
+
+def flow_image(flow, adaptive=False):
+    """The colour-wheel picture of one flow (the pictures-alone call of ``pgdvs_flow_pair_export``): flow[H,W,2] float32 on
+    the GPU -> (rad_max[1], scanlines[H,1+3W] uint8) on the GPU; with ``adaptive=False`` ``scanlines[:, 1:]`` is the packed
+    [H,W,3] picture."""
+    f = _req(flow, torch.float32, "flow")
+    if f.ndim != 3 or f.shape[2] != 2 or f.shape[0] < 1 or f.shape[1] < 1:
+        raise ValueError(f"flow_image: flow [H,W,2] expected, got {tuple(f.shape)}")
+    H, W = int(f.shape[0]), int(f.shape[1])
+    rad_max, out = _flow_export(f, None, H, W, adaptive, None, None, None, "flow_image")
+    return rad_max, out[0]
+
+
 def epipolar_mask(flow, coord_diff, F, consist_thres=1.0, threshold=1.0, want_dist=False):
     """The ``flow_epi`` motion mask of one direction (``pgdvs_epipolar_mask``; include/pgdvs_hip.h): flow[H,W,2] and
     coord_diff[H,W,2] float32 on the GPU, the numpy float64 fundamental matrix ``F[3,3]`` (l_2 = F p_1) -> mask[H,W] uint8
