@@ -700,6 +700,41 @@ void pgdvs_view_geo_host_stats(int64_t *calls, double *seconds);
 int pgdvs_png_scanlines(const float *img_planar, int B, int H, int W, int quant, int adaptive, uint8_t *out,
                         pgdvs_stream_t stream);
 
+/* ---- visualiser video ------------------------------------------------------ */
+/* The frames of the visualiser's video (pgdvs/engines/visualizer_pgdvs.py:141-177, pgdvs/utils/rendering.py:79-116
+ * images_to_video) as baseline JPEG, compressed on the device (csrc/jpeg.hip); pgdvs_amd/video.py holds the same codec in
+ * numpy integers, the JPEG headers and the AVI container.  Upstream encodes H.264 through ffmpeg; this is Motion-JPEG.
+ *
+ * Coefficients: img_planar[B,3,H,W] float32 -> coef[B,nby,nbx,3,64] int16 with nby = ceil(H / 8), nbx = ceil(W / 8): per
+ * 8 x 8 pixel block the quantised DCT coefficients of Y, Cb and Cr in zigzag order.  One pass: the pixel is quantised as
+ * pgdvs_png_scanlines' quant 0 quantises it (so a frame and its *_combined.png hold the same 8-bit image), pixels past the
+ * right / bottom edge replicate the last column / row; Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R -
+ * 21709 G + 32768 B + 8421375) >> 16, Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16, each - 128; the 13-bit integer
+ * DCT of Loeffler, Ligtenberg and Moschytz in the Independent JPEG Group's scaling, rows then columns in int32, which gives
+ * 8 x the coefficient; quantisation with one rounding, sign(c) ((|c| + 4 Q) / (8 Q)).  These are libjpeg's coefficients: at
+ * the same tables and 4:4:4 PIL writes the same scan.  qtab_luma[64], qtab_chroma[64]: HOST uint16 in natural
+ * (row-major) order, each 1 .. 255.  One wavefront per block triple, no atomics, no workspace.  img_planar and coef 4-byte
+ * aligned.  Shapes: B >= 1, H and W in 1 .. 65535, 3 B H W and 192 B nby nbx below 2^31, else PGDVS_ERR_INVALID. */
+int pgdvs_jpeg_coefficients(const float *img_planar, int B, int H, int W, const uint16_t *qtab_luma, const uint16_t *qtab_chroma,
+                            int16_t *coef, pgdvs_stream_t stream);
+/* Entropy coding (rendering.py:79-116, the frame writer's place): coef[B,nby,nbx,3,64] int16 -> per frame b the scan data
+ * of its one interleaved scan, everything between the SOS header and EOI, contiguous from out + b out_stride, its length in
+ * nbytes[b] (device int32); bytes of the slot past that length are not written.  The four typical Huffman tables of T.81
+ * Annex K.3; DC as the difference to the previous block of the component, 0 at the start of a restart segment; AC run / size
+ * symbols, ZRL, EOB unless coefficient 63 is non-zero; every segment padded with ones to a byte, 0xFF followed by 0x00; RSTm
+ * (m cycling 0 .. 7) between segments of restart_mcus MCUs.  On read DC is clamped to -1024 .. 1023 and AC to +-1023, so
+ * every symbol exists in the tables whatever the input holds (pgdvs_jpeg_coefficients stays inside those ranges).
+ * restart_mcus in 1 .. 65535 (larger than the frame: one segment, no marker); 0, a scan without restart markers, is
+ * host-only (video.encode_scan): the device pass compresses segments independently and they must end on bytes.  Three
+ * launches, no global atomics, no workgroup waits for another.  out_stride >= 1248 nby nbx + 2 (segments - 1) with
+ * segments = ceil(nby nbx / min(restart_mcus, nby nbx)): a block costs at most 20 + 63 x 26 = 1658 bits = 208 bytes,
+ * doubled by stuffing.  workspace: pgdvs_jpeg_scan_workspace_bytes bytes, 256-byte aligned (-1 for shapes the call rejects);
+ * coef 16-byte aligned, out none.  Shapes: B >= 1, nby and nbx in 1 .. 8192, B out_stride and the workspace below 2^31, else
+ * PGDVS_ERR_INVALID. */
+int64_t pgdvs_jpeg_scan_workspace_bytes(int B, int nby, int nbx, int restart_mcus);
+int pgdvs_jpeg_scan(const int16_t *coef, int B, int nby, int nbx, int restart_mcus, uint8_t *out, int64_t out_stride,
+                    int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+
 /* ---- evaluator export ------------------------------------------------------ */
 /* The images save_vis_for_eval writes for one view (pgdvs/engines/evaluator_pgdvs.py:417-465: *_gt.png :432-433,
  * *_combined.png :435-440, *_gnt.png :442-452 / *_geo_static.png :453-465) up to the deflate, in ONE launch from the RAW

@@ -627,14 +627,30 @@ def _view_scanlines(img: torch.Tensor, quant: str):
     return png.filter_scanlines(png.QUANTIZERS[quant](img).permute(0, 2, 3, 1).contiguous().cpu(), adaptive=True)
 
 
+def _video_frames(img: torch.Tensor, writer):
+    """img[B,3,H,W] -> what ``MjpegWriter.submit`` takes per view: for a GPU float32 batch the ``DeviceScan`` views of ONE
+    ``ops.jpeg_encode`` (csrc/jpeg.hip) behind one event, the host images otherwise"""
+    if not (img.is_cuda and img.dtype == torch.float32):
+        return list(img.float().cpu())
+    from . import ops, video
+
+    data, nbytes = ops.jpeg_encode(img, quality=writer.quality, restart_mcus=writer.restart_mcus)
+    ready = torch.cuda.current_stream(img.device).record_event()
+    return [video.DeviceScan(data[i], nbytes[i:i + 1], img.shape[2], img.shape[3], ready) for i in range(img.shape[0])]
+
+
 @torch.no_grad()
-def vis_step(model, data: dict, render_cfg, vis_dir, *, device=None, writer=None, disable_tqdm=True, return_ret=False):
+def vis_step(model, data: dict, render_cfg, vis_dir, *, device=None, writer=None, disable_tqdm=True, return_ret=False, video=None):
     """The body of ``PGDVSVisualizer.vis_model``'s loop for one batch: to-device, ``forward`` under no_grad, the geometry
     path's status words checked as ``eval_step`` checks them, then per view ``vis_dir / split / scene_id /
     {tgt_idx:05d}_combined.png`` from ``combined_rgb`` (``torchvision.utils.save_image``'s quantisation) and, when the
     renderer returns ``static_coarse_rgb``, ``{tgt_idx:05d}_gnt.png`` from it (the truncating cast).  ``writer``: a
     ``png.PngWriter`` that copies, deflates and writes behind this thread (the files are complete once it is closed);
-    without one the step writes each file before it returns.  Returns the paths (and ``ret`` with ``return_ret``)."""
+    without one the step writes each file before it returns.  ``video``: a ``video.MjpegWriter``; each view's ``combined_rgb``
+    also becomes a frame of ``vis_dir / split / {scene_id}_combined.avi`` (upstream's ``_combined.mp4``, :141-177, as
+    Motion-JPEG), written when that writer is closed: a GPU batch is compressed by one ``ops.jpeg_encode`` and the frames
+    are fetched behind this thread, host images are encoded by the writer's workers.  Returns the paths of the PNGs (and
+    ``ret`` with ``return_ret``)."""
     import pathlib
 
     from . import png
@@ -648,12 +664,15 @@ def vis_step(model, data: dict, render_cfg, vis_dir, *, device=None, writer=None
     if "static_coarse_rgb" in ret:  # the pure GNT result (:127-139)
         outputs.append(("gnt", ret["static_coarse_rgb"], "truncate"))
     lines = [(tag, _view_scanlines(img, quant), int(img.shape[2]), int(img.shape[3])) for tag, img, quant in outputs]
+    frames = _video_frames(ret["combined_rgb"], video) if video is not None else None
     _check_geo_status(ret, data_gpu)
     paths = []
     misc = data["misc"]
     for i_b in range(ret["combined_rgb"].shape[0]):
         scene_dir = pathlib.Path(vis_dir) / misc[i_b].get("split", "") / misc[i_b]["scene_id"]
         scene_dir.mkdir(parents=True, exist_ok=True)
+        if frames is not None:
+            video.submit((scene_dir.parent, misc[i_b]["scene_id"]), misc[i_b]["tgt_idx"], frames[i_b])
         for tag, scan, h, w in lines:
             path = scene_dir / f"{misc[i_b]['tgt_idx']:05d}_{tag}.png"
             if writer is not None:
@@ -695,26 +714,48 @@ def _run_batches(what, dataset, batch_size, n_max_data, rank, world):
     return batches()
 
 
-def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, writer=None):
+def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, writer=None,
+            video=False, video_fps=10, video_quality=90):
     """``vis_model``'s outer loop without Hydra: this rank's items in ``DistributedSampler(shuffle=False)`` order
     (``dist.shard_indices``), ``batch_size`` of them per step (the per-process batch size), collated as upstream collates
     them, at most ``ceil(min(len(dataset), n_max_data) / (batch_size * world))`` steps (``n_max_data <= 0``: all), each
     through ``vis_step``.  The files go through one ``png.PngWriter``: the given one, which stays open for its owner to
     close, or one made here and closed (every file complete) before the function returns.  Returns ``{scene_id:
-    directory}``.  The reference's mp4 step is not part of this."""
+    directory}``.
+
+    ``video=True`` (or a ``video.MjpegWriter``, which is closed here): every view's ``combined_rgb`` also becomes a frame of
+    ``<vis_dir>/<split or "">/<scene_id>_combined.avi`` at ``video_fps`` frames per second and libjpeg quality
+    ``video_quality``, frames in ``tgt_idx`` order: upstream's ``_combined.mp4`` (:141-177) as Motion-JPEG, see
+    ``pgdvs_amd/video.py``.  With ``world > 1`` each rank leaves hidden part files instead; under an initialised process
+    group of that size the ranks then meet at a barrier and rank 0 merges them (``video.assemble``), without one call
+    ``video.assemble(vis_dir, world)`` once every rank has returned.  The default writes no video and nothing else changes."""
     from . import png
+    from . import video as vid
 
     batches = _run_batches("vis_run", dataset, batch_size, n_max_data, rank, world)
     own = writer is None
     w = png.PngWriter() if own else writer
+    mj = None
+    if video is not None and video is not False:
+        mj = vid.MjpegWriter(fps=video_fps, quality=video_quality, rank=rank, world=world) if video is True else video
     dirs = {}
     try:
         for batch in batches:
-            for path in vis_step(model, batch, render_cfg, vis_dir, device=device, writer=w):
+            for path in vis_step(model, batch, render_cfg, vis_dir, device=device, writer=w, video=mj):
                 dirs[path.parent.name] = path.parent
     finally:
-        if own:
-            w.close()
+        try:
+            if own:
+                w.close()
+        finally:
+            if mj is not None:
+                mj.close()
+    if mj is not None and mj.world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized() and (
+            torch.distributed.get_world_size() == mj.world):
+        torch.distributed.barrier()
+        if mj.rank == 0:
+            vid.assemble(vis_dir, mj.world)
+        torch.distributed.barrier()
     return dirs
 
 
