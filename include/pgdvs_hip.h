@@ -735,6 +735,28 @@ int64_t pgdvs_jpeg_scan_workspace_bytes(int B, int nby, int nbx, int restart_mcu
 int pgdvs_jpeg_scan(const int16_t *coef, int B, int nby, int nbx, int restart_mcus, uint8_t *out, int64_t out_stride,
                     int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
 
+/* ---- PNG deflate ------------------------------------------------------------ */
+/* The deflate of the PNG export.  Upstream's images leave through PIL / torchvision (pgdvs/engines/visualizer_pgdvs.py:118-139,
+ * evaluator_pgdvs.py:417-465), whose zlib runs on the host, and png.PngWriter's default does the same with
+ * zlib.compress(scanlines, 1); this entry point (csrc/png_deflate.hip) writes a zlib stream on the device instead, so that
+ * only the compressed bytes cross to the host.  scanlines[n_img][img_bytes]: any bytes (the call knows nothing of rows) ->
+ * per image i a complete zlib stream, contiguous from out + i out_stride, its length in nbytes[i] (device int32); bytes of
+ * the row past that length are not written.  If the stream would not fit out_stride, nbytes[i] = -1 and nothing of the row
+ * is written.  The stream, which pgdvs_amd/png.py restates in integers (deflate_rle) and zlib.decompress accepts: 0x78 0x01;
+ * per segment of seg_bytes input bytes (the last one shorter) one non-final dynamic-Huffman block and an empty stored block,
+ * so segments start and end on bytes; one final empty fixed block; the Adler-32.  Tokens: runs of equal bytes, cut at segment
+ * starts; a run of n is a literal, then (n - 1) / 258 matches of length 258 and distance 1, then for the r bytes left one
+ * match if r >= 3, else r literals.  One literal/length code per image from the image's token histogram (286 symbols, the end
+ * of block once per segment), limited to 15 bits, canonical and complete, its lengths repeated in every segment's header at
+ * 4 bits each; one distance code of length 1.  Three launches, no global atomics, no workgroup waits for another.
+ * out_stride >= 8 + 160 segments + ceil(15 img_bytes / 8) always fits (png.deflate_capacity).  workspace:
+ * pgdvs_png_deflate_workspace_bytes bytes, 256-byte aligned (-1 for shapes the call rejects); scanlines and out need no
+ * alignment.  Shapes: n_img >= 1, img_bytes in 1 .. 2^30, seg_bytes a power of two in 4096 .. 65536, n_img x segments <= 2^20,
+ * else PGDVS_ERR_INVALID. */
+int64_t pgdvs_png_deflate_workspace_bytes(int n_img, int64_t img_bytes, int seg_bytes);
+int pgdvs_png_deflate(const uint8_t *scanlines, int n_img, int64_t img_bytes, int seg_bytes, uint8_t *out, int64_t out_stride,
+                      int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+
 /* ---- evaluator export ------------------------------------------------------ */
 /* The images save_vis_for_eval writes for one view (pgdvs/engines/evaluator_pgdvs.py:417-465: *_gt.png :432-433,
  * *_combined.png :435-440, *_gnt.png :442-452 / *_geo_static.png :453-465) up to the deflate, in ONE launch from the RAW

@@ -67,6 +67,26 @@ template <class T> __device__ __forceinline__ T wave_incl_scan(T x) {
   return x;
 }
 
+// Inclusive scans under any of the operations above (OpMax for "the last run start at or before me", OpMin for "the first
+// one at or after me": the segmented scans of png_deflate.hip).  All 64 lanes call.  up: lane l holds op over lanes 0 .. l;
+// down: over lanes l .. 63.
+template <class Op, class T> __device__ __forceinline__ T wave_incl_scan_up(T x, Op op = Op()) {
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int off = 1; off < kWave; off <<= 1) {
+    const T y = __shfl_up(x, off, kWave);
+    if (lane >= off) x = op(x, y);
+  }
+  return x;
+}
+template <class Op, class T> __device__ __forceinline__ T wave_incl_scan_down(T x, Op op = Op()) {
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int off = 1; off < kWave; off <<= 1) {
+    const T y = __shfl_down(x, off, kWave);
+    if (lane + off < kWave) x = op(x, y);
+  }
+  return x;
+}
+
 // Block-wide exclusive offset of `c` in thread order, for a block of kWaves whole wavefronts; `total` = the block's sum
 // (in every thread).  Every thread of the block calls it: it contains ONE __syncthreads().  The caller owns
 // s_wsum[kWaves] (shared memory) and puts a barrier of its own before the array is written again.

@@ -645,7 +645,8 @@ def vis_step(model, data: dict, render_cfg, vis_dir, *, device=None, writer=None
     path's status words checked as ``eval_step`` checks them, then per view ``vis_dir / split / scene_id /
     {tgt_idx:05d}_combined.png`` from ``combined_rgb`` (``torchvision.utils.save_image``'s quantisation) and, when the
     renderer returns ``static_coarse_rgb``, ``{tgt_idx:05d}_gnt.png`` from it (the truncating cast).  ``writer``: a
-    ``png.PngWriter`` that copies, deflates and writes behind this thread (the files are complete once it is closed);
+    ``png.PngWriter`` that copies, deflates and writes behind this thread (the files are complete once it is closed; one
+    in device mode gets the view's images in one ``submit_batch``);
     without one the step writes each file before it returns.  ``video``: a ``video.MjpegWriter``; each view's ``combined_rgb``
     also becomes a frame of ``vis_dir / split / {scene_id}_combined.avi`` (upstream's ``_combined.mp4``, :141-177, as
     Motion-JPEG), written when that writer is closed: a GPU batch is compressed by one ``ops.jpeg_encode`` and the frames
@@ -673,13 +674,16 @@ def vis_step(model, data: dict, render_cfg, vis_dir, *, device=None, writer=None
         scene_dir.mkdir(parents=True, exist_ok=True)
         if frames is not None:
             video.submit((scene_dir.parent, misc[i_b]["scene_id"]), misc[i_b]["tgt_idx"], frames[i_b])
-        for tag, scan, h, w in lines:
-            path = scene_dir / f"{misc[i_b]['tgt_idx']:05d}_{tag}.png"
-            if writer is not None:
-                writer.submit(path, scan[i_b])
-            else:
-                png.write_file(path, scan[i_b].cpu().numpy() if isinstance(scan, torch.Tensor) else scan[i_b], h, w)
-            paths.append(path)
+        view_paths = [scene_dir / f"{misc[i_b]['tgt_idx']:05d}_{tag}.png" for tag, _, _, _ in lines]
+        if writer is not None and getattr(writer, "deflate", "zlib") == "device":
+            writer.submit_batch(view_paths, [scan[i_b] for _, scan, _, _ in lines])  # one deflate call for the view's images
+        else:
+            for path, (tag, scan, h, w) in zip(view_paths, lines):
+                if writer is not None:
+                    writer.submit(path, scan[i_b])
+                else:
+                    png.write_file(path, scan[i_b].cpu().numpy() if isinstance(scan, torch.Tensor) else scan[i_b], h, w)
+        paths += view_paths
     return (paths, ret) if return_ret else paths
 
 
@@ -715,13 +719,14 @@ def _run_batches(what, dataset, batch_size, n_max_data, rank, world):
 
 
 def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, writer=None,
-            video=False, video_fps=10, video_quality=90):
+            video=False, video_fps=10, video_quality=90, png_deflate="zlib"):
     """``vis_model``'s outer loop without Hydra: this rank's items in ``DistributedSampler(shuffle=False)`` order
     (``dist.shard_indices``), ``batch_size`` of them per step (the per-process batch size), collated as upstream collates
     them, at most ``ceil(min(len(dataset), n_max_data) / (batch_size * world))`` steps (``n_max_data <= 0``: all), each
     through ``vis_step``.  The files go through one ``png.PngWriter``: the given one, which stays open for its owner to
-    close, or one made here and closed (every file complete) before the function returns.  Returns ``{scene_id:
-    directory}``.
+    close, or one made here -- ``png.PngWriter(deflate=png_deflate)``: "zlib", or "device" for the deflate in HIP
+    (``ops.png_deflate``: the same pixels in files of other bytes); a given writer decides for itself -- and closed (every
+    file complete) before the function returns.  Returns ``{scene_id: directory}``.
 
     ``video=True`` (or a ``video.MjpegWriter``, which is closed here): every view's ``combined_rgb`` also becomes a frame of
     ``<vis_dir>/<split or "">/<scene_id>_combined.avi`` at ``video_fps`` frames per second and libjpeg quality
@@ -734,7 +739,7 @@ def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1,
 
     batches = _run_batches("vis_run", dataset, batch_size, n_max_data, rank, world)
     own = writer is None
-    w = png.PngWriter() if own else writer
+    w = png.PngWriter(deflate=png_deflate) if own else writer
     mj = None
     if video is not None and video is not False:
         mj = vid.MjpegWriter(fps=video_fps, quality=video_quality, rank=rank, world=world) if video is True else video
@@ -787,7 +792,7 @@ def _write_record(path, info):
 
 @torch.no_grad()
 def eval_run(model, dataset, render_cfg, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, quant_type="nvidia",
-             with_ssim=False, lpips=None, save_individual=False, info_dir=None, vis_dir=None, writer=None, run_ahead=0) -> dict:
+             with_ssim=False, lpips=None, save_individual=False, info_dir=None, vis_dir=None, writer=None, run_ahead=0, png_deflate="zlib") -> dict:
     """``run_eval_single_ckpt`` without Hydra: the items and steps of ``vis_run`` (``_run_batches``), each step the work of
     ``eval_step`` (same keys, protocols and errors), the per-step float32 sums accumulated as upstream accumulates them.
     Returns ``{"eval/count": int, "eval/<key>": the average (sum / count) as a float, ..., "sums": {"eval/count": int,
@@ -799,7 +804,8 @@ def eval_run(model, dataset, render_cfg, *, batch_size=1, n_max_data=-1, rank=0,
     record: ``src_frame_ids``, then the view's values as Python floats under upstream's names in upstream's order, the
     metrics not asked for left out -- and ``<vis_dir>/<split>/<scene_id>/<fname>_gt.png``, ``_combined.png``, ``_gnt.png``
     (``static_coarse_rgb``) and ``_geo_static.png`` (``geo_static_rgb``) with upstream's pixels (NaN as 0), through ``writer``
-    (a ``png.PngWriter``, left open) or one made and closed here.  On the fused GPU path the scanlines are one
+    (a ``png.PngWriter``, left open) or one made and closed here (``png.PngWriter(deflate=png_deflate)``: "zlib", or
+    "device" for the deflate in HIP, one ``ops.png_deflate`` call per view; a given writer decides for itself).  On the fused GPU path the scanlines are one
     ``ops.eval_export_scanlines`` launch per view, on the torch path ``png.py``'s.
     ``run_ahead`` = k (0..3): step j + k is enqueued before step j is finished; everything stays on the caller's stream in
     the same order, so every result is that of k = 0 and only the waiting moves.  (``STAGE_SECONDS``, when set, gets the loop's
@@ -823,8 +829,10 @@ def eval_run(model, dataset, render_cfg, *, batch_size=1, n_max_data=-1, rank=0,
                          f"{torch.distributed.get_world_size()}")
     lap = _Laps()
     ring = _LazyRing(run_ahead + 1)
+    if png_deflate not in png.DEFLATE_MODES:
+        raise ValueError(f"eval_run: png_deflate {png_deflate!r} (one of {png.DEFLATE_MODES})")
     own = save_individual and writer is None
-    w = png.PngWriter() if own else writer
+    w = png.PngWriter(deflate=png_deflate) if own else writer
     record_keys = RECORD_KEYS[quant_type]
     sums, records, pending = {}, [], collections.deque()
     out_device = [torch.device("cpu")]
@@ -856,8 +864,11 @@ def eval_run(model, dataset, render_cfg, *, batch_size=1, n_max_data=-1, rank=0,
             scene_vis.mkdir(parents=True, exist_ok=True)
             _write_record(scene_info / f"{fname}_rank_{rank}.pkl", info)
             views, ready = pend.exports[i_b]
-            for tag, scan in views:
-                w.submit(scene_vis / f"{fname}_{tag}.png", scan, ready=ready)
+            if getattr(w, "deflate", "zlib") == "device":
+                w.submit_batch([scene_vis / f"{fname}_{tag}.png" for tag, _ in views], [scan for _, scan in views], ready=ready)
+            else:
+                for tag, scan in views:
+                    w.submit(scene_vis / f"{fname}_{tag}.png", scan, ready=ready)
         lap("post")
 
     failed = False

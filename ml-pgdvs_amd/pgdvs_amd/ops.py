@@ -1084,6 +1084,51 @@ def png_scanlines(img, *, quant="save_image", adaptive=True, out=None):
     return out.view(shape)
 
 
+# the step of csrc/png_deflate.hip: a workgroup tokenises PNG_DEFLATE_PAYLOAD bytes at a time out of a window of
+# PNG_DEFLATE_WINDOW (the rest is look-ahead), a thread owns PNG_DEFLATE_PER consecutive bytes, a wavefront 64 of those
+PNG_DEFLATE_PER = 16
+PNG_DEFLATE_WINDOW = 4096
+PNG_DEFLATE_HALO = 272
+PNG_DEFLATE_PAYLOAD = PNG_DEFLATE_WINDOW - PNG_DEFLATE_HALO
+
+
+def png_deflate_capacity(img_bytes: int, seg_bytes=None) -> int:
+    """The bytes an image's stream can take at most (an ``out_stride`` of ``pgdvs_png_deflate`` that always fits): 15 bits
+    per input byte, 160 bytes of header and flush per segment, 8 for the stream's head and tail (``png.deflate_capacity``)."""
+    from . import png
+
+    return png.deflate_capacity(img_bytes, seg_bytes)
+
+
+def png_deflate(scanlines, seg_bytes=None, out=None):
+    """The deflate of the PNG export on the device (``pgdvs_png_deflate``; include/pgdvs_hip.h): scanlines uint8 [n,H,L] or
+    [n,nbytes] on the GPU (any bytes) -> (data uint8 [n,stride], nbytes int32 [n]) on the GPU: ``data[i, :nbytes[i]]`` is image
+    i's zlib stream, byte for byte ``png.deflate_rle``; the rest of a row is not written.  ``seg_bytes``: a power of two in
+    4096 .. 65536, None for ``png.DEFLATE_SEG_DEFAULT``.  ``out``: a contiguous uint8 GPU tensor [n,stride] to fill in place;
+    an image whose stream does not fit ``stride`` gets ``nbytes = -1`` and an untouched row (``png_deflate_capacity`` always
+    fits).  Runs on the current stream; nothing synchronises."""
+    from . import png
+
+    if not isinstance(scanlines, torch.Tensor) or not scanlines.is_cuda:
+        raise PgdvsHipError("png_deflate: scanlines must be a GPU tensor (the host path is png.deflate_rle)")
+    if scanlines.dtype != torch.uint8 or scanlines.ndim not in (2, 3) or scanlines.shape[0] < 1 or scanlines[0].numel() < 1:
+        raise ValueError(f"png_deflate: uint8 [n,H,L] or [n,nbytes] expected, got {scanlines.dtype} {tuple(scanlines.shape)}")
+    x = scanlines.contiguous()
+    n, img_bytes = int(x.shape[0]), int(x[0].numel())
+    seg = png.check_seg_bytes(seg_bytes)
+    if out is None:
+        out = torch.empty((n, png.deflate_capacity(img_bytes, seg)), dtype=torch.uint8, device=x.device)
+    elif not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.uint8 and out.is_contiguous()
+              and out.ndim == 2 and out.shape[0] == n and out.shape[1] >= 1):
+        raise ValueError(f"png_deflate: out must be a contiguous uint8 tensor [{n}, stride] on {x.device}")
+    lib = _lib.load()
+    ws = _ws(lib.pgdvs_png_deflate_workspace_bytes(n, img_bytes, seg), x.device)
+    nbytes = torch.empty((n,), dtype=torch.int32, device=x.device)
+    check(lib.pgdvs_png_deflate(_ptr(x), n, img_bytes, seg, _ptr(out), int(out.shape[1]), _ptr(nbytes), _ptr(ws), ws.numel(), _stream()),
+          "pgdvs_png_deflate")
+    return out, nbytes
+
+
 def _quant_ptr(table, name):
     t = np.ascontiguousarray(np.asarray(table).reshape(-1), dtype=np.int64)
     if t.shape != (64,) or t.min() < 1 or t.max() > 255:

@@ -8,7 +8,11 @@
            reference's datasets do) with the PngWriter at 1, 8 and 16 threads, against a baseline measured in the same
            process and alternated with it: the reference's export restated (forward, .clamp(0, 1), save_image's expression,
            .cpu(), PIL.Image.save at its default level, synchronously per view); the forward-only rate (no export) as the
-           ceiling; bytes written by each
+           ceiling; bytes written by each; the writer in device mode (deflate="device": ops.png_deflate on the copy stream,
+           the workers fetch, wrap and write) at 8 and 16 threads in the same alternation
+  deflate  GPU time of ops.png_deflate alone (HIP events, median, warmed, output preallocated) on the resident scanlines of a
+           rendered view and of uniform noise, for segments of 8192, 16384 and 32768 bytes, with the stream's bytes beside
+           zlib level 1's and zlib's Z_RLE strategy's on the same scanlines
 Prints one JSON object.
 Usage (GPU box): timeout -k 10 900 python tools/vis_bench.py [--views 64] [--rounds 2] [--out profiles/vis_bench.json]"""
 import argparse
@@ -120,6 +124,24 @@ def main():
                 case[f"png_scanlines_{name}_share_of_bound"] = bound_ms / med
             types = np.bincount(ops.png_scanlines(img)[0, :, 0].cpu().numpy(), minlength=5).tolist()
             case["filter_types_chosen"] = types
+            import zlib
+
+            case["png_deflate"] = {}
+            noise = torch.rand((1, 3, H, W), generator=torch.Generator().manual_seed(7)).to(dev)
+            for name, x in (("render", img), ("noise", noise)):
+                scan = ops.png_scanlines(x)
+                raw = scan.cpu().numpy().tobytes()
+                co = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_RLE)
+                entry = {"scanline_bytes": len(raw), "zlib_level_1_bytes": len(zlib.compress(raw, 1)),
+                         "zlib_rle_bytes": len(co.compress(raw) + co.flush())}
+                for seg in (8192, 16384, 32768):
+                    buf = torch.empty((1, ops.png_deflate_capacity(len(raw), seg)), dtype=torch.uint8, device=dev)
+                    med, mn = event_median(lambda: ops.png_deflate(scan, seg, out=buf), args.reps, 4)  # noqa: B023
+                    n = int(ops.png_deflate(scan, seg, out=buf)[1][0])
+                    assert zlib.decompress(buf[0, :n].cpu().numpy().tobytes()) == raw
+                    entry[f"seg_{seg}"] = {"ms_median": med, "ms_min": mn, "bytes": n}
+                case["png_deflate"][name] = entry
+            del noise
 
             def forward_only(n):
                 t0 = time.perf_counter()
@@ -142,12 +164,12 @@ def main():
                 dt = time.perf_counter() - t0
                 return n / dt, tree_bytes(d)
 
-            def ours(threads):
+            def ours(threads, deflate="zlib"):
                 def run(n):
-                    d = scratch / f"ours_{H}_{threads}"
+                    d = scratch / f"ours_{H}_{threads}_{deflate}"
                     shutil.rmtree(d, ignore_errors=True)
                     t0 = time.perf_counter()
-                    with png.PngWriter(n_threads=threads) as w:
+                    with png.PngWriter(n_threads=threads, deflate=deflate) as w:
                         harness.vis_run(renderer, Views(views, n), rc, d, device=dev, writer=w)
                     dt = time.perf_counter() - t0
                     return n / dt, tree_bytes(d)
@@ -156,7 +178,8 @@ def main():
             forward_only(8)  # warm-up
             runs = [("forward_only", forward_only, args.views), ("baseline_pil_default", baseline, args.baseline_views),
                     ("writer_1_thread", ours(1), args.views), ("writer_8_threads", ours(8), args.views),
-                    ("writer_16_threads", ours(16), args.views)]
+                    ("writer_16_threads", ours(16), args.views), ("device_writer_8_threads", ours(8, "device"), args.views),
+                    ("device_writer_16_threads", ours(16, "device"), args.views)]
             rates = {k: [] for k, _, _ in runs}
             sizes = {}
             for _ in range(args.rounds):  # alternated: every round runs each variant once
