@@ -917,6 +917,35 @@ int pgdvs_mask_combine(const uint8_t *raw_no_warp, const uint8_t *sam, int n_seg
  * listed.  One launch, no workspace.  Shapes: H, W >= 1, each < 2^20, H W < 2^31, else PGDVS_ERR_INVALID. */
 int pgdvs_semantic_mask(const int64_t *sem_ade20k, const int64_t *sem_coco, int H, int W, const int32_t *ids_ade20k, int n_ade20k,
                         const int32_t *ids_coco, int n_coco, uint8_t *ade20k, uint8_t *coco, uint8_t *sem, pgdvs_stream_t stream);
+/* CoTracker's correlation step without the correlation volume (csrc/cotracker.hip).
+ * pgdvs_cotracker_pyramid replaces CorrBlock.__init__ (pgdvs/models/cotracker/models/core/cotracker/blocks.py:270-284):
+ * fmaps[S,C=128,H,W] float32 on the device -> the four levels fmaps, avg_pool2d(2, stride=2) of it, and so on, level l of
+ * H >> l x W >> l pixels (an odd last row or column is dropped), each mean ((a00 + a01) + a10) + a11 times 0.25.  The
+ * levels are stored channels-last, [S, H_l, W_l, 128], one after the other in `workspace`, each from a 256-byte boundary: a
+ * pixel's 128 channels are one 512-byte line.  The workspace IS the pyramid that pgdvs_cotracker_corr_lookup reads.
+ * workspace: pgdvs_cotracker_pyramid_workspace_bytes(S, C, H, W) bytes, 256-byte aligned.  Shapes: S >= 1 (the call itself:
+ * S < 65536), C = 128, 16 <= H, W < 2^15 (every level 2 x 2 or more: on a 1-pixel level the reference divides by W - 1 = 0),
+ * S H W < 2^31, else PGDVS_ERR_INVALID (the workspace query too) and nothing is launched.
+ * pgdvs_cotracker_corr_lookup replaces CorrBlock.corr followed by CorrBlock.sample (:286-328, bilinear_sampler :251-266):
+ * pyramid as above for (S, H, W), feats[S,N,128] and coords[S,N,2] (x, y in level-0 pixels) float32 on the device ->
+ * 196 float32 per (s, n) at out[(s N + n) row_stride + col_offset + level 49 + i 7 + j], nothing else of out written:
+ * the sample of corr_l = <feats[s,n], level l> / sqrt(128) (float32 square root and division) at
+ * (x / 2^l + (i - 3), y / 2^l + (j - 3)): the SLOW index i moves x, as in the reference, whose delta is (dy, dx) added to
+ * (x, y).  Sampling is grid_sample(align_corners=True, zero padding) after the float32 round trip g = 2 x / (W_l - 1) - 1,
+ * ix = (g + 1) / 2 * (W_l - 1), every operation rounded on its own.  Since bilinear sampling is linear the samples are
+ * taken from the dots <feats, tap> of the 8 x 8 taps they touch, each sample blending the 2 x 2 taps around its own
+ * round-tripped position with grid_sample's weights; a tap outside the level is 0.  Within a few float32 spacings of an
+ * integer the round trip can put the samples of an axis on either side of their integers; they then touch nine taps along
+ * it, and all nine are fetched.  No coordinate becomes an index before it is known to lie in the level: positions are
+ * clamped as floats to [-16, W_l + 16] before they become integers (nothing that far out touches the level), every tap is
+ * compared with the level; non-finite coordinates give unspecified values and no fault.  No atomics: sums have a fixed
+ * order and two calls give the same bits.  feats 16-byte aligned.  Shapes as above and N >= 1, S N 196 < 2^31, 0 <=
+ * col_offset, col_offset + 196 <= row_stride (in floats), else PGDVS_ERR_INVALID and nothing is launched. */
+int64_t pgdvs_cotracker_pyramid_workspace_bytes(int S, int C, int H, int W);
+int pgdvs_cotracker_pyramid(const float *fmaps, int S, int C, int H, int W, void *workspace, int64_t workspace_bytes,
+                            pgdvs_stream_t stream);
+int pgdvs_cotracker_corr_lookup(const void *pyramid, int S, int H, int W, const float *feats, const float *coords, int N, float *out,
+                                int64_t row_stride, int64_t col_offset, pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 //  - the partial-width butterflies of the MFMA layouts (gnt_mfma.h: steps 16 and 32 only; gnt_view.hip: step 32 only);
 //  - the width-8 shuffles that pack eight lanes' words in static_agg.hip (agg_bits kernels);
 //  - the in-register array trees of knn.hip and knn_grid.hip (they merge per-lane arrays, not one value per lane);
+//  - the halving butterfly of cotracker.hip (corr_lookup_kernel: 32 values per lane in, one finished sum per lane out);
 //  - block_partials in eval_common.h: the same tree as wave_sum_down, spelled out, because two metric kernels allocate
 //    more registers through the helper.
 // Block offsets that use wave_incl_scan with cross-wavefront lines of their own instead of block_excl_scan: those that

@@ -132,6 +132,9 @@ SIGNATURES.update({
     "pgdvs_mask_combine": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_semantic_mask": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pgdvs_cotracker_pyramid_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "pgdvs_cotracker_pyramid": (_i, [_vp, _i, _i, _i, _i, _vp, _i64, _vp]),
+    "pgdvs_cotracker_corr_lookup": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i64, _i64, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

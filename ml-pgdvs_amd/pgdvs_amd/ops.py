@@ -1345,6 +1345,52 @@ def gnt_gather(ray_o, ray_d, depth_range, n_samples: int, inv_uniform: bool, cam
     return out
 
 
+# ---- CoTracker's correlation step (csrc/cotracker.hip) ------------------------------------
+class CotrackerPyramid:
+    """The four channels-last levels of ``CorrBlock.__init__`` in one device buffer (``ops.cotracker_pyramid``)."""
+
+    def __init__(self, buf, S, H, W):
+        self.buf, self.S, self.H, self.W = buf, S, H, W
+
+    def level(self, i):
+        """level ``i`` as a [S, H >> i, W >> i, 128] view (tests, diagnostics)"""
+        off = 0
+        for k in range(i):
+            n = self.S * (self.H >> k) * (self.W >> k) * 128 * 4
+            off += (n + 255) // 256 * 256
+        h, w = self.H >> i, self.W >> i
+        return self.buf[off:off + self.S * h * w * 512].view(torch.float32).view(self.S, h, w, 128)
+
+
+def cotracker_pyramid(fmaps, reject_ok: bool = False):
+    """fmaps[S,128,H,W] -> the pyramid ``cotracker_corr_lookup`` reads.  A shape the kernels do not cover (C != 128, a level
+    below 2 x 2) raises PgdvsHipError, or returns None with ``reject_ok`` (the caller then runs its torch statement)."""
+    fm = _req(fmaps, torch.float32, "fmaps")
+    assert fm.ndim == 4, fm.shape
+    S, Cc, H, W = fm.shape
+    lib = _lib.load()
+    nbytes = lib.pgdvs_cotracker_pyramid_workspace_bytes(S, Cc, H, W)
+    if nbytes < 0 and reject_ok:
+        return None
+    ws = _ws(nbytes, fm.device)
+    check(lib.pgdvs_cotracker_pyramid(_ptr(fm), S, Cc, H, W, _ptr(ws), ws.numel(), _stream()), "pgdvs_cotracker_pyramid")
+    return CotrackerPyramid(ws, S, H, W)
+
+
+def cotracker_corr_lookup(pyramid: CotrackerPyramid, feats, coords, out=None, col_offset: int = 0):
+    """``CorrBlock.corr(feats)`` + ``CorrBlock.sample(coords)``: feats[S,N,128], coords[S,N,2] (x, y) -> [S,N,196].  With
+    ``out`` [S,N,width] (float32, contiguous) the 196 values of a row land at ``col_offset`` and the other columns stay."""
+    ft, cd = _req(feats, torch.float32, "feats"), _req(coords, torch.float32, "coords")
+    S, N = ft.shape[0], ft.shape[1]
+    assert ft.shape == (S, N, 128) and cd.shape == (S, N, 2) and S == pyramid.S, (ft.shape, cd.shape, pyramid.S)
+    if out is None:
+        out = torch.empty((S, N, 196), dtype=torch.float32, device=ft.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape[:2] == (S, N), (out.shape, out.dtype)
+    check(_lib.load().pgdvs_cotracker_corr_lookup(_ptr(pyramid.buf), S, pyramid.H, pyramid.W, _ptr(ft), _ptr(cd), N, _ptr(out),
+                                                  out.shape[2], int(col_offset), _stream()), "pgdvs_cotracker_corr_lookup")
+    return out
+
+
 # ---- packed-weight caches of the fused GNT kernels ---------------------------------------
 def _param_key(*modules):
     """(storage address, in-place version) of every parameter: changes on `.to(device)`, on

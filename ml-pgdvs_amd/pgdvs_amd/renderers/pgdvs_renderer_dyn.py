@@ -42,8 +42,8 @@ class PGDVSDynamicRenderer(PGDVSBaseRenderer):
         self.tracker = None
         self.use_tracker = use_tracker
         if self.use_tracker:
-            # :52-61.  The point trackers (TAPIR / CoTracker) are pretrained third-party
-            # networks outside this build: any module with the reference's interface contract
+            # :52-61.  CoTracker is built here (pgdvs_amd.models.cotracker, configs/tracker/cotracker_hip.yaml); TAPIR
+            # (JAX) stays upstream.  Any module with the reference's interface contract
             # (``tracker(frames=[N,H,W,3], query_points=[#pt,3]) -> tracks, visibles`` and a
             # ``query_chunk_size`` attribute) can be plugged in through cfg.tracker; without
             # one the tracks must be supplied in the data dict (see
@@ -72,7 +72,7 @@ class PGDVSDynamicRenderer(PGDVSBaseRenderer):
             rgb_1, rgb_2, cam_1, cam_2, times)
         info = {"pcl_dense": pcl, "rgb_dense": rgbf, "valid": valid}
         # pytorch3d's kNN runs unconditionally upstream (:405-410) but its result is only
-        # observable through the outlier flags (and the tracker, not built): skip it when
+        # observable through the outlier flags (and by the tracker row, below): skip it when
         # it cannot influence any output.
         if render_cfg.dyn_pcl_remove_outlier or self.use_tracker:  # the tracker row needs the threshold (:508)
             idx, cnt = ops.compact_u8(valid)

@@ -1,8 +1,9 @@
 """Mirror of ``pgdvs.renderers.pgdvs_renderer_dyn_track.PGDVSDynamicTrackRenderer``
 (pgdvs/renderers/pgdvs_renderer_dyn_track.py:26-764), row A17 of SURVEY.md 8a.
 
-The point trackers (TAPIR / CoTracker) are third-party pretrained networks outside this
-build.  Everything around them is here: ``prepare_data`` (frame window assembly),
+Of the point trackers CoTracker is part of this package (``pgdvs_amd.models.cotracker``, selected by
+``configs/tracker/cotracker_hip.yaml``; its correlation look-up is csrc/cotracker.hip); TAPIR is JAX and stays a
+third-party plug-in.  Everything around them is here: ``prepare_data`` (frame window assembly),
 ``run_track`` / ``run_track_func`` (query construction + chunked tracker calls, for a
 plugged-in tracker with the reference's interface), ``compute_pcl_for_tgt`` (HIP: validity,
 frame-pair selection, sampling, unprojection, time interpolation, track-to-base and
