@@ -484,7 +484,8 @@ int pgdvs_lpips_sums(const float *pred_planar, const float *gt_hwc, const float 
  * k1 = 0.01, k2 = 0.03, max_val 1, the mask applied as a partial convolution, separably in two "valid" passes (first along W,
  * then along H; each z' = conv(z m, f) 11 / conv(m, 1) where conv(m, 1) != 0, else 0, the next pass's mask conv(m, 1) != 0),
  * variances clamped at 0, covariance clipped to sign(s01) min(sqrt(s00 s11), |s01|), then the mean over ALL (H-10)(W-10) 3
- * map entries (a window that saw no mask gives exactly 1).  fp32 arithmetic, fixed-order float64 sums (deterministic).
+ * map entries (a window that saw no mask gives exactly 1).  float64 arithmetic on the fp32 quantised values, fixed-order sums
+ * (deterministic).
  *   pred_planar[3,H,W] raw render (combined_rgb); gt_hwc[H,W,3] raw ground truth; mask_hw[H,W] eval_mask (its one channel)
  *   sums: DEVICE double[8] (the width of the PSNR row, so that all rows of a step come back in one transfer):
  *     [0] sum d^2   [1] sum d^2 m   [2] sum S (full mask)   [3] 3 H W   [4] 3 sum m   [5] sum S (covisibility mask)

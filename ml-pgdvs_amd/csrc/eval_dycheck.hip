@@ -10,7 +10,7 @@
 //            for the full mask and the covisibility mask.  Blocks of blockIdx.y = 0 run the full mask, blockIdx.y = 1 the
 //            covisibility mask and the PSNR sums.  A block owns a 32 x 32 tile of the (H - 10) x (W - 10) map: its 42 x 42
 //            haloed input tile sits in LDS, the W pass writes its 42 x 32 moments to LDS, and the H pass reads them back.
-//            fp32 throughout, fixed-order float64 sums.
+//            The inputs are the fp32 quantised values; moments, map and sums are float64, the sums in a fixed order.
 // lpips      lpips 0.1.4 LPIPS(net="alex", spatial=True), version "0.1" (so the ScalingLayer IS applied), called as
 //            metrics.py:189-230 calls it: im2tensor(img m, factor=1/2) = 2 img m - 1 of the quantised images, AlexNet
 //            relu1..relu5 (lpips.hip's backbone, here on FOUR images: gt, pred, gt m, pred m), normalize_tensor, the squared
@@ -37,15 +37,20 @@ constexpr int kDcMoments = 5;                   // a, b, a^2, b^2, a b
 static_assert(kDcRows * (kDcThreads / kDcT) == kDcT, "the H pass covers the tile");
 
 struct DcFilter {
-  float f[kDcTaps];
+  double f[kDcTaps];
 };
+
+// the value of moment j (a, b, a^2, b^2, a b) at one pixel; the products of two fp32 values are exact in float64
+__device__ __forceinline__ double dc_moment(int j, float a, float b) {
+  return j == 0 ? (double)a : j == 1 ? (double)b : j == 2 ? (double)a * (double)a : j == 3 ? (double)b * (double)b : (double)a * (double)b;
+}
 
 __global__ void __launch_bounds__(kDcThreads)
 dycheck_ssim_partials_kernel(const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ mask, int H, int W,
                              int tiles_x, int tiles_y, DcFilter filt, double *__restrict__ partials) {
   __shared__ float qa[kDcIn][kDcInPitch], qb[kDcIn][kDcInPitch], mk[kDcIn][kDcInPitch];
-  __shared__ float msum[kDcIn][kDcHPitch];               // conv(m, 1) of the W pass
-  __shared__ float hz[kDcMoments][kDcIn][kDcHPitch];     // z' of the W pass
+  __shared__ double msum[kDcIn][kDcHPitch];  // conv(m, 1) of the W pass
+  __shared__ double hz[kDcIn][kDcHPitch];    // z' of the W pass, one moment at a time
   __shared__ double red[kDcThreads / kWave][kDcSums];
 
   const int tid = threadIdx.x;
@@ -54,8 +59,8 @@ dycheck_ssim_partials_kernel(const float *__restrict__ pred, const float *__rest
   const int x0 = tx * kDcT, y0 = ty * kDcT;
   const int Ho = H - kDcHalo, Wo = W - kDcHalo;
   const uint32_t P = (uint32_t)H * (uint32_t)W;
-  const float c1 = (float)(0.01 * 0.01), c2 = (float)(0.03 * 0.03);
-  const float ntaps = (float)kDcTaps;
+  const double c1 = 0.01 * 0.01, c2 = 0.03 * 0.03;
+  const double ntaps = (double)kDcTaps;
 
   // ---- the mask of the haloed tile (the full mask: 1 on the image) and its W-pass sums.  Elements past the image edge are 0;
   // only outputs outside the valid map read them, and those are discarded.
@@ -68,13 +73,16 @@ dycheck_ssim_partials_kernel(const float *__restrict__ pred, const float *__rest
   __syncthreads();
   for (int t = tid; t < kDcIn * kDcT; t += kDcThreads) {
     const int r = t / kDcT, x = t - r * kDcT;
-    float s = 0.0f;
+    double s = 0.0;
 #pragma unroll
-    for (int k = 0; k < kDcTaps; ++k) s += mk[r][x + k];
+    for (int k = 0; k < kDcTaps; ++k) s += (double)mk[r][x + k];
     msum[r][x] = s;
   }
 
-  float ssim = 0.0f;  // this thread's <= 12 map entries, then one float64 add
+  // The moments, the map entry and this thread's <= 12 entries are float64.  In fp32 the variances mu[2] - mu00 of a flat image
+  // are pure rounding (the entry then lands anywhere within 7e-5 of its value, by the order of the taps alone), a steep ramp
+  // loses 4.5e-6 to the eleven sequential taps, and an fp32 sum of 12 entries near 1 is off by 1.8e-7 on a constant map.
+  double ssim = 0.0;
   double psnr[3] = {0.0, 0.0, 0.0};
   const int vx = tid % kDcT, vr0 = (tid / kDcT) * kDcRows;
   for (int c = 0; c < 3; ++c) {
@@ -103,53 +111,48 @@ dycheck_ssim_partials_kernel(const float *__restrict__ pred, const float *__rest
     psnr[1] += (double)pdm;
     if (c == 0) psnr[2] += (double)pm;
     __syncthreads();
-    // ---- W pass: 42 rows x 32 outputs
-    for (int t = tid; t < kDcIn * kDcT; t += kDcThreads) {
-      const int r = t / kDcT, x = t - r * kDcT;
-      float s[kDcMoments] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    // ---- one moment at a time: the W pass (42 rows x 32 outputs) to LDS, then the H pass, one column x 4 output rows per thread
+    double mu[kDcMoments][kDcRows];
 #pragma unroll
-      for (int k = 0; k < kDcTaps; ++k) {
-        const float a = qa[r][x + k], b = qb[r][x + k], m = mk[r][x + k], f = filt.f[k];
-        s[0] += f * (a * m);
-        s[1] += f * (b * m);
-        s[2] += f * ((a * a) * m);
-        s[3] += f * ((b * b) * m);
-        s[4] += f * ((a * b) * m);
+    for (int j = 0; j < kDcMoments; ++j) {
+      for (int t = tid; t < kDcIn * kDcT; t += kDcThreads) {
+        const int r = t / kDcT, x = t - r * kDcT;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < kDcTaps; ++k) s += filt.f[k] * (dc_moment(j, qa[r][x + k], qb[r][x + k]) * (double)mk[r][x + k]);
+        const double ms = msum[r][x];
+        hz[r][x] = ms != 0.0 ? s * ntaps / ms : 0.0;
       }
-      const float ms = msum[r][x];
+      __syncthreads();
 #pragma unroll
-      for (int j = 0; j < kDcMoments; ++j) hz[j][r][x] = ms != 0.0f ? s[j] * ntaps / ms : 0.0f;
+      for (int o = 0; o < kDcRows; ++o) {
+        const int y = vr0 + o;
+        double s = 0.0, cnt = 0.0;
+#pragma unroll
+        for (int k = 0; k < kDcTaps; ++k) {
+          const double m = msum[y + k][vx] != 0.0 ? 1.0 : 0.0;
+          cnt += m;
+          s += filt.f[k] * (hz[y + k][vx] * m);
+        }
+        mu[j][o] = cnt != 0.0 ? s * ntaps / cnt : 0.0;
+      }
+      __syncthreads();  // (the next moment, or the next channel, overwrites the moments and the tile)
     }
-    __syncthreads();
-    // ---- H pass and S: one column x 4 output rows per thread
 #pragma unroll
     for (int o = 0; o < kDcRows; ++o) {
-      const int y = vr0 + o;
-      float s[kDcMoments] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, cnt = 0.0f;
-#pragma unroll
-      for (int k = 0; k < kDcTaps; ++k) {
-        const float m = msum[y + k][vx] != 0.0f ? 1.0f : 0.0f, f = filt.f[k];
-        cnt += m;
-#pragma unroll
-        for (int j = 0; j < kDcMoments; ++j) s[j] += f * (hz[j][y + k][vx] * m);
-      }
-      float mu[kDcMoments];
-#pragma unroll
-      for (int j = 0; j < kDcMoments; ++j) mu[j] = cnt != 0.0f ? s[j] * ntaps / cnt : 0.0f;
-      if (y0 + y < Ho && x0 + vx < Wo) {
-        const float mu00 = mu[0] * mu[0], mu11 = mu[1] * mu[1], mu01 = mu[0] * mu[1];
-        const float s00 = fmaxf(0.0f, mu[2] - mu00), s11 = fmaxf(0.0f, mu[3] - mu11);
-        float s01 = mu[4] - mu01;
-        const float sg = s01 > 0.0f ? 1.0f : (s01 < 0.0f ? -1.0f : 0.0f);
-        s01 = sg * fminf(sqrtf(s00 * s11), fabsf(s01));
-        const float numer = (2.0f * mu01 + c1) * (2.0f * s01 + c2);
-        const float denom = (mu00 + mu11 + c1) * (s00 + s11 + c2);
+      if (y0 + vr0 + o < Ho && x0 + vx < Wo) {
+        const double mu00 = mu[0][o] * mu[0][o], mu11 = mu[1][o] * mu[1][o], mu01 = mu[0][o] * mu[1][o];
+        const double s00 = fmax(0.0, mu[2][o] - mu00), s11 = fmax(0.0, mu[3][o] - mu11);
+        double s01 = mu[4][o] - mu01;
+        const double sg = s01 > 0.0 ? 1.0 : (s01 < 0.0 ? -1.0 : 0.0);
+        s01 = sg * fmin(sqrt(s00 * s11), fabs(s01));
+        const double numer = (2.0 * mu01 + c1) * (2.0 * s01 + c2);
+        const double denom = (mu00 + mu11 + c1) * (s00 + s11 + c2);
         ssim += numer / denom;  // (IEEE division: an unmasked window gives exactly c1 c2 / (c1 c2) = 1)
       }
     }
-    __syncthreads();  // (the next channel overwrites the tile and the moments)
   }
-  const double v[kDcSums] = {(double)ssim, psnr[0], psnr[1], psnr[2]};
+  const double v[kDcSums] = {ssim, psnr[0], psnr[1], psnr[2]};
   block_partials<kDcSums, kDcThreads>(tid, v, red, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kDcSums);
 }
 
@@ -360,7 +363,7 @@ PGDVS_API int pgdvs_dycheck_psnr_ssim_sums(const float *pred_planar, const float
     set_error("pgdvs_dycheck_psnr_ssim_sums: workspace too small");
     return PGDVS_ERR_WORKSPACE;
   }
-  // the 1-D Gaussian of metrics.py:148-153 (float64 here, rounded once to fp32)
+  // the 1-D Gaussian of metrics.py:148-153 in float64
   DcFilter filt;
   {
     double g[kDcTaps], s = 0.0;
@@ -369,7 +372,7 @@ PGDVS_API int pgdvs_dycheck_psnr_ssim_sums(const float *pred_planar, const float
       g[k] = std::exp(-0.5 * u * u);
       s += g[k];
     }
-    for (int k = 0; k < kDcTaps; ++k) filt.f[k] = (float)(g[k] / s);
+    for (int k = 0; k < kDcTaps; ++k) filt.f[k] = g[k] / s;
   }
   hipStream_t st = as_stream(stream);
   double *partials = reinterpret_cast<double *>(workspace);

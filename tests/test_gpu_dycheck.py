@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import metric_cases as M
 import test_dycheck_host as R
 
 pytestmark = pytest.mark.gpu
@@ -63,41 +64,9 @@ def _q(x):
 
 
 def _np_reference(pred, gt, mask):
-    """float64 numpy restatement of metrics.py:63-186 on the quantised images: psnr, ssim, mpsnr, mssim"""
-    a = _q(gt.cpu().numpy()).astype(np.float64)  # [H,W,3]
-    b = _q(pred.cpu().numpy().transpose(1, 2, 0)).astype(np.float64)
-    m = mask.cpu().numpy()[..., 0].astype(np.float64)
-    f = np.exp(-0.5 * ((np.arange(11) - 5) / 1.5) ** 2)
-    f /= f.sum()
-
-    def psnr(mm):
-        mse = ((a - b) ** 2 * mm[..., None]).sum() / max(3 * mm.sum(), 1e-6)
-        return math.inf if mse == 0 else -10.0 / math.log(10.0) * math.log(mse)
-
-    def pconv(z, mm, axis):  # z[H,W,3], mm[H,W]; "valid" along axis (0 = H, 1 = W)
-        n = z.shape[axis] - 10
-        zm = z * mm[..., None]
-        zc = sum(f[k] * np.take(zm, np.arange(k, k + n), axis=axis) for k in range(11))
-        mw = sum(np.take(mm, np.arange(k, k + n), axis=axis) for k in range(11))
-        with np.errstate(invalid="ignore", divide="ignore"):
-            out = np.where(mw[..., None] != 0, zc * 11 / mw[..., None], 0.0)
-        return out, (mw != 0).astype(np.float64)
-
-    def filt(z, mm):
-        z1, m1 = pconv(z, mm, 1)
-        return pconv(z1, m1, 0)[0]
-
-    def ssim(mm):
-        mu0, mu1 = filt(a, mm), filt(b, mm)
-        s00 = np.maximum(0, filt(a * a, mm) - mu0 * mu0)
-        s11 = np.maximum(0, filt(b * b, mm) - mu1 * mu1)
-        s01 = filt(a * b, mm) - mu0 * mu1
-        s01 = np.sign(s01) * np.minimum(np.sqrt(s00 * s11), np.abs(s01))
-        c1, c2 = 0.01 ** 2, 0.03 ** 2
-        return float((((2 * mu0 * mu1 + c1) * (2 * s01 + c2)) / ((mu0 ** 2 + mu1 ** 2 + c1) * (s00 + s11 + c2))).mean())
-
-    ones = np.ones_like(m)
-    return [psnr(ones), ssim(ones), psnr(m), ssim(m)]
+    """the float64 numpy restatement of metrics.py:63-186 (metric_cases.dycheck_reference) on the quantised images: psnr, ssim,
+    mpsnr, mssim"""
+    return M.dycheck_reference(_q(gt.cpu().numpy()), _q(pred.cpu().numpy().transpose(1, 2, 0)), mask.cpu().numpy()[..., 0])[0]
 
 
 def _values(row, H, W):
