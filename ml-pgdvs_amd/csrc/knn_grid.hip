@@ -1059,17 +1059,38 @@ grid_query_body(const GridParams *__restrict__ gp, const float4 *__restrict__ so
 // registers as a sorted list, inserting with one median-of-three per slot.  Lanes are
 // consecutive in cell-sorted order, so a wavefront's lanes walk (nearly) the same nine x-runs
 // of the sorted point array: the per-lane candidate loads coalesce into broadcasts.  A
-// candidate that beats the lane's (K+1)-th best is parked in a 4-deep per-lane queue; the
-// (K+1)-instruction insertion chain runs only when some lane's queue is full, i.e. about
-// once per four *accepted* candidates of the busiest lane instead of once per candidate.
-// About 350 vector instructions per query.  Queries whose list is not provably complete after
-// ring 1 (the same criterion as above) are handed to the wavefront-per-query search.
-// The average is summed in the same 64-slot butterfly order as knn_finish.
+// candidate that beats the lane's (K+1)-th best is parked in a per-lane queue of kTpqQueue registers; the
+// (K+1)-instruction insertion chain runs for all 64 lanes only when some lane's queue has no room for the next step's
+// two candidates, and then ONCE, on every lane's newest entry (lanes with an empty queue insert +inf).  The busiest
+// lane of a wavefront accepts 72 candidates, a lane 64 on average: a flush of the whole queue whenever one lane's was
+// full (rounds 4 to 6, depth 4) ran 148 chains per wavefront, 57 % of their slots on +inf; one chain per trigger
+// runs 125 / 114 / 106 at depth 4 / 6 / 8 with one candidate per step and 133 / 119 / 110 / 98 at 4 / 6 / 8 / 12 with
+// two (counter build, benchmark cloud) -- the lanes of a wavefront are neighbours and accept together, which this
+// policy uses and waiting lanes (below) did not.  A step evaluates TWO candidates of the lane's run: the row switch,
+// the run bookkeeping and the ballots are paid once per pair, 116 steps per wavefront instead of 225 half-steps.
+// Queries whose list is not provably complete after ring 1 (the same criterion as above) are handed to the
+// wavefront-per-query search.  The average is summed in the same 64-slot butterfly order as knn_finish.
+//
+// Why the result does not depend on any of this (every result is compared bit for bit with the brute-force kernel):
+// the list is the K+1 smallest of {starting threshold x (K+1)} u {accepted distances}.  The acceptance test `d < mx`
+// with a stale mx never rejects a member -- a stale mx is at least the current (K+1)-th value -- and the set of
+// candidates visited is the same, so the accepted set only ever holds extra candidates that no longer qualify; those
+// fall off the end of the chain.  The contents of a sorted list do not depend on the order of the insertions or on how
+// many are queued between two chains, and the walk ends with every queue drained.  The distance is dist2() as in the
+// other two searches; the completeness test (s_safe), the `cut` test (mx == s_thr), the second attempt per wavefront
+// and the summation order are as they were.
+//
+// Measured on one MI355X, benchmark cloud (311 k queries, K = 50), the pass alone, parent 156-163 us
+// (profiles/knn_tpq_queue.txt): one chain per trigger with one candidate per step 144-152 (depth 4), 142-149 (6),
+// 141-148 (8, two registers spilled at five waves per SIMD); with two candidates per step 137-141 (4, four spilled at
+// five waves), 133-141 (6), 132-138 (8), 133-138 (10), 135-139 (12), 138-145 (16).  From depth 6 on the pair step needs
+// more than 96 registers: four workgroups per CU (104 registers at depth 8, nothing spilled), which costs the pair
+// step nothing at depth 4 (138-143 against 137-141).
 // (Round 5, measured and dropped: lanes that stop requesting candidates at 3 / 4 / 5 queued ones, a flush of as many chains
 // as the fullest queue holds once 8 or 16 lanes wait -- an independent-lanes model promised -17 % vector instructions;
 // bit-exact, and 192-213 us against 160: the lanes of a wavefront are neighbours and accept together, waiting only
-// lengthens the walk.  Queues of 5 / 6 / 8 without waiting: 155-158 us.)
-constexpr int kTpqQueue = 4;
+// lengthens the walk.  Queues of 5 / 6 / 8 with a flush of the whole queue: 155-158 us.)
+constexpr int kTpqQueue = 8;
 // second attempt of a wavefront (below): four times the first threshold, at most what the block can certify.  (Until round 5:
 // that bound itself -- every list of the wavefront then takes whatever the block holds, 535 us for the noisy scene's pass
 // against 470 with 4 x and 420 with 2.5 x, where 13 k lists come out short a second time and the ring search grows by 50 us.)
@@ -1089,7 +1110,7 @@ __device__ __forceinline__ void tpq_insert(float (&a)[KK], float c) {
 }
 
 template <int KK>
-__global__ void __launch_bounds__(256, 5)
+__global__ void __launch_bounds__(256, 4)
 grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restrict__ sorted,
                       const CellIndex cell_start, int first_col, float *__restrict__ avg_out,
                       int32_t *__restrict__ open_count, int32_t *__restrict__ open_list, float thr_mult) {
@@ -1129,7 +1150,7 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
   // r^2 / ((K+1) h^2 / candidates) is 3.3 in the median, 4.0 at the 99th percentile.  Starting from 4.5 x that instead
   // of +inf, a lane accepts ~70 candidates instead of ~100 (every accepted candidate costs all 64 lanes a (K+1)-long
   // insertion chain) and skips rows farther than the threshold.  The list simply starts out filled with the threshold
-  // (no register beside it -- the kernel sits at the 96-register edge of five waves per SIMD -- and a copy in LDS for
+  // (no register beside it -- the kernel holds 104 of the 128 registers of four waves per SIMD -- and a copy in LDS for
   // the check at the end): accepted candidates are strictly smaller and push it out.  A lane whose last slot still holds it at the end (0.5 %: the estimate was too
   // small for it) proves nothing and goes to the wavefront-per-query search like any other open query, so the results
   // do not depend on the estimate.
@@ -1259,15 +1280,34 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
   // 2^27 points): the load then takes scalar base + 32-bit vector offset as it stands -- no sign extension, no
   // 64-bit shift-add per candidate
   unsigned j = 0u, e = 0u;
-  // Two candidate buffers: each half-step requests a candidate into one buffer -- for every lane,
-  // unconditionally, from a clamped index, so that no exec-masked move forces a wait right
-  // behind the load -- and evaluates the candidate the previous half-step requested into the
-  // other.  The load of a candidate is thus always a full half-step (and the other wavefronts'
-  // turns) ahead of its use.
-  float4 ca = make_float4(0.f, 0.f, 0.f, 0.f), cb = ca;
-  bool va = false, vb = false;
-  auto half_step = [&](float4 &c_issue, bool &v_issue, const float4 &c_use, const bool v_use) -> bool {
-    if (j >= e && k < 9) {  // this lane's run is exhausted: next row (one per half-step)
+  // the queue is a stack: a push moves every slot up by one and writes slot 0, a pop inserts slot 0 (a static register
+  // index) and moves every slot down by one; the slots past the lane's qc entries hold +inf
+  auto push = [&](float d) {
+#pragma unroll
+    for (int u = kTpqQueue - 1; u > 0; --u) qd[u] = qd[u - 1];
+    qd[0] = d;
+    ++qc;
+  };
+  // one chain for all 64 lanes (a lane with an empty queue inserts +inf: nothing changes)
+  auto pop_insert = [&]() {
+    tpq_insert<KK>(a, qd[0]);
+#pragma unroll
+    for (int u = 0; u + 1 < kTpqQueue; ++u) qd[u] = qd[u + 1];
+    qd[kTpqQueue - 1] = __builtin_inff();
+    qc = qc > 0 ? qc - 1 : 0;
+    mx = a[KK - 1];
+    __builtin_amdgcn_sched_barrier(0);  // one chain at a time: interleaved chains double the live registers
+  };
+  // Two buffers of two candidates: each step requests the next TWO candidates of the lane's run into one buffer -- for
+  // every lane, unconditionally, from clamped offsets, so that no exec-masked move forces a wait right behind the
+  // loads -- and evaluates the two the previous step requested into the other.  The loads of a pair are thus always a
+  // full step (and the other wavefronts' turns) ahead of their use, and the row switch, the run bookkeeping and the two
+  // ballots are paid once per two candidates.
+  float4 ca0 = make_float4(0.f, 0.f, 0.f, 0.f), ca1 = ca0, cb0 = ca0, cb1 = ca0;
+  bool va0 = false, va1 = false, vb0 = false, vb1 = false;
+  auto step = [&](float4 &c_issue0, float4 &c_issue1, bool &v_issue0, bool &v_issue1, const float4 &c_use0,
+                  const float4 &c_use1, const bool v_use0, const bool v_use1) -> bool {
+    if (j >= e && k < 9) {  // this lane's run is exhausted: next row (one per step)
       ++k;
       if (k < 9) {
         const int row = (int)(s_order[tid] >> (4 * k)) & 15;
@@ -1276,39 +1316,30 @@ grid_query_tpq_kernel(const GridParams *__restrict__ gp, const float4 *__restric
         e = s_bd[row][tid] < mx ? (unsigned)se.y * 16u : j;  // no point of the run can enter the list: skip it
       }
     }
-    v_issue = j < e;
-    c_issue = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sorted) + (size_t)(v_issue ? j : 0u));
-    j += v_issue ? 16u : 0u;
-    if (v_use) {
-      const float d = dist2(qx, qy, qz, c_use);
-      if (d < mx) {  // (stale threshold: a candidate that no longer qualifies lands beyond column K)
-#pragma unroll
-        for (int u = kTpqQueue - 1; u > 0; --u) qd[u] = qd[u - 1];
-        qd[0] = d;
-        ++qc;
-      }
+    v_issue0 = j < e;
+    v_issue1 = j + 16u < e;  // (implies v_issue0; offsets stay below 2^31)
+    c_issue0 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sorted) + (size_t)(v_issue0 ? j : 0u));
+    c_issue1 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sorted) + (size_t)(v_issue1 ? j + 16u : 0u));
+    j += (v_issue0 ? 16u : 0u) + (v_issue1 ? 16u : 0u);
+    // (stale threshold for both: a candidate that no longer qualifies lands beyond column K)
+    if (v_use0) {
+      const float d = dist2(qx, qy, qz, c_use0);
+      if (d < mx) push(d);
     }
-    if (__builtin_amdgcn_ballot_w64(qc == kTpqQueue) != 0) {
-#pragma unroll
-      for (int u = 0; u < kTpqQueue; ++u) {
-        tpq_insert<KK>(a, qd[u]);
-        qd[u] = __builtin_inff();
-        __builtin_amdgcn_sched_barrier(0);  // one chain at a time: interleaved chains double the live registers
-      }
-      qc = 0;
-      mx = a[KK - 1];
+    if (v_use1) {
+      const float d = dist2(qx, qy, qz, c_use1);
+      if (d < mx) push(d);
     }
-    return __builtin_amdgcn_ballot_w64(v_issue || k < 9) != 0;  // anything requested or left to visit?
+    // a lane never pushes into a full queue: drain until every lane has room for the next step's two
+    while (__builtin_amdgcn_ballot_w64(qc > kTpqQueue - 2) != 0) pop_insert();
+    return __builtin_amdgcn_ballot_w64(v_issue0 || k < 9) != 0;  // anything requested or left to visit?
   };
   for (;;) {
-    if (!half_step(cb, vb, ca, va)) break;
-    if (!half_step(ca, va, cb, vb)) break;
+    if (!step(cb0, cb1, vb0, vb1, ca0, ca1, va0, va1)) break;
+    if (!step(ca0, ca1, va0, va1, cb0, cb1, vb0, vb1)) break;
   }
-#pragma unroll
-  for (int u = 0; u < kTpqQueue; ++u) {
-    tpq_insert<KK>(a, qd[u]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  // what is still queued: as many chains as the fullest queue of the wavefront holds
+  while (__builtin_amdgcn_ballot_w64(qc > 0) != 0) pop_insert();
   mx = a[KK - 1];
   cut = mx < __builtin_inff() && mx == s_thr[tid];  // the threshold left the list short
   const float safe2 = s_safe[tid];
