@@ -735,6 +735,34 @@ int pgdvs_jpeg_coefficients(const float *img_planar, int B, int H, int W, const 
 int64_t pgdvs_jpeg_scan_workspace_bytes(int B, int nby, int nbx, int restart_mcus);
 int pgdvs_jpeg_scan(const int16_t *coef, int B, int nby, int nbx, int restart_mcus, uint8_t *out, int64_t out_stride,
                     int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+/* The same codec at 4:2:0, upstream's chroma format (visualizer_pgdvs.py:141-177 / rendering.py:79-116: imageio's ffmpeg
+ * writer without a pixelformat writes yuv420p): chroma at half resolution in both directions, MCUs of 16 x 16 pixels and six
+ * blocks in the order Y00, Y01, Y10, Y11, Cb, Cr.  With nmy = ceil(H / 16), nmx = ceil(W / 16), nby = ceil(H / 8), nbx =
+ * ceil(W / 8): img_planar[B,3,H,W] float32 -> coef[B,nmy,nmx,6,64] int16 in zigzag order, bit for bit
+ * video.jpeg_coefficients(..., subsampling="4:2:0"); PIL writes the same scan at the same tables and subsampling=2.
+ *   1 colour   the pixel quantised and transformed as above; columns beyond W - 1 replicate column W - 1 out to 16 nmx.
+ *   2 luma     a block with block column < nbx and block row < nby is coded as at 4:4:4 (rows beyond H - 1 replicate row
+ *              H - 1).  Every other luma block of the MCU is a dummy block: 63 zero AC coefficients and a QUANTISED DC copied
+ *              inside the MCU: a right-edge dummy (block column >= nbx) takes its left neighbour's (Y01 from Y00, Y11 from
+ *              Y10); a bottom dummy row (block row >= nby) gives both its blocks the DC of Y01, the block in front of the row
+ *              in MCU order, dummy or not, and wins over the right-edge rule.
+ *   3 chroma   sample (j, i) with j < ceil(H / 2) is (a + b + c + d + bias) >> 2 over rows min(2j, H - 1), min(2j + 1, H - 1)
+ *              and columns 2i, 2i + 1 of the column-replicated Cb (Cr) plane, bias 1 for even i and 2 for odd i, then - 128;
+ *              rows j >= ceil(H / 2) replicate the DOWNSAMPLED row ceil(H / 2) - 1.  Chroma has no dummy blocks.
+ * One wavefront per MCU, no atomics, no workspace; pointers, tables and the limits on B, H and W as pgdvs_jpeg_coefficients,
+ * with 3 B H W and 384 B nmy nmx below 2^31, else PGDVS_ERR_INVALID.
+ * pgdvs_jpeg_scan_420: coef[B,nmy,nmx,6,64] -> the one interleaved scan as pgdvs_jpeg_scan writes it, six blocks per MCU:
+ * luminance tables for blocks 0 .. 3, chrominance tables for 4 and 5; DC prediction per component in stream order (Y from
+ * the previous Y block, across MCUs; Cb from the previous Cb; Cr from the previous Cr), all three 0 at the start of a
+ * restart segment; dummy blocks are coded like any other (DC difference, EOB).  restart_mcus counts 16 x 16 MCUs, 1 .. 65535;
+ * 0 is host-only as above.  Shapes: B >= 1, nmy and nmx in 1 .. 4096, out_stride >= 2496 nmy nmx + 2 (segments - 1) (six
+ * blocks of at most 416 bytes), B out_stride and the workspace below 2^31, else PGDVS_ERR_INVALID (-1 from the query).
+ * Alignment and workspace as pgdvs_jpeg_scan. */
+int pgdvs_jpeg_coefficients_420(const float *img_planar, int B, int H, int W, const uint16_t *qtab_luma, const uint16_t *qtab_chroma,
+                                int16_t *coef, pgdvs_stream_t stream);
+int64_t pgdvs_jpeg_scan_420_workspace_bytes(int B, int nmy, int nmx, int restart_mcus);
+int pgdvs_jpeg_scan_420(const int16_t *coef, int B, int nmy, int nmx, int restart_mcus, uint8_t *out, int64_t out_stride,
+                        int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
 
 /* ---- PNG deflate ------------------------------------------------------------ */
 /* The deflate of the PNG export.  Upstream's images leave through PIL / torchvision (pgdvs/engines/visualizer_pgdvs.py:118-139,

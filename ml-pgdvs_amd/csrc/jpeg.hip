@@ -24,6 +24,10 @@
 //                    the marker.
 // The coefficients are read twice (the second time from the cache) rather than kept as codes in LDS: a block's codes can take
 // 1658 bits, 256 of them more than the bit buffer itself.
+//
+// pgdvs_jpeg_coefficients_420 / pgdvs_jpeg_scan_420: the same codec at 4:2:0, upstream's chroma format (its ffmpeg writer's
+// yuv420p): MCUs of 16 x 16 pixels and six blocks, Y00 Y01 Y10 Y11 Cb Cr, with libjpeg's 2 x 2 chroma average, edge rules and
+// dummy blocks (jpeg_coefficients_420_kernel), and the entropy coder above with six blocks per MCU (jpeg_segments_kernel<6>).
 #include "common.h"
 #include "wave.h"
 
@@ -156,6 +160,25 @@ __device__ __forceinline__ int fdct_1d(const int *d, int k) {
   return r;
 }
 
+// One 8 x 8 block of a wavefront: the lane's level-shifted sample -> the quantised coefficient at the lane's natural index
+// (vertical frequency r = lane >> 3, horizontal c = lane & 7).  a, b: the wavefront's 64 words of LDS each; q: the table in LDS.
+// Holds two workgroup barriers (the first also orders the tables' staging before their first use).
+__device__ __forceinline__ int block_coefficient(int sample, int *a, int *b, const int *q, int lane, int r, int c) {
+  a[lane] = sample;
+  __syncthreads();
+  int d[8];
+#pragma unroll
+  for (int n = 0; n < 8; ++n) d[n] = a[r * 8 + n];
+  b[lane] = fdct_1d<true>(d, c);  // row r, horizontal frequency c
+  __syncthreads();
+#pragma unroll
+  for (int n = 0; n < 8; ++n) d[n] = b[n * 8 + c];
+  const int u = fdct_1d<false>(d, r);  // vertical frequency r, horizontal frequency c, times 8
+  const int Q8 = q[lane] << 3;
+  const int mag = (abs(u) + (Q8 >> 1)) / Q8;
+  return u < 0 ? -mag : mag;
+}
+
 __global__ void __launch_bounds__(kBlock) jpeg_coefficients_kernel(CoefParams p) {
   __shared__ int s_q[2][64];
   __shared__ int s_a[kWaves][64];
@@ -182,21 +205,84 @@ __global__ void __launch_bounds__(kBlock) jpeg_coefficients_kernel(CoefParams p)
   int16_t *out = p.coef + (size_t)mcu * 3 * 64;
 #pragma unroll
   for (int comp = 0; comp < 3; ++comp) {
-    s_a[wave][lane] = s[comp];
-    __syncthreads();  // (also orders the tables' staging before their first use)
-    int d[8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n) d[n] = s_a[wave][r * 8 + n];
-    s_b[wave][lane] = fdct_1d<true>(d, c);  // row r, horizontal frequency c
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < 8; ++n) d[n] = s_b[wave][n * 8 + c];
-    const int u = fdct_1d<false>(d, r);  // vertical frequency r, horizontal frequency c, times 8
-    const int Q8 = s_q[comp ? 1 : 0][lane] << 3;
-    const int mag = (abs(u) + (Q8 >> 1)) / Q8;
-    s_zz[wave][kZigzagPos[lane]] = (int16_t)(u < 0 ? -mag : mag);
+    s_zz[wave][kZigzagPos[lane]] = (int16_t)block_coefficient(s[comp], s_a[wave], s_b[wave], s_q[comp ? 1 : 0], lane, r, c);
     __syncthreads();
     if (live && lane < 32) reinterpret_cast<uint32_t *>(out + comp * 64)[lane] = reinterpret_cast<const uint32_t *>(s_zz[wave])[lane];
+  }
+}
+
+// ---- coefficients, 4:2:0 ---------------------------------------------------------------------------------------------------------
+// libjpeg's 4:2:0 (include/pgdvs_hip.h states the rules; pgdvs_amd/video.py restates them in numpy): one wavefront per 16 x 16
+// MCU, six blocks in the order Y00, Y01, Y10, Y11, Cb, Cr, lane = sample of the current 8 x 8 block, the DCT as above.
+struct Coef420Params {
+  const float *img;  // [B,3,H,W]
+  int16_t *coef;     // [B,nmy,nmx,6,64]
+  int H, W, nmy, nmx;
+  int nby, nbx;      // ceil(H / 8), ceil(W / 8): luma blocks past them are dummies
+  int n_mcu;         // B nmy nmx
+  uint16_t q[2][64];  // natural order
+};
+
+// Cb and Cr (0 .. 255) of the pixel at px, packed as Cb | Cr << 16 so that the four of a quad add up in one register
+__device__ __forceinline__ int cbcr_packed(const float *px, size_t plane) {
+  const int R = quantise_save_image(px[0]), G = quantise_save_image(px[plane]), B = quantise_save_image(px[2 * plane]);
+  const int cb = (-11059 * R - 21709 * G + 32768 * B + 8421375) >> 16;
+  const int cr = (32768 * R - 27439 * G - 5329 * B + 8421375) >> 16;
+  return cb | (cr << 16);
+}
+
+__global__ void __launch_bounds__(kBlock) jpeg_coefficients_420_kernel(Coef420Params p) {
+  __shared__ int s_q[2][64];
+  __shared__ int s_a[kWaves][64];
+  __shared__ int s_b[kWaves][64];
+  __shared__ __attribute__((aligned(16))) int16_t s_zz[kWaves][64];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if (threadIdx.x < 128) s_q[threadIdx.x >> 6][threadIdx.x & 63] = p.q[threadIdx.x >> 6][threadIdx.x & 63];
+  // a wavefront past the last MCU redoes the last one and stores nothing: every barrier below is met by all four
+  const int mcu_raw = blockIdx.x * kWaves + wave;
+  const bool live = mcu_raw < p.n_mcu;
+  const int mcu = live ? mcu_raw : p.n_mcu - 1;
+  const int per = p.nmy * p.nmx;
+  const int b = mcu / per, rem = mcu - b * per;
+  const int my = rem / p.nmx, mx = rem - my * p.nmx;
+  const int r = lane >> 3, c = lane & 7;
+  const size_t plane = (size_t)p.H * p.W;
+  const float *img = p.img + (size_t)b * 3 * plane;
+  // every index below is clamped into the image: the samples of dummy blocks are read and transformed like any others (the
+  // wavefronts of a workgroup meet the same barriers) and only their result is replaced
+  int s[6];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = min((2 * my + (k >> 1)) * 8 + r, p.H - 1), x = min((2 * mx + (k & 1)) * 8 + c, p.W - 1);
+    const float *px = img + (size_t)y * p.W + x;
+    const int R = quantise_save_image(px[0]), G = quantise_save_image(px[plane]), B = quantise_save_image(px[2 * plane]);
+    s[k] = ((19595 * R + 38470 * G + 7471 * B + 32768) >> 16) - 128;
+  }
+  {
+    // chroma sample (j, i) = (8 my + r, 8 mx + c): rows past the last downsampled one repeat it, then the quad's own clamps
+    const int j = min(8 * my + r, ((p.H + 1) >> 1) - 1), i = 8 * mx + c;
+    const int y0 = min(2 * j, p.H - 1), y1 = min(2 * j + 1, p.H - 1), x0 = min(2 * i, p.W - 1), x1 = min(2 * i + 1, p.W - 1);
+    const float *row0 = img + (size_t)y0 * p.W, *row1 = img + (size_t)y1 * p.W;
+    const int sum = cbcr_packed(row0 + x0, plane) + cbcr_packed(row0 + x1, plane) + cbcr_packed(row1 + x0, plane) +
+                    cbcr_packed(row1 + x1, plane);  // each half at most 1020: no carry between them
+    const int bias = 1 + (c & 1);                   // (8 mx is even: the parity of i is that of c)
+    s[4] = (((sum & 0xffff) + bias) >> 2) - 128;
+    s[5] = (((sum >> 16) + bias) >> 2) - 128;
+  }
+  const bool right_dummy = 2 * mx + 1 >= p.nbx, bottom_dummy = 2 * my + 1 >= p.nby;
+  int16_t *out = p.coef + (size_t)mcu * 6 * 64;
+  int dc[3];  // the quantised DC of Y00, Y01, Y10 as stored (wavefront-uniform)
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    int v = block_coefficient(s[k], s_a[wave], s_b[wave], s_q[k < 4 ? 0 : 1], lane, r, c);
+    // dummy blocks: no AC, the DC of Y01 for the bottom row (which wins), of the left neighbour for the right column
+    if (k == 1 && right_dummy) v = lane == 0 ? dc[0] : 0;
+    if (k == 2 && bottom_dummy) v = lane == 0 ? dc[1] : 0;
+    if (k == 3 && (bottom_dummy || right_dummy)) v = lane == 0 ? (bottom_dummy ? dc[1] : dc[2]) : 0;
+    if (k < 3) dc[k] = __builtin_amdgcn_readfirstlane(v);  // lane 0 holds natural index 0
+    s_zz[wave][kZigzagPos[lane]] = (int16_t)v;
+    __syncthreads();
+    if (live && lane < 32) reinterpret_cast<uint32_t *>(out + k * 64)[lane] = reinterpret_cast<const uint32_t *>(s_zz[wave])[lane];
   }
 }
 
@@ -249,7 +335,7 @@ __device__ __forceinline__ void walk_block(const int16_t *__restrict__ blk, int 
 constexpr int kBufWords = (7 + kBlock * kBlockMaxBits + 31) / 32 + 2;  // + the word a code may spill into, never past it
 
 struct ScanParams {
-  const int16_t *coef;  // [B,n_mcu,3,64]
+  const int16_t *coef;  // [B,n_mcu,kBpm,64]
   int n_mcu;            // per frame
   int seg_mcus;         // MCUs per restart segment (>= 1)
   int n_seg;            // per frame
@@ -263,8 +349,12 @@ struct ScanParams {
 };
 
 // bits are big-endian throughout: bit 0 of the buffer is the most significant bit of word 0, byte i of the buffer is bits
-// 31 - 8 (i & 3) .. 24 - 8 (i & 3) of word i >> 2
+// 31 - 8 (i & 3) .. 24 - 8 (i & 3) of word i >> 2.
+// kBpm: blocks per MCU.  3: Y Cb Cr, each predicted from the block 3 back.  6 (4:2:0): Y00 Y01 Y10 Y11 Cb Cr; the previous
+// block of the component is 3 back for Y00 (the Y11 of the MCU before), 1 back for Y01 .. Y11, 6 back for Cb and Cr.
+template <int kBpm>
 __global__ void __launch_bounds__(kBlock) jpeg_segments_kernel(ScanParams p) {
+  static_assert(kBpm == 3 || kBpm == 6, "4:4:4 or 4:2:0");
   __shared__ HuffTables s_huff;
   __shared__ uint32_t s_buf[kBufWords];
   __shared__ int s_wsum[kWaves];
@@ -272,8 +362,8 @@ __global__ void __launch_bounds__(kBlock) jpeg_segments_kernel(ScanParams p) {
   for (int i = tid; i < kHuffWords; i += kBlock) reinterpret_cast<uint32_t *>(&s_huff)[i] = reinterpret_cast<const uint32_t *>(&kHuff)[i];
   const int frame = blockIdx.x / p.n_seg, seg = blockIdx.x - frame * p.n_seg;
   const int mcu0 = seg * p.seg_mcus;
-  const int n_blk = 3 * min(p.seg_mcus, p.n_mcu - mcu0);  // blocks of this segment
-  const int16_t *blocks = p.coef + ((size_t)frame * p.n_mcu + mcu0) * 3 * 64;
+  const int n_blk = kBpm * min(p.seg_mcus, p.n_mcu - mcu0);  // blocks of this segment
+  const int16_t *blocks = p.coef + ((size_t)frame * p.n_mcu + mcu0) * kBpm * 64;
   uint8_t *slot = p.slots + (size_t)blockIdx.x * p.slot_stride;
   uint32_t carry = 0u;  // the bits left over by the blocks before, left-aligned in a byte
   int n_carry = 0;
@@ -283,8 +373,11 @@ __global__ void __launch_bounds__(kBlock) jpeg_segments_kernel(ScanParams p) {
     const int j = j0 + tid;
     const bool have = j < n_blk;
     const int16_t *blk = blocks + (size_t)(have ? j : 0) * 64;
-    const int t = (j % 3) ? 1 : 0;
-    const int pred = (have && j >= 3) ? clamp_dc((int)blk[-3 * 64]) : 0;
+    const int at = j % kBpm;  // the block's place in its MCU
+    const int t = at >= (kBpm == 3 ? 1 : 4) ? 1 : 0;
+    const int back = kBpm == 3 ? 3 : (at == 0 ? 3 : at < 4 ? 1 : 6);
+    // the first block of a component in the segment predicts from 0 (those 1 back always have a block in front of them)
+    const int pred = (have && (back == 1 || j >= kBpm)) ? clamp_dc((int)blk[-back * 64]) : 0;
     int len = 0;
     if (have) walk_block(blk, pred, s_huff, t, [&](uint32_t, int n) { len += n; });
     int total;
@@ -375,13 +468,15 @@ __global__ void __launch_bounds__(kBlock) jpeg_gather_kernel(ScanParams p) {
 struct ScanShape {
   int64_t n_mcu, seg_mcus, n_seg, slot_stride, capacity;
 };
-bool scan_shape(int B, int nby, int nbx, int restart_mcus, ScanShape &s) {
-  if (B < 1 || nby < 1 || nby > 8192 || nbx < 1 || nbx > 8192 || restart_mcus < 1 || restart_mcus > 65535) return false;
+// nby, nbx: the MCU grid (16 x 16 pixel MCUs at bpm = 6); either way no more than 65536 pixels a side
+bool scan_shape(int B, int nby, int nbx, int restart_mcus, int bpm, ScanShape &s) {
+  const int side = bpm == 3 ? 8192 : 4096;
+  if (B < 1 || nby < 1 || nby > side || nbx < 1 || nbx > side || restart_mcus < 1 || restart_mcus > 65535) return false;
   s.n_mcu = (int64_t)nby * nbx;
   s.seg_mcus = restart_mcus < s.n_mcu ? restart_mcus : s.n_mcu;
   s.n_seg = cdiv(s.n_mcu, s.seg_mcus);
-  s.slot_stride = s.seg_mcus * 3 * kBlockMaxBytes;
-  s.capacity = s.n_mcu * 3 * kBlockMaxBytes + 2 * (s.n_seg - 1);
+  s.slot_stride = s.seg_mcus * bpm * kBlockMaxBytes;
+  s.capacity = s.n_mcu * bpm * kBlockMaxBytes + 2 * (s.n_seg - 1);
   return (int64_t)B * s.n_seg * s.slot_stride < (1ll << 31) && (int64_t)B * s.capacity < (1ll << 31);
 }
 
@@ -397,6 +492,28 @@ struct ScanWorkspace {
     bytes = c.off;
   }
 };
+
+// the three launches of a scan over checked shapes
+template <int kBpm>
+void launch_scan(const int16_t *coef, int B, const ScanShape &s, const ScanWorkspace &ws, uint8_t *out, int64_t out_stride,
+                 int32_t *nbytes, hipStream_t st) {
+  ScanParams p;
+  p.coef = coef;
+  p.n_mcu = (int)s.n_mcu;
+  p.seg_mcus = (int)s.seg_mcus;
+  p.n_seg = (int)s.n_seg;
+  p.slots = ws.slots;
+  p.slot_stride = s.slot_stride;
+  p.sizes = ws.sizes;
+  p.offsets = ws.offsets;
+  p.out = out;
+  p.out_stride = out_stride;
+  p.nbytes = nbytes;
+  const unsigned n_slots = (unsigned)(B * s.n_seg);
+  PGDVS_LAUNCH("jpeg_segments", jpeg_segments_kernel<kBpm>, dim3(n_slots), dim3(kBlock), 0, st, p);
+  PGDVS_LAUNCH("jpeg_offsets", jpeg_offsets_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, p);
+  PGDVS_LAUNCH("jpeg_gather", jpeg_gather_kernel, dim3(n_slots), dim3(kBlock), 0, st, p);
+}
 
 }  // namespace
 }  // namespace pgdvs
@@ -435,7 +552,7 @@ PGDVS_API int pgdvs_jpeg_coefficients(const float *img_planar, int B, int H, int
 
 PGDVS_API int64_t pgdvs_jpeg_scan_workspace_bytes(int B, int nby, int nbx, int restart_mcus) {
   ScanShape s;
-  if (!scan_shape(B, nby, nbx, restart_mcus, s)) {
+  if (!scan_shape(B, nby, nbx, restart_mcus, 3, s)) {
     set_error("pgdvs_jpeg_scan_workspace_bytes: bad shape B=%d nby=%d nbx=%d restart_mcus=%d (B >= 1, nby and nbx in 1 .. 8192, "
               "restart_mcus in 1 .. 65535, B x the frame's capacity below 2^31)", B, nby, nbx, restart_mcus);
     return -1;
@@ -449,7 +566,7 @@ PGDVS_API int pgdvs_jpeg_scan(const int16_t *coef, int B, int nby, int nbx, int 
   PGDVS_REQUIRE(restart_mcus != 0, "pgdvs_jpeg_scan: restart_mcus 0 (no restart markers) is host-only: the segments of the device "
                                    "pass are byte-aligned; use 1 .. 65535");
   ScanShape s;
-  PGDVS_REQUIRE(scan_shape(B, nby, nbx, restart_mcus, s),
+  PGDVS_REQUIRE(scan_shape(B, nby, nbx, restart_mcus, 3, s),
                 "pgdvs_jpeg_scan: bad shape B=%d nby=%d nbx=%d restart_mcus=%d (B >= 1, nby and nbx in 1 .. 8192, restart_mcus in "
                 "1 .. 65535, B x the frame's capacity below 2^31)", B, nby, nbx, restart_mcus);
   PGDVS_REQUIRE(out_stride >= s.capacity && (int64_t)B * out_stride < (1ll << 31),
@@ -461,22 +578,71 @@ PGDVS_API int pgdvs_jpeg_scan(const int16_t *coef, int B, int nby, int nbx, int 
   ScanWorkspace ws(workspace, B, s);
   PGDVS_REQUIRE(workspace_bytes >= ws.bytes, "pgdvs_jpeg_scan: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
                 (long long)ws.bytes);
-  ScanParams p;
-  p.coef = coef;
-  p.n_mcu = (int)s.n_mcu;
-  p.seg_mcus = (int)s.seg_mcus;
-  p.n_seg = (int)s.n_seg;
-  p.slots = ws.slots;
-  p.slot_stride = s.slot_stride;
-  p.sizes = ws.sizes;
-  p.offsets = ws.offsets;
-  p.out = out;
-  p.out_stride = out_stride;
-  p.nbytes = nbytes;
-  const hipStream_t st = as_stream(stream);
-  const unsigned n_slots = (unsigned)(B * s.n_seg);
-  PGDVS_LAUNCH("jpeg_segments", jpeg_segments_kernel, dim3(n_slots), dim3(kBlock), 0, st, p);
-  PGDVS_LAUNCH("jpeg_offsets", jpeg_offsets_kernel, dim3((unsigned)B), dim3(kBlock), 0, st, p);
-  PGDVS_LAUNCH("jpeg_gather", jpeg_gather_kernel, dim3(n_slots), dim3(kBlock), 0, st, p);
+  launch_scan<3>(coef, B, s, ws, out, out_stride, nbytes, as_stream(stream));
   return check_launch("pgdvs_jpeg_scan");
+}
+
+PGDVS_API int pgdvs_jpeg_coefficients_420(const float *img_planar, int B, int H, int W, const uint16_t *qtab_luma,
+                                          const uint16_t *qtab_chroma, int16_t *coef, pgdvs_stream_t stream) {
+  PGDVS_REQUIRE(img_planar && qtab_luma && qtab_chroma && coef, "pgdvs_jpeg_coefficients_420: null pointer");
+  PGDVS_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535,
+                "pgdvs_jpeg_coefficients_420: bad shape B=%d H=%d W=%d (B >= 1, H and W in 1 .. 65535)", B, H, W);
+  const int nmy = (H + 15) / 16, nmx = (W + 15) / 16;
+  PGDVS_REQUIRE((int64_t)B * 3 * H * W < (1ll << 31) && (int64_t)B * nmy * nmx * 384 < (1ll << 31),
+                "pgdvs_jpeg_coefficients_420: B=%d H=%d W=%d: 3 B H W and the %lld coefficients must stay below 2^31", B, H, W,
+                (long long)B * nmy * nmx * 384);
+  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(img_planar) & 3) == 0 && (reinterpret_cast<uintptr_t>(coef) & 3) == 0,
+                "pgdvs_jpeg_coefficients_420: img_planar or coef is not 4-byte aligned");
+  Coef420Params p;
+  p.img = img_planar;
+  p.coef = coef;
+  p.H = H;
+  p.W = W;
+  p.nmy = nmy;
+  p.nmx = nmx;
+  p.nby = (H + 7) / 8;
+  p.nbx = (W + 7) / 8;
+  p.n_mcu = B * nmy * nmx;
+  for (int i = 0; i < 64; ++i) {
+    PGDVS_REQUIRE(qtab_luma[i] >= 1 && qtab_luma[i] <= 255 && qtab_chroma[i] >= 1 && qtab_chroma[i] <= 255,
+                  "pgdvs_jpeg_coefficients_420: quantisation table entry %d is %d / %d (1 .. 255: baseline, 8-bit tables)", i,
+                  (int)qtab_luma[i], (int)qtab_chroma[i]);
+    p.q[0][i] = qtab_luma[i];
+    p.q[1][i] = qtab_chroma[i];
+  }
+  PGDVS_LAUNCH("jpeg_coefficients_420", jpeg_coefficients_420_kernel, dim3((unsigned)cdiv(p.n_mcu, kWaves)), dim3(kBlock), 0,
+               as_stream(stream), p);
+  return check_launch("pgdvs_jpeg_coefficients_420");
+}
+
+PGDVS_API int64_t pgdvs_jpeg_scan_420_workspace_bytes(int B, int nmy, int nmx, int restart_mcus) {
+  ScanShape s;
+  if (!scan_shape(B, nmy, nmx, restart_mcus, 6, s)) {
+    set_error("pgdvs_jpeg_scan_420_workspace_bytes: bad shape B=%d nmy=%d nmx=%d restart_mcus=%d (B >= 1, nmy and nmx in 1 .. 4096, "
+              "restart_mcus in 1 .. 65535, B x the frame's capacity below 2^31)", B, nmy, nmx, restart_mcus);
+    return -1;
+  }
+  return ScanWorkspace(nullptr, B, s).bytes;
+}
+
+PGDVS_API int pgdvs_jpeg_scan_420(const int16_t *coef, int B, int nmy, int nmx, int restart_mcus, uint8_t *out, int64_t out_stride,
+                                  int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
+  PGDVS_REQUIRE(coef && out && nbytes && workspace, "pgdvs_jpeg_scan_420: null pointer");
+  PGDVS_REQUIRE(restart_mcus != 0, "pgdvs_jpeg_scan_420: restart_mcus 0 (no restart markers) is host-only: the segments of the "
+                                   "device pass are byte-aligned; use 1 .. 65535");
+  ScanShape s;
+  PGDVS_REQUIRE(scan_shape(B, nmy, nmx, restart_mcus, 6, s),
+                "pgdvs_jpeg_scan_420: bad shape B=%d nmy=%d nmx=%d restart_mcus=%d (B >= 1, nmy and nmx in 1 .. 4096, restart_mcus in "
+                "1 .. 65535, B x the frame's capacity below 2^31)", B, nmy, nmx, restart_mcus);
+  PGDVS_REQUIRE(out_stride >= s.capacity && (int64_t)B * out_stride < (1ll << 31),
+                "pgdvs_jpeg_scan_420: out_stride %lld (at least the capacity %lld = 2496 nmy nmx + 2 (segments - 1), B out_stride < 2^31)",
+                (long long)out_stride, (long long)s.capacity);
+  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(coef) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0 &&
+                    (reinterpret_cast<uintptr_t>(nbytes) & 3) == 0,
+                "pgdvs_jpeg_scan_420: coef must be 16-byte, workspace 256-byte and nbytes 4-byte aligned");
+  ScanWorkspace ws(workspace, B, s);
+  PGDVS_REQUIRE(workspace_bytes >= ws.bytes, "pgdvs_jpeg_scan_420: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)ws.bytes);
+  launch_scan<6>(coef, B, s, ws, out, out_stride, nbytes, as_stream(stream));
+  return check_launch("pgdvs_jpeg_scan_420");
 }

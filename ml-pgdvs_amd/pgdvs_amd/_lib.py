@@ -116,6 +116,9 @@ SIGNATURES.update({
     "pgdvs_jpeg_coefficients": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "pgdvs_jpeg_scan_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "pgdvs_jpeg_scan": (_i, [_vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "pgdvs_jpeg_coefficients_420": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "pgdvs_jpeg_scan_420_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "pgdvs_jpeg_scan_420": (_i, [_vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     "pgdvs_png_deflate_workspace_bytes": (_i64, [_i, _i64, _i]),
     "pgdvs_png_deflate": (_i, [_vp, _i, _i64, _i, _vp, _i64, _vp, _vp, _i64, _vp]),
     "pgdvs_flow_consistency": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),

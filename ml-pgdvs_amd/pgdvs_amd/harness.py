@@ -634,9 +634,9 @@ def _video_frames(img: torch.Tensor, writer):
         return list(img.float().cpu())
     from . import ops, video
 
-    data, nbytes = ops.jpeg_encode(img, quality=writer.quality, restart_mcus=writer.restart_mcus)
+    data, nbytes = ops.jpeg_encode(img, quality=writer.quality, restart_mcus=writer.restart_mcus, subsampling=writer.subsampling)
     ready = torch.cuda.current_stream(img.device).record_event()
-    return [video.DeviceScan(data[i], nbytes[i:i + 1], img.shape[2], img.shape[3], ready) for i in range(img.shape[0])]
+    return [video.DeviceScan(data[i], nbytes[i:i + 1], img.shape[2], img.shape[3], ready, writer.subsampling) for i in range(img.shape[0])]
 
 
 @torch.no_grad()
@@ -719,7 +719,7 @@ def _run_batches(what, dataset, batch_size, n_max_data, rank, world):
 
 
 def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1, rank=0, world=1, device=None, writer=None,
-            video=False, video_fps=10, video_quality=90, png_deflate="zlib"):
+            video=False, video_fps=10, video_quality=90, png_deflate="zlib", video_subsampling="4:4:4"):
     """``vis_model``'s outer loop without Hydra: this rank's items in ``DistributedSampler(shuffle=False)`` order
     (``dist.shard_indices``), ``batch_size`` of them per step (the per-process batch size), collated as upstream collates
     them, at most ``ceil(min(len(dataset), n_max_data) / (batch_size * world))`` steps (``n_max_data <= 0``: all), each
@@ -733,7 +733,9 @@ def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1,
     ``video_quality``, frames in ``tgt_idx`` order: upstream's ``_combined.mp4`` (:141-177) as Motion-JPEG, see
     ``pgdvs_amd/video.py``.  With ``world > 1`` each rank leaves hidden part files instead; under an initialised process
     group of that size the ranks then meet at a barrier and rank 0 merges them (``video.assemble``), without one call
-    ``video.assemble(vis_dir, world)`` once every rank has returned.  The default writes no video and nothing else changes."""
+    ``video.assemble(vis_dir, world)`` once every rank has returned.  ``video_subsampling``: "4:4:4", or "4:2:0" for chroma
+    at half resolution in both directions, upstream's chroma format (its ffmpeg writer's yuv420p); a given writer decides for
+    itself.  The default writes no video and nothing else changes."""
     from . import png
     from . import video as vid
 
@@ -742,7 +744,8 @@ def vis_run(model, dataset, render_cfg, vis_dir, *, batch_size=1, n_max_data=-1,
     w = png.PngWriter(deflate=png_deflate) if own else writer
     mj = None
     if video is not None and video is not False:
-        mj = vid.MjpegWriter(fps=video_fps, quality=video_quality, rank=rank, world=world) if video is True else video
+        mj = vid.MjpegWriter(fps=video_fps, quality=video_quality, rank=rank, world=world,
+                             subsampling=video_subsampling) if video is True else video
     dirs = {}
     try:
         for batch in batches:

@@ -1136,13 +1136,16 @@ def _quant_ptr(table, name):
     return (C.c_uint16 * 64)(*t.tolist())
 
 
-def jpeg_coefficients(img, quality=90, out=None):
+def jpeg_coefficients(img, quality=90, out=None, subsampling="4:4:4"):
     """The first half of a video frame's compression (``pgdvs_jpeg_coefficients``; include/pgdvs_hip.h): img[B,3,H,W] (or
     [3,H,W]) float32 on the GPU, unclamped -> int16 [B,nby,nbx,3,64]: per 8 x 8 block the quantised DCT coefficients of Y, Cb
     and Cr in zigzag order, bit for bit ``video.jpeg_coefficients`` of the image quantised as ``*_combined.png`` is.
-    ``quality``: libjpeg's 1 .. 100 (``video.quant_tables``), or a pair of tables in natural order."""
+    ``quality``: libjpeg's 1 .. 100 (``video.quant_tables``), or a pair of tables in natural order.
+    ``subsampling="4:2:0"`` (``pgdvs_jpeg_coefficients_420``): int16 [B,nmy,nmx,6,64] over 16 x 16 MCUs, blocks Y00, Y01, Y10,
+    Y11, Cb, Cr, with libjpeg's chroma averaging, edge rules and dummy blocks."""
     from . import video
 
+    video.check_subsampling(subsampling)
     x = _req(img, torch.float32, "img")
     if x.ndim == 3:
         x = x[None]
@@ -1150,31 +1153,36 @@ def jpeg_coefficients(img, quality=90, out=None):
         raise ValueError(f"jpeg_coefficients: img [B,3,H,W] expected, got {tuple(x.shape)}")
     luma, chroma = video.quant_tables(quality) if np.isscalar(quality) else quality
     B, _, H, W = (int(v) for v in x.shape)
-    shape = (B, (H + 7) // 8, (W + 7) // 8, 3, 64)
+    shape = (B, *video.mcu_grid(H, W, subsampling), video.BLOCKS_PER_MCU[subsampling], 64)
     if out is None:
         out = torch.empty(shape, dtype=torch.int16, device=x.device)
     elif not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.int16 and out.is_contiguous()
               and tuple(out.shape) == shape):
         raise ValueError(f"jpeg_coefficients: out must be a contiguous int16 tensor of {shape} on {x.device}")
-    check(_lib.load().pgdvs_jpeg_coefficients(_ptr(x), B, H, W, _quant_ptr(luma, "jpeg_coefficients"),
-                                              _quant_ptr(chroma, "jpeg_coefficients"), _ptr(out), _stream()), "pgdvs_jpeg_coefficients")
+    name = "pgdvs_jpeg_coefficients" if subsampling == "4:4:4" else "pgdvs_jpeg_coefficients_420"
+    check(getattr(_lib.load(), name)(_ptr(x), B, H, W, _quant_ptr(luma, "jpeg_coefficients"), _quant_ptr(chroma, "jpeg_coefficients"),
+                                     _ptr(out), _stream()), name)
     return out
 
 
-def jpeg_scan_capacity(nby: int, nbx: int, restart_mcus: int) -> int:
+def jpeg_scan_capacity(nby: int, nbx: int, restart_mcus: int, blocks_per_mcu: int = 3) -> int:
     """The bytes a frame's scan data can take at most (the least ``out_stride`` of ``pgdvs_jpeg_scan``): 1248 per MCU -- a
-    block costs at most 1658 bits = 208 bytes, doubled by stuffing -- plus 2 per restart marker."""
+    block costs at most 1658 bits = 208 bytes, doubled by stuffing -- plus 2 per restart marker.  ``blocks_per_mcu=6``: the
+    4:2:0 layout (``nby``, ``nbx`` its MCU grid), 2496 per MCU."""
+    if blocks_per_mcu not in (3, 6):
+        raise ValueError(f"jpeg_scan_capacity: blocks_per_mcu {blocks_per_mcu} (3 or 6)")
     n_mcu = int(nby) * int(nbx)
     seg = max(1, min(int(restart_mcus), n_mcu))
-    return 1248 * n_mcu + 2 * ((n_mcu + seg - 1) // seg - 1)
+    return 416 * blocks_per_mcu * n_mcu + 2 * ((n_mcu + seg - 1) // seg - 1)
 
 
 def jpeg_scan(coef, restart_mcus=None, out=None):
-    """The second half (``pgdvs_jpeg_scan``; include/pgdvs_hip.h): coef[B,nby,nbx,3,64] (or [nby,nbx,3,64]) int16 on the GPU ->
+    """The second half (``pgdvs_jpeg_scan``; include/pgdvs_hip.h): coef[B,nby,nbx,3,64] (or [nby,nbx,3,64]) int16 on the GPU, or
+    the 4:2:0 layout [B,nmy,nmx,6,64] (recognised by ``coef.shape[-2]``; ``pgdvs_jpeg_scan_420``, MCUs of 16 x 16 pixels) ->
     (data uint8 [B,stride], nbytes int32 [B]) on the GPU: ``data[b, :nbytes[b]]`` is frame b's entropy-coded scan, byte for
     byte ``video.encode_scan``; the rest of a row is not written.  ``restart_mcus``: MCUs per restart interval, None for one
     MCU row; 0 (no restart markers) is host-only and refused.  ``out``: a contiguous uint8 GPU tensor [B,stride] with
-    stride >= ``jpeg_scan_capacity(nby, nbx, restart_mcus)`` to fill in place.  Nothing synchronises."""
+    stride >= ``jpeg_scan_capacity(nby, nbx, restart_mcus, coef.shape[-2])`` to fill in place.  Nothing synchronises."""
     if not isinstance(coef, torch.Tensor) or not coef.is_cuda:
         raise PgdvsHipError("jpeg_scan: coef must be a GPU tensor (the host path is video.encode_scan)")
     if coef.dtype != torch.int16:
@@ -1182,34 +1190,34 @@ def jpeg_scan(coef, restart_mcus=None, out=None):
     c = coef.contiguous()
     if c.ndim == 4:
         c = c[None]
-    if c.ndim != 5 or tuple(c.shape[3:]) != (3, 64) or c.shape[0] < 1 or c.shape[1] < 1 or c.shape[2] < 1:
-        raise ValueError(f"jpeg_scan: coef [B,nby,nbx,3,64] expected, got {tuple(coef.shape)}")
-    B, nby, nbx = (int(v) for v in c.shape[:3])
+    if c.ndim != 5 or tuple(c.shape[3:]) not in ((3, 64), (6, 64)) or c.shape[0] < 1 or c.shape[1] < 1 or c.shape[2] < 1:
+        raise ValueError(f"jpeg_scan: coef [B,nby,nbx,3,64] or [B,nmy,nmx,6,64] expected, got {tuple(coef.shape)}")
+    B, nby, nbx, bpm = (int(v) for v in c.shape[:4])
+    name = "pgdvs_jpeg_scan" if bpm == 3 else "pgdvs_jpeg_scan_420"
     R = nbx if restart_mcus is None else int(restart_mcus)
     if R == 0:
         raise PgdvsHipError("jpeg_scan: restart_mcus 0 (no restart markers) is host-only (video.encode_scan); the device pass "
                             "needs restart_mcus >= 1")
     if not 1 <= R <= 65535:
         raise ValueError(f"jpeg_scan: restart_mcus {restart_mcus} (1 .. 65535)")
-    cap = jpeg_scan_capacity(nby, nbx, R)
+    cap = jpeg_scan_capacity(nby, nbx, R, bpm)
     if out is None:
         out = torch.empty((B, cap), dtype=torch.uint8, device=c.device)
     elif not (isinstance(out, torch.Tensor) and out.device == c.device and out.dtype == torch.uint8 and out.is_contiguous()
               and out.ndim == 2 and out.shape[0] == B and out.shape[1] >= cap):
         raise ValueError(f"jpeg_scan: out must be a contiguous uint8 tensor [{B}, >= {cap}] on {c.device}")
     lib = _lib.load()
-    ws = _ws(lib.pgdvs_jpeg_scan_workspace_bytes(B, nby, nbx, R), c.device)
+    ws = _ws(getattr(lib, name + "_workspace_bytes")(B, nby, nbx, R), c.device)
     nbytes = torch.empty((B,), dtype=torch.int32, device=c.device)
-    check(lib.pgdvs_jpeg_scan(_ptr(c), B, nby, nbx, R, _ptr(out), int(out.shape[1]), _ptr(nbytes), _ptr(ws), ws.numel(), _stream()),
-          "pgdvs_jpeg_scan")
+    check(getattr(lib, name)(_ptr(c), B, nby, nbx, R, _ptr(out), int(out.shape[1]), _ptr(nbytes), _ptr(ws), ws.numel(), _stream()), name)
     return out, nbytes
 
 
-def jpeg_encode(img, quality=90, restart_mcus=None):
+def jpeg_encode(img, quality=90, restart_mcus=None, subsampling="4:4:4"):
     """``jpeg_coefficients`` then ``jpeg_scan``: img[B,3,H,W] (or [3,H,W]) float32 on the GPU -> (data [B,stride], nbytes [B]);
-    ``video.jpeg_frame(data[b, :nbytes[b]], H, W, quality, restart_mcus)`` is frame b's JPEG file, the bytes of
+    ``video.jpeg_frame(data[b, :nbytes[b]], H, W, quality, restart_mcus, subsampling)`` is frame b's JPEG file, the bytes of
     ``video.encode_jpeg`` on the same image."""
-    return jpeg_scan(jpeg_coefficients(img, quality), restart_mcus)
+    return jpeg_scan(jpeg_coefficients(img, quality, subsampling=subsampling), restart_mcus)
 
 
 def eval_export_scanlines(pred, gt_hwc, static=None, adaptive=True, out=None):

@@ -1,7 +1,7 @@
 """The visualiser's video without ffmpeg: a Motion-JPEG AVI in place of ``<scene_id>_combined.mp4``
 (pgdvs/engines/visualizer_pgdvs.py:141-177, pgdvs/utils/rendering.py:79-116 ``images_to_video(..., fps=10, quality=9)``).
 
-It is a substitute for the mp4, not an mp4: every frame is an independent baseline JPEG (8 bit, 4:4:4, one interleaved
+It is a substitute for the mp4, not an mp4: every frame is an independent baseline JPEG (8 bit, 4:4:4 or on request 4:2:0, one interleaved
 scan, the four standard Huffman tables, IJG quality scaling of the Annex K tables) inside a RIFF AVI with an ``idx1``
 index.  imageio's ``quality=9`` has no counterpart here; ``quality`` is libjpeg's 1..100.
 
@@ -17,6 +17,25 @@ The codec is defined in integers so that this module and csrc/jpeg.hip agree byt
             ZRL, EOB; per restart segment: bits padded with ones, 0xFF -> 0xFF 0x00, RSTm between segments.  On read DC is
             clamped to -1024 .. 1023 and AC to +-1023, so that every symbol exists in the standard tables (a DC difference
             is then at most 2047, category 11).
+
+``subsampling="4:2:0"`` (the default stays "4:4:4") is upstream's chroma format -- imageio's ffmpeg writer without a
+``pixelformat`` writes yuv420p -- and the same codec with a 16 x 16 MCU of six blocks, Y00 Y01 Y10 Y11 Cb Cr:
+coef[nmy, nmx, 6, 64] with nmy = ceil(H / 16), nmx = ceil(W / 16).  Its edges are libjpeg's, and PIL writes the same scan
+bytes at ``subsampling=2`` (nby = ceil(H / 8), nbx = ceil(W / 8)):
+
+  columns   beyond W - 1 replicate column W - 1 out to 16 nmx; quantisation and colour transform as at 4:4:4
+  luma      a block with block column < nbx and block row < nby is coded as at 4:4:4 (rows beyond H - 1 replicate row H - 1).
+            Every other luma block of the MCU is a dummy: 63 zero AC coefficients and a QUANTISED DC copied inside the MCU --
+            a right-edge dummy (column >= nbx) takes its left neighbour's (Y01 from Y00, Y11 from Y10); a bottom dummy row
+            (row >= nby) gives both its blocks the DC of Y01, the block in front of the row in MCU order, dummy or not, and
+            wins over the right-edge rule.  Dummies are entropy-coded like any block: a DC difference, then EOB
+  chroma    sample (j, i), j < ceil(H / 2): (a + b + c + d + bias) >> 2 over rows min(2j, H-1), min(2j+1, H-1) and columns
+            2i, 2i+1 of the column-replicated Cb (Cr) plane, bias 1 for even i and 2 for odd i, then - 128.  Rows
+            j >= ceil(H / 2) replicate the DOWNSAMPLED row ceil(H / 2) - 1.  No dummy blocks: ceil(ceil(W / 2) / 8) = nmx
+  entropy   luma tables for blocks 0 .. 3, chroma tables for 4 and 5; DC prediction per component in stream order: Y from
+            the previous Y block (across MCUs), Cb from the previous Cb, Cr from the previous Cr, all 0 at a restart.
+            ``restart_mcus`` counts 16 x 16 MCUs
+  header    SOF0 sampling 2x2 for Y, 1x1 for Cb and Cr; DRI in MCUs; the rest as at 4:4:4
 
 ``jpeg_coefficients`` / ``encode_scan`` are the host restatement (numpy integers; the fallback for host tensors, not
 meant to be fast), ``ops.jpeg_coefficients`` / ``ops.jpeg_scan`` the HIP path.  ``jpeg_frame`` puts the headers round a
@@ -96,8 +115,25 @@ def quant_tables(quality: int):
     return tuple(np.clip((t * scale + 50) // 100, 1, 255) for t in (QUANT_LUMA, QUANT_CHROMA))
 
 
+SUBSAMPLINGS = ("4:4:4", "4:2:0")
+BLOCKS_PER_MCU = {"4:4:4": 3, "4:2:0": 6}
+MCU_SIZE = {"4:4:4": 8, "4:2:0": 16}
+
+
+def check_subsampling(subsampling) -> str:
+    if subsampling not in SUBSAMPLINGS:
+        raise ValueError(f"subsampling {subsampling!r} ('4:4:4' or '4:2:0')")
+    return subsampling
+
+
+def mcu_grid(H: int, W: int, subsampling="4:4:4"):
+    """(MCU rows, MCU columns) of an H x W frame: MCUs of 8 x 8 pixels at 4:4:4, of 16 x 16 at 4:2:0"""
+    m = MCU_SIZE[check_subsampling(subsampling)]
+    return (int(H) + m - 1) // m, (int(W) + m - 1) // m
+
+
 def default_restart(nbx: int) -> int:
-    """The default restart interval: one MCU row."""
+    """The default restart interval: one MCU row (``nbx``: the MCUs in a row of the layout at hand)."""
     return int(nbx)
 
 
@@ -150,20 +186,59 @@ def fdct_int(s: np.ndarray) -> np.ndarray:
     return np.swapaxes(_fdct_1d(np.swapaxes(t, -1, -2), False), -1, -2)
 
 
-def jpeg_coefficients(q_uint8_hwc, quality: int = 90) -> np.ndarray:
-    """The quantised image q[H,W,3] uint8 -> coef[nby,nbx,3,64] int16, zigzag order (component order Y, Cb, Cr)."""
+def _quantised_blocks(plane, Q):
+    """plane[8 r, 8 c] level-shifted samples -> [r, c, 64] int64 quantised coefficients in zigzag order"""
+    r, c = plane.shape[0] // 8, plane.shape[1] // 8
+    co = fdct_int(plane.reshape(r, 8, c, 8).transpose(0, 2, 1, 3)).reshape(r, c, 64)
+    return (np.sign(co) * ((np.abs(co) + 4 * Q) // (8 * Q)))[..., ZIGZAG]  # the DCT carries a factor of 8: ONE rounding
+
+
+def _coefficients_420(q, quality) -> np.ndarray:
+    """q[H,W,3] uint8 -> coef[nmy,nmx,6,64] int16: libjpeg's 4:2:0 (h2v2 downsampling, its edge expansion and its dummy
+    blocks), see the module text"""
+    H, W, _ = q.shape
+    nmy, nmx = (H + 15) // 16, (W + 15) // 16
+    nby, nbx = (H + 7) // 8, (W + 7) // 8
+    QL, QC = quant_tables(quality)
+    ycc = rgb_to_ycc(q[:, np.minimum(np.arange(16 * nmx), W - 1)])  # columns replicated out to whole MCUs
+    out = np.empty((nmy, nmx, 6, 64), dtype=np.int16)
+    # luma: rows replicated; the blocks past nby / nbx are computed here and replaced below
+    Y = _quantised_blocks(ycc[np.minimum(np.arange(16 * nmy), H - 1), :, 0] - 128, QL)
+    out[:, :, :4] = Y.reshape(nmy, 2, nmx, 2, 64).transpose(0, 2, 1, 3, 4).reshape(nmy, nmx, 4, 64)
+    if nbx & 1:  # the dummy column: no AC, the quantised DC of the left neighbour
+        out[:, -1, 1:4:2, 1:] = 0
+        out[:, -1, 1:4:2, 0] = out[:, -1, 0:4:2, 0]
+    if nby & 1:  # the dummy row: no AC, both blocks the quantised DC of Y01, the block before them in the MCU
+        out[-1, :, 2:4, 1:] = 0
+        out[-1, :, 2:4, 0] = out[-1, :, 1:2, 0]
+    # chroma: the 2 x 2 mean with the alternating bias over the real rows, then the last DOWNSAMPLED row replicated
+    hc = (H + 1) // 2
+    r0, r1 = np.minimum(2 * np.arange(hc), H - 1), np.minimum(2 * np.arange(hc) + 1, H - 1)
+    bias = 1 + (np.arange(8 * nmx) & 1)
+    for c in (1, 2):
+        p = ycc[..., c]
+        down = (p[r0][:, 0::2] + p[r0][:, 1::2] + p[r1][:, 0::2] + p[r1][:, 1::2] + bias) >> 2
+        out[:, :, 3 + c] = _quantised_blocks(down[np.minimum(np.arange(8 * nmy), hc - 1)] - 128, QC)
+    return out
+
+
+def jpeg_coefficients(q_uint8_hwc, quality: int = 90, subsampling="4:4:4") -> np.ndarray:
+    """The quantised image q[H,W,3] uint8 -> coef[nby,nbx,3,64] int16, zigzag order (component order Y, Cb, Cr); at
+    ``subsampling="4:2:0"`` coef[nmy,nmx,6,64] with nmy = ceil(H / 16), nmx = ceil(W / 16), block order Y00, Y01, Y10, Y11,
+    Cb, Cr."""
+    check_subsampling(subsampling)
     q = q_uint8_hwc.cpu().numpy() if isinstance(q_uint8_hwc, torch.Tensor) else np.asarray(q_uint8_hwc)
     if q.dtype != np.uint8 or q.ndim != 3 or q.shape[2] != 3 or q.shape[0] < 1 or q.shape[1] < 1:
         raise ValueError(f"jpeg_coefficients: uint8 [H,W,3] expected, got {q.dtype} {q.shape}")
+    if subsampling == "4:2:0":
+        return _coefficients_420(q, quality)
     H, W, _ = q.shape
     nby, nbx = (H + 7) // 8, (W + 7) // 8
     pad = q[np.minimum(np.arange(nby * 8), H - 1)][:, np.minimum(np.arange(nbx * 8), W - 1)]
     ycc = rgb_to_ycc(pad) - 128
     out = np.empty((nby, nbx, 3, 64), dtype=np.int16)
     for c, Q in enumerate((quant_tables(quality)[0], quant_tables(quality)[1], quant_tables(quality)[1])):
-        co = fdct_int(ycc[..., c].reshape(nby, 8, nbx, 8).transpose(0, 2, 1, 3)).reshape(nby, nbx, 64)
-        qq = np.sign(co) * ((np.abs(co) + 4 * Q) // (8 * Q))  # the DCT carries a factor of 8: ONE rounding
-        out[:, :, c, :] = qq[..., ZIGZAG]
+        out[:, :, c, :] = _quantised_blocks(ycc[..., c], Q)
     return out
 
 
@@ -235,37 +310,42 @@ def _block_entries(zz, pred, tab):
 
 
 def encode_scan(coef, restart_mcus=None) -> bytes:
-    """coef[nby,nbx,3,64] int16 (zigzag) -> the entropy-coded data of the frame's one scan: everything between the SOS header
+    """coef[nby,nbx,3,64] int16 (zigzag), or the 4:2:0 layout [nmy,nmx,6,64] (recognised by ``coef.shape[2]``) -> the
+    entropy-coded data of the frame's one scan: everything between the SOS header
     and EOI, the RSTm markers included.  ``restart_mcus``: MCUs per restart interval, 0 for none, None for one MCU row.
     Structured as the device pass is: per block the (code, length) entries, a running sum of the lengths for the bit
     positions, the bits ORed together, then per segment the padding with ones and the byte stuffing."""
     coef = coef.cpu().numpy() if isinstance(coef, torch.Tensor) else np.asarray(coef)
-    if coef.dtype != np.int16 or coef.ndim != 4 or coef.shape[2:] != (3, 64) or coef.shape[0] < 1 or coef.shape[1] < 1:
-        raise ValueError(f"encode_scan: int16 [nby,nbx,3,64] expected, got {coef.dtype} {coef.shape}")
-    nby, nbx = coef.shape[:2]
+    if coef.dtype != np.int16 or coef.ndim != 4 or coef.shape[2:] not in ((3, 64), (6, 64)) or coef.shape[0] < 1 or coef.shape[1] < 1:
+        raise ValueError(f"encode_scan: int16 [nby,nbx,3,64] or [nmy,nmx,6,64] expected, got {coef.dtype} {coef.shape}")
+    nby, nbx, bpm = coef.shape[:3]
     n_mcu = nby * nbx
     R = _resolve_restart(restart_mcus, nbx)
     seg_mcus = R if R > 0 else n_mcu
-    zz = coef.reshape(n_mcu * 3, 64).astype(np.int64)
+    zz = coef.reshape(n_mcu * bpm, 64).astype(np.int64)
     zz[:, 0] = np.clip(zz[:, 0], DC_MIN, DC_MAX)
     zz[:, 1:] = np.clip(zz[:, 1:], -AC_MAX, AC_MAX)
-    blk = np.arange(n_mcu * 3)
-    first = (blk // 3) % seg_mcus == 0  # the first MCU of a segment predicts from 0
-    pred = np.where(first, 0, np.concatenate([np.zeros(3, dtype=np.int64), zz[:-3, 0]]))
-    tab = (blk % 3 != 0).astype(np.int64)
+    blk = np.arange(n_mcu * bpm)
+    pos = blk % bpm
+    # the previous block of the component: 3 back at 4:4:4; at 4:2:0 Y00 follows the Y11 of the MCU before (3 back), Y01 ..
+    # Y11 the block before, Cb and Cr the MCU before (6 back)
+    back = np.array([3, 3, 3] if bpm == 3 else [3, 1, 1, 1, 6, 6])[pos]
+    first = ((blk // bpm) % seg_mcus == 0) & (back >= 3)  # the first block of a component in a segment predicts from 0
+    pred = np.where(first, 0, zz[np.maximum(blk - back, 0), 0])
+    tab = (pos != 0).astype(np.int64) if bpm == 3 else (pos >= 4).astype(np.int64)
     out = bytearray()
     slab = max(1, 8192 // seg_mcus) * seg_mcus  # whole segments, a few thousand MCUs at a time
     for m0 in range(0, n_mcu, slab):
         m1 = min(n_mcu, m0 + slab)
-        val, length = _block_entries(zz[3 * m0:3 * m1], pred[3 * m0:3 * m1], tab[3 * m0:3 * m1])
+        val, length = _block_entries(zz[bpm * m0:bpm * m1], pred[bpm * m0:bpm * m1], tab[bpm * m0:bpm * m1])
         block_bits = length.sum(axis=1)
-        seg_first = np.arange(0, 3 * (m1 - m0), 3 * seg_mcus)
+        seg_first = np.arange(0, bpm * (m1 - m0), bpm * seg_mcus)
         seg_bits = np.add.reduceat(block_bits, seg_first)
         pad = (-seg_bits) % 8
         seg_bytes = (seg_bits + pad) // 8
         # one more entry behind each segment: the padding ones
-        n_blk = 3 * (m1 - m0)
-        seg_of = np.arange(n_blk) // (3 * seg_mcus)
+        n_blk = bpm * (m1 - m0)
+        seg_of = np.arange(n_blk) // (bpm * seg_mcus)
         is_last = np.concatenate([seg_of[1:] != seg_of[:-1], [True]])
         val = np.concatenate([val, np.where(is_last, (1 << pad[seg_of]) - 1, 0).astype(np.uint64)[:, None]], axis=1).reshape(-1)
         length = np.concatenate([length, np.where(is_last, pad[seg_of], 0)[:, None]], axis=1).reshape(-1)
@@ -286,16 +366,18 @@ def encode_scan(coef, restart_mcus=None) -> bytes:
     return bytes(out)
 
 
-def jpeg_frame(scan_bytes, H: int, W: int, quality: int = 90, restart_mcus=None) -> bytes:
-    """The JPEG file round one frame's scan data: SOI, JFIF APP0, two DQT, SOF0 (8 bit, three components, 1x1 sampling), the
-    four DHT, DRI when ``restart_mcus`` (None: one MCU row) is not 0, SOS, the data, EOI."""
+def jpeg_frame(scan_bytes, H: int, W: int, quality: int = 90, restart_mcus=None, subsampling="4:4:4") -> bytes:
+    """The JPEG file round one frame's scan data: SOI, JFIF APP0, two DQT, SOF0 (8 bit, three components, 1x1 sampling, or
+    2x2 for Y at ``subsampling="4:2:0"``), the four DHT, DRI when ``restart_mcus`` (in MCUs of the sampling; None: one MCU
+    row) is not 0, SOS, the data, EOI."""
     if not (1 <= H <= 65535 and 1 <= W <= 65535):
         raise ValueError(f"jpeg_frame: H {H}, W {W} (1 .. 65535)")
-    R = _resolve_restart(restart_mcus, (W + 7) // 8)
+    R = _resolve_restart(restart_mcus, mcu_grid(H, W, subsampling)[1])
+    luma_sampling = 0x11 if subsampling == "4:4:4" else 0x22
     hd = bytearray(b"\xff\xd8\xff\xe0" + struct.pack(">H", 16) + b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0")
     for t, Q in enumerate(quant_tables(quality)):
         hd += b"\xff\xdb" + struct.pack(">HB", 67, t) + bytes(int(v) for v in Q[ZIGZAG])
-    hd += b"\xff\xc0" + struct.pack(">HBHHB", 17, 8, H, W, 3) + bytes([1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1])
+    hd += b"\xff\xc0" + struct.pack(">HBHHB", 17, 8, H, W, 3) + bytes([1, luma_sampling, 0, 2, 0x11, 1, 3, 0x11, 1])
     for tc in (0x00, 0x10, 0x01, 0x11):
         bits, vals = HUFFMAN[tc]
         hd += b"\xff\xc4" + struct.pack(">HB", 19 + len(vals), tc) + bytes(bits) + bytes(vals)
@@ -305,15 +387,17 @@ def jpeg_frame(scan_bytes, H: int, W: int, quality: int = 90, restart_mcus=None)
     return bytes(hd) + bytes(scan_bytes) + b"\xff\xd9"
 
 
-def encode_jpeg(img, quality: int = 90, restart_mcus=None) -> bytes:
-    """One image -> a JPEG file on the host.  ``img``: float [3,H,W] (quantised as ``*_combined.png`` is) or uint8 [H,W,3]."""
+def encode_jpeg(img, quality: int = 90, restart_mcus=None, subsampling="4:4:4") -> bytes:
+    """One image -> a JPEG file on the host.  ``img``: float [3,H,W] (quantised as ``*_combined.png`` is) or uint8 [H,W,3].
+    ``subsampling``: "4:4:4", or "4:2:0" for chroma at half resolution in both directions (16 x 16 MCUs)."""
+    check_subsampling(subsampling)
     if isinstance(img, torch.Tensor) and img.dtype != torch.uint8:
         if img.ndim != 3 or img.shape[0] != 3:
             raise ValueError(f"encode_jpeg: float [3,H,W] or uint8 [H,W,3] expected, got {tuple(img.shape)}")
         img = png.quantize_save_image(img.detach().cpu()).permute(1, 2, 0).contiguous()
     q = img.cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
     H, W = int(q.shape[0]), int(q.shape[1])
-    return jpeg_frame(encode_scan(jpeg_coefficients(q, quality), restart_mcus), H, W, quality, restart_mcus)
+    return jpeg_frame(encode_scan(jpeg_coefficients(q, quality, subsampling), restart_mcus), H, W, quality, restart_mcus, subsampling)
 
 
 # ---- the container -----------------------------------------------------------------------------------------------------------
@@ -462,10 +546,12 @@ def assemble(vis_dir, world: int) -> list:
 # ---- the writer ----------------------------------------------------------------------------------------------------------------
 class DeviceScan:
     """One frame's scan data on the GPU, as ``ops.jpeg_encode`` leaves it: ``data`` uint8 [capacity] and ``nbytes`` int32 [1]
-    device tensors (views of a batch's), the frame's H and W, and ``ready``, an event recorded behind the kernels."""
+    device tensors (views of a batch's), the frame's H and W, ``ready``, an event recorded behind the kernels, and the
+    ``subsampling`` the scan was made with, which the frame's header has to name."""
 
-    def __init__(self, data, nbytes, H, W, ready=None):
+    def __init__(self, data, nbytes, H, W, ready=None, subsampling="4:4:4"):
         self.data, self.nbytes, self.H, self.W, self.ready = data, nbytes, int(H), int(W), ready
+        self.subsampling = check_subsampling(subsampling)
 
 
 class MjpegWriter:
@@ -479,9 +565,12 @@ class MjpegWriter:
     -- ``<directory>/<scene_id>_combined.avi`` with the frames sorted by ``tgt_idx``, or for ``world > 1`` this rank's
     hidden part file for ``assemble`` -- and re-raises the first worker error.  The frames of a scene must share H and W
     (``ValueError`` at ``submit``).  ``restart_mcus``: None = one MCU row; the GPU path needs >= 1.  A GPU frame's buffer
-    has its worst-case capacity (``ops.jpeg_scan_capacity``: 40 MB at 1080p) and lives until a worker has fetched its bytes."""
+    has its worst-case capacity (``ops.jpeg_scan_capacity``: 40 MB at 1080p) and lives until a worker has fetched its bytes.
+    ``subsampling``: "4:4:4", or "4:2:0" (upstream's chroma format) for every frame of the writer; a ``DeviceScan`` made
+    with another one is refused at ``submit``."""
 
-    def __init__(self, fps: int = 10, quality: int = 90, restart_mcus=None, n_threads: int = 4, rank: int = 0, world: int = 1):
+    def __init__(self, fps: int = 10, quality: int = 90, restart_mcus=None, n_threads: int = 4, rank: int = 0, world: int = 1,
+                 subsampling="4:4:4"):
         if not 1 <= int(n_threads) <= png.MAX_THREADS:
             raise ValueError(f"MjpegWriter: n_threads {n_threads} (1 .. {png.MAX_THREADS})")
         if int(fps) < 1 or world < 1 or not 0 <= rank < world:
@@ -490,6 +579,7 @@ class MjpegWriter:
         if restart_mcus is not None:
             _resolve_restart(restart_mcus, 1)
         self.fps, self.quality, self.restart_mcus = int(fps), int(quality), restart_mcus
+        self.subsampling = check_subsampling(subsampling)
         self.rank, self.world = int(rank), int(world)
         self._pool = ThreadPoolExecutor(max_workers=int(n_threads), thread_name_prefix="mjpeg")
         self._lock = threading.Lock()
@@ -526,7 +616,7 @@ class MjpegWriter:
                     self._error = e
 
     def _work_host(self, key, tgt_idx, img):
-        self._keep(key, tgt_idx, encode_jpeg(img, self.quality, self.restart_mcus))
+        self._keep(key, tgt_idx, encode_jpeg(img, self.quality, self.restart_mcus, self.subsampling))
 
     def _work_device(self, key, tgt_idx, scan, cs):
         if scan.ready is not None:
@@ -546,7 +636,7 @@ class MjpegWriter:
             host = buf[:n]
             host.copy_(scan.data[:n], non_blocking=True)
             cs.synchronize()
-        self._keep(key, tgt_idx, jpeg_frame(host.numpy().tobytes(), scan.H, scan.W, self.quality, self.restart_mcus))
+        self._keep(key, tgt_idx, jpeg_frame(host.numpy().tobytes(), scan.H, scan.W, self.quality, self.restart_mcus, scan.subsampling))
 
     def submit(self, scene_key, tgt_idx, frame) -> None:
         if self._closed:
@@ -557,9 +647,12 @@ class MjpegWriter:
 
             if frame.ndim != 3:
                 raise ValueError(f"MjpegWriter.submit: [3,H,W] expected, got {tuple(frame.shape)}")
-            data, nbytes = ops.jpeg_encode(frame, quality=self.quality, restart_mcus=self.restart_mcus)
-            frame = DeviceScan(data[0], nbytes[0:1], frame.shape[1], frame.shape[2], torch.cuda.current_stream(frame.device).record_event())
+            data, nbytes = ops.jpeg_encode(frame, quality=self.quality, restart_mcus=self.restart_mcus, subsampling=self.subsampling)
+            frame = DeviceScan(data[0], nbytes[0:1], frame.shape[1], frame.shape[2], torch.cuda.current_stream(frame.device).record_event(),
+                               self.subsampling)
         if isinstance(frame, DeviceScan):
+            if frame.subsampling != self.subsampling:
+                raise ValueError(f"MjpegWriter.submit: a {frame.subsampling} scan for a {self.subsampling} writer")
             H, W = frame.H, frame.W
         elif isinstance(frame, torch.Tensor) and frame.ndim == 3 and frame.shape[0] == 3:
             H, W = int(frame.shape[1]), int(frame.shape[2])
