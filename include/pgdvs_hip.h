@@ -975,6 +975,27 @@ int pgdvs_cotracker_pyramid(const float *fmaps, int S, int C, int H, int W, void
                             pgdvs_stream_t stream);
 int pgdvs_cotracker_corr_lookup(const void *pyramid, int S, int H, int W, const float *feats, const float *coords, int N, float *out,
                                 int64_t row_stride, int64_t col_offset, pgdvs_stream_t stream);
+/* The resident loaders' item builder (csrc/item_gather.hip; pgdvs_amd/datasets/resident.py).  A scene's source frames stay on
+ * the device as stored: rgb uint8 [H,W,3] (the pixels before / 255), dyn_mask uint8 [H,W], depth float32 [H,W], frame f of
+ * each table at base + f * slot BYTES; bases and slots are multiples of 16.  depth may be NULL when no group asks for it.
+ * pgdvs_item_views builds every source-view entry of one item in one launch: ids[n_views] (HOST, 0 <= id < F, repeats in
+ * any order allowed) are the frames of the item's groups one after the other, group g of group_sizes[g] (HOST) views;
+ * out[5 g + 0..4] (HOST array of device pointers) are group g's rgb [n,H,W,3], dyn_mask [n,H,W,1], dyn_rgb [n,H,W,3],
+ * static_rgb [n,H,W,3] and depth [n,H,W,1] or NULL (a group without depth), float32, 4-byte aligned.  Ids and bases travel
+ * as kernel arguments.  For view v of frame f: rgb = float(byte) / 255.0f (an IEEE division), dyn_mask = float(mask byte),
+ * dyn_rgb = rgb * dyn_mask, static_rgb = rgb * (1 - dyn_mask), depth copied: the bits of the loaders' numpy statements.
+ * Four pixels per lane with 16-byte stores where a view's output bases are 16-byte aligned (always when H W % 4 == 0 and
+ * the tensors' bases are), one pixel per lane otherwise and for the last H W % 4 pixels.  Nothing outside the outputs is
+ * written.  Shapes: F, H, W >= 1, H, W < 2^20, H W < 2^31, 1 <= n_views <= PGDVS_ITEM_MAX_VIEWS, 1 <= n_groups <=
+ * PGDVS_ITEM_MAX_GROUPS, every group_sizes[g] >= 1 and their sum n_views, else PGDVS_ERR_INVALID and nothing is launched.
+ * pgdvs_flow_occ is the flow files' occlusion mask (pgdvs/datasets/nvidia_eval.py:1005-1009): coord_diff[H,W,2] float32, 8-byte
+ * aligned -> occ[H,W] float32 = |cd.x| + |cd.y| > thres ? 1 : 0, the sum in float32, the compare strict; NaN gives 0. */
+#define PGDVS_ITEM_MAX_VIEWS 64
+#define PGDVS_ITEM_MAX_GROUPS 4
+int pgdvs_item_views(const uint8_t *rgb, const uint8_t *dyn_mask, const float *depth, int F, int H, int W, int64_t rgb_slot,
+                     int64_t mask_slot, int64_t depth_slot, const int32_t *ids, int n_views, const int32_t *group_sizes, int n_groups,
+                     float *const *out, pgdvs_stream_t stream);
+int pgdvs_flow_occ(const float *coord_diff, int H, int W, float thres, float *occ, pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,8 @@ small circular "bullet-time" offset whose radius follows the scene's near depth
 
 Host-side numpy / PIL input plumbing, like ``datasets/nvidia_eval.py``; resizes that upstream
 does with OpenCV (only taken when files differ in size) use PIL filters.  ``depth_range`` comes from
-``nvidia_eval.spatial_depth_range``: numpy with ``device=None``, the HIP op on a GPU ``device``.
+``nvidia_eval.spatial_depth_range``: numpy with ``device=None``, the HIP op on a GPU ``device``.  ``resident=True``: the
+source frames are decoded once and the items built from a ``datasets.resident.SceneStore``.
 """
 import pathlib
 from math import acos, sin
@@ -26,6 +27,7 @@ from torch.utils.data import Dataset
 
 from ._common import F32, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views, tracker_entries
 from .nvidia_eval import spatial_depth_range
+from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
 N_BT_REPS = 8
 
@@ -115,7 +117,8 @@ class MonoVisualizationDataset(Dataset):
 
     def __init__(self, *, data_root, max_hw, mode, rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
-                 vis_bt_max_disp=32, flow_consist_thres=1.0, device=None):
+                 vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
+                 resident_max_bytes=DEFAULT_MAX_BYTES):
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
@@ -123,6 +126,8 @@ class MonoVisualizationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
+        # the source frames kept in memory (datasets/resident.py)
+        self.store = SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres) if resident else None
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
         self.c2w_dict, self.K_dict, self.valid_fs = {}, {}, []
@@ -139,22 +144,54 @@ class MonoVisualizationDataset(Dataset):
     def __len__(self):
         return len(self.valid_fs)
 
+    @staticmethod
+    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None):
+        """(image uint8, dynamic mask, depth) of an input frame at the target's size; ``raw``: the image file's pixels, where
+        the caller has opened it already"""
+        h, w = tgt_shape
+        rgb = resize(np.array(PIL.Image.open(img_f)) if raw is None else raw, h, w, PIL.Image.Resampling.BOX)
+        name = pathlib.Path(img_f).stem
+        mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w, PIL.Image.Resampling.NEAREST)
+        depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
+        return rgb, mask, depth
+
     def _source_view(self, scene_dir, img_f, c2w, K, tgt_shape):
         h, w = tgt_shape
-        rgb = resize(np.array(PIL.Image.open(img_f)), h, w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0
-        name = pathlib.Path(img_f).stem
-        mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w,
-                       PIL.Image.Resampling.NEAREST).astype(np.float32)
-        depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
+        rgb, mask, depth = self._decode_frame(scene_dir, img_f, tgt_shape)
+        rgb, mask = rgb.astype(np.float32) / 255.0, mask.astype(np.float32)
         return {"rgb": rgb, "flat_cam": flat_cam(h, w, K, c2w), "dyn_mask": mask, "depth": depth, "dyn_rgb": rgb * mask[..., None],
                 "static_rgb": rgb * (1 - mask[..., None]), "K": np.asarray(K), "c2w": np.asarray(c2w)}
 
     def _stack_views(self, scene_dir, img_fs, frame_ids, all_c2w, all_K, tgt_shape):
         return stack_views([self._source_view(scene_dir, img_fs[f], all_c2w[f], all_K[f], tgt_shape) for f in frame_ids])
 
+    @staticmethod
+    def _flow_path(scene_dir, img_fs, a, b):
+        """the pair's flow file; None for the placeholder pair (a frame with itself)"""
+        return None if a == b else scene_dir / "flows" / f"interval_{abs(b - a)}" / f"{img_fs[a].stem}_{img_fs[b].stem}.npz"
+
     def _read_flow(self, scene_dir, img_fs, a, b, tgt_shape):
-        f = scene_dir / "flows" / f"interval_{abs(b - a)}" / f"{img_fs[a].stem}_{img_fs[b].stem}.npz"
-        return read_flow_pair_or_zeros(f if a != b else None, tgt_shape, self.flow_consist_thres)
+        return read_flow_pair_or_zeros(self._flow_path(scene_dir, img_fs, a, b), tgt_shape, self.flow_consist_thres)
+
+    def _tgt_shape(self, scene_id, scene_dir, img_fs):
+        """(h, w) of frame 0, the items' size.  With the store the opened frame goes into its slot, so its files are read once."""
+        if self.store is None:
+            return np.array(PIL.Image.open(img_fs[0])).shape[:2]
+        scene = self.store.scenes.get(scene_id)
+        if scene is None:
+            raw = np.array(PIL.Image.open(img_fs[0]))
+            scene = self.store.scene(scene_id, len(img_fs), raw.shape[:2])
+            self.store.put(scene, 0, *self._decode_frame(scene_dir, img_fs[0], raw.shape[:2], raw=raw))
+        return scene.h, scene.w
+
+    def _resident_item(self, scene_id, scene_dir, img_fs, shape, all_c2w, all_K, **kw):
+        """``resident.build_item`` over this loader's readers and cameras"""
+        def cams(ids):
+            return np.stack([flat_cam(*shape, all_K[f], all_c2w[f]) for f in ids]), all_K[list(ids)], all_c2w[list(ids)]
+
+        scene = self.store.scene(scene_id, len(img_fs), shape)
+        return build_item(self.store, scene, lambda f: self._decode_frame(scene_dir, img_fs[f], shape), cams=cams,
+                          flow_path=lambda a, b: self._flow_path(scene_dir, img_fs, a, b), owner=type(self).__name__, **kw)
 
     def __getitem__(self, index):
         scene_id, scene_dir, tgt_time, tgt_idx, tgt_c2w, _ = self.valid_fs[index]
@@ -166,8 +203,15 @@ class MonoVisualizationDataset(Dataset):
         sel = select_frames_for_time(tgt_time, n, self.n_src_views_temporal_track_one_side)
         d = np.linalg.norm(tgt_c2w[None, :3, 3] - all_c2w[:, :3, 3], axis=1)
         spatial_ids = sorted(np.argsort(d)[: self.n_src_views_spatial].tolist())
-        tgt_h, tgt_w = np.array(PIL.Image.open(img_fs[0])).shape[:2]
+        tgt_h, tgt_w = self._tgt_shape(scene_id, scene_dir, img_fs)
         shape = (tgt_h, tgt_w)
+        if self.store is not None:
+            return self._resident_item(
+                scene_id, scene_dir, img_fs, shape, all_c2w, all_K, sel=sel, spatial_ids=spatial_ids, spatial_depth=False,
+                c2w_tgt=tgt_c2w, trackers=True,
+                fixed={"scene_id": scene_id, "misc": {"scene_id": scene_id, "tgt_time": tgt_time, "tgt_idx": tgt_idx}},
+                host={"seq_ids": torch.LongTensor(np.array([tgt_time, *spatial_ids, *sel["temporal"]])),
+                      "flat_cam_tgt": F32(flat_cam(tgt_h, tgt_w, all_K[0], tgt_c2w)), "time_tgt": torch.FloatTensor([tgt_time])})
         stack = lambda ids: self._stack_views(scene_dir, img_fs, ids, all_c2w, all_K, shape)  # noqa: E731
         spatial = stack(spatial_ids)
         item = {

@@ -33,6 +33,11 @@ The pure-geometry variant builds the static cloud once per scene with the HIP ag
 The per-item ``depth_range`` (:446-456) is computed in numpy with ``device=None``; with a GPU ``device`` by the HIP op
 ``ops.nvidia_depth_range``, bit-identical (DESIGN.md, row 8f-3 NVIDIA), and then no host point cloud is formed.  The
 point clouds upstream computes for the temporal and tracker views and then discards are skipped on both paths.
+
+``resident=True`` (with ``resident_scenes``, ``resident_max_bytes``; disparity depths only): every source frame is decoded
+once and kept in a ``datasets.resident.SceneStore`` on ``device`` (None: host memory), and the items' source views are built
+from it, on a GPU by ``ops.item_views`` in one launch; the same keys, shapes, dtypes and bits, every tensor on the store's
+device.  The target image and the evaluation mask, one item's each, stay disk reads.  DESIGN.md 7f.
 """
 import io
 import os
@@ -48,6 +53,7 @@ from torch.utils.data import Dataset
 from ._common import (F32, TGT_HEIGHT, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
                       read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
 from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
+from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 from .static_aggregation import hwf_to_K
 
 ALL_SCENE_IDS_NVIDIA_DYN = ["Balloon1", "Balloon2", "Jumping", "Playground", "Skating", "Truck", "Umbrella", "dynamicFace"]
@@ -212,11 +218,14 @@ class NvidiaDynEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
-                 flow_consist_thres=1.0, device=None):
+                 flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES):
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
         assert rgb_range == "0_1", rgb_range
+        if resident and use_zoe_depth != "none":
+            raise ValueError(f"resident=True keeps the depths of the DynIBaR disparities; use_zoe_depth={use_zoe_depth!r} has its own "
+                             "fused device path (ops.nvidia_zoe_depth): use one or the other")
         self.zoe_k_dict = make_zoe_k_dict()
         assert use_zoe_depth in ["none", "moe"] + list(self.zoe_k_dict), f"{use_zoe_depth}, {self.zoe_k_dict.keys()}"
         self.use_zoe_depth = use_zoe_depth
@@ -231,6 +240,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
@@ -259,6 +269,29 @@ class NvidiaDynEvaluationDataset(Dataset):
 
     def __len__(self):
         return len(self.valid_fs)
+
+    # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
+    store = None  # the SceneStore of ``resident=True``
+
+    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device):
+        if resident:
+            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres)
+
+    def _decode_frame(self, scene_id, frame_id, tgt_shape):
+        """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them"""
+        h, w = tgt_shape
+        depth = _resize(self._read_depth(scene_id, frame_id), h, w, PIL.Image.Resampling.NEAREST)
+        return self._read_src_rgb(self._src_img_f(scene_id, frame_id), h, w), self._read_mask(scene_id, frame_id, h, w), depth
+
+    def _resident_item(self, scene_id, tgt_shape, all_c2w, all_hwf, **kw):
+        """``resident.build_item`` over this loader's readers and cameras"""
+        def cams(ids):
+            Kc = [self._view_cam(all_c2w[f], all_hwf[f], tgt_shape) for f in ids]
+            return (np.stack([flat_cam(*tgt_shape, K, c) for K, c in Kc]), np.stack([K for K, _ in Kc]), np.stack([c for _, c in Kc]))
+
+        scene = self.store.scene(scene_id, all_c2w.shape[0], tgt_shape)
+        return build_item(self.store, scene, lambda f: self._decode_frame(scene_id, f, tgt_shape), cams=cams,
+                          flow_path=lambda a, b: self._flow_path(scene_id, a, b), owner=type(self).__name__, **kw)
 
     # ------------------------------------------------------------------ ZoeDepth
     use_zoe_depth, zoe_depth_data_path = "none", None  # (subclasses that build themselves never read ZoeDepth)
@@ -316,9 +349,14 @@ class NvidiaDynEvaluationDataset(Dataset):
         return 1 / (np.load(self.depth_data_dir / scene_id / "disp" / f"{frame_id:05d}.npy") + 1e-8)
 
     def _read_flow(self, scene_id, src_frame_id, tgt_frame_id, tgt_shape):
+        return read_flow_pair_or_zeros(self._flow_path(scene_id, src_frame_id, tgt_frame_id), tgt_shape, self.flow_consist_thres)
+
+    def _flow_path(self, scene_id, src_frame_id, tgt_frame_id):
+        """the pair's flow file; None for the placeholder pair (a frame with itself)"""
         k = abs(tgt_frame_id - src_frame_id)
-        f = self.flow_data_dir / scene_id / "dense" / "flows" / f"interval_{k}" / f"{src_frame_id:05d}_{tgt_frame_id:05d}.npz"
-        return read_flow_pair_or_zeros(f if k else None, tgt_shape, self.flow_consist_thres)
+        if k == 0:
+            return None
+        return self.flow_data_dir / scene_id / "dense" / "flows" / f"interval_{k}" / f"{src_frame_id:05d}_{tgt_frame_id:05d}.npz"
 
     def _read_eval_mask(self, scene_id, frame_id, cam_id, h, w):
         f = self.raw_data_dir / scene_id / "dense" / "mv_masks" / f"{frame_id:05d}" / f"cam{cam_id + 1:02d}.png"
@@ -348,6 +386,16 @@ class NvidiaDynEvaluationDataset(Dataset):
         """Frame i of the monocular video is camera i % 12 of time step i (:647-653)."""
         return self.scene_img_dict[scene_id][frame_id][frame_id % N_CAMS]
 
+    @staticmethod
+    def _read_src_rgb(img_f, h, w):
+        return _resize(np.array(PIL.Image.open(img_f)), h, w, PIL.Image.Resampling.BOX)
+
+    def _view_cam(self, c2w, hwf, tgt_shape):
+        """(K [4,4], c2w [4,4]) of a view at the target's size"""
+        K = np.eye(4)
+        K[:3, :3] = hwf_to_K(*hwf, tgt_shape=tgt_shape)
+        return K, self._aug_c2w(np.asarray(c2w))
+
     def _source_view(self, scene_id, frame_id, c2w, hwf, tgt_shape, with_geometry=True, img_f=None, depth=None):
         """image, flat camera and (optionally) dynamic mask / depth / camera matrices of an input
         frame (:728-838); spatial_depth_range makes the world points from depth, K and c2w.
@@ -355,10 +403,8 @@ class NvidiaDynEvaluationDataset(Dataset):
         h, w = tgt_shape
         if img_f is None:
             img_f = self._src_img_f(scene_id, frame_id)
-        rgb = _resize(np.array(PIL.Image.open(img_f)), h, w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0
-        K = np.eye(4)
-        K[:3, :3] = hwf_to_K(*hwf, tgt_shape=tgt_shape)
-        c2w = self._aug_c2w(np.asarray(c2w))
+        rgb = self._read_src_rgb(img_f, h, w).astype(np.float32) / 255.0
+        K, c2w = self._view_cam(c2w, hwf, tgt_shape)
         out = {"rgb": rgb, "flat_cam": flat_cam(h, w, K, c2w)}
         if with_geometry:
             mask = self._read_mask(scene_id, frame_id, h, w).astype(np.float32)
@@ -391,7 +437,8 @@ class NvidiaDynEvaluationDataset(Dataset):
         return out
 
     # ------------------------------------------------------------------ item
-    def _common_item(self, index):
+    def _item_head(self, index):
+        """the target's entries and the item's selection: everything in front of the source views"""
         scene_id, scene_dir, tgt_frame_id, tgt_cam_id, img_f = self.valid_fs[index]
         all_hwf, all_c2w = self._read_cam(scene_id)
         n_frames = all_hwf.shape[0]
@@ -403,7 +450,6 @@ class NvidiaDynEvaluationDataset(Dataset):
         # NOTE upstream indexes the poses with the CAMERA id: the 12 camera poses repeat (:319-323)
         tgt = self._source_view(scene_id, tgt_frame_id, all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape,
                                 with_geometry=False, img_f=img_f)
-        temporal = self._stack_views(scene_id, sel["temporal"], all_c2w, all_hwf, tgt_shape)
         item = {
             "scene_id": scene_id,
             "rgb_tgt": F32(tgt["rgb"]),
@@ -412,14 +458,39 @@ class NvidiaDynEvaluationDataset(Dataset):
             "time_tgt": torch.FloatTensor([tgt_frame_id]),
             "misc": {"scene_id": scene_id, "tgt_frame_id": tgt_frame_id, "tgt_cam_id": tgt_cam_id},
         }
-        item.update(group_entries("temporal", temporal, sel["temporal"], sel["n_actual_temporal"]))
-        item.update(flow_entries(self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape),
-                                 self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)))
         ctx = dict(scene_id=scene_id, tgt_frame_id=tgt_frame_id, tgt_cam_id=tgt_cam_id, all_hwf=all_hwf, all_c2w=all_c2w,
                    n_frames=n_frames, sel=sel, tgt_shape=tgt_shape)
         return item, ctx
 
+    def _common_item(self, index):
+        item, c = self._item_head(index)
+        sel, scene_id, tgt_shape = c["sel"], c["scene_id"], c["tgt_shape"]
+        temporal = self._stack_views(scene_id, sel["temporal"], c["all_c2w"], c["all_hwf"], tgt_shape)
+        item.update(group_entries("temporal", temporal, sel["temporal"], sel["n_actual_temporal"]))
+        item.update(flow_entries(self._read_flow(scene_id, sel["temporal"][0], sel["temporal"][1], tgt_shape),
+                                 self._read_flow(scene_id, sel["temporal"][1], sel["temporal"][0], tgt_shape)))
+        return item, c
+
+    def _resident_eval_item(self, index, with_spatial):
+        """the evaluation loaders' item from the store; the target image and the evaluation mask, one item's each, stay disk
+        reads and travel with the small entries"""
+        head, c = self._item_head(index)
+        spatial_ids = None
+        seq = [c["tgt_frame_id"], *c["sel"]["temporal"]]
+        if with_spatial:
+            spatial_ids = select_spatial_frames(c["tgt_frame_id"], c["tgt_cam_id"], c["n_frames"], c["all_c2w"], self.n_src_views_spatial)
+            assert self.n_src_views_spatial < N_CAMS * 2
+            seq = [c["tgt_frame_id"], *spatial_ids, *c["sel"]["temporal"]]
+        host = {k: v for k, v in head.items() if isinstance(v, torch.Tensor)}
+        host["seq_ids"] = torch.LongTensor(np.array(seq))
+        return self._resident_item(c["scene_id"], c["tgt_shape"], c["all_c2w"], c["all_hwf"],
+                                   fixed={k: v for k, v in head.items() if k not in host}, host=host, sel=c["sel"],
+                                   spatial_ids=spatial_ids, spatial_depth=True, c2w_tgt=c["all_c2w"][c["tgt_cam_id"]],
+                                   trackers=with_spatial)
+
     def __getitem__(self, index):
+        if self.store is not None:
+            return self._resident_eval_item(index, with_spatial=True)
         item, c = self._common_item(index)
         sel, scene_id = c["sel"], c["scene_id"]
         spatial_ids = select_spatial_frames(c["tgt_frame_id"], c["tgt_cam_id"], c["n_frames"], c["all_c2w"], self.n_src_views_spatial)
@@ -444,12 +515,14 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
     dataset_fname = "nvidia_eval_pure_geo"
 
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
-                 rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda"):
+                 rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
+                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES):
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
                          mask_data_dir=mask_data_dir, flow_data_dir=flow_data_dir, max_hw=max_hw, mode=mode,
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,
                          n_src_views_temporal_track_one_side=0, flow_consist_thres=flow_consist_thres)
         self.device = device
+        self._init_resident(resident, resident_scenes, resident_max_bytes, device)  # the store lives where the cloud is built
         self.st_pcl_dict = {scene: self._aggregate_static_pcl(scene) for scene in sorted(self.scene_img_dict)}
 
     def _load_mono_video(self, scene_id):
@@ -477,6 +550,16 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
         return cloud.cpu()
 
     def __getitem__(self, index):
+        if self.store is not None:
+            item = self._resident_eval_item(index, with_spatial=False)
+            if self.store.device is not None:  # the scene's cloud, moved once: the item's tensors are all on the store's device
+                on_dev = self.__dict__.setdefault("_st_pcl_on_device", {})
+                if item["scene_id"] not in on_dev:
+                    on_dev[item["scene_id"]] = self.st_pcl_dict[item["scene_id"]].to(self.store.device)
+                item["st_pcl_rgb"] = on_dev[item["scene_id"]]
+            else:
+                item["st_pcl_rgb"] = self.st_pcl_dict[item["scene_id"]]
+            return item
         item, c = self._common_item(index)
         item["seq_ids"] = torch.LongTensor(np.array([c["tgt_frame_id"], *c["sel"]["temporal"]]))
         item["st_pcl_rgb"] = self.st_pcl_dict[c["scene_id"]]  # [#pt, 6]: xyz, rgb

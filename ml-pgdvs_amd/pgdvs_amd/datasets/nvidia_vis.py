@@ -11,7 +11,8 @@ is +-12 frames around the two temporal frames (not the target), ordered by camer
 source images are ``mv_images/<frame>/cam<frame % 12 + 1>.jpg``; the target camera goes through
 ``_compute_cam_info`` / ``augment_cam("none")``, i.e. ``inv(inv(c2w))`` in float64.  ``depth_range`` comes from
 ``nvidia_eval.spatial_depth_range``: numpy with ``device=None``, the HIP op on a GPU ``device``.  ZoeDepth inputs are not
-mirrored (upstream's own branch reads an attribute it never sets).
+mirrored (upstream's own branch reads an attribute it never sets).  ``resident=True``: the source frames are decoded once
+and the items built from a ``datasets.resident.SceneStore`` (see ``nvidia_eval``).
 """
 import numpy as np
 import torch
@@ -20,6 +21,7 @@ from ._common import F32, flat_cam, flow_entries, group_entries, mono_size, trac
 from .mono_vis import render_path, select_frames_for_time
 from .nvidia_eval import (ALL_SCENE_IDS_NVIDIA_DYN, N_CAMS, TGT_HEIGHT, NvidiaDynEvaluationDataset, read_llff_cams,
                           spatial_depth_range)
+from .resident import DEFAULT_MAX_BYTES
 from .static_aggregation import hwf_to_K
 
 
@@ -31,7 +33,7 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_f=None,
                  flow_consist_thres=1.0, vis_center_time=50, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32,
-                 device=None):
+                 device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES):
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["vis"], mode
@@ -44,6 +46,7 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         self.c2w_dict, self.hwf_dict, self.valid_fs = {}, {}, []
@@ -80,6 +83,12 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         aug_c2w = self._aug_c2w(tgt_c2w)
         aug_K = np.eye(4)
         aug_K[:3, :3] = hwf_to_K(*all_hwf[0], tgt_shape=tgt_shape)
+        if self.store is not None:
+            return self._resident_item(
+                scene_id, tgt_shape, all_c2w, all_hwf, sel=sel, spatial_ids=spatial_ids, spatial_depth=False, c2w_tgt=aug_c2w,
+                trackers=True, fixed={"scene_id": scene_id, "misc": {"scene_id": scene_id, "tgt_time": tgt_time, "tgt_idx": tgt_idx}},
+                host={"seq_ids": torch.LongTensor(np.array([tgt_time, *spatial_ids, *sel["temporal"]])),
+                      "flat_cam_tgt": F32(flat_cam(*tgt_shape, aug_K, aug_c2w)), "time_tgt": torch.FloatTensor([tgt_time])})
         stack = lambda ids: self._stack_views(scene_id, ids, all_c2w, all_hwf, tgt_shape)  # noqa: E731
         spatial = stack(spatial_ids)
         item = {

@@ -1,0 +1,257 @@
+"""A scene's source frames kept in memory in their stored form, and the loaders' items built from them (``resident=True``).
+
+An item of the NVIDIA-family loaders stacks 20-odd source views, each decoded from an image, a mask and a depth file, and a
+scene has only as many distinct source frames as its monocular video: frame ``i`` is always the same files.  ``SceneStore``
+decodes a frame on its first use, through the loader's own readers, and keeps per scene
+
+  rgb       uint8   [F,H,W,3]  the pixels before ``/ 255``
+  dyn_mask  uint8   [F,H,W]    the mask file's values (0 / 1 for the 1-bit files)
+  depth     float32 [F,H,W]    after the loader's resize, cast as ``F32`` casts it
+
+each frame in a slot padded to a multiple of 16 bytes, a host bitmap of the filled slots, and the flow pairs ``(a, b)`` read so
+far: ``flow`` float32 [H,W,2] and the occlusion mask [H,W] computed once, when the file is read.  With ``device=None`` the
+tables are host memory and an item's views are gathered with numpy, statement for statement the disk path's; with a GPU
+``device`` they live there and ``ops.item_views`` writes all of an item's views in one launch (``ops.flow_occ`` the occlusion
+mask), bit-identical.  Once its frames are in, building an item on the GPU never waits for the device.
+
+``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
+it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
+"""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from ._common import F32, read_flow_npz
+
+DEFAULT_MAX_BYTES = 4 << 30
+VIEW_KEYS = ("rgb", "dyn_rgb", "static_rgb", "dyn_mask", "depth")
+
+
+def _pad16(nbytes):
+    return -(-nbytes // 16) * 16
+
+
+def table_bytes(n_frames, h, w):
+    """bytes of one scene's three frame tables, the slots padded"""
+    n = h * w
+    return n_frames * (_pad16(n * 3) + _pad16(n) + _pad16(n * 4))
+
+
+class _Scene:
+    def __init__(self, n_frames, h, w, device):
+        n = h * w
+        self.n_frames, self.h, self.w = n_frames, h, w
+        self.filled = np.zeros(n_frames, dtype=bool)  # host bitmap of the decoded slots
+        tab = lambda slot, dtype: torch.empty((n_frames, slot), dtype=dtype, device=device)  # noqa: E731
+        self.rgb = tab(_pad16(n * 3), torch.uint8)[:, :n * 3].view(n_frames, h, w, 3)
+        self.dyn_mask = tab(_pad16(n), torch.uint8)[:, :n].view(n_frames, h, w)
+        self.depth = tab(_pad16(n * 4) // 4, torch.float32)[:, :n].view(n_frames, h, w)
+        self.nbytes = table_bytes(n_frames, h, w)
+        self.flows = OrderedDict()  # (a, b) -> (flow [H,W,2], occ [H,W]), least recently used first
+
+
+class SceneStore:
+    """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``)."""
+
+    def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0):
+        if resident_scenes < 1 or resident_max_bytes < 0:
+            raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != "cuda":
+            raise ValueError(f"SceneStore: device None (host memory) or a GPU, got {self.device}")
+        if type(occ_thres) not in (int, float):  # (np.float64 is a float subclass)
+            raise TypeError(f"flow_consist_thres must be a Python number (a NumPy scalar changes the compare's type), got {type(occ_thres)}")
+        self.resident_scenes, self.resident_max_bytes, self.occ_thres = int(resident_scenes), int(resident_max_bytes), occ_thres
+        self.scenes = OrderedDict()  # key -> _Scene, least recently used first
+        self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0}
+
+    @property
+    def nbytes(self):
+        return sum(s.nbytes + sum(self._pair_bytes(s) for _ in s.flows) for s in self.scenes.values())
+
+    @staticmethod
+    def _pair_bytes(scene):
+        return scene.h * scene.w * 12
+
+    # ------------------------------------------------------------------ scenes
+    def scene(self, key, n_frames, shape):
+        """the scene's tables, made on first use (nothing is decoded yet); the least recently used scenes leave"""
+        s = self.scenes.get(key)
+        if s is not None:
+            assert (s.n_frames, s.h, s.w) == (n_frames, *shape), (key, (s.n_frames, s.h, s.w), n_frames, shape)
+            self.scenes.move_to_end(key)
+            return s
+        need = table_bytes(n_frames, *shape)
+        if need > self.resident_max_bytes:
+            raise ValueError(f"scene {key!r}: the tables of {n_frames} frames of {shape[0]} x {shape[1]} take {need} bytes, "
+                             f"resident_max_bytes is {self.resident_max_bytes}")
+        while len(self.scenes) >= self.resident_scenes:
+            self.scenes.popitem(last=False)
+        while self.scenes and self.nbytes + need > self.resident_max_bytes:  # flow pairs go first, then the oldest scene
+            if not self._drop_flow_pair():
+                self.scenes.popitem(last=False)
+        s = self.scenes[key] = _Scene(n_frames, shape[0], shape[1], self.device)
+        return s
+
+    def _drop_flow_pair(self, keep=None):
+        """drop the least recently used flow pair of the least recently used scene that has one; False when there is none"""
+        for s in self.scenes.values():
+            for k in s.flows:
+                if (s, k) != keep:
+                    del s.flows[k]
+                    return True
+        return False
+
+    # ------------------------------------------------------------------ frames
+    def _fill(self, scene, frame_ids, decode):
+        for f in sorted(set(frame_ids)):
+            if not scene.filled[f]:
+                self.put(scene, f, *decode(f))
+
+    def put(self, scene, f, rgb, mask, depth):
+        """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into its slot"""
+        shape = (scene.h, scene.w)
+        if rgb.dtype != np.uint8 or rgb.shape != shape + (3,):
+            raise ValueError(f"frame {f}: image {rgb.dtype} {rgb.shape}, the store keeps uint8 {shape + (3,)}")
+        if mask.dtype not in (np.bool_, np.uint8) or mask.shape != shape:
+            raise ValueError(f"frame {f}: mask {mask.dtype} {mask.shape}, the store keeps bool or uint8 {shape}")
+        if depth.shape != shape:
+            raise ValueError(f"frame {f}: depth {depth.shape}, expected {shape}")
+        scene.rgb[f].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
+        scene.dyn_mask[f].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
+        scene.depth[f].copy_(F32(depth))
+        scene.filled[f] = True
+        self.stats["frames_decoded"] += 1
+
+    def views(self, scene, groups, decode):
+        """one dict per group ``(frame ids, with_depth)``: rgb, dyn_rgb, static_rgb [n,H,W,3], dyn_mask and (with_depth) depth
+        [n,H,W,1], float32 on the store's device; ``decode(frame id) -> (rgb uint8, mask, depth)`` fills missing slots"""
+        self._fill(scene, [f for ids, _ in groups for f in ids], decode)
+        self.stats["items_built"] += 1
+        if self.device is not None:
+            from .. import ops
+
+            return ops.item_views(scene.rgb, scene.dyn_mask, scene.depth, groups)
+        out = []
+        for ids, with_depth in groups:
+            idx = torch.as_tensor(list(ids), dtype=torch.int64)
+            rgb = scene.rgb[idx].numpy().astype(np.float32) / 255.0  # the disk path's statements, on the gathered stack
+            mask = scene.dyn_mask[idx].numpy().astype(np.float32)
+            o = {"rgb": F32(rgb), "dyn_rgb": F32(rgb * mask[..., None]), "static_rgb": F32(rgb * (1 - mask[..., None])),
+                 "dyn_mask": F32(mask)[..., None]}
+            if with_depth:
+                o["depth"] = scene.depth[idx][..., None]
+            out.append(o)
+        return out
+
+    # ------------------------------------------------------------------ flow pairs
+    def flow(self, scene, a, b, path):
+        """(flow [H,W,2], occlusion mask [H,W,1]) of the pair, fresh tensors on the store's device; ``path`` None is the
+        placeholder pair (a frame with itself): zeros"""
+        dev = self.device if self.device is not None else "cpu"
+        if path is None:
+            return (torch.zeros((scene.h, scene.w, 2), dtype=torch.float32, device=dev),
+                    torch.zeros((scene.h, scene.w, 1), dtype=torch.float32, device=dev))
+        pair = scene.flows.get((a, b))
+        if pair is None:
+            pair = scene.flows[a, b] = self._read_flow(scene, path)
+            while self.nbytes > self.resident_max_bytes and self._drop_flow_pair(keep=(scene, (a, b))):
+                pass
+            if self.nbytes > self.resident_max_bytes:  # no room for even this pair: it serves this item and is not kept
+                del scene.flows[a, b]
+        else:
+            scene.flows.move_to_end((a, b))
+        return pair[0].clone(), pair[1].clone()[..., None]
+
+    def _read_flow(self, scene, path):
+        self.stats["flow_files_read"] += 1
+        if self.device is None:
+            flow, occ = read_flow_npz(path, self.occ_thres)
+            assert flow.shape[:2] == (scene.h, scene.w), (flow.shape, (scene.h, scene.w))
+            return F32(flow), F32(occ)
+        from .. import ops
+
+        info = np.load(path)
+        flow, cd = info["flow"], info["coord_diff"]
+        assert flow.shape[:2] == (scene.h, scene.w), (flow.shape, (scene.h, scene.w))
+        if cd.dtype != np.float32:
+            raise ValueError(f"{path}: coord_diff is {cd.dtype}; ops.flow_occ states the float32 files' sum and compare")
+        return F32(flow).to(self.device), ops.flow_occ(torch.from_numpy(np.ascontiguousarray(cd)).to(self.device), self.occ_thres)
+
+
+# ---------------------------------------------------------------------------- items
+def pack_to_device(entries, device):
+    """the host tensors of ``entries`` on ``device`` through ONE pinned buffer and one asynchronous copy: each entry becomes a
+    view of the uploaded bytes at a 16-byte boundary (entries are disjoint; nothing else refers to the buffer)"""
+    offs, total = {}, 0
+    for k, t in entries.items():
+        offs[k] = total
+        total += _pad16(t.numel() * t.element_size())
+    host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+    for k, t in entries.items():
+        n = t.numel() * t.element_size()
+        host[offs[k]:offs[k] + n].copy_(t.contiguous().view(-1).view(torch.uint8))
+    dev = host.to(device, non_blocking=True)
+    return {k: dev[offs[k]:offs[k] + t.numel() * t.element_size()].view(t.dtype).view(t.shape) for k, t in entries.items()}
+
+
+def group_host_entries(group, flat_cams, times=None, n_actual=None):
+    """the host-made entries of one group, as ``_common.group_entries`` makes them"""
+    out = {f"flat_cam_src_{group}": F32(flat_cams)}
+    if times is not None:
+        out[f"time_src_{group}"] = torch.FloatTensor(times)
+    if n_actual is not None:
+        out[f"n_actual_{group}"] = torch.LongTensor([n_actual])
+    return out
+
+
+def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner):
+    """An item of the NVIDIA-family loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
+    non-tensor entries; ``host``: the host-made tensors (on a GPU store they travel in ONE packed copy, with the groups'
+    cameras and times); ``cams(frame ids) -> (flat_cam [V,34], K [V,4,4], c2w [V,4,4])``; ``sel``: the loader's temporal
+    selection; ``spatial_ids`` (None: no spatial group and no ``depth_range``) with ``spatial_depth`` False where the item
+    carries no spatial depth (the range is still taken over it); ``flow_path(a, b)``: the pair's file, None for the
+    placeholder pair.  ``depth_range``: ``nvidia_eval.spatial_depth_range`` on the host, ``ops.nvidia_depth_range`` on the
+    gathered depths on a GPU store, where nothing here waits for the device."""
+    from . import nvidia_eval as NE
+
+    dev = store.device
+    if dev is not None:
+        NE.refuse_gpu_in_worker(owner)
+    host, groups, rng = dict(host), [], None
+
+    def add(name, ids, with_depth, times=None, n_actual=None):
+        flat, Ks, c2ws = cams(ids)
+        host.update(group_host_entries(name, flat, times, n_actual))
+        groups.append((name, [int(i) for i in ids], with_depth))
+        return Ks, c2ws
+
+    if spatial_ids is not None:
+        rng = add("spatial", spatial_ids, spatial_depth)
+        if dev is not None:
+            host["__rays"] = F32(NE.ray_rows(*rng))
+    add("temporal", sel["temporal"], True, sel["temporal"], sel["n_actual_temporal"])
+    if trackers:
+        for side in ("fwd2tgt", "bwd2tgt"):
+            add(f"temporal_track_{side}", sel[side], True, sel[side], sel[f"n_actual_{side}"])
+    # the range needs the spatial depths even where the item carries none (the visualisation loaders)
+    views = store.views(scene, [(ids, with_depth or name == "spatial") for name, ids, with_depth in groups], decode)
+    small = pack_to_device(host, dev) if dev is not None else host
+    rays = small.pop("__rays", None)
+    item = dict(fixed)
+    item.update(small)
+    for (name, _, with_depth), v in zip(groups, views):
+        if name == "spatial":
+            depth = v["depth"][..., 0]
+            if dev is not None:
+                from .. import ops
+
+                item["depth_range"] = ops.nvidia_depth_range(depth, rays, np.linalg.inv(c2w_tgt))
+            else:
+                item["depth_range"] = NE.spatial_depth_range({"depth": depth.numpy(), "K": rng[0], "c2w": rng[1]}, c2w_tgt)
+        item.update({f"{k}_src_{name}": v[k] for k in VIEW_KEYS if k != "depth" or with_depth})
+    a, b = sel["temporal"]
+    for key, (x, y) in (("fwd", (a, b)), ("bwd", (b, a))):
+        item[f"flow_{key}"], item[f"flow_{key}_occ_mask"] = store.flow(scene, x, y, flow_path(x, y))
+    return item

@@ -819,6 +819,89 @@ def nvidia_zoe_depth(depth_pred, scale_shift, rays=None, inv_c2w_tgt=None, near_
     return out, rng
 
 
+ITEM_MAX_VIEWS, ITEM_MAX_GROUPS = 64, 4
+ITEM_VIEW_KEYS = ("rgb", "dyn_mask", "dyn_rgb", "static_rgb", "depth")
+
+
+def _store_table(t, dtype, shape, name):
+    """a table of the resident store: frames [F, *shape] of ``dtype`` on the GPU, each frame contiguous, the base and (for
+    F > 1) the frame stride multiples of 16 bytes -> (tensor, frame stride in bytes)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PgdvsHipError(f"{name}: expected a GPU tensor (no CPU fallback)")
+    if t.dtype != dtype or tuple(t.shape[1:]) != tuple(shape) or t.ndim != len(shape) + 1:
+        raise ValueError(f"item_views: {name} {t.dtype} {tuple(t.shape)}, expected {dtype} [F, {', '.join(str(s) for s in shape)}]")
+    if t.shape[0] < 1 or not t[0].is_contiguous():
+        raise ValueError(f"item_views: {name} needs at least one frame and contiguous frames, strides {t.stride()}")
+    frame = int(np.prod(shape)) * t.element_size()
+    slot = t.stride(0) * t.element_size() if t.shape[0] > 1 else -(-frame // 16) * 16
+    if t.data_ptr() % 16 or slot % 16 or slot < frame:
+        raise ValueError(f"item_views: {name} at {t.data_ptr():#x} with frames {slot} bytes apart: both must be multiples of 16 "
+                         "(pad the frame slots)")
+    return t, slot
+
+
+def item_views(rgb, dyn_mask, depth, groups, out=None):
+    """The resident loaders' item builder (``pgdvs_item_views``; include/pgdvs_hip.h).  The store's tables on the GPU: rgb
+    uint8 [F,H,W,3], dyn_mask uint8 [F,H,W], depth float32 [F,H,W], frames contiguous and a multiple of 16 bytes apart.
+    ``groups``: up to 4 pairs (frame ids, with_depth) of together up to 64 views; ids may repeat.  Returns one dict per
+    group: rgb, dyn_rgb, static_rgb float32 [n,H,W,3], dyn_mask [n,H,W,1] and, with depth, depth [n,H,W,1], filled by one
+    launch: rgb = byte / 255, dyn_mask = float(byte), dyn_rgb = rgb * dyn_mask, static_rgb = rgb * (1 - dyn_mask), the bits
+    of the loaders' numpy statements.  ``out``: such dicts of contiguous GPU tensors to fill in place.  Does not synchronise."""
+    groups = [([int(i) for i in ids], bool(with_depth)) for ids, with_depth in groups]
+    if not 1 <= len(groups) <= ITEM_MAX_GROUPS or any(not ids for ids, _ in groups):
+        raise ValueError(f"item_views: {len(groups)} groups of {[len(ids) for ids, _ in groups]} views (1 to {ITEM_MAX_GROUPS} "
+                         "groups, none empty)")
+    ids = [i for g, _ in groups for i in g]
+    if len(ids) > ITEM_MAX_VIEWS:
+        raise ValueError(f"item_views: {len(ids)} views, at most {ITEM_MAX_VIEWS}")
+    if rgb.ndim != 4:
+        raise ValueError(f"item_views: rgb [F,H,W,3] expected, got {tuple(rgb.shape)}")
+    F, H, W = (int(x) for x in rgb.shape[:3])
+    c, c_slot = _store_table(rgb, torch.uint8, (H, W, 3), "rgb")
+    m, m_slot = _store_table(dyn_mask, torch.uint8, (H, W), "dyn_mask")
+    d, d_slot = _store_table(depth, torch.float32, (H, W), "depth")
+    if not (m.shape[0] == d.shape[0] == F and m.device == d.device == c.device):
+        raise ValueError(f"item_views: tables of {F}, {m.shape[0]}, {d.shape[0]} frames on {c.device}, {m.device}, {d.device}")
+    if min(ids) < 0 or max(ids) >= F:
+        raise ValueError(f"item_views: frame ids {ids} outside the store's {F} frames")
+    shapes = {"rgb": 3, "dyn_mask": 1, "dyn_rgb": 3, "static_rgb": 3, "depth": 1}
+    if out is None:
+        out = [{k: torch.empty((len(g), H, W, shapes[k]), dtype=torch.float32, device=c.device)
+                for k in ITEM_VIEW_KEYS if k != "depth" or with_depth} for g, with_depth in groups]
+    ptrs = []
+    for (g, with_depth), o in zip(groups, out):
+        if set(o) != set(ITEM_VIEW_KEYS) - (set() if with_depth else {"depth"}):
+            raise ValueError(f"item_views: out keys {sorted(o)} for a group with{'' if with_depth else 'out'} depth")
+        for k in ITEM_VIEW_KEYS:
+            t = o.get(k)
+            if t is not None and (not t.is_cuda or t.device != c.device or t.dtype != torch.float32 or not t.is_contiguous() or
+                                  tuple(t.shape) != (len(g), H, W, shapes[k])):
+                raise ValueError(f"item_views: out[{k!r}] must be a contiguous float32 {(len(g), H, W, shapes[k])} tensor on {c.device}")
+            ptrs.append(0 if t is None else t.data_ptr())
+    if len(out) != len(groups):
+        raise ValueError(f"item_views: {len(out)} out dicts for {len(groups)} groups")
+    sizes = [len(g) for g, _ in groups]
+    check(_lib.load().pgdvs_item_views(_ptr(c), _ptr(m), _ptr(d), F, H, W, c_slot, m_slot, d_slot, (C.c_int32 * len(ids))(*ids), len(ids),
+                                       (C.c_int32 * len(sizes))(*sizes), len(sizes), (C.c_void_p * len(ptrs))(*ptrs), _stream()),
+          "pgdvs_item_views")
+    return out
+
+
+def flow_occ(coord_diff, thres):
+    """A flow file's occlusion mask (``pgdvs_flow_occ``; include/pgdvs_hip.h): coord_diff[H,W,2] float32 on the GPU and the
+    Python number ``thres`` -> float32 [H,W] = sum |coord_diff| > thres, the sum and the compare in float32 as NumPy 2
+    compares a float32 array with a Python scalar (``datasets._common.read_flow_npz``); NaN gives 0.  Does not synchronise."""
+    cd = _req(coord_diff, torch.float32, "coord_diff")
+    if cd.ndim != 3 or cd.shape[2] != 2 or cd.shape[0] < 1 or cd.shape[1] < 1:
+        raise ValueError(f"flow_occ: coord_diff [H,W,2] expected, got {tuple(cd.shape)}")
+    if type(thres) not in (int, float):  # (np.float64 is a float subclass)
+        raise TypeError(f"flow_occ: thres must be a Python number (a NumPy scalar would change the compare's type), got {type(thres)}")
+    H, W = int(cd.shape[0]), int(cd.shape[1])
+    occ = torch.empty((H, W), dtype=torch.float32, device=cd.device)
+    check(_lib.load().pgdvs_flow_occ(_ptr(cd), H, W, float(np.float32(thres)), _ptr(occ), _stream()), "pgdvs_flow_occ")
+    return occ
+
+
 def _flow_pair(a, b, names, what):
     """two float32 [H,W,2] GPU tensors of one shape, H, W >= 2 (the preprocessing ops' inputs)"""
     a, b = _req(a, torch.float32, names[0]), _req(b, torch.float32, names[1])

@@ -1,0 +1,258 @@
+#!/usr/bin/env python3
+"""The loaders with and without resident source frames, on a real ``--data_root`` (the NVIDIA tree of
+INTEGRATION.md 2b, ``--scene``) or on a synthetic NVIDIA scene this tool writes into a temporary directory: 288 x 550, 48
+frames, the monocular video's JPEG sources stored at 1080 x 2062 so that the BOX resize is taken, and the same video in the
+monocular layout for ``mono_vis``:
+  items    items/s of each loader's ``__getitem__`` with ``resident=False`` (the disk path), and with ``resident=True`` on
+           the first pass (frames are decoded on the way) and on the second (nothing is opened), the same indices each
+           time, the device drained at the end of each pass; every resident item is compared with the disk item, bit for bit
+  vis_run  views/s of ``harness.vis_run`` over nvidia_vis items both ways, through the geometric renderer with the scene's
+           static cloud resident (tools/vis_bench.py), PNGs written by an 8-thread writer
+  gather   GPU time of the ``ops.item_views`` launch alone (HIP events, median, warmed) for an item of 22 views in four
+           groups at 288 x 550, its algorithmic bytes, and its share of the 6.29 TB/s stream rate of MI355X_MICROARCH.md
+Prints one JSON object.
+Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--out FILE]"""
+import argparse
+import json
+import pathlib
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+import PIL.Image
+import torch
+
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+for p in (str(ROOT), str(ROOT / "ml-pgdvs_amd"), str(ROOT / "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+HBM_BYTES_PER_S = 6.29e12
+H, W, F, N_CAMS = 288, 550, 48, 12
+SRC_H, SRC_W = 1080, 2062
+SCENE, MONO_SCENE = "Balloon1", "synthetic_video"
+
+
+def _pose(i):
+    y = np.deg2rad(2.5 * (i % N_CAMS) - 12)
+    c2w = np.eye(4)
+    c2w[:3, :3] = [[np.cos(y), 0, np.sin(y)], [0, 1, 0], [-np.sin(y), 0, np.cos(y)]]
+    c2w[:3, 3] = [0.11 * (i % N_CAMS) + 0.003 * i, 0.02 * (i % 3), 0.01 * i]
+    return c2w
+
+
+def write_trees(root, frames=F):
+    """the synthetic NVIDIA scene (two cameras per time step: the monocular video's, a JPEG at 1080 x 2062, and its
+    neighbour's, a PNG at the target size) and the same video in the monocular layout"""
+    root = pathlib.Path(root)
+    rng = np.random.default_rng(7)
+    dense, mono = root / "nvidia" / "raw" / SCENE / "dense", root / "mono" / MONO_SCENE
+    for d in (dense / f"images_{W}x{H}", root / "nvidia" / "masks" / SCENE / "dense" / "masks" / "final",
+              root / "nvidia" / "depths" / SCENE / "disp", mono / "rgbs", mono / "poses", mono / "depths", mono / "masks" / "final"):
+        d.mkdir(parents=True)
+    rows = []
+    for i in range(frames):
+        c2w = _pose(i)
+        m = np.stack([c2w[:3, 1], c2w[:3, 0], -c2w[:3, 2], c2w[:3, 3], np.array([SRC_H, SRC_W, 0.9 * SRC_W])], 1)
+        rows.append(np.concatenate([m.reshape(-1), [0.5 + 0.01 * i, 9.0]]))
+    np.save(dense / "poses_bounds_cvd.npy", np.stack(rows))
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    for f in range(frames):
+        img = np.stack([127 + 100 * np.sin(xx / 45 + f), 127 + 100 * np.cos(yy / 37 + 0.3 * f), 30.0 * ((xx + yy + f) % 8)], -1)
+        img = np.clip(img + rng.integers(-3, 4, img.shape), 0, 255).astype(np.uint8)
+        big = PIL.Image.fromarray(img).resize((SRC_W, SRC_H), resample=PIL.Image.Resampling.BICUBIC)
+        (dense / "mv_images" / f"{f:05d}").mkdir(parents=True)
+        (dense / "mv_masks" / f"{f:05d}").mkdir(parents=True)
+        c = f % N_CAMS
+        big.save(dense / "mv_images" / f"{f:05d}" / f"cam{c + 1:02d}.jpg", quality=92)
+        PIL.Image.fromarray(img).save(dense / "mv_images" / f"{f:05d}" / f"cam{(c + 1) % N_CAMS + 1:02d}.png")
+        PIL.Image.fromarray(img).save(dense / f"images_{W}x{H}" / f"{f:05d}.png")
+        PIL.Image.fromarray(img).save(mono / "rgbs" / f"{f:05d}.png")
+        em = np.repeat(((((xx - W * 0.5) ** 2 + (yy - H * 0.4) ** 2) < (0.3 * H) ** 2) * 255).astype(np.uint8)[..., None], 3, -1)
+        for cam in (c, (c + 1) % N_CAMS):
+            PIL.Image.fromarray(em).save(dense / "mv_masks" / f"{f:05d}" / f"cam{cam + 1:02d}.png")
+        dyn = ((xx - W * (0.3 + 0.005 * f)) ** 2 + (yy - H * 0.5) ** 2) < (0.2 * H) ** 2
+        disp = (1.0 / (2.0 + 0.4 * np.sin(xx / W * 2 + f) + 0.2 * np.cos(yy / H * 5))).astype(np.float32)
+        PIL.Image.fromarray(dyn).save(root / "nvidia" / "masks" / SCENE / "dense" / "masks" / "final" / f"{f:05d}_final.png")
+        PIL.Image.fromarray(dyn).save(mono / "masks" / "final" / f"{f:05d}_final.png")
+        np.save(root / "nvidia" / "depths" / SCENE / "disp" / f"{f:05d}.npy", disp)
+        np.savez(mono / "depths" / f"{f:05d}.npz", depth=(1 / (disp + 1e-8)).astype(np.float32))
+        K = np.eye(4)
+        K[0, 0] = K[1, 1] = 0.9 * W
+        K[0, 2], K[1, 2] = W / 2.0, H / 2.0
+        np.savez(mono / "poses" / f"{f:05d}.npz", K=K, c2w=_pose(f))
+    for k in (1, 2):
+        a_dir, m_dir = root / "nvidia" / "flows" / SCENE / "dense" / "flows" / f"interval_{k}", mono / "flows" / f"interval_{k}"
+        a_dir.mkdir(parents=True)
+        m_dir.mkdir(parents=True)
+        for a in range(frames):
+            for b in (a - k, a + k):
+                if 0 <= b < frames:
+                    pair = dict(flow=rng.normal(0, 1.5, (H, W, 2)).astype(np.float32), coord_diff=rng.normal(0, 0.6, (H, W, 2)).astype(np.float32))
+                    np.savez(a_dir / f"{a:05d}_{b:05d}.npz", **pair)
+                    if k == 1:
+                        np.savez(m_dir / f"{a:05d}_{b:05d}.npz", **pair)
+    return root
+
+
+def loaders(nvidia_root, mono_root, scene, mono_scene, center):
+    """name -> factory(resident) of the four loaders, on cuda:0"""
+    from pgdvs_amd.datasets.mono_vis import MonoVisualizationDataset
+    from pgdvs_amd.datasets.nvidia_eval import NvidiaDynEvaluationDataset, NvidiaDynPureGeoEvaluationDataset
+    from pgdvs_amd.datasets.nvidia_vis import NvidiaDynVisualizationDataset
+
+    nv = dict(data_root=nvidia_root, raw_data_dir="raw", depth_data_dir="depths", mask_data_dir="masks", flow_data_dir="flows",
+              max_hw=-1, scene_ids=[scene], device="cuda:0")
+    vis = dict(vis_center_time=center, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32)
+    out = {"nvidia_eval": lambda r: NvidiaDynEvaluationDataset(mode="eval", resident=r, **nv),
+           "nvidia_pure_geo": lambda r: NvidiaDynPureGeoEvaluationDataset(mode="eval", resident=r, **nv),
+           "nvidia_vis": lambda r: NvidiaDynVisualizationDataset(mode="vis", resident=r, **vis, **nv)}
+    if mono_root is not None:
+        out["mono_vis"] = lambda r: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[mono_scene],
+                                                             device="cuda:0", resident=r, **vis)
+    return out
+
+
+def timed_pass(ds, indices):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    items = [ds[i] for i in indices]
+    torch.cuda.synchronize()
+    return len(indices) / (time.perf_counter() - t0), items
+
+
+def same_bits(a, b):
+    return a.keys() == b.keys() and all(
+        (v.dtype == b[k].dtype and v.shape == b[k].shape and torch.equal(v.cpu().contiguous().view(torch.uint8), b[k].cpu().contiguous().view(torch.uint8)))
+        if isinstance(v, torch.Tensor) else v == b[k] for k, v in a.items())
+
+
+def gather_case(reps):
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import ops
+    from pgdvs_amd.datasets.resident import _Scene
+
+    dev = torch.device("cuda:0")
+    scene = _Scene(F, H, W, dev)
+    scene.rgb.copy_(torch.randint(0, 256, (F, H, W, 3), dtype=torch.uint8, device=dev))
+    scene.dyn_mask.copy_(torch.randint(0, 2, (F, H, W), dtype=torch.uint8, device=dev))
+    scene.depth.copy_(torch.rand((F, H, W), device=dev) + 0.5)
+    groups = [(list(range(14, 24)), True), ([23, 24], True), (list(range(18, 23)), True), (list(range(25, 30)), True)]
+    out = ops.item_views(scene.rgb, scene.dyn_mask, scene.depth, groups)
+    med, mn = event_median(lambda: ops.item_views(scene.rgb, scene.dyn_mask, scene.depth, groups, out=out), reps, 4)
+    views = sum(len(g) for g, _ in groups)
+    read, written = views * H * W * 8, views * H * W * 44
+    bound_ms = (read + written) / HBM_BYTES_PER_S * 1e3
+    return {"views": views, "H": H, "W": W, "bytes_read": read, "bytes_written": written, "ms_median": med, "ms_min": mn,
+            "streaming_bound_ms": bound_ms, "share_of_stream_rate": bound_ms / med,
+            "distinct_frames_read": len({f for g, _ in groups for f in g})}
+
+
+def vis_run_case(make, n_views, scratch):
+    """views/s of harness.vis_run over nvidia_vis items, disk and resident (second pass), geometric renderer, resident cloud"""
+    from pgdvs_amd import harness, ops, png
+    from pgdvs_amd.datasets.static_aggregation import hwf_to_K
+    from pgdvs_amd.instantiate import load_config
+    from pgdvs_amd.renderers.pgdvs_renderer import PGDVSRenderer
+    from vis_bench import ResidentCloudRenderer
+
+    dev = torch.device("cuda:0")
+    cfg = load_config(static_renderer="geo")
+    rc = cfg.engine.engine_cfg.render_cfg
+    model = PGDVSRenderer(cfg, render_cfg=rc, softsplat_metric_abs_alpha=100.0).to(dev).eval()
+    res = make(True)
+    scene_id = res.valid_fs[0][0]
+    n = res.c2w_dict[scene_id].shape[0]
+    first = res[0]  # (gives the store its scene)
+    scene = res.store.scenes[scene_id]
+    shape = (scene.h, scene.w)
+    for f in range(n):  # the whole video into the store: the static cloud is aggregated from it
+        if not scene.filled[f]:
+            res.store.put(scene, f, *res._decode_frame(scene_id, f, shape))
+    del first
+    K3s = np.stack([hwf_to_K(*res.hwf_dict[scene_id][f], tgt_shape=shape) for f in range(n)])
+    cloud, count, xyz = ops.static_aggregate(scene.rgb.float() / 255.0, scene.depth.contiguous(), scene.dyn_mask.contiguous(), K3s,
+                                             res.c2w_dict[scene_id], capacity=n * shape[0] * shape[1], return_xyz=True)
+    renderer = ResidentCloudRenderer(model, cloud, count, xyz)
+    indices = [int(round(j * (len(res) - 1) / max(n_views - 1, 1))) for j in range(n_views)]
+
+    class Sub:
+        def __init__(self, ds):
+            self.ds = ds
+
+        def __len__(self):
+            return len(indices)
+
+        def __getitem__(self, i):
+            return self.ds[indices[i]]
+
+    def run(ds, tag):
+        d = scratch / f"vis_{tag}"
+        shutil.rmtree(d, ignore_errors=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with png.PngWriter(n_threads=8) as w:
+            harness.vis_run(renderer, Sub(ds), rc, d, device=dev, writer=w)
+        torch.cuda.synchronize()
+        return len(indices) / (time.perf_counter() - t0)
+
+    run(res, "warm")
+    return {"views": n_views, "disk_views_per_s": run(make(False), "disk"), "resident_views_per_s": run(res, "resident"),
+            "static_points": int(count.reshape(-1)[0].item())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--data_root", default=None, help="a real NVIDIA tree (raw/, depths/, masks/, flows/); default: a synthetic one")
+    ap.add_argument("--scene", default=SCENE)
+    ap.add_argument("--items", type=int, default=32)
+    ap.add_argument("--vis-views", type=int, default=48)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "loader_bench.py measures on the GPU"
+    from pgdvs_amd import _lib
+
+    _lib.load()
+    scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
+    rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
+    try:
+        if args.data_root is None:
+            t0 = time.perf_counter()
+            write_trees(scratch / "tree")
+            rec["tree"] = {"synthetic": True, "H": H, "W": W, "frames": F, "source_jpeg": [SRC_H, SRC_W], "written_s": time.perf_counter() - t0}
+            nvidia_root, mono_root, center = scratch / "tree" / "nvidia", scratch / "tree" / "mono", F // 2
+        else:
+            nvidia_root, mono_root, center = pathlib.Path(args.data_root), None, 50
+            rec["tree"] = {"synthetic": False, "scene": args.scene}
+        make = loaders(nvidia_root, mono_root, args.scene, MONO_SCENE, center)
+        for name, fn in make.items():
+            disk, res = fn(False), fn(True)
+            idx = [int(round(j * (len(disk) - 1) / max(args.items - 1, 1))) for j in range(args.items)]
+            disk[idx[0]]  # (warm-up: the depth-range op's first call)
+            r_disk, want = timed_pass(disk, idx)
+            r_first, got1 = timed_pass(res, idx)
+            r_second, got2 = timed_pass(res, idx)
+            rec["loaders"][name] = {
+                "len": len(disk), "disk_items_per_s": r_disk, "resident_first_pass_items_per_s": r_first,
+                "resident_second_pass_items_per_s": r_second, "second_pass_over_disk": r_second / r_disk,
+                "bit_identical": all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2)),
+                "views_per_item": int(sum(v.shape[0] for k, v in want[0].items() if k.startswith("rgb_src_"))),
+                "store_bytes": res.store.nbytes, "stats": dict(res.store.stats)}
+            print(f"{name}: {rec['loaders'][name]}", file=sys.stderr, flush=True)
+            del want, got1, got2, disk, res
+            torch.cuda.empty_cache()
+        rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
+        rec["gather"] = gather_case(args.reps)
+    finally:
+        shutil.rmtree(scratch, ignore_errors=True)
+    js = json.dumps(rec, indent=1)
+    if args.out:
+        pathlib.Path(args.out).write_text(js + "\n")
+    print(js)
+
+
+if __name__ == "__main__":
+    main()
