@@ -996,6 +996,15 @@ int pgdvs_item_views(const uint8_t *rgb, const uint8_t *dyn_mask, const float *d
                      int64_t mask_slot, int64_t depth_slot, const int32_t *ids, int n_views, const int32_t *group_sizes, int n_groups,
                      float *const *out, pgdvs_stream_t stream);
 int pgdvs_flow_occ(const float *coord_diff, int H, int W, float thres, float *occ, pgdvs_stream_t stream);
+/* The DyCheck loader's target (pgdvs/datasets/dycheck_iphone_eval.py:410-417, 617, 642), expanded on the device from the bytes
+ * the files hold: rgb uint8 [H,W,3] -> rgb_out float32 [H,W,3] = float(byte) / 255.0f (an IEEE division: the bits of
+ * ``raw.astype(np.float32) / 255.0``); covisible uint8 [H,W] -> mask_out float32 [H,W,1] = covisible > 0 ? 1 : 0 (the bits of
+ * ``(covisible > 0).astype(np.float32)``).  covisible and mask_out are both NULL (an image alone) or both given.  Four
+ * pixels per lane with 16-byte stores where the inputs and the outputs are 16-byte aligned, one pixel per lane for the last
+ * H W % 4 pixels and for the whole image otherwise; outputs 4-byte aligned.  Nothing outside the outputs is written.  H, W
+ * >= 1, H, W < 2^20, H W < 2^31, else PGDVS_ERR_INVALID and nothing is launched. */
+int pgdvs_item_target(const uint8_t *rgb, const uint8_t *covisible, int H, int W, float *rgb_out, float *mask_out,
+                      pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,10 @@
 //             tests) a view whose bases are not aligned takes the scalar statement for all of its pixels: the choice is
 //             uniform over the launch's y.  The scalar statement also finishes the H W % 4 pixels behind the quads.
 //             rgb = byte / 255 is a true division (__fdiv_rn): a multiply by 1 / 255 differs at 126 of the 256 values.
+// item_target one launch per item of the DyCheck loader: the target's colour bytes and covisible bytes, uploaded as stored, to
+//             the float32 image and mask.  The layout of item_views: a lane takes four pixels, three dwords of colour and
+//             one of mask, and writes four 16-byte stores (three without a mask); 4 bytes read and 16 written per pixel.
+//             The four bases decide on the host: all 16-byte aligned, or the scalar statement for the whole image.
 // flow_occ    one pixel per lane: float32 |cd.x| + |cd.y|, then a strict compare; a NaN compares false, as numpy's >.
 #include "common.h"
 
@@ -119,6 +123,32 @@ __global__ void __launch_bounds__(kBlock) flow_occ_kernel(const float2 *__restri
   occ[i] = (fabsf(d.x) + fabsf(d.y)) > thres ? 1.0f : 0.0f;
 }
 
+// One image, both outputs: rgb_out = byte / 255 (the division of unit()), mask_out = covisible > 0.  `quads`: the pixels
+// taken four per lane (0 when a base is not 16-byte aligned: the host decides, the choice is uniform over the launch).
+__global__ void __launch_bounds__(kBlock) item_target_kernel(const uint8_t *__restrict__ rgb, const uint8_t *__restrict__ cov, int64_t n,
+                                                             int64_t quads, float *__restrict__ rgb_out, float *__restrict__ mask_out) {
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t q = t; q < quads; q += stride) {  // (the grid covers the quads: one trip)
+    const uint32_t *cw = reinterpret_cast<const uint32_t *>(rgb) + q * 3;
+    const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2];
+    float4 *r4 = reinterpret_cast<float4 *>(rgb_out) + q * 3;
+    r4[0] = make_float4(unit(w0, 0), unit(w0, 1), unit(w0, 2), unit(w0, 3));
+    r4[1] = make_float4(unit(w1, 0), unit(w1, 1), unit(w1, 2), unit(w1, 3));
+    r4[2] = make_float4(unit(w2, 0), unit(w2, 1), unit(w2, 2), unit(w2, 3));
+    if (cov) {
+      const uint32_t mw = reinterpret_cast<const uint32_t *>(cov)[q];
+      reinterpret_cast<float4 *>(mask_out)[q] = make_float4((mw & 0xffu) ? 1.0f : 0.0f, (mw & 0xff00u) ? 1.0f : 0.0f,
+                                                            (mw & 0xff0000u) ? 1.0f : 0.0f, (mw & 0xff000000u) ? 1.0f : 0.0f);
+    }
+  }
+  for (int64_t i = (quads << 2) + t; i < n; i += stride) {  // the scalar statement: the tail, or a whole unaligned image
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rgb_out[i * 3 + c] = __fdiv_rn((float)rgb[i * 3 + c], 255.0f);
+    if (cov) mask_out[i] = cov[i] > 0 ? 1.0f : 0.0f;
+  }
+}
+
 bool shape_ok(int H, int W) { return H >= 1 && W >= 1 && H < (1 << 20) && W < (1 << 20) && (int64_t)H * W < (1ll << 31); }
 
 }  // namespace
@@ -174,6 +204,23 @@ PGDVS_API int pgdvs_item_views(const uint8_t *rgb, const uint8_t *dyn_mask, cons
   const dim3 grid((unsigned)cdiv(work, kBlock), (unsigned)n_views);
   PGDVS_LAUNCH("item_views", item_views_kernel, grid, dim3(kBlock), 0, as_stream(stream), p);
   return check_launch("pgdvs_item_views");
+}
+
+PGDVS_API int pgdvs_item_target(const uint8_t *rgb, const uint8_t *covisible, int H, int W, float *rgb_out, float *mask_out,
+                                 pgdvs_stream_t stream) {
+  PGDVS_REQUIRE(shape_ok(H, W), "pgdvs_item_target: bad shape H=%d W=%d (H, W >= 1, each < 2^20, H W < 2^31)", H, W);
+  PGDVS_REQUIRE(rgb && rgb_out, "pgdvs_item_target: null pointer");
+  PGDVS_REQUIRE((covisible != nullptr) == (mask_out != nullptr), "pgdvs_item_target: covisible and mask_out go together (%s is NULL)",
+                covisible ? "mask_out" : "covisible");
+  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(rgb_out) & 3) == 0 && (reinterpret_cast<uintptr_t>(mask_out) & 3) == 0,
+                "pgdvs_item_target: the outputs must be 4-byte aligned");
+  const int64_t n = (int64_t)H * W;
+  const bool vec = aligned16(rgb) && aligned16(covisible) && aligned16(rgb_out) && aligned16(mask_out);  // (NULL counts as aligned)
+  const int64_t quads = vec ? n >> 2 : 0;
+  const int64_t work = quads > n - (quads << 2) ? quads : n - (quads << 2);  // the longer of the two loops (the tail is under 4)
+  PGDVS_LAUNCH("item_target", item_target_kernel, dim3((unsigned)cdiv(work, kBlock)), dim3(kBlock), 0, as_stream(stream), rgb, covisible,
+               n, quads, rgb_out, mask_out);
+  return check_launch("pgdvs_item_target");
 }
 
 PGDVS_API int pgdvs_flow_occ(const float *coord_diff, int H, int W, float thres, float *occ, pgdvs_stream_t stream) {

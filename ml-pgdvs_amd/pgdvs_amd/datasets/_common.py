@@ -1,4 +1,4 @@
-"""What the four loaders (``nvidia_eval``, ``nvidia_vis``, ``mono_vis``, ``dycheck_iphone``) share: file readers, resizes,
+"""What the four loader modules (``nvidia_eval`` with its two classes, ``nvidia_vis``, ``mono_vis``, ``dycheck_iphone``) share: file readers, resizes,
 the per-view camera row and the item's per-group and flow entries.  Host numpy / PIL input plumbing."""
 import pathlib
 

@@ -12,6 +12,13 @@ bit-identical (DESIGN.md, row 8f-3 DyCheck).  Differences, all outside what the 
 undistortion (upstream asserts it off; distortion terms are read and ignored), and resizes that upstream does with OpenCV
 (image ``INTER_AREA``, depth ``INTER_NEAREST``; taken only when a file's size differs from the target's) use PIL's BOX /
 NEAREST filters.  The point clouds upstream computes for the temporal and tracker views and then discards are skipped.
+
+``resident=True`` (with ``resident_scenes``, ``resident_max_bytes``; Python keywords only): every train frame is decoded once
+and kept in a ``datasets.resident.SceneStore`` on ``device`` (None: host memory), slots addressed by time id; what is derived
+from the camera JSON files is cached per scene, time id and camera; the items' source views are built from the store, on a
+GPU by ``ops.item_views`` in one launch, with ``depth_range`` left on the device and the target's colour and covisible bytes
+expanded by ``ops.item_target``: the same keys in the same order, shapes, dtypes and bits, every tensor on the store's
+device.  The default is the disk path, unchanged.
 """
 import json
 import os
@@ -24,6 +31,7 @@ from torch.utils.data import Dataset
 
 from ._common import (F32, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
                       resize, stack_views, tracker_entries)
+from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
 ALL_SCENE_IDS_DYCHECK_IPHONE = ["apple", "block", "paper-windmill", "space-out", "spin", "teddy", "wheel"]
 
@@ -160,9 +168,11 @@ class iPhoneParser:  # noqa: N801 -- upstream's name
             rgba = np.concatenate([rgba, np.full_like(rgba[..., :1], 255)], axis=-1)
         return rgba
 
+    def depth_path(self, time_id, camera_id):
+        return os.path.join(self.data_dir, "depth", f"{self._factor}x", self._frame_names_map[time_id, camera_id] + ".npy")
+
     def load_depth(self, time_id, camera_id):
-        path = os.path.join(self.data_dir, "depth", f"{self._factor}x", self._frame_names_map[time_id, camera_id] + ".npy")
-        return np.load(path, allow_pickle=True) * self.scale
+        return np.load(self.depth_path(time_id, camera_id), allow_pickle=True) * self.scale
 
     def load_camera(self, time_id, camera_id):
         name = self._frame_names_map[time_id, camera_id]
@@ -343,7 +353,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
 
     def __init__(self, *, data_root, raw_data_dir, mask_data_dir, flow_data_dir, max_hw, mode, rgb_range="0_1", use_aug=False,
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
-                 n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None):
+                 n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
+                 resident_max_bytes=DEFAULT_MAX_BYTES):
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -355,6 +366,9 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.device = None if device is None else torch.device(device)
+        # resident source frames (datasets/resident.py): the store, and per scene the frame size and the cameras' derived values
+        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres) if resident else None
+        self._scene_shape, self._cam_cache = {}, {}
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.mask_data_dir, self.flow_data_dir = root / raw_data_dir, root / mask_data_dir, root / flow_data_dir
         for d in (self.raw_data_dir, self.mask_data_dir, self.flow_data_dir):
@@ -430,10 +444,15 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def _read_flow(self, scene_id, src_time_id, tgt_time_id, tgt_shape):
         """:920-983 -- zeros for the placeholder pair; otherwise flows/interval_k/<a>_<b>.npz with the occlusion mask
         sum|coord_diff| > flow_consist_thres."""
+        return read_flow_pair_or_zeros(self._flow_path(scene_id, src_time_id, tgt_time_id), tgt_shape, self.flow_consist_thres)
+
+    def _flow_path(self, scene_id, src_time_id, tgt_time_id):
+        """the pair's file; None for the placeholder pair (a frame with itself)"""
+        if src_time_id == tgt_time_id:
+            return None
         p, cam = self.parser_dict[scene_id], self.get_train_cam_id(scene_id)
-        f = (self.flow_data_dir / f"{scene_id}" / f"flows/interval_{abs(tgt_time_id - src_time_id)}" /
-             f"{p.get_frame_name(src_time_id, cam)}_{p.get_frame_name(tgt_time_id, cam)}.npz")
-        return read_flow_pair_or_zeros(f if src_time_id != tgt_time_id else None, tgt_shape, self.flow_consist_thres)
+        return (self.flow_data_dir / f"{scene_id}" / f"flows/interval_{abs(tgt_time_id - src_time_id)}" /
+                f"{p.get_frame_name(src_time_id, cam)}_{p.get_frame_name(tgt_time_id, cam)}.npz")
 
     def _depth_range(self, spatial, raw_c2w_tgt, flat_cam_tgt, near, far, tgt_shape):
         h, w = tgt_shape
@@ -452,8 +471,127 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
             near, far)
         return out.cpu()
 
+    # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
+    def _scene_frame_shape(self, scene_id):
+        """(h, w) of the scene's tables: the size of its first train frame, from the file's header"""
+        if scene_id not in self._scene_shape:
+            p, info = self.parser_dict[scene_id], self.train_info_dict[scene_id]
+            with PIL.Image.open(os.path.join(p.data_dir, "rgb", f"{p.factor}x", info["frame_names"][0] + ".png")) as im:
+                self._scene_shape[scene_id] = (im.size[1], im.size[0])
+        return self._scene_shape[scene_id]
+
+    def _cam(self, scene_id, time_id, cam_id):
+        """what __getitem__, _process_view and _depth_range derive from a frame's camera JSON, by the same statements, made
+        once: raw_c2w (the inverse of extrin), K4, the thrice-inverted c2w, flat_cam and the ray constants"""
+        key = (scene_id, int(time_id), int(cam_id))
+        c = self._cam_cache.get(key)
+        if c is None:
+            cam = self.parser_dict[scene_id].load_camera(time_id, cam_id)
+            K, w2c = cam.intrin, cam.extrin
+            c2w = np.linalg.inv(np.linalg.inv(np.linalg.inv(w2c)))
+            K4 = np.eye(4)
+            K4[:3, :3] = K
+            c = self._cam_cache[key] = {"raw_c2w": np.linalg.inv(w2c), "K4": K4, "c2w": c2w, "rays": ray_constants(K4, c2w),
+                                        "flat_cam": flat_cam(*self._scene_frame_shape(scene_id), K4, c2w)}
+        return c
+
+    def _decode_frame(self, scene_id, time_id, shape):
+        """(image uint8, dynamic mask, depth) of a train frame at the scene's size, as _process_view reads them"""
+        p, cam_id, (h, w) = self.parser_dict[scene_id], self.get_train_cam_id(scene_id), shape
+        raw = resize(p.load_rgba(time_id, cam_id)[..., :3], h, w, PIL.Image.Resampling.BOX)
+        name = p.get_frame_name(time_id, cam_id)
+        m = np.array(PIL.Image.open(self.mask_data_dir / scene_id / f"masks/final/{name}_final.png"))
+        depth = p.load_depth(time_id, cam_id)
+        if depth.dtype == np.float64:
+            raise ValueError(f"{p.depth_path(time_id, cam_id)}: the depth times the scene's scale is float64; resident=True keeps "
+                             "float32 depths, and the disk path would take the depth range over the doubles")
+        return raw, resize(m, h, w, PIL.Image.Resampling.NEAREST), resize(depth[..., 0], h, w, PIL.Image.Resampling.NEAREST)
+
+    @staticmethod
+    def _item_key_order():
+        """the disk item's keys in its order"""
+        def group(name, timed):
+            return [f"{k}_src_{name}" for k in ("rgb", "dyn_rgb", "static_rgb", "flat_cam", "dyn_mask", "depth") + (("time",) if timed else ())] + \
+                ([f"n_actual_{name}"] if timed else [])
+
+        return (["scene_id", "seq_ids", "rgb_tgt", "eval_mask", "flat_cam_tgt", "depth_range", "time_tgt", "misc"] + group("spatial", False) +
+                group("temporal", True) + ["flow_fwd", "flow_fwd_occ_mask", "flow_bwd", "flow_bwd_occ_mask"] +
+                group("temporal_track_fwd2tgt", True) + group("temporal_track_bwd2tgt", True))
+
+    def _resident_item(self, index):
+        """``resident.build_item`` over this loader's readers and cached cameras.  The target image and the covisible mask, one
+        item's each, stay disk reads; on a GPU store they cross as bytes in the item's packed copy and ``ops.item_target``
+        expands them there"""
+        scene_id, tgt_frame_name, tgt_time_id, tgt_cam_id = self.valid_fs[index]
+        info, p = self.train_info_dict[scene_id], self.parser_dict[scene_id]
+        assert (tgt_frame_name, tgt_time_id, tgt_cam_id) not in info["unique_ids"]
+        shape, dev, cam_id = self._scene_frame_shape(scene_id), self.store.device, self.get_train_cam_id(scene_id)
+        tgt_cam = self._cam(scene_id, tgt_time_id, tgt_cam_id)
+        raw_c2w_tgt, flat_cam_tgt = tgt_cam["raw_c2w"], tgt_cam["flat_cam"]
+        sel = select_temporal_frames(tgt_time_id, info["time_ids"], self.n_src_views_temporal_track_one_side)
+        clusters = self.scene_clusters(scene_id) if self.spatial_src_view_type == "clustered" else None
+        spatial_ids = select_spatial_frames(self.spatial_src_view_type, tgt_time_id, raw_c2w_tgt, info["time_ids"], info["train_c2w"],
+                                            self.n_src_views_spatial, clusters)
+        frame_ids = np.array([tgt_time_id, *spatial_ids, *sel["temporal"]]).astype(int)
+        tgt_rgb = p.load_rgba(tgt_time_id, tgt_cam_id)[..., :3]
+        tgt_shape = tgt_rgb.shape[:2]
+        covis = p.load_covisible(tgt_time_id, tgt_cam_id, "val")
+        assert covis.shape[:2] == tgt_shape, (covis.shape, tgt_shape)
+        if tuple(tgt_shape) != shape:
+            raise ValueError(f"{scene_id}: target {tgt_frame_name} is {tuple(tgt_shape)}, the scene's tables hold frames of {shape}")
+        train = {int(t) for t in info["time_ids"]}
+        for t in (*spatial_ids, *sel["temporal"], *sel["fwd2tgt"], *sel["bwd2tgt"]):  # (the disk path's order)
+            if int(t) not in train:  # e.g. the clustered rule's train-list indices: no slot is touched
+                self._process_view(scene_id, t, cam_id, tgt_shape, True)  # raises what the disk path raises
+                raise ValueError(f"{scene_id}: frame id {int(t)} is no train frame ({min(train)}..{max(train)})")
+        host = {"seq_ids": torch.LongTensor(frame_ids), "flat_cam_tgt": F32(np.array(flat_cam_tgt)),
+                "time_tgt": torch.FloatTensor([tgt_time_id])}
+        as_bytes = dev is not None and tgt_rgb.dtype == np.uint8 and tgt_rgb.ndim == 3 and tgt_rgb.shape[2] == 3
+        if as_bytes:
+            host["__rgb_tgt"] = torch.from_numpy(np.ascontiguousarray(tgt_rgb))
+        else:
+            host["rgb_tgt"] = F32(tgt_rgb.astype(np.float32) / 255.0)
+        if as_bytes and covis.ndim == 2 and covis.dtype in (np.bool_, np.uint8):
+            host["__covisible"] = torch.from_numpy(np.ascontiguousarray(covis).view(np.uint8))
+        else:
+            host["eval_mask"] = F32((covis > 0).astype(np.float32))[..., None]
+
+        def cams(ids):
+            cs = [self._cam(scene_id, t, cam_id) for t in ids]
+            return tuple(np.stack([c[k] for c in cs]) for k in ("flat_cam", "K4", "c2w"))
+
+        def depth_range(depth, dyn_mask, rays):
+            if dev is None:
+                pcl = np.concatenate([compute_pcl(*shape, r[:9].reshape(3, 3), r[9:], d) for r, d in zip(rays, depth.numpy())], axis=0)
+                return torch.from_numpy(depth_range_numpy(pcl, dyn_mask.numpy(), raw_c2w_tgt, flat_cam_tgt, p.near, p.far, *shape))
+            from .. import ops
+
+            return ops.dycheck_depth_range(depth, dyn_mask, rays, np.linalg.inv(raw_c2w_tgt), np.linalg.inv(flat_cam_tgt[18:34].reshape((4, 4))),
+                                           flat_cam_tgt[2:18].reshape((4, 4))[:3, :3], p.near, p.far)
+
+        scene = self.store.scene(scene_id, len(info["time_ids"]), shape, first_id=int(min(info["time_ids"])))
+        item = build_item(self.store, scene, lambda t: self._decode_frame(scene_id, t, shape),
+                          fixed={"scene_id": scene_id, "misc": {"scene_id": scene_id, "tgt_frame_id": tgt_time_id, "tgt_cam_id": tgt_cam_id,
+                                                                "tgt_frame_name": tgt_frame_name}},
+                          host=host, cams=cams, sel=sel, spatial_ids=spatial_ids, spatial_depth=True, c2w_tgt=None,
+                          flow_path=lambda a, b: self._flow_path(scene_id, a, b),
+                          trackers=True, owner=type(self).__name__, depth_range=depth_range,
+                          ray_rows=lambda ids: ray_rows([self._cam(scene_id, t, cam_id)["rays"] for t in ids]))
+        if as_bytes:
+            from .. import ops
+
+            rgb, mask = ops.item_target(item.pop("__rgb_tgt"), item.pop("__covisible", None))
+            item["rgb_tgt"] = rgb
+            if mask is not None:
+                item["eval_mask"] = mask
+        order = self._item_key_order()
+        assert len(order) == len(item), sorted(set(order) ^ set(item))
+        return {k: item[k] for k in order}
+
     # ------------------------------------------------------------------ item
     def __getitem__(self, index):
+        if self.store is not None:
+            return self._resident_item(index)
         scene_id, tgt_frame_name, tgt_time_id, tgt_cam_id = self.valid_fs[index]
         info, p = self.train_info_dict[scene_id], self.parser_dict[scene_id]
         assert (tgt_frame_name, tgt_time_id, tgt_cam_id) not in info["unique_ids"]

@@ -1,8 +1,9 @@
 """A scene's source frames kept in memory in their stored form, and the loaders' items built from them (``resident=True``).
 
-An item of the NVIDIA-family loaders stacks 20-odd source views, each decoded from an image, a mask and a depth file, and a
-scene has only as many distinct source frames as its monocular video: frame ``i`` is always the same files.  ``SceneStore``
-decodes a frame on its first use, through the loader's own readers, and keeps per scene
+An item of the five loaders (the four of the NVIDIA family and the DyCheck iPhone one) stacks 20-odd source views, each
+decoded from an image, a mask and a depth file, and a scene has only as many distinct source frames as its monocular video
+(DyCheck: its train camera): frame ``i`` is always the same files.  ``SceneStore`` decodes a frame on its first use, through
+the loader's own readers, and keeps per scene
 
   rgb       uint8   [F,H,W,3]  the pixels before ``/ 255``
   dyn_mask  uint8   [F,H,W]    the mask file's values (0 / 1 for the 1-bit files)
@@ -13,6 +14,11 @@ far: ``flow`` float32 [H,W,2] and the occlusion mask [H,W] computed once, when t
 tables are host memory and an item's views are gathered with numpy, statement for statement the disk path's; with a GPU
 ``device`` they live there and ``ops.item_views`` writes all of an item's views in one launch (``ops.flow_occ`` the occlusion
 mask), bit-identical.  Once its frames are in, building an item on the GPU never waits for the device.
+
+Slots are addressed by frame id: frame ``f`` of a scene lives in slot ``f - first_id``.  The NVIDIA-family loaders' frame
+ids are the monocular video's indices (``first_id`` 0); the DyCheck loader's are its train camera's time ids, a consecutive
+run that need not start at 0 (``first_id`` = the smallest; the scene has as many slots as train frames).  An id outside the
+run is refused before anything is decoded.
 
 ``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
 it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
@@ -39,9 +45,9 @@ def table_bytes(n_frames, h, w):
 
 
 class _Scene:
-    def __init__(self, n_frames, h, w, device):
+    def __init__(self, n_frames, h, w, device, first_id=0):
         n = h * w
-        self.n_frames, self.h, self.w = n_frames, h, w
+        self.n_frames, self.h, self.w, self.first_id = n_frames, h, w, int(first_id)
         self.filled = np.zeros(n_frames, dtype=bool)  # host bitmap of the decoded slots
         tab = lambda slot, dtype: torch.empty((n_frames, slot), dtype=dtype, device=device)  # noqa: E731
         self.rgb = tab(_pad16(n * 3), torch.uint8)[:, :n * 3].view(n_frames, h, w, 3)
@@ -75,11 +81,12 @@ class SceneStore:
         return scene.h * scene.w * 12
 
     # ------------------------------------------------------------------ scenes
-    def scene(self, key, n_frames, shape):
-        """the scene's tables, made on first use (nothing is decoded yet); the least recently used scenes leave"""
+    def scene(self, key, n_frames, shape, first_id=0):
+        """the scene's tables, made on first use (nothing is decoded yet); the least recently used scenes leave.  Frame id
+        ``f`` lives in slot ``f - first_id``"""
         s = self.scenes.get(key)
         if s is not None:
-            assert (s.n_frames, s.h, s.w) == (n_frames, *shape), (key, (s.n_frames, s.h, s.w), n_frames, shape)
+            assert (s.n_frames, s.h, s.w, s.first_id) == (n_frames, *shape, first_id), (key, (s.n_frames, s.h, s.w, s.first_id), n_frames, shape, first_id)
             self.scenes.move_to_end(key)
             return s
         need = table_bytes(n_frames, *shape)
@@ -91,7 +98,7 @@ class SceneStore:
         while self.scenes and self.nbytes + need > self.resident_max_bytes:  # flow pairs go first, then the oldest scene
             if not self._drop_flow_pair():
                 self.scenes.popitem(last=False)
-        s = self.scenes[key] = _Scene(n_frames, shape[0], shape[1], self.device)
+        s = self.scenes[key] = _Scene(n_frames, shape[0], shape[1], self.device, first_id)
         return s
 
     def _drop_flow_pair(self, keep=None):
@@ -104,30 +111,41 @@ class SceneStore:
         return False
 
     # ------------------------------------------------------------------ frames
+    @staticmethod
+    def slots(scene, frame_ids):
+        """the frame ids' slots; an id outside the scene's run is refused (an index below 0 would wrap around)"""
+        slots = [int(f) - scene.first_id for f in frame_ids]
+        if slots and not 0 <= min(slots) <= max(slots) < scene.n_frames:
+            raise ValueError(f"frame ids {[int(f) for f in frame_ids]} outside the scene's {scene.first_id}..{scene.first_id + scene.n_frames - 1}")
+        return slots
+
     def _fill(self, scene, frame_ids, decode):
         for f in sorted(set(frame_ids)):
-            if not scene.filled[f]:
+            if not scene.filled[f - scene.first_id]:
                 self.put(scene, f, *decode(f))
 
     def put(self, scene, f, rgb, mask, depth):
-        """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into its slot"""
+        """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into the slot of frame id ``f``"""
         shape = (scene.h, scene.w)
+        (slot,) = self.slots(scene, [f])
         if rgb.dtype != np.uint8 or rgb.shape != shape + (3,):
             raise ValueError(f"frame {f}: image {rgb.dtype} {rgb.shape}, the store keeps uint8 {shape + (3,)}")
         if mask.dtype not in (np.bool_, np.uint8) or mask.shape != shape:
             raise ValueError(f"frame {f}: mask {mask.dtype} {mask.shape}, the store keeps bool or uint8 {shape}")
         if depth.shape != shape:
             raise ValueError(f"frame {f}: depth {depth.shape}, expected {shape}")
-        scene.rgb[f].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
-        scene.dyn_mask[f].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
-        scene.depth[f].copy_(F32(depth))
-        scene.filled[f] = True
+        scene.rgb[slot].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
+        scene.dyn_mask[slot].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
+        scene.depth[slot].copy_(F32(depth))
+        scene.filled[slot] = True
         self.stats["frames_decoded"] += 1
 
     def views(self, scene, groups, decode):
         """one dict per group ``(frame ids, with_depth)``: rgb, dyn_rgb, static_rgb [n,H,W,3], dyn_mask and (with_depth) depth
         [n,H,W,1], float32 on the store's device; ``decode(frame id) -> (rgb uint8, mask, depth)`` fills missing slots"""
-        self._fill(scene, [f for ids, _ in groups for f in ids], decode)
+        frame_ids = [int(f) for ids, _ in groups for f in ids]
+        groups = [(self.slots(scene, ids), with_depth) for ids, with_depth in groups]  # (checked before anything is decoded)
+        self._fill(scene, frame_ids, decode)
         self.stats["items_built"] += 1
         if self.device is not None:
             from .. import ops
@@ -206,20 +224,25 @@ def group_host_entries(group, flat_cams, times=None, n_actual=None):
     return out
 
 
-def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner):
-    """An item of the NVIDIA-family loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
+def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner,
+               ray_rows=None, depth_range=None):
+    """An item of the five loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
     non-tensor entries; ``host``: the host-made tensors (on a GPU store they travel in ONE packed copy, with the groups'
-    cameras and times); ``cams(frame ids) -> (flat_cam [V,34], K [V,4,4], c2w [V,4,4])``; ``sel``: the loader's temporal
+    cameras and times; entries named ``__...`` are the loader's own cargo: they come back in the item, on the device, for
+    the loader to take out); ``cams(frame ids) -> (flat_cam [V,34], K [V,4,4], c2w [V,4,4])``; ``sel``: the loader's temporal
     selection; ``spatial_ids`` (None: no spatial group and no ``depth_range``) with ``spatial_depth`` False where the item
     carries no spatial depth (the range is still taken over it); ``flow_path(a, b)``: the pair's file, None for the
     placeholder pair.  ``depth_range``: ``nvidia_eval.spatial_depth_range`` on the host, ``ops.nvidia_depth_range`` on the
-    gathered depths on a GPU store, where nothing here waits for the device."""
+    gathered depths on a GPU store, where nothing here waits for the device.  The DyCheck loader brings its own:
+    ``ray_rows(spatial ids) -> [V,12] float32`` (its cached ray constants; default: ``nvidia_eval.ray_rows`` of the cameras,
+    formed on a GPU store only) and ``depth_range(depth [V,H,W], dyn_mask [V,H,W], rays) -> tensor`` on the store's device,
+    ``rays`` the rows as a device tensor on a GPU store and as the numpy array on a host store; ``c2w_tgt`` is unused then."""
     from . import nvidia_eval as NE
 
     dev = store.device
     if dev is not None:
         NE.refuse_gpu_in_worker(owner)
-    host, groups, rng = dict(host), [], None
+    host, groups, rng, rows = dict(host), [], None, None
 
     def add(name, ids, with_depth, times=None, n_actual=None):
         flat, Ks, c2ws = cams(ids)
@@ -229,8 +252,12 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
 
     if spatial_ids is not None:
         rng = add("spatial", spatial_ids, spatial_depth)
+        if ray_rows is not None:
+            rows = np.ascontiguousarray(ray_rows(spatial_ids), dtype=np.float32)
+        elif dev is not None:
+            rows = NE.ray_rows(*rng)
         if dev is not None:
-            host["__rays"] = F32(NE.ray_rows(*rng))
+            host["__rays"] = F32(rows)
     add("temporal", sel["temporal"], True, sel["temporal"], sel["n_actual_temporal"])
     if trackers:
         for side in ("fwd2tgt", "bwd2tgt"):
@@ -244,7 +271,9 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
     for (name, _, with_depth), v in zip(groups, views):
         if name == "spatial":
             depth = v["depth"][..., 0]
-            if dev is not None:
+            if depth_range is not None:
+                item["depth_range"] = depth_range(depth, v["dyn_mask"][..., 0], rays if dev is not None else rows)
+            elif dev is not None:
                 from .. import ops
 
                 item["depth_range"] = ops.nvidia_depth_range(depth, rays, np.linalg.inv(c2w_tgt))

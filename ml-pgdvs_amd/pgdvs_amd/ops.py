@@ -902,6 +902,41 @@ def flow_occ(coord_diff, thres):
     return occ
 
 
+def _bytes_image(t, shape, name):
+    """a contiguous uint8 GPU tensor of ``shape``, passed as it lies (no copy: its address decides the kernel's path)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise PgdvsHipError(f"item_target: {name}: expected a GPU tensor (no CPU fallback)")
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"item_target: {name} {t.dtype} {tuple(t.shape)}, expected a contiguous uint8 {tuple(shape)}")
+    return t
+
+
+def item_target(rgb_u8, covisible_u8=None, out=None):
+    """The DyCheck loader's target from its bytes (``pgdvs_item_target``; include/pgdvs_hip.h): rgb_u8 uint8 [H,W,3] and,
+    optionally, covisible_u8 uint8 [H,W] on the GPU -> (rgb float32 [H,W,3] = byte / 255, mask float32 [H,W,1] = covisible
+    > 0, or None without a covisible image), the bits of ``raw.astype(np.float32) / 255.0`` and ``(covisible >
+    0).astype(np.float32)[..., None]``.  ``out``: such a pair of contiguous float32 GPU tensors to fill in place (the
+    second None exactly when there is no covisible image).  One launch; does not synchronise."""
+    if not isinstance(rgb_u8, torch.Tensor) or rgb_u8.ndim != 3 or rgb_u8.shape[2] != 3:
+        raise ValueError(f"item_target: rgb_u8 [H,W,3] expected, got {tuple(getattr(rgb_u8, 'shape', ()))}")
+    H, W = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
+    c = _bytes_image(rgb_u8, (H, W, 3), "rgb_u8")
+    m = None if covisible_u8 is None else _bytes_image(covisible_u8, (H, W), "covisible_u8")
+    if m is not None and m.device != c.device:
+        raise ValueError(f"item_target: rgb_u8 on {c.device}, covisible_u8 on {m.device}")
+    if out is None:
+        out = (torch.empty((H, W, 3), dtype=torch.float32, device=c.device),
+               None if m is None else torch.empty((H, W, 1), dtype=torch.float32, device=c.device))
+    if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[1] is None) != (m is None):
+        raise ValueError("item_target: out is a pair (rgb, mask), the mask None exactly when covisible_u8 is")
+    for t, shape, name in ((out[0], (H, W, 3), "out[0]"), (out[1], (H, W, 1), "out[1]")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != c.device or t.dtype != torch.float32 or
+                              not t.is_contiguous() or tuple(t.shape) != shape):
+            raise ValueError(f"item_target: {name} must be a contiguous float32 {shape} tensor on {c.device}")
+    check(_lib.load().pgdvs_item_target(_ptr(c), _ptr(m), H, W, _ptr(out[0]), _ptr(out[1]), _stream()), "pgdvs_item_target")
+    return out[0], out[1]
+
+
 def _flow_pair(a, b, names, what):
     """two float32 [H,W,2] GPU tensors of one shape, H, W >= 2 (the preprocessing ops' inputs)"""
     a, b = _req(a, torch.float32, names[0]), _req(b, torch.float32, names[1])

@@ -10,8 +10,12 @@ monocular layout for ``mono_vis``:
            static cloud resident (tools/vis_bench.py), PNGs written by an 8-thread writer
   gather   GPU time of the ``ops.item_views`` launch alone (HIP events, median, warmed) for an item of 22 views in four
            groups at 288 x 550, its algorithmic bytes, and its share of the 6.29 TB/s stream rate of MI355X_MICROARCH.md
-Prints one JSON object.
-Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--out FILE]"""
+  dycheck  the DyCheck iPhone loader on a synthetic scene of its own (360 x 480, 48 train frames, two val cameras; 10
+           spatial views, tracker windows of 5, device cuda:0): items/s as under ``items``, every resident item compared with
+           the disk item (keys in order, bits), the target's upload bytes, and the ``ops.item_target`` launch alone (events,
+           bytes, achieved bandwidth, share of the stream rate)
+``--legs nvidia,dycheck`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
+Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--legs dycheck] [--out FILE]"""
 import argparse
 import json
 import pathlib
@@ -150,6 +154,90 @@ def gather_case(reps):
             "distinct_frames_read": len({f for g, _ in groups for f in g})}
 
 
+DY_H, DY_W, DY_F, DY_FACTOR, DY_SCENE = 360, 480, 48, 2, "synthetic-iphone"
+
+
+def write_dycheck_tree(root, frames=DY_F):
+    """a synthetic DyCheck iPhone scene in the layout iPhoneParser reads: 360 x 480 (the 2x frames), ``frames`` train frames on
+    camera 0 at time ids 0.., two val cameras at every second instant (val frames sit on train instants, as the dataset's do,
+    so every item's temporal pair is the placeholder one and no flow file is read)"""
+    root = pathlib.Path(root)
+    rng = np.random.default_rng(11)
+    sd, md = root / "iphone" / DY_SCENE, root / "flow_mask" / DY_SCENE / "masks" / "final"
+    for d in (sd / "camera", sd / f"rgb/{DY_FACTOR}x", sd / f"depth/{DY_FACTOR}x", sd / f"covisible/{DY_FACTOR}x/val", md,
+              root / "flow_mask" / DY_SCENE / "flows"):
+        d.mkdir(parents=True)
+    shots = [(0, t) for t in range(frames)] + [(c, t) for c in (1, 2) for t in range(0, frames, 2)]
+    names = [f"{c}_{t:05d}" for c, t in shots]
+    (sd / "scene.json").write_text(json.dumps({"center": [0.0, 0.0, 0.0], "scale": 0.5, "near": 0.2, "far": 6.0}))
+    (sd / "dataset.json").write_text(json.dumps({"count": len(names), "num_exemplars": frames, "ids": names}))
+    (sd / "metadata.json").write_text(json.dumps({n: {"warp_id": t, "appearance_id": t, "camera_id": c} for n, (c, t) in zip(names, shots)}))
+    (sd / "extra.json").write_text(json.dumps({"factor": DY_FACTOR, "fps": 30.0, "bbox": [[-1, -1, -1], [1, 1, 1]], "lookat": [0, 0, 1],
+                                               "up": [0, -1, 0]}))
+    yy, xx = np.mgrid[0:DY_H, 0:DY_W].astype(np.float32)
+    for n, (c, t) in zip(names, shots):
+        a = 0.01 * t - 0.2 + 0.05 * c
+        R = np.array([[np.cos(a), 0, -np.sin(a)], [0, 1, 0], [np.sin(a), 0, np.cos(a)]])
+        (sd / "camera" / f"{n}.json").write_text(json.dumps({
+            "orientation": R.tolist(), "position": [-0.6 + 0.025 * t, 0.1 * c, 0.02 * c], "focal_length": 1.7 * DY_W,
+            "principal_point": [DY_W * 1.0, DY_H * 1.0], "image_size": [DY_W * DY_FACTOR, DY_H * DY_FACTOR], "skew": 0.0,
+            "pixel_aspect_ratio": 1.0, "radial_distortion": [0.0, 0.0, 0.0], "tangential_distortion": [0.0, 0.0]}))
+        img = np.stack([127 + 100 * np.sin(xx / 45 + t), 127 + 100 * np.cos(yy / 37 + 0.3 * t + c), 30.0 * ((xx + yy + t) % 8)], -1)
+        img = np.clip(img + rng.integers(-3, 4, img.shape), 0, 255).astype(np.uint8)
+        PIL.Image.fromarray(img).save(sd / f"rgb/{DY_FACTOR}x" / f"{n}.png")
+        if c == 0:
+            depth = (4.0 + 0.8 * np.sin(xx / DY_W * 3 + 0.1 * t) + 0.4 * np.cos(yy / DY_H * 5)).astype(np.float32)
+            np.save(sd / f"depth/{DY_FACTOR}x" / f"{n}.npy", depth[..., None])
+            dyn = ((xx - DY_W * (0.3 + 0.005 * t)) ** 2 + (yy - DY_H * 0.5) ** 2) < (0.2 * DY_H) ** 2
+            PIL.Image.fromarray(dyn).save(md / f"{n}_final.png")
+        else:
+            PIL.Image.fromarray((((xx + yy + t) % 7 != 0) * 255).astype(np.uint8)).save(sd / f"covisible/{DY_FACTOR}x/val" / f"{n}.png")
+    return root
+
+
+def dycheck_case(scratch, n_items, reps):
+    """the DyCheck loader, ``resident=False`` against ``resident=True`` on cuda:0 (10 spatial views by the closest_wo_temporal
+    rule, tracker windows of 5), and the ``ops.item_target`` launch alone"""
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import ops
+    from pgdvs_amd.datasets.dycheck_iphone import DyCheckiPhoneEvaluationDataset
+
+    t0 = time.perf_counter()
+    root = write_dycheck_tree(scratch / "dycheck")
+    rec = {"tree": {"synthetic": True, "H": DY_H, "W": DY_W, "train_frames": DY_F, "val_cameras": 2, "written_s": time.perf_counter() - t0}}
+    kw = dict(data_root=root, raw_data_dir="iphone", mask_data_dir="flow_mask", flow_data_dir="flow_mask", max_hw=-1, mode="eval",
+              scene_ids=[DY_SCENE], spatial_src_view_type="closest_wo_temporal", n_src_views_spatial=10,
+              n_src_views_temporal_track_one_side=5, device="cuda:0")
+    disk, res = DyCheckiPhoneEvaluationDataset(**kw), DyCheckiPhoneEvaluationDataset(resident=True, **kw)
+    idx = [int(round(j * (len(disk) - 1) / max(n_items - 1, 1))) for j in range(n_items)]
+    disk[idx[0]]  # (warm-up: the depth-range op's first call)
+    r_disk, want = timed_pass(disk, idx)
+    r_first, got1 = timed_pass(res, idx)
+    r_second, got2 = timed_pass(res, idx)
+    n = DY_H * DY_W
+    rec["loader"] = {
+        "len": len(disk), "items": n_items, "disk_items_per_s": r_disk, "resident_first_pass_items_per_s": r_first,
+        "resident_second_pass_items_per_s": r_second, "second_pass_over_disk": r_second / r_disk,
+        "bit_identical": all(list(a) == list(b) == list(c) and same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2)),
+        "on_device": all(v.is_cuda for it in got2 for v in it.values() if isinstance(v, torch.Tensor)),
+        "views_per_item": int(sum(v.shape[0] for k, v in want[0].items() if k.startswith("rgb_src_"))),
+        "store_bytes": res.store.nbytes, "stats": dict(res.store.stats),
+        "target_upload_bytes_per_item": {"as_bytes": n * 4, "as_float32": n * 16}}
+    del want, got1, got2, disk, res
+    torch.cuda.empty_cache()
+    dev = torch.device("cuda:0")
+    rgb = torch.randint(0, 256, (DY_H, DY_W, 3), dtype=torch.uint8, device=dev)
+    cov = torch.randint(0, 2, (DY_H, DY_W), dtype=torch.uint8, device=dev) * 255
+    out = ops.item_target(rgb, cov)
+    med, mn = event_median(lambda: ops.item_target(rgb, cov, out=out), reps, 4)
+    read, written = n * 4, n * 16
+    bound_ms = (read + written) / HBM_BYTES_PER_S * 1e3
+    rec["item_target"] = {"H": DY_H, "W": DY_W, "bytes_read": read, "bytes_written": written, "ms_median": med, "ms_min": mn,
+                          "achieved_bytes_per_s": (read + written) / (med * 1e-3), "streaming_bound_ms": bound_ms,
+                          "share_of_stream_rate": bound_ms / med}
+    return rec
+
+
 def vis_run_case(make, n_views, scratch):
     """views/s of harness.vis_run over nvidia_vis items, disk and resident (second pass), geometric renderer, resident cloud"""
     from pgdvs_amd import harness, ops, png
@@ -210,6 +298,7 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--vis-views", type=int, default=48)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "loader_bench.py measures on the GPU"
@@ -218,8 +307,15 @@ def main():
     _lib.load()
     scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
     rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
+    legs = set(args.legs.split(","))
+    assert legs and legs <= {"nvidia", "dycheck"}, args.legs
     try:
-        if args.data_root is None:
+        if "dycheck" in legs:
+            rec["dycheck"] = dycheck_case(scratch, args.items, args.reps)
+            print(f"dycheck: {rec['dycheck']}", file=sys.stderr, flush=True)
+        if "nvidia" not in legs:
+            nvidia_root = mono_root = center = None
+        elif args.data_root is None:
             t0 = time.perf_counter()
             write_trees(scratch / "tree")
             rec["tree"] = {"synthetic": True, "H": H, "W": W, "frames": F, "source_jpeg": [SRC_H, SRC_W], "written_s": time.perf_counter() - t0}
@@ -227,7 +323,7 @@ def main():
         else:
             nvidia_root, mono_root, center = pathlib.Path(args.data_root), None, 50
             rec["tree"] = {"synthetic": False, "scene": args.scene}
-        make = loaders(nvidia_root, mono_root, args.scene, MONO_SCENE, center)
+        make = loaders(nvidia_root, mono_root, args.scene, MONO_SCENE, center) if "nvidia" in legs else {}
         for name, fn in make.items():
             disk, res = fn(False), fn(True)
             idx = [int(round(j * (len(disk) - 1) / max(args.items - 1, 1))) for j in range(args.items)]
@@ -244,8 +340,9 @@ def main():
             print(f"{name}: {rec['loaders'][name]}", file=sys.stderr, flush=True)
             del want, got1, got2, disk, res
             torch.cuda.empty_cache()
-        rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
-        rec["gather"] = gather_case(args.reps)
+        if "nvidia" in legs:
+            rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
+            rec["gather"] = gather_case(args.reps)
     finally:
         shutil.rmtree(scratch, ignore_errors=True)
     js = json.dumps(rec, indent=1)
