@@ -1005,6 +1005,34 @@ int pgdvs_flow_occ(const float *coord_diff, int H, int W, float thres, float *oc
  * >= 1, H, W < 2^20, H W < 2^31, else PGDVS_ERR_INVALID and nothing is launched. */
 int pgdvs_item_target(const uint8_t *rgb, const uint8_t *covisible, int H, int W, float *rgb_out, float *mask_out,
                       pgdvs_stream_t stream);
+/* The loaders' image resize on the device (csrc/resample.hip): Pillow's 8-bit resampler, Image.resize(resample=BOX) and
+ * Image.resize(resample=LANCZOS) of "L" and "RGB" images, bit for bit.
+ * pgdvs_resample_table (HOST only; never touches the GPU) replaces precompute_coeffs + normalize_coeffs_8bpc
+ * (src/libImaging/Resample.c) for one axis of in_size -> out_size pixels: bounds[out_size][2] = (first input index, tap
+ * count n) and kk[out_size][ksize] = the 22-bit fixed-point coefficients, zero past n, the doubles formed in Pillow's order
+ * with libm's sin.  Returns ksize = 2 ceil(support max(in / out, 1)) + 1 (support 0.5 for box, 3 for lanczos); with bounds
+ * and kk both NULL only that.  Sizes outside 1 .. PGDVS_RESAMPLE_MAX_SIZE, another filter, or ksize above
+ * PGDVS_RESAMPLE_MAX_TAPS (a lanczos reduction beyond 42 : 1, a box reduction beyond 254 : 1; the horizontal pass stages a
+ * tile's taps in 16 KB of LDS): -1 with a pgdvs_last_error text, nothing written.
+ * pgdvs_resample_u8 replaces ImagingResampleHorizontal_8bpc + ImagingResampleVertical_8bpc: in uint8 [N,Hin,Win,C], C 1 or 3,
+ * frame i at in + i * in_stride BYTES, -> out [N,Hout,Wout,C], frame i at out + i * out_stride bytes (a frame contiguous; the
+ * strides at least a frame, so the output may be a padded slot of the resident store; bytes between frames are not
+ * written).  The tables of the axes that change are DEVICE pointers, as pgdvs_resample_table made them for (Win, Wout) and
+ * (Hin, Hout) with the same filter: the caller uploads them; for an axis that keeps its size they are ignored and the pass
+ * is skipped, and with both kept the op is a copy.  Horizontal pass first, over the input rows the vertical pass reads,
+ * into a uint8 intermediate image in the workspace (its 8-bit rounding is part of the result); each pass is
+ * clamp((2^21 + sum k * byte) >> 22, 0, 255) in int32.  No alignment is asked of in or out; the workspace is 4-byte aligned,
+ * >= pgdvs_resample_u8_workspace_bytes (0 unless both axes change).  One stream, no host synchronisation.  1 <= N <= 65535
+ * and the table entry's limits, else PGDVS_ERR_INVALID (the workspace query too) and nothing is launched. */
+#define PGDVS_RESAMPLE_BOX 0
+#define PGDVS_RESAMPLE_LANCZOS 1
+#define PGDVS_RESAMPLE_MAX_SIZE 16384
+#define PGDVS_RESAMPLE_MAX_TAPS 256
+int pgdvs_resample_table(int in_size, int out_size, int filter, int32_t *bounds, int32_t *kk);
+int64_t pgdvs_resample_u8_workspace_bytes(int N, int Hin, int Win, int C, int Hout, int Wout, int filter);
+int pgdvs_resample_u8(const uint8_t *in, int64_t in_stride, int N, int Hin, int Win, int C, uint8_t *out, int64_t out_stride, int Hout,
+                      int Wout, int filter, const int32_t *bounds_h, const int32_t *kk_h, const int32_t *bounds_v, const int32_t *kk_v,
+                      void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -73,6 +73,17 @@ def refuse_gpu_in_worker(owner):
                            "touch: use n_dataloader_workers=0 (or device=None)")
 
 
+def check_device_resize(device_resize, resident, device, owner):
+    """``device_resize=True`` resizes into the resident store on a GPU: refused, naming what is missing, without either"""
+    if not device_resize:
+        return False
+    if not resident:
+        raise ValueError(f"{owner}(device_resize=True) resizes decoded frames into the resident store: it needs resident=True")
+    if device is None or torch.device(device).type != "cuda":
+        raise ValueError(f"{owner}(device_resize=True) resizes on the device: it needs the store on a GPU, got device={device!r}")
+    return True
+
+
 def group_entries(group, views, times=None, n_actual=None, depth=True):
     """The item's entries of one group of stacked source views: "spatial", "temporal" or "temporal_track_{fwd,bwd}2tgt".
     The temporal and tracker groups also carry their frames' ``times`` and ``n_actual``, the count before padding; the

@@ -18,7 +18,9 @@ and kept in a ``datasets.resident.SceneStore`` on ``device`` (None: host memory)
 from the camera JSON files is cached per scene, time id and camera; the items' source views are built from the store, on a
 GPU by ``ops.item_views`` in one launch, with ``depth_range`` left on the device and the target's colour and covisible bytes
 expanded by ``ops.item_target``: the same keys in the same order, shapes, dtypes and bits, every tensor on the store's
-device.  The default is the disk path, unchanged.
+device.  ``device_resize=True`` (with ``resident=True`` on a GPU): a train frame whose file is not of the
+scene's size goes to the store as decoded and is BOX-resized on the device; the target sets the item's size
+and is never resized.  The default is the disk path, unchanged.
 """
 import json
 import os
@@ -29,7 +31,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
+from ._common import (F32, check_device_resize, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
                       resize, stack_views, tracker_entries)
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
@@ -354,7 +356,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, mask_data_dir, flow_data_dir, max_hw, mode, rgb_range="0_1", use_aug=False,
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
                  n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False):
+        check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -367,7 +370,7 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.device = None if device is None else torch.device(device)
         # resident source frames (datasets/resident.py): the store, and per scene the frame size and the cameras' derived values
-        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres) if resident else None
+        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize) if resident else None
         self._scene_shape, self._cam_cache = {}, {}
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.mask_data_dir, self.flow_data_dir = root / raw_data_dir, root / mask_data_dir, root / flow_data_dir
@@ -498,7 +501,9 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def _decode_frame(self, scene_id, time_id, shape):
         """(image uint8, dynamic mask, depth) of a train frame at the scene's size, as _process_view reads them"""
         p, cam_id, (h, w) = self.parser_dict[scene_id], self.get_train_cam_id(scene_id), shape
-        raw = resize(p.load_rgba(time_id, cam_id)[..., :3], h, w, PIL.Image.Resampling.BOX)
+        raw = p.load_rgba(time_id, cam_id)[..., :3]
+        if not self.store.device_resize:  # (else the image as decoded: the store resizes it)
+            raw = resize(raw, h, w, PIL.Image.Resampling.BOX)
         name = p.get_frame_name(time_id, cam_id)
         m = np.array(PIL.Image.open(self.mask_data_dir / scene_id / f"masks/final/{name}_final.png"))
         depth = p.load_depth(time_id, cam_id)

@@ -25,7 +25,8 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import F32, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views, tracker_entries
+from ._common import (F32, check_device_resize, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
+                      tracker_entries)
 from .nvidia_eval import spatial_depth_range
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
@@ -118,7 +119,8 @@ class MonoVisualizationDataset(Dataset):
     def __init__(self, *, data_root, max_hw, mode, rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
                  vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False):
+        check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
@@ -127,7 +129,8 @@ class MonoVisualizationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
         # the source frames kept in memory (datasets/resident.py)
-        self.store = SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres) if resident else None
+        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize)
+                      if resident else None)
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
         self.c2w_dict, self.K_dict, self.valid_fs = {}, {}, []
@@ -145,11 +148,13 @@ class MonoVisualizationDataset(Dataset):
         return len(self.valid_fs)
 
     @staticmethod
-    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None):
+    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None, resize_rgb=True):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size; ``raw``: the image file's pixels, where
-        the caller has opened it already"""
+        the caller has opened it already; ``resize_rgb`` False (``device_resize``): the image as decoded, the store resizes it"""
         h, w = tgt_shape
-        rgb = resize(np.array(PIL.Image.open(img_f)) if raw is None else raw, h, w, PIL.Image.Resampling.BOX)
+        rgb = np.array(PIL.Image.open(img_f)) if raw is None else raw
+        if resize_rgb:
+            rgb = resize(rgb, h, w, PIL.Image.Resampling.BOX)
         name = pathlib.Path(img_f).stem
         mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w, PIL.Image.Resampling.NEAREST)
         depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
@@ -190,7 +195,8 @@ class MonoVisualizationDataset(Dataset):
             return np.stack([flat_cam(*shape, all_K[f], all_c2w[f]) for f in ids]), all_K[list(ids)], all_c2w[list(ids)]
 
         scene = self.store.scene(scene_id, len(img_fs), shape)
-        return build_item(self.store, scene, lambda f: self._decode_frame(scene_dir, img_fs[f], shape), cams=cams,
+        return build_item(self.store, scene,
+                          lambda f: self._decode_frame(scene_dir, img_fs[f], shape, resize_rgb=not self.store.device_resize), cams=cams,
                           flow_path=lambda a, b: self._flow_path(scene_dir, img_fs, a, b), owner=type(self).__name__, **kw)
 
     def __getitem__(self, index):

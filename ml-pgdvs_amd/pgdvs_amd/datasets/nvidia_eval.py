@@ -38,6 +38,12 @@ point clouds upstream computes for the temporal and tracker views and then disca
 once and kept in a ``datasets.resident.SceneStore`` on ``device`` (None: host memory), and the items' source views are built
 from it, on a GPU by ``ops.item_views`` in one launch; the same keys, shapes, dtypes and bits, every tensor on the store's
 device.  The target image and the evaluation mask, one item's each, stay disk reads.  DESIGN.md 7f.
+
+``device_resize=True`` (needs ``resident=True`` and a GPU ``device``): a source frame's image goes to the store as decoded and is
+BOX-resized on the device into its slot (``ops.resample_u8``, Pillow's resampler bit for bit); the target image is decoded
+once, its shape is the file's (height 288) or the monocular video's, and its bytes are resized and expanded on the device, so
+``rgb_tgt`` is a device tensor; the pure-geometry loader's LANCZOS stack is one batched call.  Masks and depths keep the host
+NEAREST resize, and an image the device path does not serve takes the host statements.  DESIGN.md 7g.
 """
 import io
 import os
@@ -50,7 +56,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, TGT_HEIGHT, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
+from ._common import (F32, TGT_HEIGHT, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
                       read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
 from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -218,7 +224,9 @@ class NvidiaDynEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
-                 flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES):
+                 flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES,
+                 device_resize=False):
+        check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -240,7 +248,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
@@ -273,15 +281,18 @@ class NvidiaDynEvaluationDataset(Dataset):
     # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
     store = None  # the SceneStore of ``resident=True``
 
-    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device):
+    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, device_resize=False):
         if resident:
-            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres)
+            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_resize)
 
     def _decode_frame(self, scene_id, frame_id, tgt_shape):
-        """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them"""
+        """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
+        ``device_resize`` the image as decoded: the store resizes it"""
         h, w = tgt_shape
         depth = _resize(self._read_depth(scene_id, frame_id), h, w, PIL.Image.Resampling.NEAREST)
-        return self._read_src_rgb(self._src_img_f(scene_id, frame_id), h, w), self._read_mask(scene_id, frame_id, h, w), depth
+        img_f = self._src_img_f(scene_id, frame_id)
+        rgb = np.array(PIL.Image.open(img_f)) if self.store.device_resize else self._read_src_rgb(img_f, h, w)
+        return rgb, self._read_mask(scene_id, frame_id, h, w), depth
 
     def _resident_item(self, scene_id, tgt_shape, all_c2w, all_hwf, **kw):
         """``resident.build_item`` over this loader's readers and cameras"""
@@ -443,16 +454,30 @@ class NvidiaDynEvaluationDataset(Dataset):
         all_hwf, all_c2w = self._read_cam(scene_id)
         n_frames = all_hwf.shape[0]
         sel = select_temporal_frames(tgt_frame_id, tgt_cam_id, n_frames, getattr(self, "n_src_views_temporal_track_one_side", 0))
-        raw_rgb = self._target_rgb(scene_dir, img_f)
-        raw_h, raw_w = raw_rgb.shape[:2]
+        on_device = self.store is not None and self.store.device_resize
+        if on_device:  # decoded once: the LANCZOS pass of _target_rgb gave the shape alone, and the shape is known without it
+            raw_rgb = np.array(PIL.Image.open(img_f))
+            raw_h, raw_w = raw_rgb.shape[:2] if raw_rgb.shape[0] == TGT_HEIGHT else mono_size(scene_dir)
+            assert raw_h == TGT_HEIGHT, (raw_h, raw_w)
+        else:
+            raw_rgb = self._target_rgb(scene_dir, img_f)
+            raw_h, raw_w = raw_rgb.shape[:2]
         all_hwf[:, 0], all_hwf[:, 1] = raw_h, raw_w  # the stored h, w belong to the full-resolution capture (:399-401)
         tgt_shape = (raw_h, raw_w)
         # NOTE upstream indexes the poses with the CAMERA id: the 12 camera poses repeat (:319-323)
-        tgt = self._source_view(scene_id, tgt_frame_id, all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape,
-                                with_geometry=False, img_f=img_f)
+        if on_device:
+            tgt = {"flat_cam": flat_cam(raw_h, raw_w, *self._view_cam(all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape))}
+            if self.store.serves_target(raw_rgb, tgt_shape):  # the bytes travel with the item's small entries
+                rgb_tgt = ("__rgb_tgt", torch.from_numpy(np.ascontiguousarray(raw_rgb)))
+            else:  # _source_view's statements on the decoded image
+                rgb_tgt = ("rgb_tgt", F32(_resize(raw_rgb, raw_h, raw_w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0))
+        else:
+            tgt = self._source_view(scene_id, tgt_frame_id, all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape,
+                                    with_geometry=False, img_f=img_f)
+            rgb_tgt = ("rgb_tgt", F32(tgt["rgb"]))
         item = {
             "scene_id": scene_id,
-            "rgb_tgt": F32(tgt["rgb"]),
+            rgb_tgt[0]: rgb_tgt[1],
             "eval_mask": F32(self._read_eval_mask(scene_id, tgt_frame_id, tgt_cam_id, raw_h, raw_w)),
             "flat_cam_tgt": F32(tgt["flat_cam"]),
             "time_tgt": torch.FloatTensor([tgt_frame_id]),
@@ -483,10 +508,13 @@ class NvidiaDynEvaluationDataset(Dataset):
             seq = [c["tgt_frame_id"], *spatial_ids, *c["sel"]["temporal"]]
         host = {k: v for k, v in head.items() if isinstance(v, torch.Tensor)}
         host["seq_ids"] = torch.LongTensor(np.array(seq))
-        return self._resident_item(c["scene_id"], c["tgt_shape"], c["all_c2w"], c["all_hwf"],
+        item = self._resident_item(c["scene_id"], c["tgt_shape"], c["all_c2w"], c["all_hwf"],
                                    fixed={k: v for k, v in head.items() if k not in host}, host=host, sel=c["sel"],
                                    spatial_ids=spatial_ids, spatial_depth=True, c2w_tgt=c["all_c2w"][c["tgt_cam_id"]],
                                    trackers=with_spatial)
+        if "__rgb_tgt" in item:  # device_resize: the target's bytes as decoded
+            item["rgb_tgt"] = self.store.expand_target(item.pop("__rgb_tgt"), c["tgt_shape"])
+        return item
 
     def __getitem__(self, index):
         if self.store is not None:
@@ -516,13 +544,14 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
 
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
-                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES):
+                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False):
+        check_device_resize(device_resize, resident, device, type(self).__name__)
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
                          mask_data_dir=mask_data_dir, flow_data_dir=flow_data_dir, max_hw=max_hw, mode=mode,
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,
                          n_src_views_temporal_track_one_side=0, flow_consist_thres=flow_consist_thres)
         self.device = device
-        self._init_resident(resident, resident_scenes, resident_max_bytes, device)  # the store lives where the cloud is built
+        self._init_resident(resident, resident_scenes, resident_max_bytes, device, device_resize)  # the store lives where the cloud is built
         self.st_pcl_dict = {scene: self._aggregate_static_pcl(scene) for scene in sorted(self.scene_img_dict)}
 
     def _load_mono_video(self, scene_id):
@@ -533,8 +562,12 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
         all_hwf[:, 0], all_hwf[:, 1] = tgt_h, tgt_w
         n = all_hwf.shape[0]
         mono = scene_dir / f"images_{tgt_w}x{tgt_h}"
-        imgs = np.stack([_resize(np.array(PIL.Image.open(mono / f"{i:05d}.png")), tgt_h, tgt_w, PIL.Image.Resampling.LANCZOS)
-                         for i in range(n)]).astype(np.float32) / 255.0
+        if self.store is not None and self.store.device_resize:  # the frames of another size in one batched call
+            imgs = self.store.resize_stack([np.array(PIL.Image.open(mono / f"{i:05d}.png")) for i in range(n)], (tgt_h, tgt_w), "lanczos")
+            imgs = np.stack(imgs).astype(np.float32) / 255.0
+        else:
+            imgs = np.stack([_resize(np.array(PIL.Image.open(mono / f"{i:05d}.png")), tgt_h, tgt_w, PIL.Image.Resampling.LANCZOS)
+                             for i in range(n)]).astype(np.float32) / 255.0
         depths = np.stack([self._read_depth(scene_id, i) for i in range(n)]).astype(np.float32)
         masks = np.stack([self._read_mask(scene_id, i, tgt_h, tgt_w).astype(bool) for i in range(n)])
         K3s = np.stack([hwf_to_K(*all_hwf[i]) for i in range(n)])

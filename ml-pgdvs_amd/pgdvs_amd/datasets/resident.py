@@ -22,13 +22,20 @@ run is refused before anything is decoded.
 
 ``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
 it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
+
+``device_resize=True`` (a GPU store only): the loaders hand over a frame's image as decoded, at the file's size, and the store
+uploads the bytes and resizes them on the device straight into the frame's slot (``ops.resample_u8``, Pillow's BOX filter bit
+for bit); the evaluation loaders' target image goes the same way (``expand_target``) and the pure-geometry loader's LANCZOS
+stack in one batched call (``resize_stack``).  An image the device path does not serve (not uint8 [H,W,3], or a size
+``ops.resample_plan`` refuses) takes the host statements.  Masks and depths keep their host NEAREST resize.
 """
 from collections import OrderedDict
 
 import numpy as np
+import PIL.Image
 import torch
 
-from ._common import F32, read_flow_npz
+from ._common import F32, read_flow_npz, resize
 
 DEFAULT_MAX_BYTES = 4 << 30
 VIEW_KEYS = ("rgb", "dyn_rgb", "static_rgb", "dyn_mask", "depth")
@@ -60,7 +67,7 @@ class _Scene:
 class SceneStore:
     """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``)."""
 
-    def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0):
+    def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -70,7 +77,11 @@ class SceneStore:
             raise TypeError(f"flow_consist_thres must be a Python number (a NumPy scalar changes the compare's type), got {type(occ_thres)}")
         self.resident_scenes, self.resident_max_bytes, self.occ_thres = int(resident_scenes), int(resident_max_bytes), occ_thres
         self.scenes = OrderedDict()  # key -> _Scene, least recently used first
-        self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0}
+        if device_resize and self.device is None:
+            raise ValueError("SceneStore: device_resize=True resizes on a GPU, the store is in host memory (device=None)")
+        self.device_resize = bool(device_resize)
+        self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
+                      "targets_resized_on_device": 0}
 
     @property
     def nbytes(self):
@@ -124,17 +135,77 @@ class SceneStore:
             if not scene.filled[f - scene.first_id]:
                 self.put(scene, f, *decode(f))
 
+    # ------------------------------------------------------------------ the resize on the device
+    def _device_plan(self, image, shape, filter):
+        """the plan of ``image`` -> ``shape`` where the device path serves it: uint8 [H,W,3] of a size that is not refused"""
+        if not self.device_resize or image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            return None
+        from .. import ops
+
+        return ops.resample_plan(image.shape[:2], shape, filter, self.device, reject_ok=True)
+
+    def _upload(self, image):
+        """the bytes on the device through pinned memory: an asynchronous copy, nothing waits"""
+        host = torch.empty(image.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(torch.from_numpy(np.ascontiguousarray(image)))
+        return host.to(self.device, non_blocking=True)
+
+    def serves_target(self, image, shape):
+        """whether ``expand_target`` takes the image as decoded (else the caller makes the target with the host statements)"""
+        return self.device_resize and (tuple(image.shape[:2]) == tuple(shape) and image.dtype == np.uint8 and image.ndim == 3 and
+                                       image.shape[2] == 3 or self._device_plan(image, shape, "box") is not None)
+
+    def expand_target(self, image_u8, shape):
+        """a target's bytes on the device, as decoded -> float32 [h,w,3] = BOX-resized to ``shape`` where the size differs, / 255"""
+        from .. import ops
+
+        if tuple(image_u8.shape[:2]) != tuple(shape):
+            image_u8 = ops.resample_u8(image_u8, shape, "box")
+            self.stats["targets_resized_on_device"] += 1
+        return ops.item_target(image_u8)[0]
+
+    def resize_stack(self, images, shape, filter):
+        """``_common.resize(image, *shape, filter)`` of every image (host arrays in, host arrays out): images of one size that
+        the device path serves go through one batched ``ops.resample_u8``, the others through the host statement"""
+        from .. import ops
+
+        resample = {"box": PIL.Image.Resampling.BOX, "lanczos": PIL.Image.Resampling.LANCZOS}[filter]
+        out, batches = [None] * len(images), {}
+        for i, im in enumerate(images):
+            if tuple(im.shape[:2]) != tuple(shape) and self._device_plan(im, shape, filter) is not None:
+                batches.setdefault(im.shape, []).append(i)
+            else:
+                out[i] = resize(im, *shape, resample)
+        for idx in batches.values():
+            got = ops.resample_u8(self._upload(np.stack([images[i] for i in idx])), shape, filter).cpu().numpy()
+            self.stats["frames_resized_on_device"] += len(idx)
+            for i, g in zip(idx, got):
+                out[i] = g
+        return out
+
     def put(self, scene, f, rgb, mask, depth):
-        """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into the slot of frame id ``f``"""
+        """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into the slot of frame id ``f``.  With
+        ``device_resize`` the image may come at the file's size: it is BOX-resized into the slot on the device"""
         shape = (scene.h, scene.w)
         (slot,) = self.slots(scene, [f])
-        if rgb.dtype != np.uint8 or rgb.shape != shape + (3,):
+        plan = None
+        if self.device_resize and tuple(rgb.shape[:2]) != shape:
+            plan = self._device_plan(rgb, shape, "box")
+            if plan is None:
+                rgb = resize(rgb, *shape, PIL.Image.Resampling.BOX)  # the host statement
+        if plan is None and (rgb.dtype != np.uint8 or rgb.shape != shape + (3,)):
             raise ValueError(f"frame {f}: image {rgb.dtype} {rgb.shape}, the store keeps uint8 {shape + (3,)}")
         if mask.dtype not in (np.bool_, np.uint8) or mask.shape != shape:
             raise ValueError(f"frame {f}: mask {mask.dtype} {mask.shape}, the store keeps bool or uint8 {shape}")
         if depth.shape != shape:
             raise ValueError(f"frame {f}: depth {depth.shape}, expected {shape}")
-        scene.rgb[slot].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
+        if plan is not None:
+            from .. import ops
+
+            ops.resample_u8(self._upload(rgb), shape, "box", out=scene.rgb[slot])
+            self.stats["frames_resized_on_device"] += 1
+        else:
+            scene.rgb[slot].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
         scene.dyn_mask[slot].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
         scene.depth[slot].copy_(F32(depth))
         scene.filled[slot] = True

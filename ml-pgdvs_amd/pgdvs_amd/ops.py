@@ -8,6 +8,7 @@ this module computes on the CPU; CPU tensors are rejected.
 from __future__ import annotations
 
 import ctypes as C
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -935,6 +936,105 @@ def item_target(rgb_u8, covisible_u8=None, out=None):
             raise ValueError(f"item_target: {name} must be a contiguous float32 {shape} tensor on {c.device}")
     check(_lib.load().pgdvs_item_target(_ptr(c), _ptr(m), H, W, _ptr(out[0]), _ptr(out[1]), _stream()), "pgdvs_item_target")
     return out[0], out[1]
+
+
+RESAMPLE_FILTERS = {"box": 0, "lanczos": 1}
+RESAMPLE_PLANS = 32  # the plans kept, least recently used first out
+_resample_plans = OrderedDict()
+
+
+class ResamplePlan:
+    """The tables of one resize on one device: ``tables`` = (bounds_h, kk_h, bounds_v, kk_v), int32 GPU tensors as
+    ``pgdvs_resample_table`` makes them, None for an axis that keeps its size."""
+
+    def __init__(self, in_hw, out_hw, filter, device, tables):
+        self.in_hw, self.out_hw, self.filter, self.device, self.tables = in_hw, out_hw, filter, device, tables
+
+
+def _resample_axis(n_in, n_out, filter_id, device):
+    """one axis' (bounds [out,2], kk [out,ksize]) on ``device``, None when the axis keeps its size or the table entry refuses
+    it (the message stays in ``pgdvs_last_error``); the second value tells the two apart"""
+    lib = _lib.load()
+    ksize = lib.pgdvs_resample_table(n_in, n_out, filter_id, None, None)
+    if ksize < 0:
+        return None, False
+    if n_in == n_out:
+        return None, True
+    host = torch.empty(n_out * (2 + ksize), dtype=torch.int32, pin_memory=True)
+    bounds, kk = host[:n_out * 2], host[n_out * 2:]
+    if lib.pgdvs_resample_table(n_in, n_out, filter_id, C.c_void_p(bounds.data_ptr()), C.c_void_p(kk.data_ptr())) != ksize:
+        raise PgdvsHipError("pgdvs_resample_table: " + lib.pgdvs_last_error().decode("utf-8", "replace"))
+    dev = host.to(device, non_blocking=True)  # one copy from pinned memory; the stream orders it in front of its first use
+    return (dev[:n_out * 2].view(n_out, 2), dev[n_out * 2:].view(n_out, ksize)), True
+
+
+def resample_plan(in_hw, out_hw, filter, device, reject_ok: bool = False):
+    """The coefficient tables of ``resample_u8`` for images of ``in_hw`` = (H, W) resized to ``out_hw`` with ``filter`` ("box"
+    or "lanczos"): built on the host by ``pgdvs_resample_table`` (Pillow's precompute_coeffs and normalize_coeffs_8bpc),
+    uploaded to ``device`` and kept in an LRU of ``RESAMPLE_PLANS`` entries keyed by sizes, filter and device.  A size the
+    table entry refuses (outside 1 .. 16384, or more than 256 taps per output pixel) raises ValueError; with ``reject_ok``
+    it returns None instead, for callers that keep a host path.  Does not synchronise."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"resample: filter {filter!r}, expected one of {sorted(RESAMPLE_FILTERS)}")
+    in_hw, out_hw, device = tuple(int(x) for x in in_hw), tuple(int(x) for x in out_hw), torch.device(device)
+    if len(in_hw) != 2 or len(out_hw) != 2:
+        raise ValueError(f"resample: sizes (H, W) expected, got {in_hw} -> {out_hw}")
+    if device.type != "cuda":
+        raise ValueError(f"resample: the tables live on a GPU, got device {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (in_hw, out_hw, filter, device)
+    plan = _resample_plans.get(key)
+    if plan is not None:
+        _resample_plans.move_to_end(key)
+        return plan
+    fid = RESAMPLE_FILTERS[filter]
+    (tab_v, ok_v), (tab_h, ok_h) = (_resample_axis(in_hw[i], out_hw[i], fid, device) for i in (0, 1))
+    if not (ok_v and ok_h):
+        if reject_ok:
+            return None
+        raise ValueError(f"resample: {in_hw} -> {out_hw} ({filter}) is refused: " + _lib.load().pgdvs_last_error().decode("utf-8", "replace"))
+    plan = _resample_plans[key] = ResamplePlan(in_hw, out_hw, filter, device, (tab_h or (None, None)) + (tab_v or (None, None)))
+    while len(_resample_plans) > RESAMPLE_PLANS:
+        _resample_plans.popitem(last=False)
+    return plan
+
+
+def resample_u8(img, out_hw, filter, out=None):
+    """Pillow's ``Image.resize((w, h), resample=BOX | LANCZOS)`` of 8-bit images on the GPU, bit for bit (``pgdvs_resample_u8``;
+    include/pgdvs_hip.h).  ``img``: uint8 [H,W], [H,W,C] or [N,H,W,C] on the GPU, C 1 or 3, every frame contiguous (frames may
+    lie any distance apart, as a store's padded slots do); ``out_hw`` = (h, w); ``filter`` "box" or "lanczos".  Returns the
+    resized images in ``img``'s layout.  ``out``: a uint8 GPU tensor of that shape to fill in place, its frames contiguous
+    (e.g. a frame's slot of the resident store: the bytes between frames are left alone).  An axis that keeps its size is
+    skipped; with both kept the result is a copy.  Wrong dtype, device, channels, ``out`` or a refused size: ValueError before
+    anything is launched.  Does not synchronise."""
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or not img.is_cuda:
+        raise ValueError(f"resample_u8: img must be a uint8 GPU tensor, got {getattr(img, 'dtype', type(img))} on {getattr(img, 'device', None)}")
+    if img.ndim not in (2, 3, 4):
+        raise ValueError(f"resample_u8: img [H,W], [H,W,C] or [N,H,W,C] expected, got {tuple(img.shape)}")
+    x = img[None, ..., None] if img.ndim == 2 else (img[None] if img.ndim == 3 else img)
+    N, H, W, ch = (int(s) for s in x.shape)
+    if ch not in (1, 3) or N < 1:
+        raise ValueError(f"resample_u8: {N} frames of {ch} channels (at least one frame, 1 or 3 channels)")
+    if not x[0].is_contiguous() or (N > 1 and x.stride(0) < H * W * ch):
+        x = x.contiguous()
+    h, w = (int(s) for s in out_hw)
+    plan = resample_plan((H, W), (h, w), filter, x.device)
+    shape = {2: (h, w), 3: (h, w, ch), 4: (N, h, w, ch)}[img.ndim]
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != x.device or tuple(out.shape) != shape):
+        raise ValueError(f"resample_u8: out must be a uint8 {shape} tensor on {x.device}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    o = out[None, ..., None] if img.ndim == 2 else (out[None] if img.ndim == 3 else out)
+    if not o[0].is_contiguous() or (N > 1 and o.stride(0) < h * w * ch):
+        raise ValueError(f"resample_u8: out's frames must be contiguous and not overlap, strides {tuple(out.stride())}")
+    lib = _lib.load()
+    fid = RESAMPLE_FILTERS[filter]
+    ws = _ws(lib.pgdvs_resample_u8_workspace_bytes(N, H, W, ch, h, w, fid), x.device)
+    check(lib.pgdvs_resample_u8(_ptr(x), x.stride(0) if N > 1 else H * W * ch, N, H, W, ch, _ptr(o), o.stride(0) if N > 1 else h * w * ch,
+                                h, w, fid, *(_ptr(t) for t in plan.tables), _ptr(ws), ws.numel(), _stream()), "pgdvs_resample_u8")
+    return out
 
 
 def _flow_pair(a, b, names, what):

@@ -14,7 +14,11 @@ monocular layout for ``mono_vis``:
            spatial views, tracker windows of 5, device cuda:0): items/s as under ``items``, every resident item compared with
            the disk item (keys in order, bits), the target's upload bytes, and the ``ops.item_target`` launch alone (events,
            bytes, achieved bandwidth, share of the stream rate)
-``--legs nvidia,dycheck`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
+  device_resize  under ``items``: the same indices once more through a loader with ``device_resize=True`` (the
+           decoded frames are resized on the device), first and second pass, compared with the disk items bit for bit
+  resample the ``ops.resample_u8`` launches alone (HIP events, median, warmed): one 1080 x 2062 x 3 frame to 288 x 550 with
+           BOX and with LANCZOS, and the two passes' algorithmic bytes
+``--legs nvidia,dycheck,resample`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
 Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--legs dycheck] [--out FILE]"""
 import argparse
 import json
@@ -102,7 +106,7 @@ def write_trees(root, frames=F):
 
 
 def loaders(nvidia_root, mono_root, scene, mono_scene, center):
-    """name -> factory(resident) of the four loaders, on cuda:0"""
+    """name -> factory(resident, device_resize=False) of the four loaders, on cuda:0"""
     from pgdvs_amd.datasets.mono_vis import MonoVisualizationDataset
     from pgdvs_amd.datasets.nvidia_eval import NvidiaDynEvaluationDataset, NvidiaDynPureGeoEvaluationDataset
     from pgdvs_amd.datasets.nvidia_vis import NvidiaDynVisualizationDataset
@@ -110,12 +114,12 @@ def loaders(nvidia_root, mono_root, scene, mono_scene, center):
     nv = dict(data_root=nvidia_root, raw_data_dir="raw", depth_data_dir="depths", mask_data_dir="masks", flow_data_dir="flows",
               max_hw=-1, scene_ids=[scene], device="cuda:0")
     vis = dict(vis_center_time=center, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32)
-    out = {"nvidia_eval": lambda r: NvidiaDynEvaluationDataset(mode="eval", resident=r, **nv),
-           "nvidia_pure_geo": lambda r: NvidiaDynPureGeoEvaluationDataset(mode="eval", resident=r, **nv),
-           "nvidia_vis": lambda r: NvidiaDynVisualizationDataset(mode="vis", resident=r, **vis, **nv)}
+    out = {"nvidia_eval": lambda r, d=False: NvidiaDynEvaluationDataset(mode="eval", resident=r, device_resize=d, **nv),
+           "nvidia_pure_geo": lambda r, d=False: NvidiaDynPureGeoEvaluationDataset(mode="eval", resident=r, device_resize=d, **nv),
+           "nvidia_vis": lambda r, d=False: NvidiaDynVisualizationDataset(mode="vis", resident=r, device_resize=d, **vis, **nv)}
     if mono_root is not None:
-        out["mono_vis"] = lambda r: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[mono_scene],
-                                                             device="cuda:0", resident=r, **vis)
+        out["mono_vis"] = lambda r, d=False: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[mono_scene],
+                                                                      device="cuda:0", resident=r, device_resize=d, **vis)
     return out
 
 
@@ -152,6 +156,29 @@ def gather_case(reps):
     return {"views": views, "H": H, "W": W, "bytes_read": read, "bytes_written": written, "ms_median": med, "ms_min": mn,
             "streaming_bound_ms": bound_ms, "share_of_stream_rate": bound_ms / med,
             "distinct_frames_read": len({f for g, _ in groups for f in g})}
+
+
+def resample_case(reps):
+    """the two launches of ``ops.resample_u8`` alone, one source frame of the synthetic scene's size to the target's"""
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import _lib, ops
+
+    dev = torch.device("cuda:0")
+    src = torch.randint(0, 256, (SRC_H, SRC_W, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    rec = {"in": [SRC_H, SRC_W, 3], "out": [H, W, 3]}
+    for filter in ("box", "lanczos"):
+        plan = ops.resample_plan((SRC_H, SRC_W), (H, W), filter, dev)
+        ops.resample_u8(src, (H, W), filter, out=out)
+        med, mn = event_median(lambda: ops.resample_u8(src, (H, W), filter, out=out), reps, 4)
+        tmp = _lib.load().pgdvs_resample_u8_workspace_bytes(1, SRC_H, SRC_W, 3, H, W, ops.RESAMPLE_FILTERS[filter])
+        taps_v = int(plan.tables[3].shape[1])
+        # the horizontal pass reads the frame and writes the intermediate image; the vertical pass reads it once per tap row
+        # of every output row (from the L2) and writes the result
+        rec[filter] = {"ms_median": med, "ms_min": mn, "taps": [int(plan.tables[1].shape[1]), taps_v], "frame_bytes": src.numel(),
+                       "intermediate_bytes": int(tmp), "out_bytes": out.numel(),
+                       "streaming_bound_ms": (src.numel() + 2 * int(tmp) + out.numel()) / HBM_BYTES_PER_S * 1e3}
+    return rec
 
 
 DY_H, DY_W, DY_F, DY_FACTOR, DY_SCENE = 360, 480, 48, 2, "synthetic-iphone"
@@ -298,7 +325,7 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--vis-views", type=int, default=48)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck")
+    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "loader_bench.py measures on the GPU"
@@ -308,8 +335,11 @@ def main():
     scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
     rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
     legs = set(args.legs.split(","))
-    assert legs and legs <= {"nvidia", "dycheck"}, args.legs
+    assert legs and legs <= {"nvidia", "dycheck", "resample"}, args.legs
     try:
+        if "resample" in legs:
+            rec["resample"] = resample_case(args.reps)
+            print(f"resample: {rec['resample']}", file=sys.stderr, flush=True)
         if "dycheck" in legs:
             rec["dycheck"] = dycheck_case(scratch, args.items, args.reps)
             print(f"dycheck: {rec['dycheck']}", file=sys.stderr, flush=True)
@@ -331,14 +361,21 @@ def main():
             r_disk, want = timed_pass(disk, idx)
             r_first, got1 = timed_pass(res, idx)
             r_second, got2 = timed_pass(res, idx)
+            dr = fn(True, True)  # device_resize: the same indices, both passes
+            r_dr_first, got3 = timed_pass(dr, idx)
+            r_dr_second, got4 = timed_pass(dr, idx)
             rec["loaders"][name] = {
                 "len": len(disk), "disk_items_per_s": r_disk, "resident_first_pass_items_per_s": r_first,
                 "resident_second_pass_items_per_s": r_second, "second_pass_over_disk": r_second / r_disk,
                 "bit_identical": all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2)),
                 "views_per_item": int(sum(v.shape[0] for k, v in want[0].items() if k.startswith("rgb_src_"))),
-                "store_bytes": res.store.nbytes, "stats": dict(res.store.stats)}
+                "store_bytes": res.store.nbytes, "stats": dict(res.store.stats),
+                "device_resize_first_pass_items_per_s": r_dr_first, "device_resize_second_pass_items_per_s": r_dr_second,
+                "device_resize_first_pass_over_resident": r_dr_first / r_first,
+                "device_resize_bit_identical": all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got3, want, got4)),
+                "device_resize_stats": dict(dr.store.stats)}
             print(f"{name}: {rec['loaders'][name]}", file=sys.stderr, flush=True)
-            del want, got1, got2, disk, res
+            del want, got1, got2, got3, got4, disk, res, dr
             torch.cuda.empty_cache()
         if "nvidia" in legs:
             rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
