@@ -29,6 +29,7 @@
 // yuv420p): MCUs of 16 x 16 pixels and six blocks, Y00 Y01 Y10 Y11 Cb Cr, with libjpeg's 2 x 2 chroma average, edge rules and
 // dummy blocks (jpeg_coefficients_420_kernel), and the entropy coder above with six blocks per MCU (jpeg_segments_kernel<6>).
 #include "common.h"
+#include "quant8.h"
 #include "wave.h"
 
 namespace pgdvs {
@@ -107,20 +108,14 @@ constexpr int kBlockMaxBits = 20 + 63 * 26;                    // 1658: DC 9 + 1
 constexpr int kBlockMaxBytes = 2 * ((kBlockMaxBits + 7) / 8);  // 416: every byte stuffed
 
 // ---- coefficients ----------------------------------------------------------------------------------------------------------------
-// torchvision.utils.save_image's quantisation of the clamped image, as png.hip's quant 0: NaN -> 0
-__device__ __forceinline__ int quantise_save_image(float x) {
-  if (!(x == x)) return 0;
-  x = fminf(fmaxf(x, 0.0f), 1.0f);
-  const float v = fminf(fmaxf(__fadd_rn(__fmul_rn(x, 255.0f), 0.5f), 0.0f), 255.0f);
-  return (int)v;
-}
-
+// Both kernels quantise the pixels as *_combined.png is (quant8.h's quantise_save_image) and take these parameters.
 struct CoefParams {
-  const float *img;  // [B,3,H,W]
-  int16_t *coef;     // [B,nby,nbx,3,64]
-  int H, W, nby, nbx;
-  int n_mcu;         // B nby nbx
-  uint16_t q[2][64];  // natural order
+  const float *img;    // [B,3,H,W]
+  int16_t *coef;       // [B,nmy,nmx,3 or 6,64]
+  int H, W, nmy, nmx;  // the MCU grid: 8 x 8 pixels an MCU at 4:4:4, 16 x 16 at 4:2:0
+  int nby, nbx;        // ceil(H / 8), ceil(W / 8): at 4:4:4 the MCU grid again; at 4:2:0 luma blocks past them are dummies
+  int n_mcu;           // B nmy nmx
+  uint16_t q[2][64];   // natural order
 };
 
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
@@ -214,15 +209,6 @@ __global__ void __launch_bounds__(kBlock) jpeg_coefficients_kernel(CoefParams p)
 // ---- coefficients, 4:2:0 ---------------------------------------------------------------------------------------------------------
 // libjpeg's 4:2:0 (include/pgdvs_hip.h states the rules; pgdvs_amd/video.py restates them in numpy): one wavefront per 16 x 16
 // MCU, six blocks in the order Y00, Y01, Y10, Y11, Cb, Cr, lane = sample of the current 8 x 8 block, the DCT as above.
-struct Coef420Params {
-  const float *img;  // [B,3,H,W]
-  int16_t *coef;     // [B,nmy,nmx,6,64]
-  int H, W, nmy, nmx;
-  int nby, nbx;      // ceil(H / 8), ceil(W / 8): luma blocks past them are dummies
-  int n_mcu;         // B nmy nmx
-  uint16_t q[2][64];  // natural order
-};
-
 // Cb and Cr (0 .. 255) of the pixel at px, packed as Cb | Cr << 16 so that the four of a quad add up in one register
 __device__ __forceinline__ int cbcr_packed(const float *px, size_t plane) {
   const int R = quantise_save_image(px[0]), G = quantise_save_image(px[plane]), B = quantise_save_image(px[2 * plane]);
@@ -231,7 +217,7 @@ __device__ __forceinline__ int cbcr_packed(const float *px, size_t plane) {
   return cb | (cr << 16);
 }
 
-__global__ void __launch_bounds__(kBlock) jpeg_coefficients_420_kernel(Coef420Params p) {
+__global__ void __launch_bounds__(kBlock) jpeg_coefficients_420_kernel(CoefParams p) {
   __shared__ int s_q[2][64];
   __shared__ int s_a[kWaves][64];
   __shared__ int s_b[kWaves][64];
@@ -468,9 +454,10 @@ __global__ void __launch_bounds__(kBlock) jpeg_gather_kernel(ScanParams p) {
 struct ScanShape {
   int64_t n_mcu, seg_mcus, n_seg, slot_stride, capacity;
 };
-// nby, nbx: the MCU grid (16 x 16 pixel MCUs at bpm = 6); either way no more than 65536 pixels a side
+// nby, nbx: the MCU grid (16 x 16 pixel MCUs at bpm = 6), at most grid_side a side: either way no more than 65536 pixels
+constexpr int grid_side(int bpm) { return bpm == 3 ? 8192 : 4096; }
 bool scan_shape(int B, int nby, int nbx, int restart_mcus, int bpm, ScanShape &s) {
-  const int side = bpm == 3 ? 8192 : 4096;
+  const int side = grid_side(bpm);
   if (B < 1 || nby < 1 || nby > side || nbx < 1 || nbx > side || restart_mcus < 1 || restart_mcus > 65535) return false;
   s.n_mcu = (int64_t)nby * nbx;
   s.seg_mcus = restart_mcus < s.n_mcu ? restart_mcus : s.n_mcu;
@@ -515,6 +502,79 @@ void launch_scan(const int16_t *coef, int B, const ScanShape &s, const ScanWorks
   PGDVS_LAUNCH("jpeg_gather", jpeg_gather_kernel, dim3(n_slots), dim3(kBlock), 0, st, p);
 }
 
+// ---- the entry points' bodies, per blocks of an MCU (3: 4:4:4, 8 x 8 MCUs; 6: 4:2:0, 16 x 16); fn: the entry point, for the messages ----
+int coefficients(const char *fn, int bpm, const float *img_planar, int B, int H, int W, const uint16_t *qtab_luma,
+                 const uint16_t *qtab_chroma, int16_t *coef, hipStream_t st) {
+  PGDVS_REQUIRE(img_planar && qtab_luma && qtab_chroma && coef, "%s: null pointer", fn);
+  PGDVS_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "%s: bad shape B=%d H=%d W=%d (B >= 1, H and W in 1 .. 65535)", fn,
+                B, H, W);
+  const int mcu_px = bpm == 3 ? 8 : 16;
+  CoefParams p;
+  p.img = img_planar;
+  p.coef = coef;
+  p.H = H;
+  p.W = W;
+  p.nmy = (H + mcu_px - 1) / mcu_px;
+  p.nmx = (W + mcu_px - 1) / mcu_px;
+  p.nby = (H + 7) / 8;
+  p.nbx = (W + 7) / 8;
+  const int64_t n_coef = (int64_t)B * p.nmy * p.nmx * bpm * 64;
+  PGDVS_REQUIRE((int64_t)B * 3 * H * W < (1ll << 31) && n_coef < (1ll << 31),
+                "%s: B=%d H=%d W=%d: 3 B H W and the %lld coefficients must stay below 2^31", fn, B, H, W, (long long)n_coef);
+  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(img_planar) & 3) == 0 && (reinterpret_cast<uintptr_t>(coef) & 3) == 0,
+                "%s: img_planar or coef is not 4-byte aligned", fn);
+  p.n_mcu = B * p.nmy * p.nmx;
+  for (int i = 0; i < 64; ++i) {
+    PGDVS_REQUIRE(qtab_luma[i] >= 1 && qtab_luma[i] <= 255 && qtab_chroma[i] >= 1 && qtab_chroma[i] <= 255,
+                  "%s: quantisation table entry %d is %d / %d (1 .. 255: baseline, 8-bit tables)", fn, i, (int)qtab_luma[i],
+                  (int)qtab_chroma[i]);
+    p.q[0][i] = qtab_luma[i];
+    p.q[1][i] = qtab_chroma[i];
+  }
+  const dim3 grid((unsigned)cdiv(p.n_mcu, kWaves));
+  if (bpm == 3)
+    PGDVS_LAUNCH("jpeg_coefficients", jpeg_coefficients_kernel, grid, dim3(kBlock), 0, st, p);
+  else
+    PGDVS_LAUNCH("jpeg_coefficients_420", jpeg_coefficients_420_kernel, grid, dim3(kBlock), 0, st, p);
+  return check_launch(fn);
+}
+
+// scan_shape, with the entry point's complaint about a shape it refuses (the grid's names are those of the entry's arguments)
+bool checked_scan_shape(const char *fn, int bpm, int B, int ny, int nx, int restart_mcus, ScanShape &s) {
+  if (scan_shape(B, ny, nx, restart_mcus, bpm, s)) return true;
+  const char *g = bpm == 3 ? "nb" : "nm";
+  set_error("%s: bad shape B=%d %sy=%d %sx=%d restart_mcus=%d (B >= 1, %sy and %sx in 1 .. %d, restart_mcus in 1 .. 65535, B x the "
+            "frame's capacity below 2^31)", fn, B, g, ny, g, nx, restart_mcus, g, g, grid_side(bpm));
+  return false;
+}
+
+int64_t scan_workspace_bytes(const char *fn, int bpm, int B, int ny, int nx, int restart_mcus) {
+  ScanShape s;
+  if (!checked_scan_shape(fn, bpm, B, ny, nx, restart_mcus, s)) return -1;
+  return ScanWorkspace(nullptr, B, s).bytes;
+}
+
+template <int kBpm>
+int scan(const char *fn, const int16_t *coef, int B, int ny, int nx, int restart_mcus, uint8_t *out, int64_t out_stride, int32_t *nbytes,
+         void *workspace, int64_t workspace_bytes, hipStream_t st) {
+  PGDVS_REQUIRE(coef && out && nbytes && workspace, "%s: null pointer", fn);
+  PGDVS_REQUIRE(restart_mcus != 0, "%s: restart_mcus 0 (no restart markers) is host-only: the segments of the device pass are "
+                                   "byte-aligned; use 1 .. 65535", fn);
+  ScanShape s;
+  if (!checked_scan_shape(fn, kBpm, B, ny, nx, restart_mcus, s)) return PGDVS_ERR_INVALID;
+  const char *g = kBpm == 3 ? "nb" : "nm";
+  PGDVS_REQUIRE(out_stride >= s.capacity && (int64_t)B * out_stride < (1ll << 31),
+                "%s: out_stride %lld (at least the capacity %lld = %d %sy %sx + 2 (segments - 1), B out_stride < 2^31)", fn,
+                (long long)out_stride, (long long)s.capacity, kBpm * kBlockMaxBytes, g, g);
+  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(coef) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0 &&
+                    (reinterpret_cast<uintptr_t>(nbytes) & 3) == 0,
+                "%s: coef must be 16-byte, workspace 256-byte and nbytes 4-byte aligned", fn);
+  ScanWorkspace ws(workspace, B, s);
+  PGDVS_REQUIRE(workspace_bytes >= ws.bytes, "%s: workspace of %lld bytes, %lld needed", fn, (long long)workspace_bytes, (long long)ws.bytes);
+  launch_scan<kBpm>(coef, B, s, ws, out, out_stride, nbytes, st);
+  return check_launch(fn);
+}
+
 }  // namespace
 }  // namespace pgdvs
 
@@ -522,127 +582,28 @@ using namespace pgdvs;
 
 PGDVS_API int pgdvs_jpeg_coefficients(const float *img_planar, int B, int H, int W, const uint16_t *qtab_luma, const uint16_t *qtab_chroma,
                                       int16_t *coef, pgdvs_stream_t stream) {
-  PGDVS_REQUIRE(img_planar && qtab_luma && qtab_chroma && coef, "pgdvs_jpeg_coefficients: null pointer");
-  PGDVS_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535, "pgdvs_jpeg_coefficients: bad shape B=%d H=%d W=%d (B >= 1, H and W in 1 .. 65535)", B,
-                H, W);
-  const int nby = (H + 7) / 8, nbx = (W + 7) / 8;
-  PGDVS_REQUIRE((int64_t)B * 3 * H * W < (1ll << 31) && (int64_t)B * nby * nbx * 192 < (1ll << 31),
-                "pgdvs_jpeg_coefficients: B=%d H=%d W=%d: 3 B H W and the %lld coefficients must stay below 2^31", B, H, W,
-                (long long)B * nby * nbx * 192);
-  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(img_planar) & 3) == 0 && (reinterpret_cast<uintptr_t>(coef) & 3) == 0,
-                "pgdvs_jpeg_coefficients: img_planar or coef is not 4-byte aligned");
-  CoefParams p;
-  p.img = img_planar;
-  p.coef = coef;
-  p.H = H;
-  p.W = W;
-  p.nby = nby;
-  p.nbx = nbx;
-  p.n_mcu = B * nby * nbx;
-  for (int i = 0; i < 64; ++i) {
-    PGDVS_REQUIRE(qtab_luma[i] >= 1 && qtab_luma[i] <= 255 && qtab_chroma[i] >= 1 && qtab_chroma[i] <= 255,
-                  "pgdvs_jpeg_coefficients: quantisation table entry %d is %d / %d (1 .. 255: baseline, 8-bit tables)", i, (int)qtab_luma[i],
-                  (int)qtab_chroma[i]);
-    p.q[0][i] = qtab_luma[i];
-    p.q[1][i] = qtab_chroma[i];
-  }
-  PGDVS_LAUNCH("jpeg_coefficients", jpeg_coefficients_kernel, dim3((unsigned)cdiv(p.n_mcu, kWaves)), dim3(kBlock), 0, as_stream(stream), p);
-  return check_launch("pgdvs_jpeg_coefficients");
+  return coefficients("pgdvs_jpeg_coefficients", 3, img_planar, B, H, W, qtab_luma, qtab_chroma, coef, as_stream(stream));
 }
 
 PGDVS_API int64_t pgdvs_jpeg_scan_workspace_bytes(int B, int nby, int nbx, int restart_mcus) {
-  ScanShape s;
-  if (!scan_shape(B, nby, nbx, restart_mcus, 3, s)) {
-    set_error("pgdvs_jpeg_scan_workspace_bytes: bad shape B=%d nby=%d nbx=%d restart_mcus=%d (B >= 1, nby and nbx in 1 .. 8192, "
-              "restart_mcus in 1 .. 65535, B x the frame's capacity below 2^31)", B, nby, nbx, restart_mcus);
-    return -1;
-  }
-  return ScanWorkspace(nullptr, B, s).bytes;
+  return scan_workspace_bytes("pgdvs_jpeg_scan_workspace_bytes", 3, B, nby, nbx, restart_mcus);
 }
 
 PGDVS_API int pgdvs_jpeg_scan(const int16_t *coef, int B, int nby, int nbx, int restart_mcus, uint8_t *out, int64_t out_stride,
                               int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
-  PGDVS_REQUIRE(coef && out && nbytes && workspace, "pgdvs_jpeg_scan: null pointer");
-  PGDVS_REQUIRE(restart_mcus != 0, "pgdvs_jpeg_scan: restart_mcus 0 (no restart markers) is host-only: the segments of the device "
-                                   "pass are byte-aligned; use 1 .. 65535");
-  ScanShape s;
-  PGDVS_REQUIRE(scan_shape(B, nby, nbx, restart_mcus, 3, s),
-                "pgdvs_jpeg_scan: bad shape B=%d nby=%d nbx=%d restart_mcus=%d (B >= 1, nby and nbx in 1 .. 8192, restart_mcus in "
-                "1 .. 65535, B x the frame's capacity below 2^31)", B, nby, nbx, restart_mcus);
-  PGDVS_REQUIRE(out_stride >= s.capacity && (int64_t)B * out_stride < (1ll << 31),
-                "pgdvs_jpeg_scan: out_stride %lld (at least the capacity %lld = 1248 nby nbx + 2 (segments - 1), B out_stride < 2^31)",
-                (long long)out_stride, (long long)s.capacity);
-  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(coef) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0 &&
-                    (reinterpret_cast<uintptr_t>(nbytes) & 3) == 0,
-                "pgdvs_jpeg_scan: coef must be 16-byte, workspace 256-byte and nbytes 4-byte aligned");
-  ScanWorkspace ws(workspace, B, s);
-  PGDVS_REQUIRE(workspace_bytes >= ws.bytes, "pgdvs_jpeg_scan: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                (long long)ws.bytes);
-  launch_scan<3>(coef, B, s, ws, out, out_stride, nbytes, as_stream(stream));
-  return check_launch("pgdvs_jpeg_scan");
+  return scan<3>("pgdvs_jpeg_scan", coef, B, nby, nbx, restart_mcus, out, out_stride, nbytes, workspace, workspace_bytes, as_stream(stream));
 }
 
 PGDVS_API int pgdvs_jpeg_coefficients_420(const float *img_planar, int B, int H, int W, const uint16_t *qtab_luma,
                                           const uint16_t *qtab_chroma, int16_t *coef, pgdvs_stream_t stream) {
-  PGDVS_REQUIRE(img_planar && qtab_luma && qtab_chroma && coef, "pgdvs_jpeg_coefficients_420: null pointer");
-  PGDVS_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && W >= 1 && W <= 65535,
-                "pgdvs_jpeg_coefficients_420: bad shape B=%d H=%d W=%d (B >= 1, H and W in 1 .. 65535)", B, H, W);
-  const int nmy = (H + 15) / 16, nmx = (W + 15) / 16;
-  PGDVS_REQUIRE((int64_t)B * 3 * H * W < (1ll << 31) && (int64_t)B * nmy * nmx * 384 < (1ll << 31),
-                "pgdvs_jpeg_coefficients_420: B=%d H=%d W=%d: 3 B H W and the %lld coefficients must stay below 2^31", B, H, W,
-                (long long)B * nmy * nmx * 384);
-  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(img_planar) & 3) == 0 && (reinterpret_cast<uintptr_t>(coef) & 3) == 0,
-                "pgdvs_jpeg_coefficients_420: img_planar or coef is not 4-byte aligned");
-  Coef420Params p;
-  p.img = img_planar;
-  p.coef = coef;
-  p.H = H;
-  p.W = W;
-  p.nmy = nmy;
-  p.nmx = nmx;
-  p.nby = (H + 7) / 8;
-  p.nbx = (W + 7) / 8;
-  p.n_mcu = B * nmy * nmx;
-  for (int i = 0; i < 64; ++i) {
-    PGDVS_REQUIRE(qtab_luma[i] >= 1 && qtab_luma[i] <= 255 && qtab_chroma[i] >= 1 && qtab_chroma[i] <= 255,
-                  "pgdvs_jpeg_coefficients_420: quantisation table entry %d is %d / %d (1 .. 255: baseline, 8-bit tables)", i,
-                  (int)qtab_luma[i], (int)qtab_chroma[i]);
-    p.q[0][i] = qtab_luma[i];
-    p.q[1][i] = qtab_chroma[i];
-  }
-  PGDVS_LAUNCH("jpeg_coefficients_420", jpeg_coefficients_420_kernel, dim3((unsigned)cdiv(p.n_mcu, kWaves)), dim3(kBlock), 0,
-               as_stream(stream), p);
-  return check_launch("pgdvs_jpeg_coefficients_420");
+  return coefficients("pgdvs_jpeg_coefficients_420", 6, img_planar, B, H, W, qtab_luma, qtab_chroma, coef, as_stream(stream));
 }
 
 PGDVS_API int64_t pgdvs_jpeg_scan_420_workspace_bytes(int B, int nmy, int nmx, int restart_mcus) {
-  ScanShape s;
-  if (!scan_shape(B, nmy, nmx, restart_mcus, 6, s)) {
-    set_error("pgdvs_jpeg_scan_420_workspace_bytes: bad shape B=%d nmy=%d nmx=%d restart_mcus=%d (B >= 1, nmy and nmx in 1 .. 4096, "
-              "restart_mcus in 1 .. 65535, B x the frame's capacity below 2^31)", B, nmy, nmx, restart_mcus);
-    return -1;
-  }
-  return ScanWorkspace(nullptr, B, s).bytes;
+  return scan_workspace_bytes("pgdvs_jpeg_scan_420_workspace_bytes", 6, B, nmy, nmx, restart_mcus);
 }
 
 PGDVS_API int pgdvs_jpeg_scan_420(const int16_t *coef, int B, int nmy, int nmx, int restart_mcus, uint8_t *out, int64_t out_stride,
                                   int32_t *nbytes, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
-  PGDVS_REQUIRE(coef && out && nbytes && workspace, "pgdvs_jpeg_scan_420: null pointer");
-  PGDVS_REQUIRE(restart_mcus != 0, "pgdvs_jpeg_scan_420: restart_mcus 0 (no restart markers) is host-only: the segments of the "
-                                   "device pass are byte-aligned; use 1 .. 65535");
-  ScanShape s;
-  PGDVS_REQUIRE(scan_shape(B, nmy, nmx, restart_mcus, 6, s),
-                "pgdvs_jpeg_scan_420: bad shape B=%d nmy=%d nmx=%d restart_mcus=%d (B >= 1, nmy and nmx in 1 .. 4096, restart_mcus in "
-                "1 .. 65535, B x the frame's capacity below 2^31)", B, nmy, nmx, restart_mcus);
-  PGDVS_REQUIRE(out_stride >= s.capacity && (int64_t)B * out_stride < (1ll << 31),
-                "pgdvs_jpeg_scan_420: out_stride %lld (at least the capacity %lld = 2496 nmy nmx + 2 (segments - 1), B out_stride < 2^31)",
-                (long long)out_stride, (long long)s.capacity);
-  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(coef) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0 &&
-                    (reinterpret_cast<uintptr_t>(nbytes) & 3) == 0,
-                "pgdvs_jpeg_scan_420: coef must be 16-byte, workspace 256-byte and nbytes 4-byte aligned");
-  ScanWorkspace ws(workspace, B, s);
-  PGDVS_REQUIRE(workspace_bytes >= ws.bytes, "pgdvs_jpeg_scan_420: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-                (long long)ws.bytes);
-  launch_scan<6>(coef, B, s, ws, out, out_stride, nbytes, as_stream(stream));
-  return check_launch("pgdvs_jpeg_scan_420");
+  return scan<6>("pgdvs_jpeg_scan_420", coef, B, nmy, nmx, restart_mcus, out, out_stride, nbytes, workspace, workspace_bytes, as_stream(stream));
 }

@@ -32,6 +32,7 @@
 // pgdvs_flow_pair_export; the first, in flow_export.hip, left the radius maximum as per-block keys).
 #include "common.h"
 #include "flow_pixel.h"
+#include "quant8.h"
 #include "wave.h"
 
 namespace pgdvs {
@@ -104,13 +105,8 @@ __device__ __forceinline__ uint32_t flow_colour(float2 f, float denom) {
   return rgb;
 }
 
-__device__ __forceinline__ uint32_t quantise(float x, int quant) {
-  if (!(x == x)) return 0u;
-  x = fminf(fmaxf(x, 0.0f), 1.0f);
-  float v = __fmul_rn(x, 255.0f);
-  if (quant == 0) v = fminf(fmaxf(__fadd_rn(v, 0.5f), 0.0f), 255.0f);
-  return (uint32_t)(int)v;
-}
+// quant: 0 save_image, 1 truncate (quant8.h)
+__device__ __forceinline__ uint32_t quantise(float x, int quant) { return quantise8(x, quant == 0); }
 
 // Stage pixels [c0, c0 + n) of an image row (kPlanar: plane 0 of it at `src`; kHwc, kFlow: its first float at `src`) into `dst`: pixel
 // c0 + i at bytes kLead + 3 i, the pixel to the left of c0 (zero for c0 = 0) at bytes 5..7.  zero: the row above row 0.

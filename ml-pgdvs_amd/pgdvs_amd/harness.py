@@ -777,20 +777,11 @@ MAX_RUN_AHEAD = 3
 
 
 def _write_record(path, info):
-    import os
     import pickle
 
-    tmp = path.with_name(f".{path.name}.{os.getpid()}.tmp")
-    try:
-        with open(tmp, "wb") as f:
-            pickle.dump(info, f)
-        os.replace(tmp, path)
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
+    from . import png
+
+    png.atomic_write(path, pickle.dumps(info))
 
 
 @torch.no_grad()

@@ -8,6 +8,7 @@ this module computes on the CPU; CPU tensors are rejected.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections import OrderedDict
 
 import numpy as np
@@ -63,6 +64,37 @@ def _ws(nbytes: int, device) -> torch.Tensor:
         msg = _lib.load().pgdvs_last_error().decode("utf-8", "replace")
         raise PgdvsHipError(f"workspace query rejected the shape (status {int(nbytes)}): {msg}")
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+def _out(out, shape, dtype, device, what, *, at_least=None, flat=False, shown=None):
+    """A caller's ``out=`` tensor after its check -- a contiguous ``dtype`` tensor of ``shape`` on the GPU ``device`` -- or a
+    fresh one when ``out`` is None.  ``at_least``: the last dimension may be anything from ``at_least`` up (rows with room to
+    spare).  ``flat``: only the element count has to be ``shape``'s.  The ValueError names the argument as ``what``
+    ("op: out") and the shape as ``shown`` (by default ``shape`` itself, or its rows and ``at_least``)."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    ok = isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == dtype and out.is_contiguous()
+    if ok and flat:
+        ok = out.numel() == math.prod(shape)
+    elif ok and at_least is not None:
+        ok = out.ndim == len(shape) and out.shape[:-1] == shape[:-1] and out.shape[-1] >= at_least
+    elif ok:
+        ok = tuple(out.shape) == tuple(shape)
+    if not ok:
+        if shown is None:
+            shown = f"tensor of {shape}" if at_least is None else f"tensor [{', '.join(str(s) for s in shape[:-1])}, >= {at_least}]"
+        raise ValueError(f"{what} must be a contiguous {str(dtype).rpartition('.')[2]} {shown} on {device}")
+    return out
+
+
+def _planar_batch(img, what):
+    """img [B,3,H,W] or [3,H,W] -> (the float32 contiguous GPU tensor [B,3,H,W], B, H, W)"""
+    x = _req(img, torch.float32, "img")
+    if x.ndim == 3:
+        x = x[None]
+    if x.ndim != 4 or x.shape[1] != 3:
+        raise ValueError(f"{what}: img [B,3,H,W] expected, got {tuple(x.shape)}")
+    return (x, int(x.shape[0]), int(x.shape[2]), int(x.shape[3]))
 
 
 # ---------------------------------------------------------------------------
@@ -931,9 +963,8 @@ def item_target(rgb_u8, covisible_u8=None, out=None):
     if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[1] is None) != (m is None):
         raise ValueError("item_target: out is a pair (rgb, mask), the mask None exactly when covisible_u8 is")
     for t, shape, name in ((out[0], (H, W, 3), "out[0]"), (out[1], (H, W, 1), "out[1]")):
-        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != c.device or t.dtype != torch.float32 or
-                              not t.is_contiguous() or tuple(t.shape) != shape):
-            raise ValueError(f"item_target: {name} must be a contiguous float32 {shape} tensor on {c.device}")
+        if t is not None:
+            _out(t, shape, torch.float32, c.device, f"item_target: {name}", shown=f"{shape} tensor")
     check(_lib.load().pgdvs_item_target(_ptr(c), _ptr(m), H, W, _ptr(out[0]), _ptr(out[1]), _stream()), "pgdvs_item_target")
     return out[0], out[1]
 
@@ -1078,11 +1109,7 @@ def flow_tile_blend(tiles, origins, weight, H, W):
 
 def _flow_export(a, b, H, W, adaptive, cd1, cd2, out, what):
     shape = (1 if b is None else 2, H, 1 + 3 * W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=a.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == a.device and out.dtype == torch.uint8
-              and out.is_contiguous() and out.numel() == shape[0] * shape[1] * shape[2]):
-        raise ValueError(f"{what}: out must be a contiguous uint8 tensor of {shape} on {a.device}")
+    out = _out(out, shape, torch.uint8, a.device, f"{what}: out", flat=True)
     lib = _lib.load()
     ws = _ws(lib.pgdvs_flow_pair_export_workspace_bytes(H, W), a.device)
     rad_max = torch.empty((shape[0],), dtype=torch.float32, device=a.device)
@@ -1284,19 +1311,9 @@ def png_scanlines(img, *, quant="save_image", adaptive=True, out=None):
     B H (1 + 3 W) elements to fill in place (any alignment)."""
     if quant not in PNG_QUANT:
         raise ValueError(f"png_scanlines: quant {quant!r} (one of {sorted(PNG_QUANT)})")
-    x = _req(img, torch.float32, "img")
-    if x.ndim == 3:
-        x = x[None]
-    if x.ndim != 4 or x.shape[1] != 3:
-        raise ValueError(f"png_scanlines: img [B,3,H,W] expected, got {tuple(x.shape)}")
-    B, _, H, W = (int(v) for v in x.shape)
+    x, B, H, W = _planar_batch(img, "png_scanlines")
     shape = (B, H, 1 + 3 * W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
-    else:
-        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == x.device and out.dtype == torch.uint8
-                and out.is_contiguous() and out.numel() == B * H * (1 + 3 * W)):
-            raise ValueError(f"png_scanlines: out must be a contiguous uint8 tensor of {shape} on {x.device}")
+    out = _out(out, shape, torch.uint8, x.device, "png_scanlines: out", flat=True)
     check(_lib.load().pgdvs_png_scanlines(_ptr(x), B, H, W, PNG_QUANT[quant], 1 if adaptive else 0, _ptr(out), _stream()),
           "pgdvs_png_scanlines")
     return out.view(shape)
@@ -1334,11 +1351,8 @@ def png_deflate(scanlines, seg_bytes=None, out=None):
     x = scanlines.contiguous()
     n, img_bytes = int(x.shape[0]), int(x[0].numel())
     seg = png.check_seg_bytes(seg_bytes)
-    if out is None:
-        out = torch.empty((n, png.deflate_capacity(img_bytes, seg)), dtype=torch.uint8, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.uint8 and out.is_contiguous()
-              and out.ndim == 2 and out.shape[0] == n and out.shape[1] >= 1):
-        raise ValueError(f"png_deflate: out must be a contiguous uint8 tensor [{n}, stride] on {x.device}")
+    out = _out(out, (n, png.deflate_capacity(img_bytes, seg)), torch.uint8, x.device, "png_deflate: out", at_least=1,
+               shown=f"tensor [{n}, stride]")
     lib = _lib.load()
     ws = _ws(lib.pgdvs_png_deflate_workspace_bytes(n, img_bytes, seg), x.device)
     nbytes = torch.empty((n,), dtype=torch.int32, device=x.device)
@@ -1364,19 +1378,12 @@ def jpeg_coefficients(img, quality=90, out=None, subsampling="4:4:4"):
     from . import video
 
     video.check_subsampling(subsampling)
-    x = _req(img, torch.float32, "img")
-    if x.ndim == 3:
-        x = x[None]
-    if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] < 1 or x.shape[3] < 1:
+    x, B, H, W = _planar_batch(img, "jpeg_coefficients")
+    if H < 1 or W < 1:
         raise ValueError(f"jpeg_coefficients: img [B,3,H,W] expected, got {tuple(x.shape)}")
     luma, chroma = video.quant_tables(quality) if np.isscalar(quality) else quality
-    B, _, H, W = (int(v) for v in x.shape)
     shape = (B, *video.mcu_grid(H, W, subsampling), video.BLOCKS_PER_MCU[subsampling], 64)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int16, device=x.device)
-    elif not (isinstance(out, torch.Tensor) and out.device == x.device and out.dtype == torch.int16 and out.is_contiguous()
-              and tuple(out.shape) == shape):
-        raise ValueError(f"jpeg_coefficients: out must be a contiguous int16 tensor of {shape} on {x.device}")
+    out = _out(out, shape, torch.int16, x.device, "jpeg_coefficients: out")
     name = "pgdvs_jpeg_coefficients" if subsampling == "4:4:4" else "pgdvs_jpeg_coefficients_420"
     check(getattr(_lib.load(), name)(_ptr(x), B, H, W, _quant_ptr(luma, "jpeg_coefficients"), _quant_ptr(chroma, "jpeg_coefficients"),
                                      _ptr(out), _stream()), name)
@@ -1419,11 +1426,7 @@ def jpeg_scan(coef, restart_mcus=None, out=None):
     if not 1 <= R <= 65535:
         raise ValueError(f"jpeg_scan: restart_mcus {restart_mcus} (1 .. 65535)")
     cap = jpeg_scan_capacity(nby, nbx, R, bpm)
-    if out is None:
-        out = torch.empty((B, cap), dtype=torch.uint8, device=c.device)
-    elif not (isinstance(out, torch.Tensor) and out.device == c.device and out.dtype == torch.uint8 and out.is_contiguous()
-              and out.ndim == 2 and out.shape[0] == B and out.shape[1] >= cap):
-        raise ValueError(f"jpeg_scan: out must be a contiguous uint8 tensor [{B}, >= {cap}] on {c.device}")
+    out = _out(out, (B, cap), torch.uint8, c.device, "jpeg_scan: out", at_least=cap)
     lib = _lib.load()
     ws = _ws(getattr(lib, name + "_workspace_bytes")(B, nby, nbx, R), c.device)
     nbytes = torch.empty((B,), dtype=torch.int32, device=c.device)
@@ -1453,11 +1456,7 @@ def eval_export_scanlines(pred, gt_hwc, static=None, adaptive=True, out=None):
                          f"{tuple(g.shape)}, {tuple(s_.shape) if s_ is not None else None}")
     H, W = int(p.shape[1]), int(p.shape[2])
     shape = (3 if s_ is not None else 2, H, 1 + 3 * W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=p.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == p.device and out.dtype == torch.uint8
-              and out.is_contiguous() and out.numel() == shape[0] * shape[1] * shape[2]):
-        raise ValueError(f"eval_export_scanlines: out must be a contiguous uint8 tensor of {shape} on {p.device}")
+    out = _out(out, shape, torch.uint8, p.device, "eval_export_scanlines: out", flat=True)
     check(_lib.load().pgdvs_eval_export_scanlines(_ptr(p), _ptr(g), _ptr(s_), H, W, 1 if adaptive else 0, _ptr(out), _stream()),
           "pgdvs_eval_export_scanlines")
     return out.view(shape)

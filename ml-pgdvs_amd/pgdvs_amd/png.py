@@ -90,7 +90,7 @@ def encode(scanlines, H: int, W: int, level: int = 1) -> bytes:
 def write_file(path, scanlines, H: int, W: int, level: int = 1) -> int:
     """``encode`` to ``path`` through a temporary name and a rename (a reader never sees a partial file); returns the bytes
     written."""
-    return _write_bytes(path, encode(scanlines, H, W, level))
+    return atomic_write(path, encode(scanlines, H, W, level))
 
 
 # ---- the device deflate's stream, restated ------------------------------------------------------------------------------------
@@ -316,10 +316,11 @@ def _png_parts(zstream, H: int, W: int) -> list:
     return [head, z, struct.pack(">I", zlib.crc32(z, zlib.crc32(b"IDAT"))) + _chunk(b"IEND", b"")]
 
 
-def _write_bytes(path, data) -> int:
-    """``data`` (a buffer or a list of buffers) to ``path`` through a temporary name and a rename; returns the bytes written"""
+def atomic_write(path, parts) -> int:
+    """``parts`` (a buffer or a list of buffers) to ``path`` through a temporary name beside it and a rename, so that no reader
+    meets half a file; the temporary file is removed on any failure.  Returns the bytes written."""
     path = pathlib.Path(path)
-    parts = data if isinstance(data, list) else [data]
+    parts = parts if isinstance(parts, list) else [parts]
     tmp = path.with_name(f".{path.name}.{os.getpid()}.{threading.get_ident()}.tmp")
     try:
         with open(tmp, "wb") as f:
@@ -337,7 +338,7 @@ def _write_bytes(path, data) -> int:
 def _check_scanlines(what, x):
     if x.ndim != 2 or (x.shape[1] - 1) % 3 != 0 or x.shape[1] < 4:
         raise ValueError(f"{what}: scanlines [H,1+3W] expected, got {tuple(x.shape)}")
-    if x.dtype != torch.uint8:
+    if x.dtype not in (torch.uint8, np.dtype(np.uint8)):
         raise ValueError(f"{what}: uint8 expected, got {x.dtype}")
 
 
@@ -361,7 +362,92 @@ class _DeviceSlot:
         self.left = 0
 
 
-class PngWriter:
+class AsyncWriter:
+    """What ``PngWriter`` and ``video.MjpegWriter`` share: a thread pool whose workers' first exception is kept and raised
+    once, at ``close()`` (a second ``close()`` returns quietly), the refusal of work after ``close()``, the ``with`` protocol,
+    one copy stream per device, and a worker's fetch of a device-counted run of bytes through pinned memory.  ``n_threads``
+    is fixed by the caller (at most ``MAX_THREADS``) and never derived from the machine's CPU count."""
+
+    def __init__(self, n_threads: int, thread_name_prefix: str):
+        if not 1 <= int(n_threads) <= MAX_THREADS:
+            raise ValueError(f"{type(self).__name__}: n_threads {n_threads} (1 .. {MAX_THREADS})")
+        self.n_threads = int(n_threads)
+        self._pool = ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix=thread_name_prefix)
+        self._lock = threading.Lock()
+        self._futures = []
+        self._error = None
+        self._copy_stream = {}
+        self._tls = threading.local()
+        self._closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        try:
+            self.close()
+        except BaseException:
+            if exc_type is None:
+                raise
+        return False
+
+    def _check_open(self, what: str) -> None:
+        if self._closed:
+            raise RuntimeError(f"{what} after close()")
+
+    def _guard(self, fn, *args):
+        try:
+            fn(*args)
+        except BaseException as e:  # kept for close()
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
+    def _run(self, fn, *args) -> None:
+        """``fn(*args)`` on a worker thread; what it raises waits for ``close()``"""
+        self._futures.append(self._pool.submit(self._guard, fn, *args))
+
+    def copy_stream(self, device):
+        cs = self._copy_stream.get(device.index)
+        if cs is None:
+            cs = self._copy_stream[device.index] = torch.cuda.Stream(device=device)
+        return cs
+
+    def _fetch(self, n, row, stream, refusal):
+        """The first ``n`` bytes of the device buffer ``row`` on the host: ``n`` is a count the device wrote, already landed
+        in pinned memory, and is refused (``RuntimeError(refusal(n, capacity))``) outside 0 .. ``row.numel()``; the copy runs
+        on ``stream`` into this thread's pinned staging buffer, grown as needed, and the stream is synchronised.  The view
+        returned is good until this thread's next fetch."""
+        n = int(n)
+        if not 0 <= n <= row.numel():
+            raise RuntimeError(refusal(n, row.numel()))
+        with torch.cuda.stream(stream):
+            buf = getattr(self._tls, "buf", None)
+            if buf is None or buf.numel() < n:
+                buf = self._tls.buf = torch.empty(max(n, 1 << 20), dtype=torch.uint8).pin_memory()
+            host = buf[:n]
+            host.copy_(row[:n], non_blocking=True)
+        stream.synchronize()
+        return host
+
+    def _drained(self) -> None:
+        """what ``close()`` does once every worker has finished (an exception raised here counts as a worker's)"""
+
+    def close(self) -> None:
+        """Wait for everything submitted, stop the workers and raise the first exception one of them met."""
+        if not self._closed:
+            self._closed = True
+            for f in self._futures:
+                f.result()
+            self._futures = []
+            self._pool.shutdown(wait=True)
+            self._guard(self._drained)
+        err, self._error = self._error, None
+        if err is not None:
+            raise err
+
+
+class PngWriter(AsyncWriter):
     """Writes scanline buffers as PNG files behind the caller.
 
     ``submit(path, scanlines)`` takes one image's scanlines [H,1+3W] uint8.  For a GPU tensor it takes a free slot of the ring
@@ -388,36 +474,16 @@ class PngWriter:
             raise ValueError(f"PngWriter: deflate {deflate!r} (one of {DEFLATE_MODES})")
         self.deflate = deflate
         self.seg_bytes = check_seg_bytes(seg_bytes)
-        if not 1 <= int(n_threads) <= MAX_THREADS:
-            raise ValueError(f"PngWriter: n_threads {n_threads} (1 .. {MAX_THREADS})")
-        self.n_threads = int(n_threads)
+        super().__init__(n_threads, "png")
         self.n_slots = int(n_slots) if n_slots is not None else 2 * self.n_threads
         if self.n_slots < 1:
             raise ValueError(f"PngWriter: n_slots {n_slots}")
         self.level = int(level)
-        self._pool = ThreadPoolExecutor(max_workers=self.n_threads, thread_name_prefix="png")
         self._free = threading.Semaphore(self.n_slots)
-        self._lock = threading.Lock()
         self._slots = []  # free (pinned buffer, event) pairs
-        self._futures = []
-        self._error = None
-        self._copy_stream = {}
         self._device_slots = []  # free _DeviceSlot objects
-        self._tls = threading.local()
-        self._closed = False
         self.bytes_written = 0
         self.files_written = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, exc_type, exc, tb):
-        try:
-            self.close()
-        except BaseException:
-            if exc_type is None:
-                raise
-        return False
 
     def _take_slot(self, nbytes: int):
         self._free.acquire()
@@ -432,18 +498,16 @@ class PngWriter:
             self._slots.append(slot)
         self._free.release()
 
+    def _count(self, n_file: int) -> None:
+        with self._lock:
+            self.bytes_written += n_file
+            self.files_written += 1
+
     def _work(self, path, buf, H, W, slot):
         try:
             if slot is not None:
                 slot[1].synchronize()
-            n = write_file(path, buf, H, W, self.level)
-            with self._lock:
-                self.bytes_written += n
-                self.files_written += 1
-        except BaseException as e:  # kept for close()
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            self._count(write_file(path, buf, H, W, self.level))
         finally:
             if slot is not None:
                 self._release_slot(slot)
@@ -451,27 +515,12 @@ class PngWriter:
     def _work_device(self, path, data, i, H, W, slot):
         try:
             slot.event.synchronize()
-            n = int(slot.n_host[i])
-            if not 0 <= n <= data.shape[1]:
-                raise RuntimeError(f"PngWriter: the device deflate of {path} reports {n} bytes (capacity {data.shape[1]})")
-            fetch = getattr(self._tls, "fetch", None)  # this worker's stream and pinned staging, grown as needed
+            fetch = getattr(self._tls, "fetch", None)  # this worker's own stream
             if fetch is None or fetch.device != data.device:
                 fetch = self._tls.fetch = torch.cuda.Stream(device=data.device)
-            buf = getattr(self._tls, "buf", None)
-            if buf is None or buf.numel() < n:
-                buf = self._tls.buf = torch.empty(max(n, 1 << 20), dtype=torch.uint8).pin_memory()
-            host = buf[:n]
-            with torch.cuda.stream(fetch):
-                host.copy_(data[i, :n], non_blocking=True)
-            fetch.synchronize()
-            n_file = _write_bytes(path, _png_parts(host.numpy(), H, W))
-            with self._lock:
-                self.bytes_written += n_file
-                self.files_written += 1
-        except BaseException as e:  # kept for close()
-            with self._lock:
-                if self._error is None:
-                    self._error = e
+            host = self._fetch(slot.n_host[i], data[i], fetch, lambda n, capacity: (
+                f"PngWriter: the device deflate of {path} reports {n} bytes (capacity {capacity})"))
+            self._count(atomic_write(path, _png_parts(host.numpy(), H, W)))
         finally:
             with self._lock:
                 slot.left -= 1
@@ -492,9 +541,7 @@ class PngWriter:
         if slot is None or slot.n_host.numel() < n:
             slot = _DeviceSlot(n)
         try:
-            cs = self._copy_stream.get(dev.index)
-            if cs is None:
-                cs = self._copy_stream[dev.index] = torch.cuda.Stream(device=dev)
+            cs = self.copy_stream(dev)
             cs.wait_event(ready if ready is not None else torch.cuda.current_stream(dev).record_event())
             with torch.cuda.stream(cs):
                 data, nbytes = ops.png_deflate(_as_batch(items), self.seg_bytes)
@@ -509,11 +556,10 @@ class PngWriter:
             raise
         slot.left = n
         for i, path in enumerate(paths):
-            self._futures.append(self._pool.submit(self._work_device, path, data, i, H, W, slot))
+            self._run(self._work_device, path, data, i, H, W, slot)
 
     def submit_batch(self, paths, scanlines, ready=None) -> None:
-        if self._closed:
-            raise RuntimeError("PngWriter.submit_batch after close()")
+        self._check_open("PngWriter.submit_batch")
         paths = list(paths)
         items = [scanlines[i] for i in range(scanlines.shape[0])] if hasattr(scanlines, "shape") else list(scanlines)
         if not paths or len(paths) != len(items):
@@ -528,14 +574,10 @@ class PngWriter:
         self._submit_device(paths, items, ready)
 
     def submit(self, path, scanlines, ready=None) -> None:
-        if self._closed:
-            raise RuntimeError("PngWriter.submit after close()")
-        if scanlines.ndim != 2 or (scanlines.shape[1] - 1) % 3 != 0 or scanlines.shape[1] < 4:
-            raise ValueError(f"PngWriter.submit: scanlines [H,1+3W] expected, got {tuple(scanlines.shape)}")
+        self._check_open("PngWriter.submit")
+        _check_scanlines("PngWriter.submit", scanlines)
         H, W = int(scanlines.shape[0]), (int(scanlines.shape[1]) - 1) // 3
         if isinstance(scanlines, torch.Tensor) and scanlines.is_cuda:
-            if scanlines.dtype != torch.uint8:
-                raise ValueError(f"PngWriter.submit: uint8 expected, got {scanlines.dtype}")
             if self.deflate == "device":
                 self._submit_device([path], [scanlines], ready)
                 return
@@ -543,9 +585,7 @@ class PngWriter:
             slot = self._take_slot(src.numel())
             try:
                 dev = src.device
-                cs = self._copy_stream.get(dev.index)
-                if cs is None:
-                    cs = self._copy_stream[dev.index] = torch.cuda.Stream(device=dev)
+                cs = self.copy_stream(dev)
                 cs.wait_event(ready if ready is not None else torch.cuda.current_stream(dev).record_event())
                 host = slot[0][:src.numel()]
                 with torch.cuda.stream(cs):
@@ -555,23 +595,11 @@ class PngWriter:
             except BaseException:
                 self._release_slot(slot)
                 raise
-            self._futures.append(self._pool.submit(self._work, path, host.numpy(), H, W, slot))
+            self._run(self._work, path, host.numpy(), H, W, slot)
             return
         buf = scanlines.numpy() if isinstance(scanlines, torch.Tensor) else np.asarray(scanlines)
-        if buf.dtype != np.uint8:
-            raise ValueError(f"PngWriter.submit: uint8 expected, got {buf.dtype}")
-        self._futures.append(self._pool.submit(self._work, path, buf, H, W, None))
+        self._run(self._work, path, buf, H, W, None)
 
-    def close(self) -> None:
-        """Wait for every submitted file, stop the workers and raise the first exception one of them met."""
-        if not self._closed:
-            self._closed = True
-            for f in self._futures:
-                f.result()
-            self._futures = []
-            self._pool.shutdown(wait=True)
-            self._slots = []
-            self._device_slots = []
-        err, self._error = self._error, None
-        if err is not None:
-            raise err
+    def _drained(self) -> None:
+        self._slots = []
+        self._device_slots = []

@@ -44,11 +44,8 @@ scan, ``write_avi`` the container round the frames, ``MjpegWriter`` does both be
 The container is checked structurally and frame by frame with PIL; it has not been opened in a player."""
 from __future__ import annotations
 
-import os
 import pathlib
 import struct
-import threading
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -406,25 +403,6 @@ AVIIF_KEYFRAME = 0x10
 AVI_MAX_BYTES = 1 << 31
 
 
-def _atomic_write(path: pathlib.Path, parts) -> int:
-    """the parts to ``path`` through a temporary name and a rename, as ``png.write_file``; returns the bytes written"""
-    tmp = path.with_name(f".{path.name}.{os.getpid()}.{threading.get_ident()}.tmp")
-    n = 0
-    try:
-        with open(tmp, "wb") as f:
-            for p in parts:
-                f.write(p)
-                n += len(p)
-        os.replace(tmp, path)
-    except BaseException:
-        try:
-            os.unlink(tmp)
-        except OSError:
-            pass
-        raise
-    return n
-
-
 def write_avi(path, frames, W: int, H: int, fps: int = 10) -> int:
     """JPEG files (bytes, in play order) -> a Motion-JPEG AVI 1.0 at ``path``; returns the bytes written.
 
@@ -462,7 +440,7 @@ def write_avi(path, frames, W: int, H: int, fps: int = 10) -> int:
         idx += b"00dc" + struct.pack("<III", AVIIF_KEYFRAME, off, len(f))
         off += 8 + len(f) + (len(f) & 1)
     parts.append(b"idx1" + struct.pack("<I", len(idx)) + bytes(idx))
-    written = _atomic_write(path, parts)
+    written = png.atomic_write(path, parts)
     assert written == total
     return written
 
@@ -484,7 +462,7 @@ def _write_part(path, frames, W, H, fps) -> int:
     parts = [PART_MAGIC + struct.pack("<IIII", W, H, fps, len(frames))]
     for idx, data in frames:
         parts += [struct.pack("<iI", idx, len(data)), data]
-    return _atomic_write(pathlib.Path(path), parts)
+    return png.atomic_write(path, parts)
 
 
 def _read_part(path):
@@ -554,7 +532,7 @@ class DeviceScan:
         self.subsampling = check_subsampling(subsampling)
 
 
-class MjpegWriter:
+class MjpegWriter(png.AsyncWriter):
     """Collects frames per scene and writes one Motion-JPEG AVI per scene at ``close()``; shaped like ``png.PngWriter``.
 
     ``submit(scene_key, tgt_idx, frame)`` returns at once.  ``scene_key`` is ``(directory, scene_id)``; ``frame`` is a float
@@ -571,8 +549,7 @@ class MjpegWriter:
 
     def __init__(self, fps: int = 10, quality: int = 90, restart_mcus=None, n_threads: int = 4, rank: int = 0, world: int = 1,
                  subsampling="4:4:4"):
-        if not 1 <= int(n_threads) <= png.MAX_THREADS:
-            raise ValueError(f"MjpegWriter: n_threads {n_threads} (1 .. {png.MAX_THREADS})")
+        super().__init__(n_threads, "mjpeg")
         if int(fps) < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError(f"MjpegWriter: fps {fps}, rank {rank}, world {world}")
         quant_tables(quality)
@@ -581,39 +558,13 @@ class MjpegWriter:
         self.fps, self.quality, self.restart_mcus = int(fps), int(quality), restart_mcus
         self.subsampling = check_subsampling(subsampling)
         self.rank, self.world = int(rank), int(world)
-        self._pool = ThreadPoolExecutor(max_workers=int(n_threads), thread_name_prefix="mjpeg")
-        self._lock = threading.Lock()
-        self._futures = []
         self._scenes = {}  # scene_key -> {"hw": (H, W), "frames": [(tgt_idx, bytes)]}
-        self._error = None
-        self._copy_stream = {}
-        self._tls = threading.local()
-        self._closed = False
         self.files = []
         self.bytes_written = 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, exc_type, exc, tb):
-        try:
-            self.close()
-        except BaseException:
-            if exc_type is None:
-                raise
-        return False
 
     def _keep(self, key, tgt_idx, data):
         with self._lock:
             self._scenes[key]["frames"].append((int(tgt_idx), data))
-
-    def _guard(self, fn, *args):
-        try:
-            fn(*args)
-        except BaseException as e:  # kept for close()
-            with self._lock:
-                if self._error is None:
-                    self._error = e
 
     def _work_host(self, key, tgt_idx, img):
         self._keep(key, tgt_idx, encode_jpeg(img, self.quality, self.restart_mcus, self.subsampling))
@@ -626,21 +577,13 @@ class MjpegWriter:
             if n_host is None:
                 n_host = self._tls.n = torch.empty(1, dtype=torch.int32).pin_memory()
             n_host.copy_(scan.nbytes.reshape(1), non_blocking=True)
-            cs.synchronize()
-            n = int(n_host[0])
-            if not 0 <= n <= scan.data.numel():
-                raise RuntimeError(f"MjpegWriter: a frame's scan length {n} exceeds its capacity {scan.data.numel()}")
-            buf = getattr(self._tls, "buf", None)  # this worker's pinned staging, grown as needed
-            if buf is None or buf.numel() < n:
-                buf = self._tls.buf = torch.empty(max(n, 1 << 20), dtype=torch.uint8).pin_memory()
-            host = buf[:n]
-            host.copy_(scan.data[:n], non_blocking=True)
-            cs.synchronize()
+        cs.synchronize()
+        host = self._fetch(n_host[0], scan.data, cs, lambda n, capacity: (
+            f"MjpegWriter: a frame's scan length {n} exceeds its capacity {capacity}"))
         self._keep(key, tgt_idx, jpeg_frame(host.numpy().tobytes(), scan.H, scan.W, self.quality, self.restart_mcus, scan.subsampling))
 
     def submit(self, scene_key, tgt_idx, frame) -> None:
-        if self._closed:
-            raise RuntimeError("MjpegWriter.submit after close()")
+        self._check_open("MjpegWriter.submit")
         key = (pathlib.Path(scene_key[0]), str(scene_key[1]))
         if isinstance(frame, torch.Tensor) and frame.is_cuda:
             from . import ops
@@ -664,38 +607,24 @@ class MjpegWriter:
             raise ValueError(f"MjpegWriter.submit: scene {key[1]} has {scene['hw']} frames, got {(H, W)}")
         if isinstance(frame, DeviceScan):
             dev = frame.data.device
-            cs = self._copy_stream.get(dev.index)
-            if cs is None:
-                cs = self._copy_stream[dev.index] = torch.cuda.Stream(device=dev)
             if frame.ready is None:
                 frame.ready = torch.cuda.current_stream(dev).record_event()
-            self._futures.append(self._pool.submit(self._guard, self._work_device, key, tgt_idx, frame, cs))
+            self._run(self._work_device, key, tgt_idx, frame, self.copy_stream(dev))
         else:
-            self._futures.append(self._pool.submit(self._guard, self._work_host, key, tgt_idx, frame.detach()))
+            self._run(self._work_host, key, tgt_idx, frame.detach())
 
-    def close(self) -> None:
-        """Wait for every frame, write each scene's file (or this rank's part), raise the first worker error."""
-        if not self._closed:
-            self._closed = True
-            for f in self._futures:
-                f.result()
-            self._futures = []
-            self._pool.shutdown(wait=True)
-            if self._error is None:
-                try:
-                    for (scene_dir, scene_id), scene in sorted(self._scenes.items()):
-                        frames = _sorted_frames(scene["frames"])
-                        H, W = scene["hw"]
-                        if self.world > 1:
-                            path = part_path(scene_dir, scene_id, self.rank)
-                            self.bytes_written += _write_part(path, frames, W, H, self.fps)
-                        else:
-                            path = video_path(scene_dir, scene_id)
-                            self.bytes_written += write_avi(path, [f[1] for f in frames], W, H, self.fps)
-                        self.files.append(path)
-                except BaseException as e:
-                    self._error = e
-            self._scenes = {}
-        err, self._error = self._error, None
-        if err is not None:
-            raise err
+    def _drained(self) -> None:
+        """every frame is in: write each scene's file (or this rank's part), unless a worker failed"""
+        scenes, self._scenes = self._scenes, {}
+        if self._error is not None:
+            return
+        for (scene_dir, scene_id), scene in sorted(scenes.items()):
+            frames = _sorted_frames(scene["frames"])
+            H, W = scene["hw"]
+            if self.world > 1:
+                path = part_path(scene_dir, scene_id, self.rank)
+                self.bytes_written += _write_part(path, frames, W, H, self.fps)
+            else:
+                path = video_path(scene_dir, scene_id)
+                self.bytes_written += write_avi(path, [f[1] for f in frames], W, H, self.fps)
+            self.files.append(path)

@@ -31,41 +31,22 @@ def _require_gpu():
     _lib.load()
 
 
-def _inputs(B, H, W):
-    """seeded noise over [0, 1), a synthetic render (cropped from one with room for its objects), the value table tiled
-    (values outside [0, 1], NaN, +-inf included)"""
-    from pgdvs_amd import synth
-
-    g = torch.Generator().manual_seed(1000 * H + W + B)
-    yield "noise", torch.rand((B, 3, H, W), generator=g)
-    video = synth.make_video(B, max(H, 48), max(W, 64), seed=5)
-    yield "render", torch.from_numpy(np.ascontiguousarray(video["rgbs"][:, :H, :W])).permute(0, 3, 1, 2).contiguous()
-    yield "table", VR.table_image(H, W).repeat(B, 1, 1, 1)
-
-
-def _host_coef(x, quality):
-    from pgdvs_amd import png, video
-
-    q = png.quantize_save_image(x).permute(0, 2, 3, 1).contiguous().numpy()
-    return np.stack([video.jpeg_coefficients(v, quality) for v in q])
-
-
 # (16, 520): 65 MCUs in a row, one more than a wavefront; (288, 550): the datasets' frame
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("H,W", [(1, 1), (8, 8), (9, 17), (37, 53), (16, 520), (288, 550)])
 def test_jpeg_coefficients_equal_the_host_restatement(H, W, B):
     from pgdvs_amd import ops
 
-    for name, x in _inputs(B, H, W):
+    for name, x in R.float_inputs(B, H, W):
         xd = x.to(DEV)
         for quality in (50, 100):
             got = ops.jpeg_coefficients(xd, quality)
             assert got.shape == (B, (H + 7) // 8, (W + 7) // 8, 3, 64) and got.dtype == torch.int16 and got.is_cuda
-            want = _host_coef(x, quality)
+            want = R.host_coef(x, quality)
             bad = np.argwhere(got.cpu().numpy() != want)
             assert bad.size == 0, (name, quality, len(bad), bad[:4].tolist())
     one = ops.jpeg_coefficients(xd[0], 50)  # [3,H,W] is a batch of one
-    assert np.array_equal(one.cpu().numpy(), _host_coef(x[:1], 50))
+    assert np.array_equal(one.cpu().numpy(), R.host_coef(x[:1], 50))
 
 
 def _scan_cases(nby, nbx):
@@ -140,7 +121,7 @@ def test_jpeg_scan_arguments():
 def test_jpeg_encode_gives_the_host_files(H, W):
     from pgdvs_amd import ops, video
 
-    for name, x in _inputs(2, H, W):
+    for name, x in R.float_inputs(2, H, W):
         if name == "table":
             continue
         for quality, restart in ((90, None), (50, 7)):
@@ -151,12 +132,6 @@ def test_jpeg_encode_gives_the_host_files(H, W):
                 assert got == video.encode_jpeg(x[b], quality, restart), (name, quality, restart, b)
                 mode, size, pix = R.decode_pil(got)
                 assert mode == "RGB" and size == (W, H)
-
-
-def _avi_frames(path):
-    top = R.riff(pathlib.Path(path).read_bytes())
-    assert top.form == b"AVI "
-    return [c.data for c in top.find(b"LIST", b"movi")[0].children]
 
 
 def test_vis_step_video_on_an_nvidia_vis_item(tmp_path):
@@ -183,7 +158,7 @@ def test_vis_step_video_on_an_nvidia_vis_item(tmp_path):
     split_dir = tmp_path / "video" / item["misc"].get("split", "")
     avi = split_dir / f"{item['misc']['scene_id']}_combined.avi"
     assert w.files == [avi] and avi.exists()
-    frames = _avi_frames(avi)
+    frames = R.avi_file_frames(avi)
     img = ret["combined_rgb"].cpu()
     assert frames == [video.encode_jpeg(img[0], 90)]
     # PIL decodes the frame to the decode model of the coefficients of the PNG's pixels, within the bound of the host tests
@@ -207,8 +182,8 @@ def test_vis_step_video_with_three_views_in_a_step(tmp_path):
     with video.MjpegWriter(quality=75, restart_mcus=3) as w:
         harness.vis_step(VR.StubModel(), batch, None, tmp_path, device=DEV, video=w)
     assert sorted(p.name for p in w.files) == ["scene_a_combined.avi", "scene_b_combined.avi"]
-    assert _avi_frames(tmp_path / "scene_a_combined.avi") == [video.encode_jpeg(ds[i]["img"], 75, 3) for i in (0, 2)]
-    assert _avi_frames(tmp_path / "scene_b_combined.avi") == [video.encode_jpeg(ds[1]["img"], 75, 3)]
+    assert R.avi_file_frames(tmp_path / "scene_a_combined.avi") == [video.encode_jpeg(ds[i]["img"], 75, 3) for i in (0, 2)]
+    assert R.avi_file_frames(tmp_path / "scene_b_combined.avi") == [video.encode_jpeg(ds[1]["img"], 75, 3)]
     w = video.MjpegWriter(restart_mcus=0)  # host-only: the GPU path refuses it when the frame is submitted
     with pytest.raises(Exception, match="host-only"):
         harness.vis_step(VR.StubModel(), batch, None, tmp_path / "no", device=DEV, video=w)
@@ -227,7 +202,7 @@ def test_vis_run_video_on_the_gpu(tmp_path):
     assert sorted(p.name for p in tmp_path.iterdir()) == ["scene_a", "scene_a_combined.avi", "scene_b", "scene_b_combined.avi"]
     for scene in ("scene_a", "scene_b"):
         items = [it for it in ds.items if it["misc"]["scene_id"] == scene]
-        frames = _avi_frames(tmp_path / f"{scene}_combined.avi")
+        frames = R.avi_file_frames(tmp_path / f"{scene}_combined.avi")
         assert frames == [video.encode_jpeg(it["img"], 90) for it in items]
         for f, it in zip(frames, items):
             with PIL.Image.open(dirs[scene] / f"{it['misc']['tgt_idx']:05d}_combined.png") as im:
@@ -246,7 +221,7 @@ def test_1080p_once():
     render = torch.from_numpy(np.ascontiguousarray(synth.make_video(1, H, W, seed=5)["rgbs"])).permute(0, 3, 1, 2).contiguous()
     x = torch.cat([noise, render])
     coef = ops.jpeg_coefficients(x.to(DEV), 90)
-    want = _host_coef(x, 90)
+    want = R.host_coef(x, 90)
     assert np.array_equal(coef.cpu().numpy(), want)
     data, nbytes = ops.jpeg_scan(coef)
     n = nbytes.cpu().tolist()

@@ -34,25 +34,6 @@ def _require_gpu():
     _lib.load()
 
 
-def _inputs(B, H, W):
-    """seeded noise over [0, 1), a synthetic render (cropped from one with room for its objects), the value table tiled
-    (values outside [0, 1], NaN, +-inf included)"""
-    from pgdvs_amd import synth
-
-    g = torch.Generator().manual_seed(1000 * H + W + B)
-    yield "noise", torch.rand((B, 3, H, W), generator=g)
-    video = synth.make_video(B, max(H, 48), max(W, 64), seed=5)
-    yield "render", torch.from_numpy(np.ascontiguousarray(video["rgbs"][:, :H, :W])).permute(0, 3, 1, 2).contiguous()
-    yield "table", VR.table_image(H, W).repeat(B, 1, 1, 1)
-
-
-def _host_coef(x, quality):
-    from pgdvs_amd import png, video
-
-    q = png.quantize_save_image(x).permute(0, 2, 3, 1).contiguous().numpy()
-    return np.stack([video.jpeg_coefficients(v, quality, subsampling=S420) for v in q])
-
-
 # (8, 8): a dummy column and a dummy row at once; (8, 24) / (24, 8): a real Y01 over a dummy row / a dummy column beside a real
 # row; (16, 1040): 65 MCUs in a row, one more than a wavefront; (288, 550): the datasets' frame, nbx = 69 is odd
 @pytest.mark.parametrize("B", [1, 3])
@@ -60,16 +41,16 @@ def _host_coef(x, quality):
 def test_jpeg_coefficients_420_equal_the_host_restatement(H, W, B):
     from pgdvs_amd import ops
 
-    for name, x in _inputs(B, H, W):
+    for name, x in R.float_inputs(B, H, W):
         xd = x.to(DEV)
         for quality in (50, 100):
             got = ops.jpeg_coefficients(xd, quality, subsampling=S420)
             assert got.shape == (B, (H + 15) // 16, (W + 15) // 16, 6, 64) and got.dtype == torch.int16 and got.is_cuda
-            want = _host_coef(x, quality)
+            want = R.host_coef(x, quality, S420)
             bad = np.argwhere(got.cpu().numpy() != want)
             assert bad.size == 0, (name, quality, len(bad), bad[:4].tolist())
     one = ops.jpeg_coefficients(xd[0], 50, subsampling=S420)  # [3,H,W] is a batch of one
-    assert np.array_equal(one.cpu().numpy(), _host_coef(x[:1], 50))
+    assert np.array_equal(one.cpu().numpy(), R.host_coef(x[:1], 50, S420))
     out = torch.empty_like(one)
     assert ops.jpeg_coefficients(xd[0], 50, out=out, subsampling=S420).data_ptr() == out.data_ptr() and torch.equal(out, one)
 
@@ -159,7 +140,7 @@ def test_jpeg_420_arguments():
 def test_jpeg_encode_420_gives_the_host_files(H, W):
     from pgdvs_amd import ops, video
 
-    for name, x in _inputs(2, H, W):
+    for name, x in R.float_inputs(2, H, W):
         if name == "table":
             continue
         for quality, restart in ((90, None), (50, 7)):
@@ -181,12 +162,6 @@ def _pil_420(im, quality):
     b = io.BytesIO()
     PIL.Image.fromarray(im).save(b, "JPEG", quality=quality, subsampling=2, optimize=False)
     return b.getvalue()
-
-
-def _avi_frames(path):
-    top = R.riff(pathlib.Path(path).read_bytes())
-    assert top.form == b"AVI "
-    return [c.data for c in top.find(b"LIST", b"movi")[0].children]
 
 
 def test_vis_step_video_420_on_an_nvidia_vis_item(tmp_path):
@@ -211,7 +186,7 @@ def test_vis_step_video_420_on_an_nvidia_vis_item(tmp_path):
         paths, ret = harness.vis_step(model, batch, rc, tmp_path / "video", device=DEV, video=w, return_ret=True)
     avi = tmp_path / "video" / item["misc"].get("split", "") / f"{item['misc']['scene_id']}_combined.avi"
     assert w.files == [avi] and avi.exists()
-    frames = _avi_frames(avi)
+    frames = R.avi_file_frames(avi)
     img = ret["combined_rgb"].cpu()
     assert frames == [video.encode_jpeg(img[0], 90, subsampling=S420)]
     mode, size, pix = R.decode_pil(frames[0])
@@ -229,14 +204,14 @@ def test_vis_step_video_420_with_three_views_in_a_step(tmp_path):
     batch = harness.collate([ds[i] for i in (2, 1, 0)])  # tgt_idx 7, 4, 1: the file sorts them
     with video.MjpegWriter(quality=75, restart_mcus=3, subsampling=S420) as w:
         harness.vis_step(VR.StubModel(), batch, None, tmp_path, device=DEV, video=w)
-    assert _avi_frames(tmp_path / "scene_a_combined.avi") == [video.encode_jpeg(ds[i]["img"], 75, 3, subsampling=S420) for i in (0, 2)]
-    assert _avi_frames(tmp_path / "scene_b_combined.avi") == [video.encode_jpeg(ds[1]["img"], 75, 3, subsampling=S420)]
+    assert R.avi_file_frames(tmp_path / "scene_a_combined.avi") == [video.encode_jpeg(ds[i]["img"], 75, 3, subsampling=S420) for i in (0, 2)]
+    assert R.avi_file_frames(tmp_path / "scene_b_combined.avi") == [video.encode_jpeg(ds[1]["img"], 75, 3, subsampling=S420)]
     # through vis_run's own writer, and a GPU frame submitted directly
     harness.vis_run(VR.StubModel(), ds, None, tmp_path / "run", device=DEV, video=True, video_subsampling=S420)
-    assert _avi_frames(tmp_path / "run" / "scene_b_combined.avi") == [video.encode_jpeg(ds[1]["img"], 90, subsampling=S420)]
+    assert R.avi_file_frames(tmp_path / "run" / "scene_b_combined.avi") == [video.encode_jpeg(ds[1]["img"], 90, subsampling=S420)]
     with video.MjpegWriter(subsampling=S420) as w:
         w.submit((tmp_path / "run", "direct"), 0, ds[1]["img"].to(DEV))
-    assert _avi_frames(tmp_path / "run" / "direct_combined.avi") == [video.encode_jpeg(ds[1]["img"], 90, subsampling=S420)]
+    assert R.avi_file_frames(tmp_path / "run" / "direct_combined.avi") == [video.encode_jpeg(ds[1]["img"], 90, subsampling=S420)]
 
 
 def test_1080p_420_once():
@@ -247,7 +222,7 @@ def test_1080p_420_once():
     H, W = 1080, 1920
     x = torch.from_numpy(np.ascontiguousarray(synth.make_video(1, H, W, seed=5)["rgbs"])).permute(0, 3, 1, 2).contiguous()
     coef = ops.jpeg_coefficients(x.to(DEV), 90, subsampling=S420)
-    want = _host_coef(x, 90)
+    want = R.host_coef(x, 90, S420)
     assert want.shape == (1, 68, 120, 6, 64) and np.array_equal(coef.cpu().numpy(), want)
     assert not want[0, -1, :, 2:4, 1:].any() and np.array_equal(want[0, -1, :, 2, 0], want[0, -1, :, 1, 0])  # the dummy row
     data, nbytes = ops.jpeg_scan(coef)

@@ -212,14 +212,6 @@ def _all_files(root):
     return sorted(p.relative_to(root).as_posix() for p in pathlib.Path(root).rglob("*") if p.is_file())
 
 
-def _avi_frames(raw):
-    top = R.riff(raw)
-    assert top.form == b"AVI " and top.size == len(raw) - 8
-    movi = top.find(b"LIST", b"movi")[0]
-    assert all(c.tag == b"00dc" for c in movi.children)
-    return top, [c.data for c in movi.children]
-
-
 def test_writer_at_420(tmp_path):
     ds = VR.StubDataset(3, 9, 14)
     with video.MjpegWriter(n_threads=2, subsampling=S420) as w:
@@ -228,7 +220,7 @@ def test_writer_at_420(tmp_path):
         w.submit((tmp_path, "s"), 1, ds[1]["img"])
         with pytest.raises(ValueError):  # a scan made at another sampling would get the wrong header
             w.submit((tmp_path, "s"), 2, video.DeviceScan(None, None, 9, 14))
-    top, frames = _avi_frames((tmp_path / "s_combined.avi").read_bytes())
+    top, frames = R.avi_frames((tmp_path / "s_combined.avi").read_bytes())
     assert frames == [video.encode_jpeg(ds[1]["img"], subsampling=S420), video.encode_jpeg(ds[0]["img"], subsampling=S420)]
     assert video.MjpegWriter().subsampling == "4:4:4" and video.DeviceScan(None, None, 8, 8).subsampling == "4:4:4"
     # the container does not depend on the sampling: strf is the 4:4:4 writer's
@@ -237,7 +229,7 @@ def test_writer_at_420(tmp_path):
         w4.submit((tmp_path / "x", "s"), 4, ds[0]["img"])
         w4.submit((tmp_path / "x", "s"), 1, ds[1]["img"])
     strf = lambda t: t.children[0].children[1].children[1].data  # noqa: E731
-    top4, frames4 = _avi_frames((tmp_path / "x" / "s_combined.avi").read_bytes())
+    top4, frames4 = R.avi_frames((tmp_path / "x" / "s_combined.avi").read_bytes())
     assert strf(top) == strf(top4) and frames4 != frames
 
 
@@ -250,7 +242,7 @@ def test_vis_run_video_at_420(tmp_path):
     for name in before:  # the PNGs are the ones of a run without video
         assert (tmp_path / "plain" / name).read_bytes() == (tmp_path / "video" / name).read_bytes(), name
     for scene in ("scene_a", "scene_b"):
-        top, frames = _avi_frames((tmp_path / "video" / "val" / f"{scene}_combined.avi").read_bytes())
+        top, frames = R.avi_frames((tmp_path / "video" / "val" / f"{scene}_combined.avi").read_bytes())
         items = sorted((it for it in ds.items if it["misc"]["scene_id"] == scene), key=lambda it: it["misc"]["tgt_idx"])
         assert frames == [video.encode_jpeg(VR.expected_save_image(it["img"]).permute(1, 2, 0).numpy(), 90, subsampling=S420) for it in items]
         for f in frames:
@@ -270,7 +262,7 @@ def test_vis_run_video_at_420_across_ranks(tmp_path):
     assert _all_files(tmp_path / "one") == _all_files(tmp_path / "two")
     for name in _all_files(tmp_path / "one"):
         assert (tmp_path / "one" / name).read_bytes() == (tmp_path / "two" / name).read_bytes(), name
-    top, frames = _avi_frames((tmp_path / "one" / "scene_a_combined.avi").read_bytes())
+    top, frames = R.avi_frames((tmp_path / "one" / "scene_a_combined.avi").read_bytes())
     assert frames == [video.encode_jpeg(it["img"], 90, subsampling=S420) for it in ds.items if it["misc"]["scene_id"] == "scene_a"]
 
 

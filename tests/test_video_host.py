@@ -238,15 +238,6 @@ def test_noise_at_quality_100_is_byte_stuffed():
 
 
 # ---------------------------------------------------------------------------- container
-def _avi_frames(raw):
-    """the walker's view of a file: (top chunk, the payloads of movi's 00dc chunks)"""
-    top = R.riff(raw)
-    assert top.form == b"AVI " and top.size == len(raw) - 8
-    movi = top.find(b"LIST", b"movi")[0]
-    assert all(c.tag == b"00dc" for c in movi.children)
-    return top, [c.data for c in movi.children]
-
-
 @pytest.mark.parametrize("lengths", [(101,), (100, 33, 7, 250)])
 def test_write_avi_structure(tmp_path, lengths):
     rng = np.random.default_rng(len(lengths))
@@ -255,7 +246,7 @@ def test_write_avi_structure(tmp_path, lengths):
     n_bytes = video.write_avi(path, frames, 53, 37, fps=10)
     raw = path.read_bytes()
     assert n_bytes == len(raw) and sorted(p.name for p in tmp_path.iterdir()) == ["v.avi"]
-    top, payloads = _avi_frames(raw)
+    top, payloads = R.avi_frames(raw)
     assert payloads == frames
     assert [c.tag for c in top.children] == [b"LIST", b"LIST", b"idx1"]
     hdrl, movi, idx1 = top.children
@@ -323,7 +314,7 @@ def test_vis_run_video(tmp_path, split):
     for name in before:
         assert (tmp_path / "plain" / name).read_bytes() == (tmp_path / "video" / name).read_bytes(), name
     for scene in ("scene_a", "scene_b"):
-        top, frames = _avi_frames((tmp_path / "video" / f"{base}{scene}_combined.avi").read_bytes())
+        top, frames = R.avi_frames((tmp_path / "video" / f"{base}{scene}_combined.avi").read_bytes())
         assert frames == _expected_video(ds, range(7), scene)
         for f, it in zip(frames, sorted((it for it in ds.items if it["misc"]["scene_id"] == scene), key=lambda it: it["misc"]["tgt_idx"])):
             mode, size, pix = R.decode_pil(f)
@@ -350,7 +341,7 @@ def test_vis_run_video_across_ranks(tmp_path, n):
     assert _all_files(tmp_path / "one") == _all_files(tmp_path / "two")  # (no part is left behind)
     for name in _all_files(tmp_path / "one"):
         assert (tmp_path / "one" / name).read_bytes() == (tmp_path / "two" / name).read_bytes(), name
-    top, frames = _avi_frames((tmp_path / "one" / "scene_a_combined.avi").read_bytes())
+    top, frames = R.avi_frames((tmp_path / "one" / "scene_a_combined.avi").read_bytes())
     assert struct.unpack_from("<I", top.children[0].children[1].children[0].data, 24)[0] == 5  # strh's rate
     assert frames == [video.encode_jpeg(it["img"], 75) for it in ds.items if it["misc"]["scene_id"] == "scene_a"]
 
@@ -366,7 +357,7 @@ def test_writer_errors_and_arguments(tmp_path):
     w.submit((tmp_path, "s"), 1, ds[1]["img"])
     w.close()
     assert w.files == [tmp_path / "s_combined.avi"] and w.bytes_written == (tmp_path / "s_combined.avi").stat().st_size
-    top, frames = _avi_frames((tmp_path / "s_combined.avi").read_bytes())
+    top, frames = R.avi_frames((tmp_path / "s_combined.avi").read_bytes())
     assert frames == [video.encode_jpeg(ds[1]["img"]), video.encode_jpeg(ds[0]["img"])]  # tgt_idx 1 before 4
     with pytest.raises(RuntimeError):
         w.submit((tmp_path, "s"), 9, ds[0]["img"])

@@ -1,7 +1,9 @@
-"""Helpers of the video tests (test_video_host.py, test_gpu_video.py), written out independently of pgdvs_amd.video and
-csrc/jpeg.hip: a RIFF walker, a parser of the DHT / DQT segments of a PIL-written JPEG, the float64 decode model of a
-coefficient array, the crafted coefficient blocks and the inputs both test files share.  Not a test."""
+"""Helpers of the video tests (test_video_host.py, test_video_420_host.py, test_gpu_video.py, test_gpu_video_420.py), written
+out independently of pgdvs_amd.video and csrc/jpeg.hip: a RIFF walker, a parser of the DHT / DQT segments of a PIL-written
+JPEG, the float64 decode model of a coefficient array, the crafted coefficient blocks and the inputs the test files share.
+Not a test."""
 import io
+import pathlib
 import struct
 
 import numpy as np
@@ -49,6 +51,19 @@ def riff(raw: bytes) -> Chunk:
     top = _walk(raw, 0, len(raw))
     assert len(top) == 1 and top[0].tag == b"RIFF", [c.tag for c in top]
     return top[0]
+
+
+def avi_frames(raw: bytes):
+    """the walker's view of a file: (top chunk, the payloads of movi's 00dc chunks)"""
+    top = riff(raw)
+    assert top.form == b"AVI " and top.size == len(raw) - 8
+    movi = top.find(b"LIST", b"movi")[0]
+    assert all(c.tag == b"00dc" for c in movi.children)
+    return top, [c.data for c in movi.children]
+
+
+def avi_file_frames(path) -> list:
+    return avi_frames(pathlib.Path(path).read_bytes())[1]
 
 
 # ---- PIL's tables ----------------------------------------------------------------------------------------------------------------
@@ -145,6 +160,28 @@ def contents(H, W):
     const[...] = (200, 30, 120)
     checker = np.repeat((((np.add.outer(np.arange(H), np.arange(W)) % 2) * 255).astype(np.uint8))[..., None], 3, axis=2)
     return {"render": render, "noise": noise, "constant": const, "checker": checker}
+
+
+def float_inputs(B, H, W):
+    """(name, float32 [B,3,H,W]): seeded noise over [0, 1), a synthetic render (cropped from one with room for its objects),
+    the value table tiled (values outside [0, 1], NaN, +-inf included)"""
+    import torch
+    import vis_reference as VR
+    from pgdvs_amd import synth
+
+    g = torch.Generator().manual_seed(1000 * H + W + B)
+    yield "noise", torch.rand((B, 3, H, W), generator=g)
+    video = synth.make_video(B, max(H, 48), max(W, 64), seed=5)
+    yield "render", torch.from_numpy(np.ascontiguousarray(video["rgbs"][:, :H, :W])).permute(0, 3, 1, 2).contiguous()
+    yield "table", VR.table_image(H, W).repeat(B, 1, 1, 1)
+
+
+def host_coef(x, quality, subsampling="4:4:4"):
+    """the host restatement's coefficients of the float batch x[B,3,H,W], quantised as ``*_combined.png`` is"""
+    from pgdvs_amd import png, video
+
+    q = png.quantize_save_image(x).permute(0, 2, 3, 1).contiguous().numpy()
+    return np.stack([video.jpeg_coefficients(v, quality, subsampling=subsampling) for v in q])
 
 
 def _block(entries):
