@@ -996,6 +996,30 @@ int pgdvs_item_views(const uint8_t *rgb, const uint8_t *dyn_mask, const float *d
                      int64_t mask_slot, int64_t depth_slot, const int32_t *ids, int n_views, const int32_t *group_sizes, int n_groups,
                      float *const *out, pgdvs_stream_t stream);
 int pgdvs_flow_occ(const float *coord_diff, int H, int W, float thres, float *occ, pgdvs_stream_t stream);
+/* The resident store's ZoeDepth depths (csrc/depth_range.hip; a scene of pgdvs_amd/datasets/resident.py opened in prediction
+ * mode): the depth table holds each frame's depth_pred (float32 [H,W], frame f at pred + f * pred_slot BYTES, base and slot
+ * multiples of 16), and one launch writes the aligned depths of all of an item's groups.  ids[n_views] and group_sizes
+ * [n_groups] as pgdvs_item_views takes them (HOST; ids may repeat, in any order); scale_shift[n_views][2] HOST doubles, the
+ * (scale, shift) of every VIEW, read before the call returns (they travel as kernel arguments); out[g] (HOST array of
+ * device pointers) group g's depth [n,H,W] float32, 4-byte aligned.  Per pixel exactly the three lines of
+ * pgdvs_nvidia_zoe_depth_range (one device function serves both entries): raw = 1.0f / (pred + float32(1e-16)) in float32,
+ * disp = scale * double(raw) + shift with multiply and add rounded separately, depth64 = 1.0 / (disp + 1e-16), and the
+ * output float32(depth64).  With rays [n_range,12] (DEVICE float32), inv_c2w_tgt[16] (HOST) and depth_range[2] (DEVICE
+ * float32) given (all three or none; near_far, DEVICE double[2], only with them), n_range = group_sizes[0], the spatial
+ * group: the float64 depths of its views are unprojected as that entry unprojects them, view-major, and the select passes
+ * and the finish of pgdvs_nvidia_depth_range give the range; the float64 depth is never stored.
+ * Four pixels per lane with 16-byte loads and stores where a view's output base is 16-byte aligned, one pixel per lane for
+ * the last H W % 4 pixels and for a whole view otherwise.  Nothing outside the outputs and the workspace is written.
+ * A call without a range takes no workspace (NULL, 0); with one, workspace >= pgdvs_item_zoe_depths_workspace_bytes(n_range,
+ * H, W), 16-byte aligned.  F, H, W >= 1, H, W < 2^20, H W < 2^31, 1 <= n_views <= PGDVS_ITEM_MAX_VIEWS, 1 <= n_groups <=
+ * PGDVS_ITEM_MAX_GROUPS, every group_sizes[g] >= 1 and their sum n_views, 0 <= ids[v] < F; with a range H W >= 2 and n_range
+ * H W < 2^31: else PGDVS_ERR_INVALID (the workspace query too) and nothing is launched.  One stream, no host
+ * synchronisation. */
+int64_t pgdvs_item_zoe_depths_workspace_bytes(int n_range, int H, int W);
+int pgdvs_item_zoe_depths(const float *pred, int F, int H, int W, int64_t pred_slot, const int32_t *ids, int n_views,
+                          const double *scale_shift, const int32_t *group_sizes, int n_groups, float *const *out, const float *rays,
+                          const double *inv_c2w_tgt, float *depth_range, double *near_far, void *workspace, int64_t workspace_bytes,
+                          pgdvs_stream_t stream);
 /* The DyCheck loader's target (pgdvs/datasets/dycheck_iphone_eval.py:410-417, 617, 642), expanded on the device from the bytes
  * the files hold: rgb uint8 [H,W,3] -> rgb_out float32 [H,W,3] = float(byte) / 255.0f (an IEEE division: the bits of
  * ``raw.astype(np.float32) / 255.0``); covisible uint8 [H,W] -> mask_out float32 [H,W,1] = covisible > 0 ? 1 : 0 (the bits of

@@ -29,6 +29,10 @@
 // its float32 rounding and, on the range path, unprojects with the float64 depth still in registers: X = o + d depth in
 // float64, as upstream's float32 torch rays times a float64 numpy depth give.  Without the range arguments it is the
 // conversion alone (temporal and tracker views): one launch per kZoeViews views, no workspace.
+// pgdvs_item_zoe_depths is the same alignment over the resident store's prediction table (datasets/resident.py): item_zoe
+// gathers every view of an item by frame id, one launch with grid.y = the view and the per-view scale and shift as kernel
+// arguments, writes the float32 depths of all groups and, for the views of the spatial group, the keys of the select.
+// Both kernels call ONE device function for upstream's three lines (zoe_aligned_depth), so they cannot drift.
 //
 // Rounding: the library is built with -ffp-contract=off -fno-fast-math, so a plain * + / rounds once, exactly as the
 // __f*_rn / __d*_rn intrinsics would.  This file writes plain operators throughout and spells out only the fused steps.
@@ -339,20 +343,109 @@ struct ZoeParams {
   double ss[kZoeViews][2];  // (scale, shift) of views v0 ...
 };
 
+// upstream's three lines on one prediction: the ONE statement of the alignment, for the stacked predictions
+// (zoe_points_kernel) and for the resident store's (item_zoe_kernel)
+__device__ __forceinline__ double zoe_aligned_depth(float pred, double scale, double shift) {
+  // raw_disp = 1.0 / (depth_pred + 1e-16) in float32: numpy rounds the Python scalar to float32 first
+  const float raw = 1.0f / (pred + (float)1e-16);
+  // disp = scale * raw_disp + shift, depth = 1 / (disp + 1e-16) in float64
+  const double disp = scale * (double)raw + shift;
+  return 1.0 / (disp + 1e-16);
+}
+
+// the aligned float64 depth of pixel px, still in registers -> the key of its target-camera z
+__device__ __forceinline__ U64 zoe_key(const float *rays, const double A2[4], const Pixel &px, double d, uint32_t *nan_seen) {
+  double X[3];
+  world_point<double>(rays, px, d, X);
+  const double z = target_z<double>(A2, X);
+  if (z != z) atomicOr(nan_seen, 1u);
+  return Key<double>::enc(z);
+}
+
 __global__ void __launch_bounds__(kBlock) zoe_points_kernel(ZoeParams p, U64 *__restrict__ keys, NvState *__restrict__ st) {
   const int64_t i = (int64_t)p.v0 * p.H * p.W + (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= p.end) return;
   const Pixel px = decode(i, p.H, p.W);
-  // raw_disp = 1.0 / (depth_pred + 1e-16) in float32: numpy rounds the Python scalar to float32 first
-  const float raw = 1.0f / (p.pred[i] + (float)1e-16);
-  // disp = scale * raw_disp + shift, depth = 1 / (disp + 1e-16) in float64
-  const double disp = p.ss[px.v - p.v0][0] * (double)raw + p.ss[px.v - p.v0][1];
-  const double d = 1.0 / (disp + 1e-16);
+  const double d = zoe_aligned_depth(p.pred[i], p.ss[px.v - p.v0][0], p.ss[px.v - p.v0][1]);
   p.depth[i] = (float)d;
   if (!p.rays) return;
-  double X[3];
-  world_point<double>(p.rays, px, d, X);
-  store_key<double>(target_z<double>(p.A2, X), keys, i, &st->nan_seen);
+  keys[i] = zoe_key(p.rays, p.A2, px, d, &st->nan_seen);
+}
+
+// The resident store's ZoeDepth gather (datasets/resident.py, a scene in prediction mode): the slots hold the predictions, the
+// per-view scale and shift travel as kernel arguments like the frame ids, and the item's aligned depths are written group by
+// group in one launch, grid.y = the view.  A lane takes four pixels: 16 bytes of prediction in, 16 bytes of depth out where
+// the view's output base is 16-byte aligned (uniform per view; H W % 4 == 0 guarantees it behind an aligned tensor), else
+// the scalar statement for the whole view; the scalar statement also finishes the H W % 4 pixels behind the quads.  The
+// first n_range views (group 0, the spatial one) also unproject the float64 depth and store the key of view-major pixel
+// v H W + i, 32 bytes per lane in two 16-byte stores where v H W is even.  One fp64 divide, one fp32 divide and, on range
+// views, 12 fp64 multiply-adds per pixel: far below the rate the 4 + 4 (+ 8) bytes per pixel stream at.
+struct ItemZoeParams {
+  const float *pred;   // the store: frame f at + f * slot bytes
+  int64_t slot, n;     // n = H W
+  int W, n_groups, n_range;
+  const float *rays;   // [n_range,12]; unused when n_range == 0
+  double A2[4];
+  float *out[PGDVS_ITEM_MAX_GROUPS];  // [n,H,W] per group
+  int first[PGDVS_ITEM_MAX_GROUPS];   // the group's first view in ids
+  int ids[PGDVS_ITEM_MAX_VIEWS];
+  double ss[PGDVS_ITEM_MAX_VIEWS][2];
+};
+
+__host__ __device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+__global__ void __launch_bounds__(kBlock) item_zoe_kernel(ItemZoeParams p, U64 *__restrict__ keys, NvState *__restrict__ st) {
+  const int v = blockIdx.y;
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < PGDVS_ITEM_MAX_GROUPS; ++k)
+    if (k < p.n_groups && v >= p.first[k]) g = k;
+  const float *__restrict__ src = reinterpret_cast<const float *>(reinterpret_cast<const char *>(p.pred) + (int64_t)p.ids[v] * p.slot);
+  float *__restrict__ out = p.out[g] + (int64_t)(v - p.first[g]) * p.n;
+  const double scale = p.ss[v][0], shift = p.ss[v][1];
+  const bool range = v < p.n_range;
+  U64 *__restrict__ kv = range ? keys + (int64_t)v * p.n : nullptr;
+
+  const int64_t quads = aligned16(out) ? p.n >> 2 : 0;
+  const bool kvec = aligned16(kv);
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+
+  for (int64_t q = t; q < quads; q += stride) {  // (the grid covers the quads: one trip)
+    const float4 x = reinterpret_cast<const float4 *>(src)[q];
+    const double d[4] = {zoe_aligned_depth(x.x, scale, shift), zoe_aligned_depth(x.y, scale, shift),
+                         zoe_aligned_depth(x.z, scale, shift), zoe_aligned_depth(x.w, scale, shift)};
+    reinterpret_cast<float4 *>(out)[q] = make_float4((float)d[0], (float)d[1], (float)d[2], (float)d[3]);
+    if (range) {
+      int row = (int)((q << 2) / p.W), col = (int)((q << 2) - (int64_t)row * p.W);
+      U64 k[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        k[j] = zoe_key(p.rays, p.A2, Pixel{v, (float)col, (float)row}, d[j], &st->nan_seen);
+        if (++col == p.W) {
+          col = 0;
+          ++row;
+        }
+      }
+      if (kvec) {
+        ulonglong2 *k2 = reinterpret_cast<ulonglong2 *>(kv + (q << 2));
+        k2[0] = make_ulonglong2(k[0], k[1]);
+        k2[1] = make_ulonglong2(k[2], k[3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) kv[(q << 2) + j] = k[j];
+      }
+    }
+  }
+
+  for (int64_t i = (quads << 2) + t; i < p.n; i += stride) {  // the scalar statement: the tail, or a whole unaligned view
+    const double d = zoe_aligned_depth(src[i], scale, shift);
+    out[i] = (float)d;
+    if (range) {
+      const int row = (int)(i / p.W), col = (int)(i - (int64_t)row * p.W);
+      kv[i] = zoe_key(p.rays, p.A2, Pixel{v, (float)col, (float)row}, d, &st->nan_seen);
+    }
+  }
 }
 
 // the scaled min and quantile: depth_range (float32) and near / far (float64)
@@ -500,4 +593,81 @@ PGDVS_API int pgdvs_nvidia_zoe_depth_range(const float *depth_pred, const double
   }
   if (range) select_passes<double, 3>(kNvLabels, w, n, fin, st);
   return check_launch("pgdvs_nvidia_zoe_depth_range");
+}
+
+#define IZD_SHAPE_MSG "pgdvs_item_zoe_depths: bad shape F=%d H=%d W=%d (F, H, W >= 1, H, W < 2^20, H W < 2^31)"
+
+namespace pgdvs {
+namespace {
+bool item_shape_ok(int H, int W) { return H >= 1 && W >= 1 && H < (1 << 20) && W < (1 << 20) && (int64_t)H * W < (1ll << 31); }
+}  // namespace
+}  // namespace pgdvs
+
+PGDVS_API int64_t pgdvs_item_zoe_depths_workspace_bytes(int n_range, int H, int W) {
+  if (!item_shape_ok(H, W) || n_range < 1 || n_range > PGDVS_ITEM_MAX_VIEWS || !nv_shape_ok(n_range, H, W)) {
+    set_error("pgdvs_item_zoe_depths_workspace_bytes: bad shape n_range=%d H=%d W=%d (1 <= n_range <= %d, H, W >= 1, each < 2^20, "
+              "H W >= 2, n_range H W < 2^31)", n_range, H, W, PGDVS_ITEM_MAX_VIEWS);
+    return PGDVS_ERR_INVALID;
+  }
+  return nv_workspace_bytes(n_range, H, W);
+}
+
+PGDVS_API int pgdvs_item_zoe_depths(const float *pred, int F, int H, int W, int64_t pred_slot, const int32_t *ids, int n_views,
+                                    const double *scale_shift, const int32_t *group_sizes, int n_groups, float *const *out,
+                                    const float *rays, const double *inv_c2w_tgt, float *depth_range, double *near_far,
+                                    void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
+  const char *op = "pgdvs_item_zoe_depths";
+  PGDVS_REQUIRE(item_shape_ok(H, W) && F >= 1, IZD_SHAPE_MSG, F, H, W);
+  PGDVS_REQUIRE(pred && ids && scale_shift && group_sizes && out, "%s: null pointer", op);
+  PGDVS_REQUIRE(n_views >= 1 && n_views <= PGDVS_ITEM_MAX_VIEWS && n_groups >= 1 && n_groups <= PGDVS_ITEM_MAX_GROUPS,
+                "%s: %d views in %d groups (1 <= views <= %d, 1 <= groups <= %d)", op, n_views, n_groups, PGDVS_ITEM_MAX_VIEWS,
+                PGDVS_ITEM_MAX_GROUPS);
+  const bool range = rays && inv_c2w_tgt && depth_range;
+  PGDVS_REQUIRE(range || (!rays && !inv_c2w_tgt && !depth_range && !near_far),
+                "%s: rays, inv_c2w_tgt and depth_range go together (near_far only with them)", op);
+  const int64_t n = (int64_t)H * W;
+  PGDVS_REQUIRE(aligned16(pred) && pred_slot % 16 == 0 && pred_slot >= n * 4,
+                "%s: the table at %p with slots of %lld bytes (both multiples of 16, a slot at least one frame of %lld pixels)", op,
+                (const void *)pred, (long long)pred_slot, (long long)n);
+  ItemZoeParams p;
+  p.pred = pred;
+  p.slot = pred_slot;
+  p.n = n;
+  p.W = W;
+  p.n_groups = n_groups;
+  int first = 0;
+  for (int g = 0; g < PGDVS_ITEM_MAX_GROUPS; ++g) {
+    p.out[g] = nullptr;
+    p.first[g] = n_views;
+    if (g >= n_groups) continue;
+    PGDVS_REQUIRE(group_sizes[g] >= 1 && group_sizes[g] <= n_views - first, "%s: group %d has %d views (of %d left)", op, g,
+                  group_sizes[g], n_views - first);
+    PGDVS_REQUIRE(out[g] && (reinterpret_cast<uintptr_t>(out[g]) & 3) == 0, "%s: group %d's output is NULL or not 4-byte aligned", op, g);
+    p.out[g] = out[g];
+    p.first[g] = first;
+    first += group_sizes[g];
+  }
+  PGDVS_REQUIRE(first == n_views, "%s: the groups hold %d views, ids %d", op, first, n_views);
+  for (int v = 0; v < PGDVS_ITEM_MAX_VIEWS; ++v) {
+    PGDVS_REQUIRE(v >= n_views || (ids[v] >= 0 && ids[v] < F), "%s: ids[%d] = %d, the store has %d frames", op, v,
+                  v < n_views ? ids[v] : 0, F);
+    p.ids[v] = v < n_views ? ids[v] : 0;
+    for (int c = 0; c < 2; ++c) p.ss[v][c] = v < n_views ? scale_shift[(size_t)v * 2 + c] : 0.0;
+  }
+  p.n_range = range ? group_sizes[0] : 0;
+  p.rays = range ? rays : nullptr;
+  for (int c = 0; c < 4; ++c) p.A2[c] = range ? inv_c2w_tgt[8 + c] : 0.0;
+  PGDVS_REQUIRE(!range || nv_shape_ok(p.n_range, H, W), "%s: a range over %d views of %d x %d (H W >= 2, views H W < 2^31)", op,
+                p.n_range, H, W);
+  PGDVS_REQUIRE(!range || aligned16(workspace), "%s: the workspace must be 16-byte aligned", op);
+  hipStream_t st = as_stream(stream);
+  Work<double, NvState> w = {};  // no keys and no state without a range
+  NvFinish fin;
+  if (range)
+    if (const int rc = nv_setup(op, (int64_t)p.n_range * n, depth_range, near_far, workspace, workspace_bytes, st, w, fin)) return rc;
+  const int64_t work = n >= 4 ? n >> 2 : n;  // quads; a view that takes the scalar statement strides over them
+  PGDVS_LAUNCH("item_zoe_depths", item_zoe_kernel, dim3((unsigned)cdiv(work, kBlock), (unsigned)n_views), dim3(kBlock), 0, st, p, w.keys,
+               w.state);
+  if (range) select_passes<double, 3>(kNvLabels, w, (int64_t)p.n_range * n, fin, st);
+  return check_launch(op);
 }

@@ -141,6 +141,8 @@ SIGNATURES.update({
     "pgdvs_item_views": (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _i64, _i64, _vp, _i, _vp, _i, _vp, _vp]),
     "pgdvs_flow_occ": (_i, [_vp, _i, _i, _f, _vp, _vp]),
     "pgdvs_item_target": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "pgdvs_item_zoe_depths_workspace_bytes": (_i64, [_i, _i, _i]),
+    "pgdvs_item_zoe_depths": (_i, [_vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "pgdvs_resample_table": (_i, [_i, _i, _i, _vp, _vp]),
     "pgdvs_resample_u8_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "pgdvs_resample_u8": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -34,10 +34,15 @@ The per-item ``depth_range`` (:446-456) is computed in numpy with ``device=None`
 ``ops.nvidia_depth_range``, bit-identical (DESIGN.md, row 8f-3 NVIDIA), and then no host point cloud is formed.  The
 point clouds upstream computes for the temporal and tracker views and then discards are skipped on both paths.
 
-``resident=True`` (with ``resident_scenes``, ``resident_max_bytes``; disparity depths only): every source frame is decoded
+``resident=True`` (with ``resident_scenes``, ``resident_max_bytes``): every source frame is decoded
 once and kept in a ``datasets.resident.SceneStore`` on ``device`` (None: host memory), and the items' source views are built
 from it, on a GPU by ``ops.item_views`` in one launch; the same keys, shapes, dtypes and bits, every tensor on the store's
-device.  The target image and the evaluation mask, one item's each, stay disk reads.  DESIGN.md 7f.
+device.  The target image and the evaluation mask, one item's each, stay disk reads.  DESIGN.md 7f.  With ZoeDepth inputs
+the store keeps each frame's prediction (float32) and the selected pair's float64 scale and shift, read once per frame, and
+the alignment is restated per item: by ``ops.item_zoe_depth`` on a GPU store (one launch for all groups' depths and the
+range over the float64 depths of the spatial group; NumPy 2's result, as ``ops.nvidia_zoe_depth``), by ``zoe_align`` and
+``spatial_depth_range`` on a host store (the installed NumPy's, as the disk path).  There an unknown key or a missing path
+raises ``ValueError``, and so does, when its slot is filled, a file in other dtypes than the released ones.
 
 ``device_resize=True`` (needs ``resident=True`` and a GPU ``device``): a source frame's image goes to the store as decoded and is
 BOX-resized on the device into its slot (``ops.resample_u8``, Pillow's resampler bit for bit); the target image is decoded
@@ -231,16 +236,18 @@ class NvidiaDynEvaluationDataset(Dataset):
         assert not use_aug
         assert mode in ["eval"], mode
         assert rgb_range == "0_1", rgb_range
-        if resident and use_zoe_depth != "none":
-            raise ValueError(f"resident=True keeps the depths of the DynIBaR disparities; use_zoe_depth={use_zoe_depth!r} has its own "
-                             "fused device path (ops.nvidia_zoe_depth): use one or the other")
         self.zoe_k_dict = make_zoe_k_dict()
+        if resident and use_zoe_depth not in ["none", "moe"] + list(self.zoe_k_dict):  # (the store's checks raise ValueError)
+            raise ValueError(f"resident=True: use_zoe_depth={use_zoe_depth!r} is none of 'none', 'moe', {', '.join(self.zoe_k_dict)}")
         assert use_zoe_depth in ["none", "moe"] + list(self.zoe_k_dict), f"{use_zoe_depth}, {self.zoe_k_dict.keys()}"
         self.use_zoe_depth = use_zoe_depth
         if use_zoe_depth != "none":  # a directory or a .zip; whichever of the two forms exists (:131-147)
             zp = pathlib.Path(data_root) / zoe_depth_data_path
             if not zp.exists():
                 zp = zp.parent / zp.stem if zp.suffix in [".zip"] else zp.parent / f"{zp.name}.zip"
+            if resident and not zp.exists():
+                raise ValueError(f"resident=True, use_zoe_depth={use_zoe_depth!r}: zoe_depth_data_path={zoe_depth_data_path!r} exists "
+                                 f"neither as a directory nor as a .zip under {data_root}")
             assert zp.exists(), zp
             self.zoe_depth_data_path = zp
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
@@ -289,10 +296,31 @@ class NvidiaDynEvaluationDataset(Dataset):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
         ``device_resize`` the image as decoded: the store resizes it"""
         h, w = tgt_shape
-        depth = _resize(self._read_depth(scene_id, frame_id), h, w, PIL.Image.Resampling.NEAREST)
+        zoe = ()
+        if self.use_zoe_depth != "none":  # the prediction and its (scale, shift): the store aligns them per item
+            depth, *zoe = self._decode_zoe(scene_id, frame_id)
+        else:
+            depth = self._read_depth(scene_id, frame_id)
+        depth = _resize(depth, h, w, PIL.Image.Resampling.NEAREST)
         img_f = self._src_img_f(scene_id, frame_id)
         rgb = np.array(PIL.Image.open(img_f)) if self.store.device_resize else self._read_src_rgb(img_f, h, w)
-        return rgb, self._read_mask(scene_id, frame_id, h, w), depth
+        return (rgb, self._read_mask(scene_id, frame_id, h, w), depth, *zoe)
+
+    def _decode_zoe(self, scene_id, frame_id):
+        """(depth_pred float32, (scale, shift) 0-d float64, (model type, principle)) of a frame for its slot of the store:
+        the pair is selected once, and a file in other dtypes than the released ones is refused (the store keeps float32
+        predictions; the disk path would follow such a file's own promotion)"""
+        known = (scene_id, frame_id) in self.__dict__.get("_zoe_pairs", {})
+        pred, scale, shift = self._read_zoe(scene_id, frame_id)
+        pair = self._zoe_pairs[scene_id, frame_id]
+        self.store.stats["zoe_files_read"] += 1 + (len(ZOE_TYPES) if self.use_zoe_depth == "moe" and not known else 0)
+        if pred.dtype != np.float32 or scale.dtype != np.float64 or shift.dtype != np.float64:
+            rel = f"{scene_id}/dense/zoe_depths_{pair[0]}/{frame_id:05d}.npz"
+            k_scale, k_shift = zoe_scale_shift_keys(pair[1])
+            raise ValueError(f"{self.zoe_depth_data_path} : {rel}: depth_pred is {pred.dtype}, {k_scale} {scale.dtype}, {k_shift} "
+                             f"{shift.dtype}; resident=True keeps float32 predictions with float64 scales and shifts (use_zoe_depth="
+                             f"{self.use_zoe_depth!r} without resident=True follows the file's own types)")
+        return pred, (scale, shift), pair
 
     def _resident_item(self, scene_id, tgt_shape, all_c2w, all_hwf, **kw):
         """``resident.build_item`` over this loader's readers and cameras"""
@@ -300,7 +328,10 @@ class NvidiaDynEvaluationDataset(Dataset):
             Kc = [self._view_cam(all_c2w[f], all_hwf[f], tgt_shape) for f in ids]
             return (np.stack([flat_cam(*tgt_shape, K, c) for K, c in Kc]), np.stack([K for K, _ in Kc]), np.stack([c for _, c in Kc]))
 
-        scene = self.store.scene(scene_id, all_c2w.shape[0], tgt_shape)
+        zoe = self.use_zoe_depth != "none"
+        scene = self.store.scene(scene_id, all_c2w.shape[0], tgt_shape, prediction=zoe)
+        if zoe:  # depths and range come from the predictions; the cameras keep _aug_c2w's double inversion
+            kw["depths"] = lambda ids, range_cams, rays: self.store.zoe_depths(scene, ids, range_cams, rays, kw["c2w_tgt"])
         return build_item(self.store, scene, lambda f: self._decode_frame(scene_id, f, tgt_shape), cams=cams,
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b), owner=type(self).__name__, **kw)
 

@@ -20,6 +20,13 @@ ids are the monocular video's indices (``first_id`` 0); the DyCheck loader's are
 run that need not start at 0 (``first_id`` = the smallest; the scene has as many slots as train frames).  An id outside the
 run is refused before anything is decoded.
 
+A scene may be opened in "prediction" mode (the NVIDIA evaluation loader's ZoeDepth inputs): the ``depth`` table then holds
+each frame's monocular prediction ``depth_pred`` as float32 and the scene keeps, on the host, the float64 (scale, shift) its
+file stores for the pair the loader selected, both written when the slot is filled.  The aligned depth is not stored: under
+NumPy 2 it is float64, the item carries its float32 rounding and ``depth_range`` is taken over the float64 cloud, so the
+alignment (three pointwise lines) is restated per item, by ``zoe_align`` on a host store and by ``ops.item_zoe_depth`` on a
+GPU store, which writes the float32 depths of all groups and selects the range over the float64 ones in one launch.
+
 ``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
 it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
 
@@ -52,9 +59,12 @@ def table_bytes(n_frames, h, w):
 
 
 class _Scene:
-    def __init__(self, n_frames, h, w, device, first_id=0):
+    def __init__(self, n_frames, h, w, device, first_id=0, prediction=False):
         n = h * w
         self.n_frames, self.h, self.w, self.first_id = n_frames, h, w, int(first_id)
+        self.prediction = bool(prediction)  # the depth table holds depth_pred; scale_shift[slot] aligns it
+        self.scale_shift = np.zeros((n_frames, 2), np.float64) if prediction else None  # host, as the files give them
+        self.zoe_pairs = [None] * n_frames if prediction else None  # (model type, principle) the slot was filled from
         self.filled = np.zeros(n_frames, dtype=bool)  # host bitmap of the decoded slots
         tab = lambda slot, dtype: torch.empty((n_frames, slot), dtype=dtype, device=device)  # noqa: E731
         self.rgb = tab(_pad16(n * 3), torch.uint8)[:, :n * 3].view(n_frames, h, w, 3)
@@ -81,7 +91,7 @@ class SceneStore:
             raise ValueError("SceneStore: device_resize=True resizes on a GPU, the store is in host memory (device=None)")
         self.device_resize = bool(device_resize)
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
-                      "targets_resized_on_device": 0}
+                      "targets_resized_on_device": 0, "zoe_files_read": 0}
 
     @property
     def nbytes(self):
@@ -92,12 +102,13 @@ class SceneStore:
         return scene.h * scene.w * 12
 
     # ------------------------------------------------------------------ scenes
-    def scene(self, key, n_frames, shape, first_id=0):
+    def scene(self, key, n_frames, shape, first_id=0, prediction=False):
         """the scene's tables, made on first use (nothing is decoded yet); the least recently used scenes leave.  Frame id
-        ``f`` lives in slot ``f - first_id``"""
+        ``f`` lives in slot ``f - first_id``.  ``prediction``: the depth table holds ZoeDepth predictions (the module's text)"""
         s = self.scenes.get(key)
         if s is not None:
-            assert (s.n_frames, s.h, s.w, s.first_id) == (n_frames, *shape, first_id), (key, (s.n_frames, s.h, s.w, s.first_id), n_frames, shape, first_id)
+            assert (s.n_frames, s.h, s.w, s.first_id, s.prediction) == (n_frames, *shape, first_id, bool(prediction)), (
+                key, (s.n_frames, s.h, s.w, s.first_id, s.prediction), n_frames, shape, first_id, prediction)
             self.scenes.move_to_end(key)
             return s
         need = table_bytes(n_frames, *shape)
@@ -109,7 +120,7 @@ class SceneStore:
         while self.scenes and self.nbytes + need > self.resident_max_bytes:  # flow pairs go first, then the oldest scene
             if not self._drop_flow_pair():
                 self.scenes.popitem(last=False)
-        s = self.scenes[key] = _Scene(n_frames, shape[0], shape[1], self.device, first_id)
+        s = self.scenes[key] = _Scene(n_frames, shape[0], shape[1], self.device, first_id, prediction)
         return s
 
     def _drop_flow_pair(self, keep=None):
@@ -183,9 +194,11 @@ class SceneStore:
                 out[i] = g
         return out
 
-    def put(self, scene, f, rgb, mask, depth):
+    def put(self, scene, f, rgb, mask, depth, scale_shift=None, zoe_pair=None):
         """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into the slot of frame id ``f``.  With
-        ``device_resize`` the image may come at the file's size: it is BOX-resized into the slot on the device"""
+        ``device_resize`` the image may come at the file's size: it is BOX-resized into the slot on the device.  A scene in
+        prediction mode takes ``depth`` = the float32 ``depth_pred`` with ``scale_shift`` = the file's (scale, shift), float64,
+        and (optionally) the pair they belong to"""
         shape = (scene.h, scene.w)
         (slot,) = self.slots(scene, [f])
         plan = None
@@ -199,6 +212,15 @@ class SceneStore:
             raise ValueError(f"frame {f}: mask {mask.dtype} {mask.shape}, the store keeps bool or uint8 {shape}")
         if depth.shape != shape:
             raise ValueError(f"frame {f}: depth {depth.shape}, expected {shape}")
+        if scene.prediction != (scale_shift is not None):
+            raise ValueError(f"frame {f}: a scene in prediction mode takes a prediction with its scale and shift, any other scene a depth alone")
+        if scene.prediction:
+            scale, shift = (np.asarray(x) for x in scale_shift)
+            if depth.dtype != np.float32 or scale.dtype != np.float64 or shift.dtype != np.float64 or scale.ndim or shift.ndim:
+                raise ValueError(f"frame {f}: depth_pred {depth.dtype}, scale {scale.dtype} {scale.shape}, shift {shift.dtype} {shift.shape}; "
+                                 "the store keeps float32 predictions and 0-d float64 scales and shifts")
+            scene.scale_shift[slot] = (scale, shift)
+            scene.zoe_pairs[slot] = zoe_pair
         if plan is not None:
             from .. import ops
 
@@ -217,6 +239,8 @@ class SceneStore:
         frame_ids = [int(f) for ids, _ in groups for f in ids]
         groups = [(self.slots(scene, ids), with_depth) for ids, with_depth in groups]  # (checked before anything is decoded)
         self._fill(scene, frame_ids, decode)
+        if scene.prediction and any(with_depth for _, with_depth in groups):
+            raise ValueError("a scene in prediction mode holds no depths: zoe_depths aligns its predictions")
         self.stats["items_built"] += 1
         if self.device is not None:
             from .. import ops
@@ -233,6 +257,32 @@ class SceneStore:
                 o["depth"] = scene.depth[idx][..., None]
             out.append(o)
         return out
+
+    def zoe_depths(self, scene, ids_by_group, range_cams=None, rays=None, c2w_tgt=None):
+        """the aligned ZoeDepth depths of a scene in prediction mode, its slots filled (``views`` fills them): ([depth float32
+        [n,H,W,1] per group], depth_range float32 [2] or None) on the store's device.  The range is taken over the FIRST
+        group (the spatial one) seen from ``c2w_tgt``, on a host store with ``range_cams`` = (K [n,4,4], c2w [n,4,4]) through
+        the disk path's statements (``zoe_align`` with the stored 0-d float64 scale and shift, ``spatial_depth_range``: they
+        follow the installed NumPy as that path does), on a GPU store with ``rays`` [n,12] on the device through
+        ``ops.item_zoe_depth``, which pins NumPy 2's result as ``ops.nvidia_zoe_depth`` does and waits for nothing"""
+        from . import nvidia_eval as NE
+
+        assert scene.prediction, "zoe_depths serves a scene opened in prediction mode"
+        slots = [self.slots(scene, ids) for ids in ids_by_group]
+        flat = [s for g in slots for s in g]
+        assert scene.filled[flat].all(), "zoe_depths: views() fills the slots first"
+        if self.device is not None:
+            from .. import ops
+
+            inv = None if rays is None else np.linalg.inv(c2w_tgt)
+            return ops.item_zoe_depth(scene.depth, slots, scene.scale_shift[flat], rays, inv)
+        depths = [np.stack([NE.zoe_align(scene.depth[s].numpy(), np.asarray(scene.scale_shift[s, 0]), np.asarray(scene.scale_shift[s, 1]))
+                            for s in g]) for g in slots]
+        rng = None
+        if range_cams is not None:
+            rng = NE.spatial_depth_range({"depth": depths[0], "K": range_cams[0], "c2w": range_cams[1]}, c2w_tgt,
+                                         f64_depth=depths[0].dtype == np.float64)
+        return [F32(d)[..., None] for d in depths], rng
 
     # ------------------------------------------------------------------ flow pairs
     def flow(self, scene, a, b, path):
@@ -296,7 +346,7 @@ def group_host_entries(group, flat_cams, times=None, n_actual=None):
 
 
 def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner,
-               ray_rows=None, depth_range=None):
+               ray_rows=None, depth_range=None, depths=None):
     """An item of the five loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
     non-tensor entries; ``host``: the host-made tensors (on a GPU store they travel in ONE packed copy, with the groups'
     cameras and times; entries named ``__...`` are the loader's own cargo: they come back in the item, on the device, for
@@ -307,7 +357,10 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
     gathered depths on a GPU store, where nothing here waits for the device.  The DyCheck loader brings its own:
     ``ray_rows(spatial ids) -> [V,12] float32`` (its cached ray constants; default: ``nvidia_eval.ray_rows`` of the cameras,
     formed on a GPU store only) and ``depth_range(depth [V,H,W], dyn_mask [V,H,W], rays) -> tensor`` on the store's device,
-    ``rays`` the rows as a device tensor on a GPU store and as the numpy array on a host store; ``c2w_tgt`` is unused then."""
+    ``rays`` the rows as a device tensor on a GPU store and as the numpy array on a host store; ``c2w_tgt`` is unused then.
+    The NVIDIA evaluation loader's ZoeDepth inputs bring ``depths(ids per group, (K, c2w) of the spatial group or None, rays or
+    None) -> ([depth [n,H,W,1] per group], depth_range or None)`` on the store's device (``SceneStore.zoe_depths`` over a
+    scene in prediction mode): the store then gathers colours and masks alone, and every depth and the range come from there."""
     from . import nvidia_eval as NE
 
     dev = store.device
@@ -334,13 +387,19 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
         for side in ("fwd2tgt", "bwd2tgt"):
             add(f"temporal_track_{side}", sel[side], True, sel[side], sel[f"n_actual_{side}"])
     # the range needs the spatial depths even where the item carries none (the visualisation loaders)
-    views = store.views(scene, [(ids, with_depth or name == "spatial") for name, ids, with_depth in groups], decode)
+    views = store.views(scene, [(ids, depths is None and (with_depth or name == "spatial")) for name, ids, with_depth in groups], decode)
     small = pack_to_device(host, dev) if dev is not None else host
     rays = small.pop("__rays", None)
     item = dict(fixed)
     item.update(small)
+    if depths is not None:
+        aligned, zoe_range = depths([ids for _, ids, _ in groups], rng, rays)
+        for v, d in zip(views, aligned):
+            v["depth"] = d
+        if spatial_ids is not None:
+            item["depth_range"] = zoe_range
     for (name, _, with_depth), v in zip(groups, views):
-        if name == "spatial":
+        if name == "spatial" and depths is None:
             depth = v["depth"][..., 0]
             if depth_range is not None:
                 item["depth_range"] = depth_range(depth, v["dyn_mask"][..., 0], rays if dev is not None else rows)

@@ -920,6 +920,59 @@ def item_views(rgb, dyn_mask, depth, groups, out=None):
     return out
 
 
+def item_zoe_depth(pred_table, ids_by_group, scale_shift, rays=None, inv_c2w_tgt=None, near_far=None, out=None):
+    """The resident store's ZoeDepth depths (``pgdvs_item_zoe_depths``; include/pgdvs_hip.h).  ``pred_table``: the store's
+    depth table in prediction mode, float32 [F,H,W] on the GPU, frames contiguous and a multiple of 16 bytes apart.
+    ``ids_by_group``: up to 4 lists of frame ids, together up to 64 views; ids may repeat.  ``scale_shift``: numpy float64
+    [views, 2], the (scale, shift) of every view in the groups' order.  Returns ([depth float32 [n,H,W,1] per group], None):
+    ``datasets.nvidia_eval.zoe_align`` of every view under NumPy 2, rounded to float32, in one launch.  With ``rays``
+    (float32 [len(ids_by_group[0]),12] on the GPU, as in ``nvidia_depth_range``) and the target's float64
+    ``inv_c2w_tgt[4,4]`` the second entry is depth_range[2] float32 on the GPU over the first group's cloud, unprojected
+    with the float64 depths (``nvidia_zoe_depth``'s bits); ``near_far``: optional device float64[2] for the pair before the
+    cast.  ``out``: one contiguous float32 GPU tensor [n,H,W,1] per group to fill in place.  Does not synchronise."""
+    groups = [[int(i) for i in ids] for ids in ids_by_group]
+    if not 1 <= len(groups) <= ITEM_MAX_GROUPS or any(not g for g in groups):
+        raise ValueError(f"item_zoe_depth: {len(groups)} groups of {[len(g) for g in groups]} views (1 to {ITEM_MAX_GROUPS} "
+                         "groups, none empty)")
+    ids = [i for g in groups for i in g]
+    if len(ids) > ITEM_MAX_VIEWS:
+        raise ValueError(f"item_zoe_depth: {len(ids)} views, at most {ITEM_MAX_VIEWS}")
+    if not isinstance(pred_table, torch.Tensor) or pred_table.ndim != 3:
+        raise ValueError(f"item_zoe_depth: pred_table [F,H,W] expected, got {tuple(getattr(pred_table, 'shape', ()))}")
+    F, H, W = (int(x) for x in pred_table.shape)
+    p, slot = _store_table(pred_table, torch.float32, (H, W), "pred_table")
+    if min(ids) < 0 or max(ids) >= F:
+        raise ValueError(f"item_zoe_depth: frame ids {ids} outside the store's {F} frames")
+    ss = np.ascontiguousarray(np.asarray(scale_shift), dtype=np.float64)
+    if ss.shape != (len(ids), 2):
+        raise ValueError(f"item_zoe_depth: scale_shift {ss.shape}, expected {(len(ids), 2)}")
+    if (rays is None) != (inv_c2w_tgt is None) or (near_far is not None and rays is None):
+        raise ValueError("item_zoe_depth: rays and inv_c2w_tgt go together, near_far only with them")
+    if out is None:
+        out = [torch.empty((len(g), H, W, 1), dtype=torch.float32, device=p.device) for g in groups]
+    if len(out) != len(groups):
+        raise ValueError(f"item_zoe_depth: {len(out)} out tensors for {len(groups)} groups")
+    for g, t in zip(groups, out):
+        _out(t, (len(g), H, W, 1), torch.float32, p.device, "item_zoe_depth: out[g]")
+    lib = _lib.load()
+    sizes = [len(g) for g in groups]
+    head = (_ptr(p), F, H, W, slot, (C.c_int32 * len(ids))(*ids), len(ids), _mat64(ss, 2 * len(ids)), (C.c_int32 * len(sizes))(*sizes),
+            len(sizes), (C.c_void_p * len(out))(*[t.data_ptr() for t in out]))
+    if rays is None:
+        check(lib.pgdvs_item_zoe_depths(*head, None, None, None, None, None, 0, _stream()), "pgdvs_item_zoe_depths")
+        return out, None
+    r = _req(rays, torch.float32, "rays")
+    if tuple(r.shape) != (sizes[0], 12) or r.device != p.device:
+        raise ValueError(f"item_zoe_depth: rays {tuple(r.shape)} on {r.device}, expected {(sizes[0], 12)} (the first group's views) on "
+                         f"{p.device}")
+    mat = _mat64(inv_c2w_tgt, 16)
+    ws = _ws(lib.pgdvs_item_zoe_depths_workspace_bytes(sizes[0], H, W), p.device)
+    rng = torch.empty((2,), dtype=torch.float32, device=p.device)
+    check(lib.pgdvs_item_zoe_depths(*head, _ptr(r), mat, _ptr(rng), _out64(near_far), _ptr(ws), ws.numel(), _stream()),
+          "pgdvs_item_zoe_depths")
+    return out, rng
+
+
 def flow_occ(coord_diff, thres):
     """A flow file's occlusion mask (``pgdvs_flow_occ``; include/pgdvs_hip.h): coord_diff[H,W,2] float32 on the GPU and the
     Python number ``thres`` -> float32 [H,W] = sum |coord_diff| > thres, the sum and the compare in float32 as NumPy 2

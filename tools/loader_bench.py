@@ -18,7 +18,12 @@ monocular layout for ``mono_vis``:
            decoded frames are resized on the device), first and second pass, compared with the disk items bit for bit
   resample the ``ops.resample_u8`` launches alone (HIP events, median, warmed): one 1080 x 2062 x 3 frame to 288 x 550 with
            BOX and with LANCZOS, and the two passes' algorithmic bytes
-``--legs nvidia,dycheck,resample`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
+  zoe      nvidia_eval with ZoeDepth inputs (``--zoe-setting``, default "moe"; on the synthetic tree the files are written as one
+           zip in the released layout, on a real tree ``--zoe-path`` names them): items/s of today's device path (disk reads,
+           ``device="cuda:0"``) and of ``resident=True`` on the first and second pass, every resident item compared with the
+           disk item, the store's stats; and the ``ops.item_zoe_depth`` call alone as under ``gather``, with and without the
+           range.  A package whose loader refuses the combination reports the disk figure alone
+``--legs nvidia,dycheck,resample,zoe`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
 Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--legs dycheck] [--out FILE]"""
 import argparse
 import json
@@ -156,6 +161,97 @@ def gather_case(reps):
     return {"views": views, "H": H, "W": W, "bytes_read": read, "bytes_written": written, "ms_median": med, "ms_min": mn,
             "streaming_bound_ms": bound_ms, "share_of_stream_rate": bound_ms / med,
             "distinct_frames_read": len({f for g, _ in groups for f in g})}
+
+
+ZOE_ZIP = "nvidia_zoedepth"
+
+
+def write_zoe_files(nvidia_root, frames=F):
+    """ZoeDepth files for the synthetic NVIDIA scene in the released layout: one zip, ``<stem>/<scene>/dense/zoe_depths_{n,k,nk}/
+    <frame>.npz`` with ``depth_pred`` float32 at the target size and the fits' 0-d float64 entries; the stored mean errors make
+    "moe" move between the twelve pairs from frame to frame"""
+    import io
+    import zipfile
+
+    rng = np.random.default_rng(17)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    gain = {"n": 0.8, "k": 1.3, "nk": 1.05}
+    with zipfile.ZipFile(pathlib.Path(nvidia_root) / f"{ZOE_ZIP}.zip", "w") as z:
+        for f in range(frames):
+            for ti, t in enumerate(gain):
+                pred = (2.0 + 0.4 * np.sin(xx / W * 2 + f) + 0.2 * np.cos(yy / H * 5)) * gain[t]
+                info = {"depth_pred": (pred + 0.05 * rng.random((H, W))).astype(np.float32)}
+                for scope in ("share", "indiv"):
+                    for fit in ("med", "trim"):
+                        info[f"disp_{scope}_scale_{fit}"] = np.asarray(np.float64(gain[t] * rng.uniform(0.9, 1.1)))
+                        info[f"disp_{scope}_shift_{fit}"] = np.asarray(np.float64(rng.uniform(-0.03, 0.03)))
+                        j = ti * 4 + 2 * (fit == "trim") + (scope == "indiv")
+                        me = (0.05 + 0.01 * ((5 * j + 7 * f) % 12)) * (1.0 if (j + f) % 2 == 0 else -1.0)
+                        info[f"me_{fit}_{scope}"], info[f"mae_{fit}_{scope}"] = np.asarray(np.float64(me)), np.asarray(np.float64(abs(me) + 0.02))
+                blob = io.BytesIO()
+                np.savez(blob, **info)
+                z.writestr(f"{ZOE_ZIP}/{SCENE}/dense/zoe_depths_{t}/{f:05d}.npz", blob.getvalue())
+
+
+def zoe_case(nvidia_root, scene, zoe_path, setting, n_items):
+    """nvidia_eval with ZoeDepth inputs: today's device path (disk reads, ``device="cuda:0"``) against ``resident=True`` on
+    the device, first and second pass, every resident item compared with the disk item.  A package whose loader refuses the
+    combination gives the disk figure alone (the baseline of the commit before this row existed)."""
+    from pgdvs_amd.datasets.nvidia_eval import NvidiaDynEvaluationDataset
+
+    kw = dict(data_root=nvidia_root, raw_data_dir="raw", depth_data_dir="depths", mask_data_dir="masks", flow_data_dir="flows", max_hw=-1,
+              scene_ids=[scene], mode="eval", device="cuda:0", use_zoe_depth=setting, zoe_depth_data_path=zoe_path)
+    disk = NvidiaDynEvaluationDataset(**kw)
+    idx = [int(round(j * (len(disk) - 1) / max(n_items - 1, 1))) for j in range(n_items)]
+    disk[idx[0]]  # (warm-up: the fused op's first call)
+    r_disk, want = timed_pass(disk, idx)
+    rec = {"use_zoe_depth": setting, "container": "zip" if disk.zoe_depth_data_path.is_file() else "dir", "len": len(disk),
+           "disk_device_items_per_s": r_disk,
+           "views_per_item": int(sum(v.shape[0] for k, v in want[0].items() if k.startswith("rgb_src_")))}
+    try:
+        res = NvidiaDynEvaluationDataset(resident=True, **kw)
+    except ValueError as e:
+        rec["resident"] = f"refused: {e}"
+        return rec
+    r_first, got1 = timed_pass(res, idx)
+    r_second, got2 = timed_pass(res, idx)
+    rec.update({"resident_first_pass_items_per_s": r_first, "resident_second_pass_items_per_s": r_second,
+                "second_pass_over_disk": r_second / r_disk,
+                "bit_identical": all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2)),
+                "on_device": all(v.is_cuda for it in got2 for v in it.values() if isinstance(v, torch.Tensor)),
+                "store_bytes": res.store.nbytes, "stats": dict(res.store.stats)})
+    return rec
+
+
+def zoe_gather_case(reps):
+    """the ``ops.item_zoe_depth`` call alone (HIP events, median, warmed) for an item of 22 views in four groups at 288 x 550,
+    the range over the 10 spatial views: the gather launch's algorithmic bytes and streaming bound, with and without the
+    range (whose select passes read the 8-byte keys once per radix pass on top)"""
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import ops
+    from pgdvs_amd.datasets.resident import _Scene
+
+    dev = torch.device("cuda:0")
+    scene = _Scene(F, H, W, dev, prediction=True)
+    scene.depth.copy_(torch.rand((F, H, W), device=dev) * 4 + 0.5)
+    groups = [list(range(14, 24)), [23, 24], list(range(18, 23)), list(range(25, 30))]
+    views, n_range = sum(len(g) for g in groups), len(groups[0])
+    rng = np.random.default_rng(5)
+    ss = np.stack([rng.uniform(0.8, 1.2, views), rng.uniform(-0.02, 0.02, views)], 1)
+    rays = torch.zeros((n_range, 12), device=dev)
+    rays[:, 0], rays[:, 4], rays[:, 8] = 1.0 / (0.9 * W), 1.0 / (0.9 * W), 1.0  # (M = inv(K) without the principal point)
+    out, _ = ops.item_zoe_depth(scene.depth, groups, ss, rays, np.eye(4))
+    med, mn = event_median(lambda: ops.item_zoe_depth(scene.depth, groups, ss, rays, np.eye(4), out=out), reps, 4)
+    med0, mn0 = event_median(lambda: ops.item_zoe_depth(scene.depth, groups, ss, out=out), reps, 4)
+    n = H * W
+    read, written, keys = views * n * 4, views * n * 4, n_range * n * 8
+    bound0, bound = (read + written) / HBM_BYTES_PER_S * 1e3, (read + written + keys) / HBM_BYTES_PER_S * 1e3
+    return {"views": views, "range_views": n_range, "H": H, "W": W, "bytes_read": read, "bytes_written": written, "key_bytes_written": keys,
+            "select_passes": 6, "select_bytes_read": 6 * keys,
+            "depths_only": {"ms_median": med0, "ms_min": mn0, "streaming_bound_ms": bound0, "share_of_stream_rate": bound0 / med0},
+            "with_range": {"ms_median": med, "ms_min": mn, "gather_streaming_bound_ms": bound,
+                           "streaming_bound_ms_with_select_reads": (read + written + 7 * keys) / HBM_BYTES_PER_S * 1e3},
+            "distinct_frames_read": len({f for g in groups for f in g})}
 
 
 def resample_case(reps):
@@ -325,7 +421,9 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--vis-views", type=int, default=48)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample")
+    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe")
+    ap.add_argument("--zoe-setting", default="moe", help="use_zoe_depth of the zoe leg")
+    ap.add_argument("--zoe-path", default=None, help="zoe_depth_data_path under a real --data_root (the synthetic tree brings its own)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "loader_bench.py measures on the GPU"
@@ -335,7 +433,7 @@ def main():
     scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
     rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
     legs = set(args.legs.split(","))
-    assert legs and legs <= {"nvidia", "dycheck", "resample"}, args.legs
+    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe"}, args.legs
     try:
         if "resample" in legs:
             rec["resample"] = resample_case(args.reps)
@@ -343,7 +441,7 @@ def main():
         if "dycheck" in legs:
             rec["dycheck"] = dycheck_case(scratch, args.items, args.reps)
             print(f"dycheck: {rec['dycheck']}", file=sys.stderr, flush=True)
-        if "nvidia" not in legs:
+        if not legs & {"nvidia", "zoe"}:
             nvidia_root = mono_root = center = None
         elif args.data_root is None:
             t0 = time.perf_counter()
@@ -377,6 +475,16 @@ def main():
             print(f"{name}: {rec['loaders'][name]}", file=sys.stderr, flush=True)
             del want, got1, got2, got3, got4, disk, res, dr
             torch.cuda.empty_cache()
+        if "zoe" in legs:
+            zoe_path = args.zoe_path
+            if args.data_root is None:
+                write_zoe_files(nvidia_root)
+                zoe_path = f"{ZOE_ZIP}.zip"
+            assert zoe_path is not None, "--zoe-path: where the ZoeDepth files of --data_root are"
+            rec["nvidia_eval_zoe"] = zoe_case(nvidia_root, args.scene, zoe_path, args.zoe_setting, args.items)
+            print(f"nvidia_eval_zoe: {rec['nvidia_eval_zoe']}", file=sys.stderr, flush=True)
+            if "resident" not in rec["nvidia_eval_zoe"]:
+                rec["zoe_gather"] = zoe_gather_case(args.reps)
         if "nvidia" in legs:
             rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
             rec["gather"] = gather_case(args.reps)
