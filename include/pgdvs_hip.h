@@ -1057,6 +1057,62 @@ int64_t pgdvs_resample_u8_workspace_bytes(int N, int Hin, int Win, int C, int Ho
 int pgdvs_resample_u8(const uint8_t *in, int64_t in_stride, int N, int Hin, int Win, int C, uint8_t *out, int64_t out_stride, int Hout,
                       int Wout, int filter, const int32_t *bounds_h, const int32_t *kk_h, const int32_t *bounds_v, const int32_t *kk_v,
                       void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+/* The loaders' JPEG reader (csrc/jpeg_entropy.cpp on the host, csrc/jpeg_decode.hip on the device): what
+ * np.array(PIL.Image.open(f)) gives for a baseline YCbCr file, byte for byte (Pillow over libjpeg-turbo: the islow inverse
+ * DCT, fancy upsampling, jdcolor's tables).
+ * SERVED: SOF0 (baseline, 8 bit, Huffman), exactly three components read as YCbCr (a JFIF APP0, or component ids 1 2 3; no
+ * Adobe APP14), luma sampling 1x1, 2x1 or 2x2 with chroma 1x1, one interleaved scan (Ss 0, Se 63, Ah Al 0), 8-bit DQT, width
+ * and height 1 .. PGDVS_RESAMPLE_MAX_SIZE, with or without restart intervals, the scan closed by EOI.  Everything else --
+ * progressive, SOF1/2/..., arithmetic coding, greyscale, CMYK/YCCK, RGB (keep_rgb) streams, 4:1:1, 4:4:0 and other
+ * factors, 16-bit tables, several scans, anything truncated or malformed -- is refused, never approximated.  APPn / COM
+ * segments are skipped (EXIF orientation is not applied, as Pillow does not).
+ * The two HOST entries never touch the GPU.  Both return 0 = served, 1 = a stream this path does not serve (the reason in
+ * pgdvs_last_error; the caller falls back to Pillow; nothing was written, but for a scan found corrupt while it was decoded:
+ * coef then holds the blocks in front of the fault) and -1 for argument errors alone (a null pointer, a coef_bytes that is not
+ * the stream's).
+ * pgdvs_jpeg_parse replaces jpeg_read_header (jdmarker.c, jdinput.c's initial_setup / per_scan_setup): the markers up to
+ * SOS, then the scan's extent up to its EOI.  blocks_w / blocks_h: every component's block grid padded to whole MCUs
+ * (ceil(width / (8 hmax)) MCUs of h blocks across); coef_bytes = 128 * the blocks of all three; quant[c] = component c's
+ * table de-zigzagged into natural (row-major) order.
+ * pgdvs_jpeg_entropy_decode replaces decode_mcu (jdhuff.c) with process_restart: the scan's quantised coefficients as int16
+ * in natural order, coef[component][block row][block col][64] over the padded grids, every block an MCU carries included,
+ * zero where the stream gives none.  A bad code, a missing or misnumbered RSTn, data running out before the last MCU or a
+ * run past the 64th coefficient returns 1 (libjpeg would warn and go on: Pillow then decides).  Never reads outside
+ * data[0 .. nbytes) nor writes outside coef[0 .. coef_bytes). */
+#define PGDVS_JPEG_444 0
+#define PGDVS_JPEG_422 1
+#define PGDVS_JPEG_420 2
+typedef struct pgdvs_jpeg_info {
+  int32_t width, height;
+  int32_t sampling;         /* PGDVS_JPEG_444 / _422 / _420 */
+  int32_t restart_interval; /* MCUs; 0 = none */
+  int32_t blocks_w[3], blocks_h[3];
+  int64_t coef_bytes;
+  uint16_t quant[3][64];
+} pgdvs_jpeg_info;
+int64_t pgdvs_jpeg_info_size(void); /* sizeof(pgdvs_jpeg_info), for bindings that restate the struct */
+int pgdvs_jpeg_parse(const uint8_t *data, int64_t nbytes, pgdvs_jpeg_info *info);
+int pgdvs_jpeg_entropy_decode(const uint8_t *data, int64_t nbytes, int16_t *coef, int64_t coef_bytes);
+/* pgdvs_jpeg_reconstruct replaces everything behind the entropy decoder: jpeg_idct_islow with its dequantisation
+ * (jidctint.c), jdsample.c's h2v1 / h2v2 fancy upsampling and jdcolor.c's ycc_rgb_convert.  coef: DEVICE int16, as
+ * pgdvs_jpeg_entropy_decode wrote them, 16-byte aligned; quant: DEVICE uint16 [3][64] = info->quant, 16-byte aligned; info:
+ * HOST, as pgdvs_jpeg_parse filled it (its sizes are checked again: the block grids must be the ones width, height and
+ * sampling give); out: DEVICE uint8 [height][width][3], row y at out + y * row_stride bytes (row_stride >= 3 width, any
+ * alignment: a row whose address is a multiple of 4 is written in dwords), nothing between rows or outside the image is
+ * written.  Two launches on `stream`, no host synchronisation:
+ *   1. dequantise and inverse DCT into 8-bit component planes over the padded grids, in the workspace: columns first,
+ *      DESCALE(.., 11), then rows, DESCALE(.., 18), + 128, clamped to 0 .. 255, all in int32.  (For sums outside -384 .. 639
+ *      libjpeg's C code wraps through its range table and its SIMD code saturates; such sums do not come from an encoder
+ *      fed 8-bit images, and this path clamps.)
+ *   2. chroma to full size over the component's ceil(width / 2) x ceil(height / 2) real samples (4:2:0; 4:2:2: full height):
+ *      h2v1 (3a + b + 1) >> 2, (3a + b + 2) >> 2 with the end samples copied; h2v2 column sums 3 near + far, then (3s + last +
+ *      8) >> 4, (3s + next + 7) >> 4, (4s + 8) >> 4 and (4s + 7) >> 4 at the ends, the rows beyond the first and last
+ *      repeating them; plain replication where the component is at most 2 samples wide; then R = Y + ((91881 cr + 32768)
+ *      >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16), cb cr less 128, clamped.
+ * workspace: 256-byte aligned, >= pgdvs_jpeg_reconstruct_workspace_bytes(info) (-1 for an info it refuses). */
+int64_t pgdvs_jpeg_reconstruct_workspace_bytes(const pgdvs_jpeg_info *info);
+int pgdvs_jpeg_reconstruct(const int16_t *coef, const uint16_t *quant, const pgdvs_jpeg_info *info, uint8_t *out, int64_t row_stride,
+                           void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,14 @@ class ViewGeoDesc(C.Structure):
     ]
 
 
+class JpegInfo(C.Structure):
+    """``pgdvs_jpeg_info`` (include/pgdvs_hip.h), field for field."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("sampling", C.c_int32), ("restart_interval", C.c_int32),
+        ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("coef_bytes", _i64), ("quant", (C.c_uint16 * 64) * 3),
+    ]
+
+
 SIGNATURES.update({
     "pgdvs_eval_psnr_workspace_bytes": (_i64, []),
     "pgdvs_eval_psnr_sums": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -146,6 +154,11 @@ SIGNATURES.update({
     "pgdvs_resample_table": (_i, [_i, _i, _i, _vp, _vp]),
     "pgdvs_resample_u8_workspace_bytes": (_i64, [_i, _i, _i, _i, _i, _i, _i]),
     "pgdvs_resample_u8": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "pgdvs_jpeg_info_size": (_i64, []),
+    "pgdvs_jpeg_parse": (_i, [_vp, _i64, C.POINTER(JpegInfo)]),
+    "pgdvs_jpeg_entropy_decode": (_i, [_vp, _i64, _vp, _i64]),
+    "pgdvs_jpeg_reconstruct_workspace_bytes": (_i64, [C.POINTER(JpegInfo)]),
+    "pgdvs_jpeg_reconstruct": (_i, [_vp, _vp, C.POINTER(JpegInfo), _vp, _i64, _vp, _i64, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),
@@ -185,6 +198,9 @@ def load() -> C.CDLL:
     if lib.pgdvs_view_geo_desc_size() != C.sizeof(ViewGeoDesc):
         raise PgdvsHipError(f"pgdvs_view_geo_desc: the library's struct has {lib.pgdvs_view_geo_desc_size()} bytes, this binding's "
                             f"{C.sizeof(ViewGeoDesc)} -- rebuild the extension (stale {LIB_PATH.name})")
+    if lib.pgdvs_jpeg_info_size() != C.sizeof(JpegInfo):
+        raise PgdvsHipError(f"pgdvs_jpeg_info: the library's struct has {lib.pgdvs_jpeg_info_size()} bytes, this binding's "
+                            f"{C.sizeof(JpegInfo)} -- rebuild the extension (stale {LIB_PATH.name})")
     _lib = lib
     return lib
 

@@ -84,6 +84,14 @@ def check_device_resize(device_resize, resident, device, owner):
     return True
 
 
+def check_device_decode(device_decode, device_resize, owner):
+    """``device_decode=True`` hands the store images that are already on the device, at the file's size: refused without
+    ``device_resize=True`` (which in turn asks for ``resident=True`` and a GPU store)"""
+    if device_decode and not device_resize:
+        raise ValueError(f"{owner}(device_decode=True) decodes JPEG frames on the device at the file's size: it needs device_resize=True")
+    return bool(device_decode)
+
+
 def group_entries(group, views, times=None, n_actual=None, depth=True):
     """The item's entries of one group of stacked source views: "spatial", "temporal" or "temporal_track_{fwd,bwd}2tgt".
     The temporal and tracker groups also carry their frames' ``times`` and ``n_actual``, the count before padding; the

@@ -25,7 +25,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, check_device_resize, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
+from ._common import (F32, check_device_decode, check_device_resize, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
                       tracker_entries)
 from .nvidia_eval import spatial_depth_range
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -119,7 +119,8 @@ class MonoVisualizationDataset(Dataset):
     def __init__(self, *, data_root, max_hw, mode, rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
                  vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False):
+        check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
@@ -129,7 +130,7 @@ class MonoVisualizationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
         # the source frames kept in memory (datasets/resident.py)
-        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize)
+        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode)
                       if resident else None)
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
@@ -184,9 +185,9 @@ class MonoVisualizationDataset(Dataset):
             return np.array(PIL.Image.open(img_fs[0])).shape[:2]
         scene = self.store.scenes.get(scene_id)
         if scene is None:
-            raw = np.array(PIL.Image.open(img_fs[0]))
-            scene = self.store.scene(scene_id, len(img_fs), raw.shape[:2])
-            self.store.put(scene, 0, *self._decode_frame(scene_dir, img_fs[0], raw.shape[:2], raw=raw))
+            raw = self.store.decode_image(img_fs[0])  # (device_decode: a JPEG frame comes back on the device)
+            scene = self.store.scene(scene_id, len(img_fs), tuple(raw.shape[:2]))
+            self.store.put(scene, 0, *self._decode_frame(scene_dir, img_fs[0], tuple(raw.shape[:2]), raw=raw))
         return scene.h, scene.w
 
     def _resident_item(self, scene_id, scene_dir, img_fs, shape, all_c2w, all_K, **kw):
@@ -195,8 +196,12 @@ class MonoVisualizationDataset(Dataset):
             return np.stack([flat_cam(*shape, all_K[f], all_c2w[f]) for f in ids]), all_K[list(ids)], all_c2w[list(ids)]
 
         scene = self.store.scene(scene_id, len(img_fs), shape)
-        return build_item(self.store, scene,
-                          lambda f: self._decode_frame(scene_dir, img_fs[f], shape, resize_rgb=not self.store.device_resize), cams=cams,
+
+        def decode(f):  # device_resize: the image as the store decodes it, at the file's size
+            raw = self.store.decode_image(img_fs[f], into=(scene, f)) if self.store.device_resize else None
+            return self._decode_frame(scene_dir, img_fs[f], shape, raw=raw, resize_rgb=not self.store.device_resize)
+
+        return build_item(self.store, scene, decode, cams=cams,
                           flow_path=lambda a, b: self._flow_path(scene_dir, img_fs, a, b), owner=type(self).__name__, **kw)
 
     def __getitem__(self, index):

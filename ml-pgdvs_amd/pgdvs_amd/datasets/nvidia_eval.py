@@ -61,7 +61,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, TGT_HEIGHT, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
+from ._common import (F32, TGT_HEIGHT, check_device_decode, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
                       read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
 from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -230,7 +230,8 @@ class NvidiaDynEvaluationDataset(Dataset):
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
                  flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES,
-                 device_resize=False):
+                 device_resize=False, device_decode=False):
+        check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
@@ -255,7 +256,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize, device_decode)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
@@ -288,13 +289,14 @@ class NvidiaDynEvaluationDataset(Dataset):
     # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
     store = None  # the SceneStore of ``resident=True``
 
-    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, device_resize=False):
+    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, device_resize=False, device_decode=False):
         if resident:
-            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_resize)
+            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_resize, device_decode)
 
     def _decode_frame(self, scene_id, frame_id, tgt_shape):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
-        ``device_resize`` the image as decoded: the store resizes it"""
+        ``device_resize`` the image as decoded: the store resizes it (``device_decode``: decoded on the device, where the file is
+        a JPEG that path serves, straight into the frame's slot when it has the slot's size)"""
         h, w = tgt_shape
         zoe = ()
         if self.use_zoe_depth != "none":  # the prediction and its (scale, shift): the store aligns them per item
@@ -303,7 +305,8 @@ class NvidiaDynEvaluationDataset(Dataset):
             depth = self._read_depth(scene_id, frame_id)
         depth = _resize(depth, h, w, PIL.Image.Resampling.NEAREST)
         img_f = self._src_img_f(scene_id, frame_id)
-        rgb = np.array(PIL.Image.open(img_f)) if self.store.device_resize else self._read_src_rgb(img_f, h, w)
+        rgb = (self.store.decode_image(img_f, into=(self.store.scenes.get(scene_id), frame_id)) if self.store.device_resize else
+               self._read_src_rgb(img_f, h, w))
         return (rgb, self._read_mask(scene_id, frame_id, h, w), depth, *zoe)
 
     def _decode_zoe(self, scene_id, frame_id):
@@ -487,8 +490,8 @@ class NvidiaDynEvaluationDataset(Dataset):
         sel = select_temporal_frames(tgt_frame_id, tgt_cam_id, n_frames, getattr(self, "n_src_views_temporal_track_one_side", 0))
         on_device = self.store is not None and self.store.device_resize
         if on_device:  # decoded once: the LANCZOS pass of _target_rgb gave the shape alone, and the shape is known without it
-            raw_rgb = np.array(PIL.Image.open(img_f))
-            raw_h, raw_w = raw_rgb.shape[:2] if raw_rgb.shape[0] == TGT_HEIGHT else mono_size(scene_dir)
+            raw_rgb = self.store.decode_image(img_f, target=True)  # (device_decode: a tensor on the device)
+            raw_h, raw_w = tuple(raw_rgb.shape[:2]) if raw_rgb.shape[0] == TGT_HEIGHT else mono_size(scene_dir)
             assert raw_h == TGT_HEIGHT, (raw_h, raw_w)
         else:
             raw_rgb = self._target_rgb(scene_dir, img_f)
@@ -498,9 +501,11 @@ class NvidiaDynEvaluationDataset(Dataset):
         # NOTE upstream indexes the poses with the CAMERA id: the 12 camera poses repeat (:319-323)
         if on_device:
             tgt = {"flat_cam": flat_cam(raw_h, raw_w, *self._view_cam(all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape))}
-            if self.store.serves_target(raw_rgb, tgt_shape):  # the bytes travel with the item's small entries
-                rgb_tgt = ("__rgb_tgt", torch.from_numpy(np.ascontiguousarray(raw_rgb)))
+            if self.store.serves_target(raw_rgb, tgt_shape):  # the bytes travel with the item's small entries, or are there already
+                rgb_tgt = ("__rgb_tgt", raw_rgb if isinstance(raw_rgb, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(raw_rgb)))
             else:  # _source_view's statements on the decoded image
+                if isinstance(raw_rgb, torch.Tensor):  # (a size the device resize refuses: back to the host, which waits)
+                    raw_rgb = raw_rgb.cpu().numpy()
                 rgb_tgt = ("rgb_tgt", F32(_resize(raw_rgb, raw_h, raw_w, PIL.Image.Resampling.BOX).astype(np.float32) / 255.0))
         else:
             tgt = self._source_view(scene_id, tgt_frame_id, all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape,
@@ -575,14 +580,15 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
 
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
-                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False):
+                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False):
+        check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
                          mask_data_dir=mask_data_dir, flow_data_dir=flow_data_dir, max_hw=max_hw, mode=mode,
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,
                          n_src_views_temporal_track_one_side=0, flow_consist_thres=flow_consist_thres)
         self.device = device
-        self._init_resident(resident, resident_scenes, resident_max_bytes, device, device_resize)  # the store lives where the cloud is built
+        self._init_resident(resident, resident_scenes, resident_max_bytes, device, device_resize, device_decode)  # (where the cloud is built)
         self.st_pcl_dict = {scene: self._aggregate_static_pcl(scene) for scene in sorted(self.scene_img_dict)}
 
     def _load_mono_video(self, scene_id):

@@ -13,12 +13,12 @@ source images are ``mv_images/<frame>/cam<frame % 12 + 1>.jpg``; the target came
 ``nvidia_eval.spatial_depth_range``: numpy with ``device=None``, the HIP op on a GPU ``device``.  ZoeDepth inputs are not
 mirrored (upstream's own branch reads an attribute it never sets).  ``resident=True``: the source frames are decoded once
 and the items built from a ``datasets.resident.SceneStore`` (see ``nvidia_eval``); ``device_resize=True``: their
-images are resized on the device.
+images are resized on the device; ``device_decode=True``: their .jpg files are decoded there.
 """
 import numpy as np
 import torch
 
-from ._common import F32, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, tracker_entries
+from ._common import F32, check_device_decode, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, tracker_entries
 from .mono_vis import render_path, select_frames_for_time
 from .nvidia_eval import (ALL_SCENE_IDS_NVIDIA_DYN, N_CAMS, TGT_HEIGHT, NvidiaDynEvaluationDataset, read_llff_cams,
                           spatial_depth_range)
@@ -34,7 +34,9 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_f=None,
                  flow_consist_thres=1.0, vis_center_time=50, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32,
-                 device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False):
+                 device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False,
+                 device_decode=False):
+        check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
@@ -48,7 +50,7 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize, device_decode)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         self.c2w_dict, self.hwf_dict, self.valid_fs = {}, {}, []

@@ -35,6 +35,12 @@ uploads the bytes and resizes them on the device straight into the frame's slot 
 for bit); the evaluation loaders' target image goes the same way (``expand_target``) and the pure-geometry loader's LANCZOS
 stack in one batched call (``resize_stack``).  An image the device path does not serve (not uint8 [H,W,3], or a size
 ``ops.resample_plan`` refuses) takes the host statements.  Masks and depths keep their host NEAREST resize.
+
+``device_decode=True`` (with ``device_resize=True``): ``decode_image`` reads an image file's bytes and, where they are a JPEG
+stream that ``ops.jpeg_decode`` serves (baseline YCbCr, 4:4:4 / 4:2:2 / 4:2:0), decodes them on the device: Huffman scan on the
+host, everything behind it in HIP, byte for byte ``np.array(PIL.Image.open(path))``.  The store takes such an image where it
+takes a host one -- no second upload -- and a frame of the slot's size is decoded straight into its slot.  Every other file
+(PNG; progressive, greyscale, CMYK, truncated ... JPEG) is opened by Pillow as before, errors included.
 """
 from collections import OrderedDict
 
@@ -77,7 +83,8 @@ class _Scene:
 class SceneStore:
     """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``)."""
 
-    def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False):
+    def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False,
+                 device_decode=False):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -89,9 +96,12 @@ class SceneStore:
         self.scenes = OrderedDict()  # key -> _Scene, least recently used first
         if device_resize and self.device is None:
             raise ValueError("SceneStore: device_resize=True resizes on a GPU, the store is in host memory (device=None)")
-        self.device_resize = bool(device_resize)
+        if device_decode and not device_resize:
+            raise ValueError("SceneStore: device_decode=True hands over images at the file's size: it needs device_resize=True")
+        self.device_resize, self.device_decode = bool(device_resize), bool(device_decode)
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
-                      "targets_resized_on_device": 0, "zoe_files_read": 0}
+                      "targets_resized_on_device": 0, "zoe_files_read": 0, "frames_decoded_on_device": 0, "targets_decoded_on_device": 0,
+                      "jpeg_fallbacks": 0}
 
     @property
     def nbytes(self):
@@ -146,25 +156,56 @@ class SceneStore:
             if not scene.filled[f - scene.first_id]:
                 self.put(scene, f, *decode(f))
 
+    # ------------------------------------------------------------------ the decode on the device
+    def decode_image(self, path, target=False, into=None):
+        """An image file's pixels.  Without ``device_decode``: ``np.array(PIL.Image.open(path))``.  With it the file's bytes
+        decide, as they do for Pillow, not its name: a JPEG stream (``FF D8``) that ``ops.jpeg_decode`` serves comes back as a
+        uint8 [H,W,3] tensor on the store's device (nothing waits for it); any other file takes the Pillow statement.
+        ``target``: counted as an item's target, not as a source frame.  ``into`` = (scene or None, frame id): a frame of the
+        slot's size is decoded straight into ``scene.rgb[slot]``, which ``put`` then recognises."""
+        if self.device_decode:
+            from .. import ops
+
+            with open(path, "rb") as f:
+                data = f.read()
+            if data[:2] == b"\xff\xd8":
+                info, out = ops.jpeg_info(data), None
+                if info is not None and into is not None and into[0] is not None and (info["height"], info["width"]) == (into[0].h, into[0].w):
+                    out = into[0].rgb[self.slots(into[0], [into[1]])[0]]
+                image = None if info is None else ops.jpeg_decode(data, out=out, device=self.device, reject_ok=True)
+                if image is not None:
+                    self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
+                    return image
+                self.stats["jpeg_fallbacks"] += 1
+        return np.array(PIL.Image.open(path))
+
     # ------------------------------------------------------------------ the resize on the device
+    @staticmethod
+    def _is_u8_rgb(image):
+        """uint8 [H,W,3], a host array or a tensor on a GPU"""
+        u8 = image.dtype == torch.uint8 and image.is_cuda if isinstance(image, torch.Tensor) else image.dtype == np.uint8
+        return u8 and image.ndim == 3 and image.shape[2] == 3
+
     def _device_plan(self, image, shape, filter):
         """the plan of ``image`` -> ``shape`` where the device path serves it: uint8 [H,W,3] of a size that is not refused"""
-        if not self.device_resize or image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        if not self.device_resize or not self._is_u8_rgb(image):
             return None
         from .. import ops
 
         return ops.resample_plan(image.shape[:2], shape, filter, self.device, reject_ok=True)
 
     def _upload(self, image):
-        """the bytes on the device through pinned memory: an asynchronous copy, nothing waits"""
+        """the bytes on the device through pinned memory: an asynchronous copy, nothing waits; an image decoded there stays"""
+        if isinstance(image, torch.Tensor):
+            return image
         host = torch.empty(image.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(torch.from_numpy(np.ascontiguousarray(image)))
         return host.to(self.device, non_blocking=True)
 
     def serves_target(self, image, shape):
         """whether ``expand_target`` takes the image as decoded (else the caller makes the target with the host statements)"""
-        return self.device_resize and (tuple(image.shape[:2]) == tuple(shape) and image.dtype == np.uint8 and image.ndim == 3 and
-                                       image.shape[2] == 3 or self._device_plan(image, shape, "box") is not None)
+        return self.device_resize and (tuple(image.shape[:2]) == tuple(shape) and self._is_u8_rgb(image) or
+                                       self._device_plan(image, shape, "box") is not None)
 
     def expand_target(self, image_u8, shape):
         """a target's bytes on the device, as decoded -> float32 [h,w,3] = BOX-resized to ``shape`` where the size differs, / 255"""
@@ -196,7 +237,8 @@ class SceneStore:
 
     def put(self, scene, f, rgb, mask, depth, scale_shift=None, zoe_pair=None):
         """a decoded frame (image uint8 [H,W,3], mask bool or uint8 [H,W], depth [H,W]) into the slot of frame id ``f``.  With
-        ``device_resize`` the image may come at the file's size: it is BOX-resized into the slot on the device.  A scene in
+        ``device_resize`` the image may come at the file's size: it is BOX-resized into the slot on the device; with
+        ``device_decode`` it may be on the device already (``decode_image``), and may be the slot itself.  A scene in
         prediction mode takes ``depth`` = the float32 ``depth_pred`` with ``scale_shift`` = the file's (scale, shift), float64,
         and (optionally) the pair they belong to"""
         shape = (scene.h, scene.w)
@@ -205,8 +247,10 @@ class SceneStore:
         if self.device_resize and tuple(rgb.shape[:2]) != shape:
             plan = self._device_plan(rgb, shape, "box")
             if plan is None:
+                if isinstance(rgb, torch.Tensor):  # (a size the device resize refuses: back to the host, which waits)
+                    rgb = rgb.cpu().numpy()
                 rgb = resize(rgb, *shape, PIL.Image.Resampling.BOX)  # the host statement
-        if plan is None and (rgb.dtype != np.uint8 or rgb.shape != shape + (3,)):
+        if plan is None and (not self._is_u8_rgb(rgb) or tuple(rgb.shape) != shape + (3,)):
             raise ValueError(f"frame {f}: image {rgb.dtype} {rgb.shape}, the store keeps uint8 {shape + (3,)}")
         if mask.dtype not in (np.bool_, np.uint8) or mask.shape != shape:
             raise ValueError(f"frame {f}: mask {mask.dtype} {mask.shape}, the store keeps bool or uint8 {shape}")
@@ -226,6 +270,9 @@ class SceneStore:
 
             ops.resample_u8(self._upload(rgb), shape, "box", out=scene.rgb[slot])
             self.stats["frames_resized_on_device"] += 1
+        elif isinstance(rgb, torch.Tensor):
+            if rgb.data_ptr() != scene.rgb[slot].data_ptr():  # (else decode_image wrote the slot)
+                scene.rgb[slot].copy_(rgb)
         else:
             scene.rgb[slot].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
         scene.dyn_mask[slot].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
@@ -322,7 +369,10 @@ class SceneStore:
 # ---------------------------------------------------------------------------- items
 def pack_to_device(entries, device):
     """the host tensors of ``entries`` on ``device`` through ONE pinned buffer and one asynchronous copy: each entry becomes a
-    view of the uploaded bytes at a 16-byte boundary (entries are disjoint; nothing else refers to the buffer)"""
+    view of the uploaded bytes at a 16-byte boundary (entries are disjoint; nothing else refers to the buffer); an entry that
+    is on a GPU already is handed through as it is"""
+    there = {k: t for k, t in entries.items() if t.is_cuda}  # (e.g. a target image decoded on the device)
+    entries = {k: t for k, t in entries.items() if not t.is_cuda}
     offs, total = {}, 0
     for k, t in entries.items():
         offs[k] = total
@@ -332,7 +382,9 @@ def pack_to_device(entries, device):
         n = t.numel() * t.element_size()
         host[offs[k]:offs[k] + n].copy_(t.contiguous().view(-1).view(torch.uint8))
     dev = host.to(device, non_blocking=True)
-    return {k: dev[offs[k]:offs[k] + t.numel() * t.element_size()].view(t.dtype).view(t.shape) for k, t in entries.items()}
+    out = {k: dev[offs[k]:offs[k] + t.numel() * t.element_size()].view(t.dtype).view(t.shape) for k, t in entries.items()}
+    out.update(there)
+    return out
 
 
 def group_host_entries(group, flat_cams, times=None, n_actual=None):

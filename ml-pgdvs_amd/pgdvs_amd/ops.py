@@ -1121,6 +1121,89 @@ def resample_u8(img, out_hw, filter, out=None):
     return out
 
 
+JPEG_SAMPLINGS = ("4:4:4", "4:2:2", "4:2:0")  # pgdvs_jpeg_info.sampling
+
+
+def _jpeg_bytes(data):
+    """the stream as a read-only byte buffer and its address (no copy for bytes, bytearray or a contiguous uint8 array)"""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.ndim != 1 or not data.flags.c_contiguous:
+            raise TypeError(f"jpeg: data as an array must be contiguous uint8 [n], got {data.dtype} {data.shape}")
+        return data, C.c_void_p(data.ctypes.data), data.size
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError(f"jpeg: data must be bytes, bytearray, memoryview or a uint8 array, got {type(data)}")
+    arr = np.frombuffer(data, dtype=np.uint8)
+    return arr, C.c_void_p(arr.ctypes.data if arr.size else 0), arr.size
+
+
+def _jpeg_parse(data):
+    """(JpegInfo, keep-alive, pointer, size) of a served stream, or None with the reason in ``pgdvs_last_error``"""
+    keep, ptr, n = _jpeg_bytes(data)
+    info = _lib.JpegInfo()
+    rc = _lib.load().pgdvs_jpeg_parse(ptr, n, C.byref(info))
+    if rc < 0:
+        check(rc, "pgdvs_jpeg_parse")
+    return None if rc else (info, keep, ptr, n)
+
+
+def jpeg_info(data):
+    """What ``pgdvs_jpeg_parse`` reads from a JPEG stream (bytes-like or a uint8 array; host only, include/pgdvs_hip.h): a dict
+    of width, height, sampling ("4:4:4", "4:2:2" or "4:2:0"), restart_interval (MCUs, 0 = none), blocks (per component, (rows,
+    columns) of 8 x 8 blocks, padded to whole MCUs), coef_bytes and quant (uint16 [3,64], natural order) -- or None when
+    ``jpeg_decode`` does not serve the stream (the reason is ``pgdvs_last_error``'s)."""
+    got = _jpeg_parse(data)
+    if got is None:
+        return None
+    info = got[0]
+    return {"width": info.width, "height": info.height, "sampling": JPEG_SAMPLINGS[info.sampling], "restart_interval": info.restart_interval,
+            "blocks": [(info.blocks_h[c], info.blocks_w[c]) for c in range(3)], "coef_bytes": info.coef_bytes,
+            "quant": np.ctypeslib.as_array(info.quant).copy()}
+
+
+def jpeg_decode(data, out=None, device=None, reject_ok: bool = False):
+    """``np.array(PIL.Image.open(BytesIO(data)))`` of a baseline YCbCr JPEG as a uint8 [H,W,3] GPU tensor, byte for byte (Pillow
+    over libjpeg-turbo).  The markers and the Huffman scan are read on the host (``pgdvs_jpeg_parse``,
+    ``pgdvs_jpeg_entropy_decode``: C, the GIL released) into a fresh pinned int16 buffer that also carries the three
+    quantisation tables; one asynchronous copy takes it to ``device`` (default: ``out``'s, else the current GPU) and
+    ``pgdvs_jpeg_reconstruct`` dequantises, inverts the DCT, upsamples the chroma and converts the colours there, on the
+    current stream.  ``out``: a contiguous uint8 [H,W,3] tensor on the device to fill (e.g. a frame's slot of the resident
+    store).  A stream the path does not serve (include/pgdvs_hip.h lists what it does) raises ValueError with the library's
+    reason, or returns None under ``reject_ok`` -- in front of any device work, so the caller can hand the file to Pillow.
+    Does not synchronise."""
+    lib = _lib.load()
+
+    def refused():
+        if reject_ok:
+            return None
+        raise ValueError("jpeg_decode: the stream is not served: " + lib.pgdvs_last_error().decode("utf-8", "replace"))
+
+    got = _jpeg_parse(data)
+    if got is None:
+        return refused()
+    info, keep, ptr, n = got
+    if device is None:
+        device = out.device if isinstance(out, torch.Tensor) and out.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"jpeg_decode: the image is reconstructed on a GPU, got device {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    out = _out(out, (info.height, info.width, 3), torch.uint8, device, "jpeg_decode: out")
+    nq = C.sizeof(info.quant)
+    host = torch.empty((info.coef_bytes + nq) // 2, dtype=torch.int16, pin_memory=True)
+    rc = lib.pgdvs_jpeg_entropy_decode(ptr, n, C.c_void_p(host.data_ptr()), info.coef_bytes)
+    if rc < 0:
+        check(rc, "pgdvs_jpeg_entropy_decode")
+    if rc:
+        return refused()
+    C.memmove(host.data_ptr() + info.coef_bytes, info.quant, nq)
+    dev = host.to(device, non_blocking=True)
+    ws = _ws(lib.pgdvs_jpeg_reconstruct_workspace_bytes(C.byref(info)), device)
+    check(lib.pgdvs_jpeg_reconstruct(_ptr(dev), C.c_void_p(dev.data_ptr() + info.coef_bytes), C.byref(info), _ptr(out), info.width * 3, _ptr(ws),
+                                     ws.numel(), _stream()), "pgdvs_jpeg_reconstruct")
+    return out
+
+
 def _flow_pair(a, b, names, what):
     """two float32 [H,W,2] GPU tensors of one shape, H, W >= 2 (the preprocessing ops' inputs)"""
     a, b = _req(a, torch.float32, names[0]), _req(b, torch.float32, names[1])

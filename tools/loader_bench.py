@@ -23,7 +23,14 @@ monocular layout for ``mono_vis``:
            ``device="cuda:0"``) and of ``resident=True`` on the first and second pass, every resident item compared with the
            disk item, the store's stats; and the ``ops.item_zoe_depth`` call alone as under ``gather``, with and without the
            range.  A package whose loader refuses the combination reports the disk figure alone
-``--legs nvidia,dycheck,resample,zoe`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
+  decode   ``device_decode=True`` against ``device_resize=True`` alone: the synthetic scene's mv_images rewritten
+           as 1080 x 2062 JPEGs (both cameras of a time step; Pillow, quality 90) at 4:2:0 and then at 4:4:4; nvidia_eval and
+           nvidia_vis, first and second pass items/s of fresh loaders, the two variants alternating over ``--rounds`` rounds
+           (median, min and max are reported: the spread is the yardstick of a difference), the items compared bit for bit.  A
+           package without the keyword reports ``device_resize`` alone (the parent commit's figure).  Per frame: Pillow's
+           full decode, the host entropy decode (one thread; 16 frames on 16 threads), the reconstruction's two launches by
+           device events and each kernel's mean, with the bytes they move against the stream rate
+``--legs nvidia,dycheck,resample,zoe,decode`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
 Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--legs dycheck] [--out FILE]"""
 import argparse
 import json
@@ -111,7 +118,7 @@ def write_trees(root, frames=F):
 
 
 def loaders(nvidia_root, mono_root, scene, mono_scene, center):
-    """name -> factory(resident, device_resize=False) of the four loaders, on cuda:0"""
+    """name -> factory(resident, device_resize=False, device_decode=False) of the four loaders, on cuda:0"""
     from pgdvs_amd.datasets.mono_vis import MonoVisualizationDataset
     from pgdvs_amd.datasets.nvidia_eval import NvidiaDynEvaluationDataset, NvidiaDynPureGeoEvaluationDataset
     from pgdvs_amd.datasets.nvidia_vis import NvidiaDynVisualizationDataset
@@ -119,9 +126,10 @@ def loaders(nvidia_root, mono_root, scene, mono_scene, center):
     nv = dict(data_root=nvidia_root, raw_data_dir="raw", depth_data_dir="depths", mask_data_dir="masks", flow_data_dir="flows",
               max_hw=-1, scene_ids=[scene], device="cuda:0")
     vis = dict(vis_center_time=center, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32)
-    out = {"nvidia_eval": lambda r, d=False: NvidiaDynEvaluationDataset(mode="eval", resident=r, device_resize=d, **nv),
+    jk = lambda j: {"device_decode": True} if j else {}  # noqa: E731  (a package without the keyword still takes the rest)
+    out = {"nvidia_eval": lambda r, d=False, j=False: NvidiaDynEvaluationDataset(mode="eval", resident=r, device_resize=d, **jk(j), **nv),
            "nvidia_pure_geo": lambda r, d=False: NvidiaDynPureGeoEvaluationDataset(mode="eval", resident=r, device_resize=d, **nv),
-           "nvidia_vis": lambda r, d=False: NvidiaDynVisualizationDataset(mode="vis", resident=r, device_resize=d, **vis, **nv)}
+           "nvidia_vis": lambda r, d=False, j=False: NvidiaDynVisualizationDataset(mode="vis", resident=r, device_resize=d, **jk(j), **vis, **nv)}
     if mono_root is not None:
         out["mono_vis"] = lambda r, d=False: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[mono_scene],
                                                                       device="cuda:0", resident=r, device_resize=d, **vis)
@@ -277,6 +285,134 @@ def resample_case(reps):
     return rec
 
 
+def rewrite_jpegs(nvidia_root, subsampling, frames=F):
+    """every mv_images file of the synthetic scene -- both cameras of a time step, so that every evaluation target is one too --
+    as a 1080 x 2062 JPEG written by Pillow at quality 90 with ``subsampling``, from the monocular video's frames"""
+    dense = pathlib.Path(nvidia_root) / "raw" / SCENE / "dense"
+    for f in range(frames):
+        big = PIL.Image.open(dense / f"images_{W}x{H}" / f"{f:05d}.png").resize((SRC_W, SRC_H), resample=PIL.Image.Resampling.BICUBIC)
+        d = dense / "mv_images" / f"{f:05d}"
+        for old in d.iterdir():
+            old.unlink()
+        for cam in (f % N_CAMS, (f + 1) % N_CAMS):
+            big.save(d / f"cam{cam + 1:02d}.jpg", quality=90, subsampling=subsampling)
+
+
+def _spread(xs):
+    xs = sorted(xs)
+    return {"median": xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2]), "min": xs[0], "max": xs[-1]}
+
+
+def decode_loaders_case(make, n_items, rounds):
+    """fresh loaders each round, ``device_resize`` alone and with ``device_decode``, alternating; items/s of both passes"""
+    rec = {}
+    for name in ("nvidia_eval", "nvidia_vis"):
+        fn = make[name]
+        try:
+            fn(True, True, True)
+            variants = (("device_resize", False), ("device_decode", True))
+        except TypeError:
+            variants = (("device_resize", False),)
+        probe = fn(True, True)
+        idx = [int(round(j * (len(probe) - 1) / max(n_items - 1, 1))) for j in range(n_items)]
+        probe[idx[0]]  # (warm-up: code objects, the resize plans)
+        del probe
+        rates = {v: {"first": [], "second": []} for v, _ in variants}
+        want, same, stats = None, True, {}
+        for _ in range(rounds):
+            for v, j in variants:
+                ds = fn(True, True, j)
+                r1, got1 = timed_pass(ds, idx)
+                r2, got2 = timed_pass(ds, idx)
+                rates[v]["first"].append(r1)
+                rates[v]["second"].append(r2)
+                if want is None:
+                    want = got1
+                same = same and all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2))
+                stats[v] = dict(ds.store.stats)
+                del ds, got1, got2
+                torch.cuda.empty_cache()
+        r = rec[name] = {"items": len(idx), "rounds": rounds, "bit_identical": same, "stats": stats}
+        for v, _ in variants:
+            r[f"{v}_first_pass_items_per_s"], r[f"{v}_second_pass_items_per_s"] = _spread(rates[v]["first"]), _spread(rates[v]["second"])
+        print(f"decode {name}: {r}", file=sys.stderr, flush=True)
+    return rec
+
+
+def decode_frame_case(path, reps):
+    """one file: Pillow's decode, the host entropy decode and the reconstruction on the device"""
+    import ctypes as C
+    import io
+    from concurrent.futures import ThreadPoolExecutor
+
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import _lib, ops
+
+    lib = _lib.load()
+    data = pathlib.Path(path).read_bytes()
+    arr = np.frombuffer(data, np.uint8)
+    ptr = C.c_void_p(arr.ctypes.data)
+
+    def clock(fn, n):
+        ts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return _spread(ts)
+
+    info = _lib.JpegInfo()
+    assert lib.pgdvs_jpeg_parse(ptr, arr.size, C.byref(info)) == 0, lib.pgdvs_last_error()
+    nq = C.sizeof(info.quant)
+    bufs = [torch.empty((info.coef_bytes + nq) // 2, dtype=torch.int16, pin_memory=True) for _ in range(16)]
+    entropy = lambda b: lib.pgdvs_jpeg_entropy_decode(ptr, arr.size, C.c_void_p(b.data_ptr()), info.coef_bytes)  # noqa: E731
+    assert entropy(bufs[0]) == 0
+    rec = {"file_bytes": arr.size, "sampling": ops.JPEG_SAMPLINGS[info.sampling], "coef_bytes": info.coef_bytes,
+           "pillow_decode_ms": clock(lambda: np.array(PIL.Image.open(io.BytesIO(data))), 10),
+           "parse_ms": clock(lambda: lib.pgdvs_jpeg_parse(ptr, arr.size, C.byref(info)), 10),
+           "entropy_decode_ms_one_thread": clock(lambda: entropy(bufs[0]), 10)}
+    with ThreadPoolExecutor(16) as pool:  # one frame per thread, 16 at once (ctypes drops the GIL for the call)
+        list(pool.map(entropy, bufs))
+        rec["entropy_decode_ms_16_frames_on_16_threads"] = clock(lambda: list(pool.map(entropy, bufs)), 5)
+    C.memmove(bufs[0].data_ptr() + info.coef_bytes, info.quant, nq)
+    dev = bufs[0].to("cuda:0")
+    ws = torch.empty(lib.pgdvs_jpeg_reconstruct_workspace_bytes(C.byref(info)), dtype=torch.uint8, device="cuda:0")
+    out = torch.empty((info.height, info.width, 3), dtype=torch.uint8, device="cuda:0")
+    run = lambda: _lib.check(lib.pgdvs_jpeg_reconstruct(dev.data_ptr(), dev.data_ptr() + info.coef_bytes, C.byref(info), out.data_ptr(),  # noqa: E731
+                                                        info.width * 3, ws.data_ptr(), ws.numel(), ops._stream()), "pgdvs_jpeg_reconstruct")
+    med, mn = event_median(run, reps, 4)
+    lib.pgdvs_prof_enable(1)
+    for _ in range(reps):
+        run()
+    text = C.create_string_buffer(4096)
+    lib.pgdvs_prof_report(text, 4096)
+    lib.pgdvs_prof_enable(0)
+    kernels = {ln.split()[0]: float(ln.split()[2]) / int(ln.split()[1]) for ln in text.value.decode().splitlines() if ln.startswith("jpeg_")}
+    planes = sum(64 * info.blocks_w[c] * info.blocks_h[c] for c in range(3))
+    moved = {"jpeg_idct": info.coef_bytes + planes, "jpeg_colour": planes + out.numel()}
+    rec.update({"equals_pillow": bool(np.array_equal(out.cpu().numpy(), np.array(PIL.Image.open(io.BytesIO(data))))),
+                "reconstruct_ms_median": med, "reconstruct_ms_min": mn, "plane_bytes": planes, "rgb_bytes": out.numel(),
+                "kernels": {k: {"ms_mean": v, "bytes_moved": moved[k], "streaming_bound_ms": moved[k] / HBM_BYTES_PER_S * 1e3,
+                                "share_of_stream_rate": moved[k] / HBM_BYTES_PER_S * 1e3 / v} for k, v in kernels.items()},
+                "streaming_bound_ms": sum(moved.values()) / HBM_BYTES_PER_S * 1e3})
+    return rec
+
+
+def decode_case(nvidia_root, scene, center, n_items, reps, rounds, synthetic):
+    rec = {}
+    for sub in (("4:2:0", "4:4:4") if synthetic else (None,)):
+        if sub is not None:
+            rewrite_jpegs(nvidia_root, sub)
+        r = rec[sub or "tree"] = {"loaders": decode_loaders_case(loaders(nvidia_root, None, scene, None, center), n_items, rounds)}
+        first = sorted((pathlib.Path(nvidia_root) / "raw" / scene / "dense" / "mv_images").glob("*/*.jpg"))[0]
+        try:
+            r["frame"] = decode_frame_case(first, reps)
+        except AttributeError as e:  # (a package without the reader)
+            r["frame"] = f"not in this package: {e}"
+        print(f"decode frame {sub}: {r['frame']}", file=sys.stderr, flush=True)
+    return rec
+
+
 DY_H, DY_W, DY_F, DY_FACTOR, DY_SCENE = 360, 480, 48, 2, "synthetic-iphone"
 
 
@@ -421,7 +557,8 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--vis-views", type=int, default=48)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe")
+    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe, decode")
+    ap.add_argument("--rounds", type=int, default=3, help="decode leg: rounds of fresh loaders per variant")
     ap.add_argument("--zoe-setting", default="moe", help="use_zoe_depth of the zoe leg")
     ap.add_argument("--zoe-path", default=None, help="zoe_depth_data_path under a real --data_root (the synthetic tree brings its own)")
     ap.add_argument("--out", default=None)
@@ -433,7 +570,7 @@ def main():
     scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
     rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
     legs = set(args.legs.split(","))
-    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe"}, args.legs
+    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe", "decode"}, args.legs
     try:
         if "resample" in legs:
             rec["resample"] = resample_case(args.reps)
@@ -441,7 +578,7 @@ def main():
         if "dycheck" in legs:
             rec["dycheck"] = dycheck_case(scratch, args.items, args.reps)
             print(f"dycheck: {rec['dycheck']}", file=sys.stderr, flush=True)
-        if not legs & {"nvidia", "zoe"}:
+        if not legs & {"nvidia", "zoe", "decode"}:
             nvidia_root = mono_root = center = None
         elif args.data_root is None:
             t0 = time.perf_counter()
@@ -488,6 +625,8 @@ def main():
         if "nvidia" in legs:
             rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
             rec["gather"] = gather_case(args.reps)
+        if "decode" in legs:  # last: it rewrites the synthetic tree's image files
+            rec["decode"] = decode_case(nvidia_root, args.scene, center, args.items, args.reps, args.rounds, args.data_root is None)
     finally:
         shutil.rmtree(scratch, ignore_errors=True)
     js = json.dumps(rec, indent=1)
