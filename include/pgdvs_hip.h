@@ -1113,6 +1113,54 @@ int pgdvs_jpeg_entropy_decode(const uint8_t *data, int64_t nbytes, int16_t *coef
 int64_t pgdvs_jpeg_reconstruct_workspace_bytes(const pgdvs_jpeg_info *info);
 int pgdvs_jpeg_reconstruct(const int16_t *coef, const uint16_t *quant, const pgdvs_jpeg_info *info, uint8_t *out, int64_t row_stride,
                            void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+/* The same scan read on the device (csrc/jpeg_scan_core.h: the decoder; csrc/jpeg_entropy.cpp: preparation and host
+ * emulation; csrc/jpeg_scan_decode.hip: the kernels): pgdvs_jpeg_entropy_decode's coefficients bit for bit, with only the
+ * file's bytes crossing the bus.  The scan is cut into subsequences of sub_bytes bytes inside each restart segment; each is
+ * decoded from a guessed entry state and again whenever its predecessor's exit state says otherwise, until no state changes
+ * (the bounds are the counts themselves: an intact stream always converges); then every subsequence writes its coefficients
+ * and the DC differences are summed.
+ * pgdvs_jpeg_scan_prepare: HOST, one pass over the scan's bytes and no Huffman work.  Refuses (1, the reason in
+ * pgdvs_last_error) exactly what pgdvs_jpeg_parse refuses, a missing or misnumbered RSTn marker, and a scan of more than
+ * PGDVS_JPEG_SCAN_MAX_BYTES bytes (such files stay with the host decoder; the cap keeps every workspace below 2^31 bytes and
+ * bit positions in 32 bits).  Fills `prepared` (8-byte aligned, prepared_bytes >= pgdvs_jpeg_scan_prepare_bytes(..): pinned
+ * memory for one asynchronous copy) with a header, info->quant, the scan's six derived Huffman tables (jdhuff's maxcode /
+ * valoffset / huffval behind a 9-bit look-ahead), the segment table (bit start and end, first MCU and MCU count =
+ * restart_interval but for the last, first subsequence), every subsequence's segment, and the scan with its FF 00 stuffing
+ * and RSTn markers removed; and `info` as pgdvs_jpeg_parse does.  sub_bytes: 0 for PGDVS_JPEG_SCAN_SUB_BYTES, else a
+ * multiple of 4 in 16 .. 4096.  -1 for argument errors alone.  Never reads outside data[0 .. nbytes) nor writes outside
+ * prepared[0 .. prepared_bytes).  pgdvs_jpeg_scan_prepare_bytes: the size to provide; 0 for a stream prepare refuses, -1
+ * for argument errors.
+ * pgdvs_jpeg_scan_decode: prepared_host: HOST, the buffer as filled (only its header is read, and checked: the launch list
+ * follows from it alone); prepared: DEVICE, a copy of the same prepared_bytes bytes, 16-byte aligned; coef: DEVICE int16,
+ * coef_bytes = info->coef_bytes, 16-byte aligned, laid out as pgdvs_jpeg_entropy_decode does; status: DEVICE, one word;
+ * workspace: DEVICE, 256-byte aligned, >= pgdvs_jpeg_scan_decode_workspace_bytes(prepared_host, prepared_bytes) (-1 for a
+ * header it refuses).  Launches on `stream` and returns: no host synchronisation.  *status is 0 only if every restart
+ * segment produced exactly its MCUs (PGDVS_JPEG_SCAN_SHORT otherwise; _LEFT_OVER: a byte or more of data between a
+ * segment's last MCU and its RSTn), no verified decode met a code the table lacks, a DC size above 15, a run past
+ * coefficient 63 or the end of its segment's data (_BAD_CODE), no DC value left 16 bits (_DC_RANGE) and the verified pass
+ * met the states the synchronisation left (_NOT_SYNCHRONISED; never set by construction).  With a non-zero status coef
+ * holds no result: the caller reruns the file through pgdvs_jpeg_entropy_decode, which decides.  Whatever the bytes of
+ * `prepared` hold, nothing outside it is read and nothing outside coef, status and the workspace is written.
+ * The workspace's first two words, for tools: the rounds of the first launch (the largest of any workgroup) and the fix-up
+ * launches that did not leave at once.
+ * pgdvs_jpeg_scan_decode_host: the same launches one after the other on the CPU, HOST pointers throughout (prepared_host and
+ * prepared may be the same buffer; 8-byte alignment suffices): the same core, rounds, flags and workspace.  0, or -1 for
+ * argument errors. */
+#define PGDVS_JPEG_SCAN_SUB_BYTES 64
+#define PGDVS_JPEG_SCAN_MAX_BYTES (1 << 25)
+#define PGDVS_JPEG_SCAN_SHORT 1
+#define PGDVS_JPEG_SCAN_BAD_CODE 2
+#define PGDVS_JPEG_SCAN_DC_RANGE 4
+#define PGDVS_JPEG_SCAN_NOT_SYNCHRONISED 8
+#define PGDVS_JPEG_SCAN_LEFT_OVER 16
+int64_t pgdvs_jpeg_scan_prepare_bytes(const uint8_t *data, int64_t nbytes, int32_t sub_bytes);
+int pgdvs_jpeg_scan_prepare(const uint8_t *data, int64_t nbytes, int32_t sub_bytes, void *prepared, int64_t prepared_bytes,
+                            pgdvs_jpeg_info *info);
+int64_t pgdvs_jpeg_scan_decode_workspace_bytes(const void *prepared_host, int64_t prepared_bytes);
+int pgdvs_jpeg_scan_decode(const void *prepared_host, const void *prepared, int64_t prepared_bytes, int16_t *coef, int64_t coef_bytes,
+                           uint32_t *status, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+int pgdvs_jpeg_scan_decode_host(const void *prepared_host, const void *prepared, int64_t prepared_bytes, int16_t *coef, int64_t coef_bytes,
+                                uint32_t *status, void *workspace, int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

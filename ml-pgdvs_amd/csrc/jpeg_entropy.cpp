@@ -1,9 +1,11 @@
 // The host half of the JPEG reader: the markers (pgdvs_jpeg_parse) and the Huffman scan (pgdvs_jpeg_entropy_decode) of a
-// baseline YCbCr file.  include/pgdvs_hip.h states what is served and what each entry returns; this is how.
+// baseline YCbCr file; and for the scan read on the device (csrc/jpeg_scan_decode.hip) its preparation
+// (pgdvs_jpeg_scan_prepare) and the kernels' host emulation (pgdvs_jpeg_scan_decode_host, over csrc/jpeg_scan_core.h).
+// include/pgdvs_hip.h states what is served and what each entry returns; this is how.
 //
-// Plain C++: no HIP, no GPU, nothing of the rest of the library but set_error -- tools/jpeg_entropy_fuzz.cpp builds this file
-// alone with the host compiler and its sanitizers.  Every read of the stream goes through a bounds-checked cursor; every
-// write of a coefficient through a block pointer computed from the checked grids.
+// Plain C++: no HIP, no GPU, nothing of the rest of the library but set_error -- tools/jpeg_entropy_fuzz.cpp and
+// tools/jpeg_scan_fuzz.cpp build this file alone with the host compiler and its sanitizers.  Every read of the stream goes
+// through a bounds-checked cursor; every write of a coefficient through a block pointer computed from the checked grids.
 //
 // The scan: a 64-bit accumulator refilled a byte at a time (FF 00 unstuffed; a marker or the end of the scan feeds zero bits
 // that are counted, and consuming one of them is "data ran out"), and per Huffman table a 9-bit lookahead table (code length
@@ -13,6 +15,7 @@
 #include <string.h>
 
 #include "../../include/pgdvs_hip.h"
+#include "jpeg_scan_core.h"
 
 namespace pgdvs {
 void set_error(const char *fmt, ...);
@@ -353,4 +356,281 @@ extern "C" __attribute__((visibility("default"))) int pgdvs_jpeg_entropy_decode(
     return kBadArgument;
   }
   return decode_scan(data, hdr, coef);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The scan read on the device: its preparation, and the kernels' emulation on the host.
+namespace {
+
+namespace js = pgdvs::jscan;
+static_assert(js::kMaxScanBytes == PGDVS_JPEG_SCAN_MAX_BYTES && js::kMinSubBytes <= PGDVS_JPEG_SCAN_SUB_BYTES, "include/pgdvs_hip.h and jpeg_scan_core.h disagree");
+
+struct PrepLayout {
+  int nseg;
+  int64_t max_subs, scan_len;
+  js::Header hd;  // the offsets and total_bytes
+};
+
+int prep_layout(const Header &hdr, int32_t sub_bytes, PrepLayout *pl) {
+  pl->scan_len = hdr.scan_end - hdr.scan_begin;
+  if (pl->scan_len > js::kMaxScanBytes) return refuse("the scan is larger than PGDVS_JPEG_SCAN_MAX_BYTES: left to the host decoder");
+  const int64_t nmcu = (int64_t)hdr.mcus_w * hdr.mcus_h;
+  const int64_t ri = hdr.info.restart_interval ? hdr.info.restart_interval : nmcu;
+  pl->nseg = (int)((nmcu + ri - 1) / ri);
+  pl->max_subs = pl->scan_len / sub_bytes + pl->nseg;
+  js::Header &h = pl->hd;
+  memset(&h, 0, sizeof(h));
+  int64_t off = js::up((int64_t)sizeof(js::Header), 16);  // (pgdvs_jpeg_reconstruct takes the tables 16-byte aligned)
+  h.off_quant = off, off += 3 * 128;
+  h.off_tables = off, off += js::up((int64_t)js::kTables * (int64_t)sizeof(js::Table), 8);
+  h.off_segments = off, off += js::up((int64_t)pl->nseg * (int64_t)sizeof(js::Segment), 8);
+  h.off_sub_segment = off, off += js::up(pl->max_subs * 4, 8);
+  h.off_stream = off, off += js::up(pl->scan_len, 8) + 8;
+  h.total_bytes = off;
+  return kServed;
+}
+
+int sub_bytes_or_default(const char *what, int32_t sub_bytes, int32_t *out) {
+  *out = sub_bytes == 0 ? PGDVS_JPEG_SCAN_SUB_BYTES : sub_bytes;
+  if (*out < js::kMinSubBytes || *out > js::kMaxSubBytes || *out % 4) {
+    set_error("%s: sub_bytes %d (0 for the default, or a multiple of 4 in %d .. %d)", what, sub_bytes, js::kMinSubBytes, js::kMaxSubBytes);
+    return kBadArgument;
+  }
+  return kServed;
+}
+
+void copy_table(const HuffTable &t, js::Table *o) {
+  memcpy(o->look, t.look, sizeof(o->look));
+  memcpy(o->maxcode, t.maxcode, sizeof(o->maxcode));
+  memcpy(o->valoff, t.valoff, sizeof(o->valoff));
+  o->valoff[0] = 0;
+  o->maxcode[0] = -1;
+  o->n = t.n;
+  memset(o->vals, 0, sizeof(o->vals));
+  memcpy(o->vals, t.vals, (size_t)t.n);
+}
+
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int64_t pgdvs_jpeg_scan_prepare_bytes(const uint8_t *data, int64_t nbytes, int32_t sub_bytes) {
+  if (nbytes < 0 || (data == nullptr && nbytes > 0)) {
+    set_error("pgdvs_jpeg_scan_prepare_bytes: null pointer or negative size");
+    return kBadArgument;
+  }
+  if (sub_bytes_or_default("pgdvs_jpeg_scan_prepare_bytes", sub_bytes, &sub_bytes)) return kBadArgument;
+  Header hdr;
+  PrepLayout pl;
+  if (data == nullptr) {
+    refuse("no SOI marker: not a JPEG stream");
+    return 0;
+  }
+  if (read_header(data, nbytes, hdr) != kServed || prep_layout(hdr, sub_bytes, &pl) != kServed) return 0;
+  return pl.hd.total_bytes;
+}
+
+extern "C" __attribute__((visibility("default"))) int pgdvs_jpeg_scan_prepare(const uint8_t *data, int64_t nbytes, int32_t sub_bytes, void *prepared,
+                                                                               int64_t prepared_bytes, pgdvs_jpeg_info *info) {
+  if (prepared == nullptr || info == nullptr || nbytes < 0 || (data == nullptr && nbytes > 0) || (reinterpret_cast<uintptr_t>(prepared) & 7) != 0) {
+    set_error("pgdvs_jpeg_scan_prepare: null pointer, negative size, or a buffer that is not 8-byte aligned");
+    return kBadArgument;
+  }
+  if (sub_bytes_or_default("pgdvs_jpeg_scan_prepare", sub_bytes, &sub_bytes)) return kBadArgument;
+  Header hdr;
+  if (data == nullptr) return refuse("no SOI marker: not a JPEG stream");
+  int rc = read_header(data, nbytes, hdr);
+  if (rc != kServed) return rc;
+  PrepLayout pl;
+  if ((rc = prep_layout(hdr, sub_bytes, &pl)) != kServed) return rc;
+  if (prepared_bytes < pl.hd.total_bytes) {
+    set_error("pgdvs_jpeg_scan_prepare: a buffer of %lld bytes, the stream takes %lld (pgdvs_jpeg_scan_prepare_bytes)", (long long)prepared_bytes,
+              (long long)pl.hd.total_bytes);
+    return kBadArgument;
+  }
+  uint8_t *base = static_cast<uint8_t *>(prepared);
+  js::Header &h = pl.hd;
+  js::Segment *segs = reinterpret_cast<js::Segment *>(base + h.off_segments);
+  int32_t *sub_segment = reinterpret_cast<int32_t *>(base + h.off_sub_segment);
+  uint8_t *out = base + h.off_stream;
+  // one pass over the scan's bytes: FF 00 unstuffed, the RSTn markers checked and taken out, a segment's data up to its marker
+  const uint8_t *p = data + hdr.scan_begin, *const end = data + hdr.scan_end;
+  const int64_t nmcu = (int64_t)hdr.mcus_w * hdr.mcus_h;
+  const int64_t ri = hdr.info.restart_interval ? hdr.info.restart_interval : nmcu;
+  int64_t o = 0, nsub = 0;
+  for (int k = 0; k < pl.nseg; ++k) {
+    const int64_t begin = o;
+    for (;;) {
+      const uint8_t *q = static_cast<const uint8_t *>(p < end ? memchr(p, 0xFF, (size_t)(end - p)) : nullptr);
+      const uint8_t *stop = q ? q : end;
+      memcpy(out + o, p, (size_t)(stop - p));
+      o += stop - p;
+      p = stop;
+      if (q == nullptr || !(q + 1 < end && q[1] == 0x00)) break;  // the end of the scan, or a marker
+      out[o++] = 0xFF;
+      p = q + 2;
+    }
+    if (k < pl.nseg - 1) {  // process_restart's demands (the bits left over in front of the marker are the decoder's to check)
+      while (p + 1 < end && p[0] == 0xFF && p[1] == 0xFF) ++p;
+      if (p + 2 > end || p[0] != 0xFF || p[1] != 0xD0 + (k & 7)) return refuse("corrupt scan: a restart marker is missing or misnumbered");
+      p += 2;
+    }
+    js::Segment &sg = segs[k];
+    sg.bit_begin = (uint32_t)(begin * 8), sg.bit_end = (uint32_t)(o * 8);
+    sg.mcu_first = (int32_t)(k * ri), sg.mcu_count = (int32_t)(nmcu - k * ri < ri ? nmcu - k * ri : ri);
+    const int64_t subs = o - begin > 0 ? (o - begin + sub_bytes - 1) / sub_bytes : 1;
+    sg.sub_first = (int32_t)nsub, sg.sub_count = (int32_t)subs;
+    for (int64_t i = 0; i < subs; ++i) sub_segment[nsub + i] = k;
+    nsub += subs;
+  }
+  memset(out + o, 0, (size_t)(js::up(pl.scan_len, 8) + 8 - o));
+  memset(sub_segment + nsub, 0, (size_t)(pl.max_subs - nsub) * 4);
+  h.magic = js::kMagic, h.sub_bytes = sub_bytes, h.nseg = pl.nseg, h.nsub = (int32_t)nsub;
+  h.h = hdr.comp[0].h, h.v = hdr.comp[0].v, h.mcus_w = hdr.mcus_w, h.mcus_h = hdr.mcus_h;
+  h.restart_mcus = (int32_t)ri;
+  h.coef_bytes = hdr.info.coef_bytes, h.stream_bytes = o;
+  memcpy(base, &h, sizeof(h));
+  memcpy(base + h.off_quant, hdr.info.quant, 3 * 128);
+  js::Table *tabs = reinterpret_cast<js::Table *>(base + h.off_tables);
+  for (int c = 0; c < 3; ++c) {
+    copy_table(hdr.dc[hdr.comp[c].td], tabs + 2 * c);
+    copy_table(hdr.ac[hdr.comp[c].ta], tabs + 2 * c + 1);
+  }
+  *info = hdr.info;
+  return kServed;
+}
+
+// The kernels of csrc/jpeg_scan_decode.hip, one after the other on the host: the same core, the same rounds (a workgroup is a
+// chunk of kSubsPerGroup subsequences; a round reads every predecessor's exit first and decodes afterwards), the same
+// launches behind their flags, the same workspace.  `prepared` is read twice, as the device entry reads its two copies.
+extern "C" __attribute__((visibility("default"))) int pgdvs_jpeg_scan_decode_host(const void *prepared_host, const void *prepared, int64_t prepared_bytes,
+                                                                                   int16_t *coef, int64_t coef_bytes, uint32_t *status, void *workspace,
+                                                                                   int64_t workspace_bytes) {
+  if (prepared_host == nullptr || prepared == nullptr || coef == nullptr || status == nullptr || workspace == nullptr ||
+      (reinterpret_cast<uintptr_t>(prepared) & 7) != 0 || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
+    set_error("pgdvs_jpeg_scan_decode_host: null pointer, or a buffer that is not 8-byte aligned");
+    return kBadArgument;
+  }
+  js::Header hd;
+  if (prepared_bytes >= (int64_t)sizeof(hd)) memcpy(&hd, prepared_host, sizeof(hd));
+  js::Geo g;
+  if (const char *why = js::check_header(&hd, prepared_bytes, coef_bytes, &g)) {
+    set_error("pgdvs_jpeg_scan_decode_host: %s", why);
+    return kBadArgument;
+  }
+  js::Workspace w;
+  js::workspace_layout(g, &w);
+  if (workspace_bytes < w.total) {
+    set_error("pgdvs_jpeg_scan_decode_host: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)w.total);
+    return kBadArgument;
+  }
+  const uint8_t *base = static_cast<const uint8_t *>(prepared);
+  const js::Table *tabs = reinterpret_cast<const js::Table *>(base + hd.off_tables);
+  const js::Segment *segs = reinterpret_cast<const js::Segment *>(base + hd.off_segments);
+  const int32_t *sub_segment = reinterpret_cast<const int32_t *>(base + hd.off_sub_segment);
+  const uint32_t *words = reinterpret_cast<const uint32_t *>(base + hd.off_stream);
+  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  uint32_t *flags = reinterpret_cast<uint32_t *>(ws + w.flags), *infow = reinterpret_cast<uint32_t *>(ws + w.info);
+  uint64_t *state = reinterpret_cast<uint64_t *>(ws + w.state);
+  int32_t *count = reinterpret_cast<int32_t *>(ws + w.count), *first = reinterpret_cast<int32_t *>(ws + w.first);
+  memset(ws, 0, (size_t)w.head);
+  memset(coef, 0, (size_t)coef_bytes);
+  uint32_t st = 0;
+  constexpr int G = js::kSubsPerGroup;
+  uint64_t entry[G], ex[G], fresh[G];
+  // launch 0: every group on its own, from the known entries and the guesses
+  for (int grp = 0; grp < w.ngroups; ++grp) {
+    const int n = g.nsub - grp * G < G ? g.nsub - grp * G : G;
+    js::SubRange rg[G];
+    for (int t = 0; t < n; ++t) {
+      const int i = grp * G + t;
+      rg[t] = js::sub_range(g, segs, sub_segment, i);
+      entry[t] = js::first_entry(rg[t].begin);
+      ex[t] = js::decode_sub<false>(tabs, words, g, entry[t], rg[t].begin, rg[t].end, rg[t].seg_end, g.sub_bits, &count[i], nullptr);
+    }
+    uint32_t rounds = 1;
+    for (int r = 1; r < G + 1; ++r) {
+      bool changed = false;
+      for (int t = 0; t < n; ++t) fresh[t] = rg[t].begins || t == 0 ? entry[t] : ex[t - 1];
+      for (int t = 0; t < n; ++t) {
+        if (fresh[t] == entry[t]) continue;
+        const int i = grp * G + t;
+        entry[t] = fresh[t];
+        const uint64_t e = js::decode_sub<false>(tabs, words, g, entry[t], rg[t].begin, rg[t].end, rg[t].seg_end, g.sub_bits, &count[i], nullptr);
+        if (e != ex[t]) ex[t] = e, changed = true;
+      }
+      if (!changed) break;
+      ++rounds;
+    }
+    for (int t = 0; t < n; ++t) state[grp * G + t] = ex[t];
+    if (rounds > infow[0]) infow[0] = rounds;
+  }
+  // the fix-up launches: a group's first subsequence takes what the group in front left; a launch in front of which
+  // nothing changed leaves at once
+  for (int launch = 1; launch < w.ngroups; ++launch) {
+    if (launch >= 2 && flags[launch - 1] == 0) continue;
+    ++infow[1];
+    for (int grp = 1; grp < w.ngroups; ++grp) {
+      const int n = g.nsub - grp * G < G ? g.nsub - grp * G : G;
+      js::SubRange rg[G];
+      bool any = false;
+      for (int t = 0; t < n; ++t) {
+        const int i = grp * G + t;
+        rg[t] = js::sub_range(g, segs, sub_segment, i);
+        entry[t] = rg[t].begins ? js::first_entry(rg[t].begin) : state[i - 1];
+        ex[t] = state[i];
+      }
+      for (int r = 0; r < G + 1; ++r) {
+        bool changed = false;
+        for (int t = 0; t < n; ++t) fresh[t] = rg[t].begins || t == 0 ? entry[t] : ex[t - 1];
+        for (int t = 0; t < n; ++t) {
+          if (fresh[t] == entry[t] && !(r == 0 && t == 0)) continue;  // (the first one's stored exit may be a guess's)
+          const int i = grp * G + t;
+          entry[t] = fresh[t];
+          const uint64_t e = js::decode_sub<false>(tabs, words, g, entry[t], rg[t].begin, rg[t].end, rg[t].seg_end, g.sub_bits, &count[i], nullptr);
+          if (e != ex[t]) ex[t] = e, changed = true;
+        }
+        if (!changed) break;
+        any = true;
+      }
+      if (any) {
+        for (int t = 0; t < n; ++t) state[grp * G + t] = ex[t];
+        flags[launch] = 1;
+      }
+    }
+  }
+  // every subsequence's first block: the exclusive sum of the counts
+  first[0] = 0;
+  for (int i = 0; i < g.nsub; ++i) first[i + 1] = first[i] + count[i];
+  // the verified pass
+  for (int i = 0; i < g.nsub; ++i) {
+    const js::SubRange r = js::sub_range(g, segs, sub_segment, i);
+    const int64_t ord = (int64_t)first[i] - first[r.sub_first];
+    const int64_t owed = (int64_t)r.mcu_count * g.bpm, at = (int64_t)r.mcu_first * g.bpm;
+    js::Verify vf;
+    vf.coef = coef, vf.err = 0, vf.last_segment = r.last_segment;
+    vf.block_end = (int32_t)(at + owed < g.nblocks ? at + owed : g.nblocks);
+    vf.block = (int32_t)(at + ord < vf.block_end ? at + ord : vf.block_end);
+    int32_t n;
+    const uint64_t e = js::decode_sub<true>(tabs, words, g, r.begins ? js::first_entry(r.begin) : state[i - 1], r.begin, r.end, r.seg_end, g.sub_bits, &n, &vf);
+    st |= vf.err;
+    if (e != state[i] || n != count[i]) st |= js::kStatusNotSynchronised;
+    if (r.ends && ord + n < owed) st |= js::kStatusShort;
+  }
+  // the DC differences summed per component in stream order, from zero at every segment
+  const int hv = g.h * g.v;
+  int32_t pred[3] = {0, 0, 0};
+  for (int32_t m = 0; m < g.nmcu; ++m) {
+    if (m % g.restart_mcus == 0) pred[0] = pred[1] = pred[2] = 0;
+    for (int k = 0; k < g.bpm; ++k) {
+      const int c = k < hv ? 0 : (k == hv ? 1 : 2);
+      int16_t *dc = coef + js::block_offset(g, m * g.bpm + k);
+      pred[c] += *dc;
+      if (pred[c] < -32768 || pred[c] > 32767) {
+        st |= js::kStatusDcRange;
+        pred[c] = 0;
+      }
+      *dc = (int16_t)pred[c];
+    }
+  }
+  *status = st;
+  return kServed;
 }

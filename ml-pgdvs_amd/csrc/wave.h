@@ -88,15 +88,17 @@ template <class Op, class T> __device__ __forceinline__ T wave_incl_scan_down(T 
   return x;
 }
 
-// Block-wide exclusive offset of `c` in thread order, for a block of kWaves whole wavefronts; `total` = the block's sum
-// (in every thread).  Every thread of the block calls it: it contains ONE __syncthreads().  The caller owns
+// Block-wide exclusive offset of `c` (int, or unsigned where the sums may wrap) in thread order, for a block of kWaves
+// whole wavefronts; `total` = the block's sum (in every thread).  Every thread of the block calls it: it contains ONE __syncthreads().  The caller owns
 // s_wsum[kWaves] (shared memory) and puts a barrier of its own before the array is written again.
-template <int kWaves> __device__ __forceinline__ int block_excl_scan(const int c, int *s_wsum, int &total) {
+// (The value type is s_wsum's: `c` converts to it, as it did when the helper was int alone.)
+template <class T> struct scan_value { using type = T; };
+template <int kWaves, class T> __device__ __forceinline__ T block_excl_scan(const typename scan_value<T>::type c, T *s_wsum, T &total) {
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const int x = wave_incl_scan(c);
+  const T x = wave_incl_scan(c);
   if (lane == kWave - 1) s_wsum[wave] = x;
   __syncthreads();
-  int wave_off = 0;
+  T wave_off = 0;
   total = 0;
 #pragma unroll
   for (int w = 0; w < kWaves; ++w) {

@@ -101,6 +101,17 @@ class JpegInfo(C.Structure):
     ]
 
 
+class JpegScanHeader(C.Structure):
+    """The front of the buffer ``pgdvs_jpeg_scan_prepare`` fills (csrc/jpeg_scan_core.h ``jscan::Header``), field for field:
+    the offsets are bytes from the buffer's start."""
+    _fields_ = [
+        ("magic", C.c_uint32), ("sub_bytes", C.c_int32), ("nseg", C.c_int32), ("nsub", C.c_int32), ("h", C.c_int32), ("v", C.c_int32),
+        ("mcus_w", C.c_int32), ("mcus_h", C.c_int32), ("restart_mcus", C.c_int32), ("reserved0", C.c_int32), ("coef_bytes", _i64),
+        ("stream_bytes", _i64), ("off_quant", _i64), ("off_tables", _i64), ("off_segments", _i64), ("off_sub_segment", _i64),
+        ("off_stream", _i64), ("total_bytes", _i64), ("reserved", _i64 * 4),
+    ]
+
+
 SIGNATURES.update({
     "pgdvs_eval_psnr_workspace_bytes": (_i64, []),
     "pgdvs_eval_psnr_sums": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -159,6 +170,11 @@ SIGNATURES.update({
     "pgdvs_jpeg_entropy_decode": (_i, [_vp, _i64, _vp, _i64]),
     "pgdvs_jpeg_reconstruct_workspace_bytes": (_i64, [C.POINTER(JpegInfo)]),
     "pgdvs_jpeg_reconstruct": (_i, [_vp, _vp, C.POINTER(JpegInfo), _vp, _i64, _vp, _i64, _vp]),
+    "pgdvs_jpeg_scan_prepare_bytes": (_i64, [_vp, _i64, C.c_int32]),
+    "pgdvs_jpeg_scan_prepare": (_i, [_vp, _i64, C.c_int32, _vp, _i64, C.POINTER(JpegInfo)]),
+    "pgdvs_jpeg_scan_decode_workspace_bytes": (_i64, [_vp, _i64]),
+    "pgdvs_jpeg_scan_decode": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "pgdvs_jpeg_scan_decode_host": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

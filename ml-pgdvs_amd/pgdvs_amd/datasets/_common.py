@@ -84,6 +84,14 @@ def check_device_resize(device_resize, resident, device, owner):
     return True
 
 
+def check_device_entropy(device_entropy, device_decode, owner):
+    """``device_entropy=True`` moves the Huffman scan of the frames ``device_decode=True`` decodes onto the device too: refused
+    without it"""
+    if device_entropy and not device_decode:
+        raise ValueError(f"{owner}(device_entropy=True) decodes the scan of the JPEG frames that device_decode=True reads: it needs device_decode=True")
+    return bool(device_entropy)
+
+
 def check_device_decode(device_decode, device_resize, owner):
     """``device_decode=True`` hands the store images that are already on the device, at the file's size: refused without
     ``device_resize=True`` (which in turn asks for ``resident=True`` and a GPU store)"""

@@ -31,7 +31,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, check_device_decode, check_device_resize, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
+from ._common import (F32, check_device_decode, check_device_entropy, check_device_resize, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
                       resize, stack_views, tracker_entries)
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
@@ -356,7 +356,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, mask_data_dir, flow_data_dir, max_hw, mode, rgb_range="0_1", use_aug=False,
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
                  n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False):
+        check_device_entropy(device_entropy, device_decode, type(self).__name__)
         check_device_decode(device_decode, device_resize, type(self).__name__)  # (the dataset's images are PNG: Pillow reads them all)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
@@ -371,7 +372,7 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.device = None if device is None else torch.device(device)
         # resident source frames (datasets/resident.py): the store, and per scene the frame size and the cameras' derived values
-        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode) if resident else None
+        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy) if resident else None
         self._scene_shape, self._cam_cache = {}, {}
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.mask_data_dir, self.flow_data_dir = root / raw_data_dir, root / mask_data_dir, root / flow_data_dir

@@ -41,6 +41,11 @@ stream that ``ops.jpeg_decode`` serves (baseline YCbCr, 4:4:4 / 4:2:2 / 4:2:0), 
 host, everything behind it in HIP, byte for byte ``np.array(PIL.Image.open(path))``.  The store takes such an image where it
 takes a host one -- no second upload -- and a frame of the slot's size is decoded straight into its slot.  Every other file
 (PNG; progressive, greyscale, CMYK, truncated ... JPEG) is opened by Pillow as before, errors included.
+
+``device_entropy=True`` (with ``device_decode=True``): the Huffman scan of those files is decoded on the device as well
+(``ops.jpeg_decode(..., entropy="device")``): the file's bytes cross the bus, not its coefficients, and
+``decode_image`` waits once per file for the scan's status word.  A scan the device gives up (``stats["entropy_fallbacks"]``) is
+read again by the host decoder, which serves it or leaves the file to Pillow as above.
 """
 from collections import OrderedDict
 
@@ -84,7 +89,7 @@ class SceneStore:
     """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``)."""
 
     def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False,
-                 device_decode=False):
+                 device_decode=False, device_entropy=False):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -98,10 +103,12 @@ class SceneStore:
             raise ValueError("SceneStore: device_resize=True resizes on a GPU, the store is in host memory (device=None)")
         if device_decode and not device_resize:
             raise ValueError("SceneStore: device_decode=True hands over images at the file's size: it needs device_resize=True")
-        self.device_resize, self.device_decode = bool(device_resize), bool(device_decode)
+        if device_entropy and not device_decode:
+            raise ValueError("SceneStore: device_entropy=True decodes the scan of the frames device_decode=True reads: it needs device_decode=True")
+        self.device_resize, self.device_decode, self.device_entropy = bool(device_resize), bool(device_decode), bool(device_entropy)
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
                       "targets_resized_on_device": 0, "zoe_files_read": 0, "frames_decoded_on_device": 0, "targets_decoded_on_device": 0,
-                      "jpeg_fallbacks": 0}
+                      "jpeg_fallbacks": 0, "scans_decoded_on_device": 0, "entropy_fallbacks": 0}
 
     @property
     def nbytes(self):
@@ -172,7 +179,13 @@ class SceneStore:
                 info, out = ops.jpeg_info(data), None
                 if info is not None and into is not None and into[0] is not None and (info["height"], info["width"]) == (into[0].h, into[0].w):
                     out = into[0].rgb[self.slots(into[0], [into[1]])[0]]
-                image = None if info is None else ops.jpeg_decode(data, out=out, device=self.device, reject_ok=True)
+                if info is None:
+                    image = None
+                elif self.device_entropy:  # the scan on the device too; the call waits for its status word
+                    image, on_device = ops.jpeg_decode_device(data, out=out, device=self.device, reject_ok=True)
+                    self.stats["scans_decoded_on_device" if on_device else "entropy_fallbacks"] += 1
+                else:
+                    image = ops.jpeg_decode(data, out=out, device=self.device, reject_ok=True)
                 if image is not None:
                     self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
                     return image

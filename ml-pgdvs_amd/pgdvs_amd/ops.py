@@ -1160,7 +1160,71 @@ def jpeg_info(data):
             "quant": np.ctypeslib.as_array(info.quant).copy()}
 
 
-def jpeg_decode(data, out=None, device=None, reject_ok: bool = False):
+JPEG_SCAN_SUB_BYTES = 64  # PGDVS_JPEG_SCAN_SUB_BYTES
+JPEG_SCAN_MAX_BYTES = 1 << 25  # PGDVS_JPEG_SCAN_MAX_BYTES
+JPEG_ENTROPY_MODES = ("host", "device")
+_jpeg_side_streams = {}  # device -> the stream entropy="device" launches on
+
+
+def _cuda_device(device, what):
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"{what} on a GPU, got device {device}")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def jpeg_scan_prepare(data, sub_bytes: int = 0):
+    """``pgdvs_jpeg_scan_prepare`` (host only; include/pgdvs_hip.h): (prepared, info) -- a pinned uint8 tensor with the tables,
+    the segment table and the unstuffed scan of a baseline JPEG cut into subsequences of ``sub_bytes`` bytes (0: the
+    default, ``JPEG_SCAN_SUB_BYTES``), and the ``JpegInfo`` -- or None where the stream is refused (``pgdvs_last_error`` says
+    why: what ``jpeg_info`` refuses, a bad RSTn marker, or a scan above ``JPEG_SCAN_MAX_BYTES``)."""
+    lib = _lib.load()
+    keep, ptr, n = _jpeg_bytes(data)
+    need = lib.pgdvs_jpeg_scan_prepare_bytes(ptr, n, sub_bytes)
+    if need < 0:
+        check(int(need), "pgdvs_jpeg_scan_prepare_bytes")
+    if need == 0:
+        return None
+    prepared = torch.empty(int(need), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    info = _lib.JpegInfo()
+    rc = lib.pgdvs_jpeg_scan_prepare(ptr, n, sub_bytes, C.c_void_p(prepared.data_ptr()), prepared.numel(), C.byref(info))
+    if rc < 0:
+        check(rc, "pgdvs_jpeg_scan_prepare")
+    return None if rc else (prepared, info)
+
+
+def _jpeg_scan_launch(prepared, info, device):
+    """the copy and the scan kernels on the current stream -> (device copy of ``prepared``, coef, status word, workspace)"""
+    lib = _lib.load()
+    dev = prepared.to(device, non_blocking=True)
+    coef = torch.empty(info.coef_bytes // 2, dtype=torch.int16, device=device)
+    status = torch.empty(1, dtype=torch.int32, device=device)
+    ws = _ws(lib.pgdvs_jpeg_scan_decode_workspace_bytes(C.c_void_p(prepared.data_ptr()), prepared.numel()), device)
+    check(lib.pgdvs_jpeg_scan_decode(C.c_void_p(prepared.data_ptr()), _ptr(dev), prepared.numel(), _ptr(coef), info.coef_bytes, _ptr(status),
+                                     _ptr(ws), ws.numel(), _stream()), "pgdvs_jpeg_scan_decode")
+    return dev, coef, status, ws
+
+
+def jpeg_scan_decode(data, device=None, sub_bytes: int = 0, return_rounds: bool = False):
+    """The Huffman scan of a baseline YCbCr JPEG decoded on the GPU (``pgdvs_jpeg_scan_prepare`` on the host, then
+    ``pgdvs_jpeg_scan_decode``; include/pgdvs_hip.h): (coef, status) -- the int16 coefficients ``pgdvs_jpeg_entropy_decode``
+    gives, flat, on ``device``, and the status word as an int (0: decoded; else ``PGDVS_JPEG_SCAN_*`` bits, and ``coef`` holds
+    no result).  For tests and tools: it waits for the device.  A stream the preparation refuses raises ValueError.
+    ``return_rounds``: a third value, (rounds of the first launch, fix-up launches that ran)."""
+    device = _cuda_device(device, "jpeg_scan_decode: the scan is decoded")
+    got = jpeg_scan_prepare(data, sub_bytes)
+    if got is None:
+        raise ValueError("jpeg_scan_decode: the stream is not served: " + _lib.load().pgdvs_last_error().decode("utf-8", "replace"))
+    prepared, info = got
+    with torch.cuda.device(device):
+        _, coef, status, ws = _jpeg_scan_launch(prepared, info, device)
+        st = int(status.cpu()[0]) & 0xFFFFFFFF
+        if return_rounds:
+            return coef, st, tuple(int(x) for x in ws[:8].cpu().view(torch.int32))  # (the workspace's first two words)
+    return coef, st
+
+
+def jpeg_decode(data, out=None, device=None, reject_ok: bool = False, entropy: str = "host"):
     """``np.array(PIL.Image.open(BytesIO(data)))`` of a baseline YCbCr JPEG as a uint8 [H,W,3] GPU tensor, byte for byte (Pillow
     over libjpeg-turbo).  The markers and the Huffman scan are read on the host (``pgdvs_jpeg_parse``,
     ``pgdvs_jpeg_entropy_decode``: C, the GIL released) into a fresh pinned int16 buffer that also carries the three
@@ -1169,7 +1233,21 @@ def jpeg_decode(data, out=None, device=None, reject_ok: bool = False):
     current stream.  ``out``: a contiguous uint8 [H,W,3] tensor on the device to fill (e.g. a frame's slot of the resident
     store).  A stream the path does not serve (include/pgdvs_hip.h lists what it does) raises ValueError with the library's
     reason, or returns None under ``reject_ok`` -- in front of any device work, so the caller can hand the file to Pillow.
-    Does not synchronise."""
+    Does not synchronise.
+
+    ``entropy="device"``: the scan is decoded on the GPU too.  The host only prepares it (``pgdvs_jpeg_scan_prepare``: one
+    pass over the bytes, no Huffman work) into a pinned buffer; one asynchronous copy takes that buffer -- the file's size,
+    not the coefficients' -- to the device; ``pgdvs_jpeg_scan_decode`` and ``pgdvs_jpeg_reconstruct`` run on a side stream
+    of this op's own, which first waits for the caller's stream (``out`` may have pending work there) and which the caller's
+    stream then waits for through an event.  The scan's status word comes back through a pinned word and THIS CALL WAITS for
+    that one event: once per file, the mode's price -- "does not synchronise" belongs to ``entropy="host"`` alone.  A
+    non-zero status (a corrupt scan, or anything the device path does not settle) reruns the file through the host path
+    above, which serves it, refuses it or leaves it to the caller exactly as ``entropy="host"`` does; the second value of
+    ``jpeg_decode_device`` tells the two apart."""
+    if entropy not in JPEG_ENTROPY_MODES:
+        raise ValueError(f"jpeg_decode: entropy {entropy!r}, expected one of {JPEG_ENTROPY_MODES}")
+    if entropy == "device":
+        return jpeg_decode_device(data, out=out, device=device, reject_ok=reject_ok)[0]
     lib = _lib.load()
 
     def refused():
@@ -1202,6 +1280,43 @@ def jpeg_decode(data, out=None, device=None, reject_ok: bool = False):
     check(lib.pgdvs_jpeg_reconstruct(_ptr(dev), C.c_void_p(dev.data_ptr() + info.coef_bytes), C.byref(info), _ptr(out), info.width * 3, _ptr(ws),
                                      ws.numel(), _stream()), "pgdvs_jpeg_reconstruct")
     return out
+
+
+def jpeg_decode_device(data, out=None, device=None, reject_ok: bool = False):
+    """``jpeg_decode(..., entropy="device")`` with its account: (image or None, scan_decoded_on_device).  False: the device
+    path gave the file up (the preparation refused it, or the scan's status word was not zero) and the image, the None or the
+    ValueError is the host path's.  After a non-zero status ``out`` has been written by the reconstruction of an unfinished
+    scan before the host path fills or refuses it."""
+    lib = _lib.load()
+    got = jpeg_scan_prepare(data)
+    if got is None:  # what the markers refuse, a bad RSTn, an oversized scan: the host path says which and decides
+        return jpeg_decode(data, out=out, device=device, reject_ok=reject_ok), False
+    prepared, info = got
+    if device is None and isinstance(out, torch.Tensor) and out.is_cuda:
+        device = out.device
+    device = _cuda_device(device, "jpeg_decode: the image is reconstructed")
+    out = _out(out, (info.height, info.width, 3), torch.uint8, device, "jpeg_decode: out")
+    hd = _lib.JpegScanHeader.from_address(prepared.data_ptr())
+    with torch.cuda.device(device):
+        main = torch.cuda.current_stream(device)
+        side = _jpeg_side_streams.get(device)
+        if side is None:
+            side = _jpeg_side_streams[device] = torch.cuda.Stream(device)
+        side.wait_stream(main)  # (``out`` may still be read or written there)
+        with torch.cuda.stream(side):
+            dev, coef, status, _ = _jpeg_scan_launch(prepared, info, device)
+            word = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            word.copy_(status, non_blocking=True)
+            fetched = torch.cuda.Event()
+            fetched.record(side)
+            ws = _ws(lib.pgdvs_jpeg_reconstruct_workspace_bytes(C.byref(info)), device)
+            check(lib.pgdvs_jpeg_reconstruct(_ptr(coef), C.c_void_p(dev.data_ptr() + hd.off_quant), C.byref(info), _ptr(out), info.width * 3,
+                                             _ptr(ws), ws.numel(), _stream()), "pgdvs_jpeg_reconstruct")
+        main.wait_stream(side)
+        fetched.synchronize()  # the mode's one wait
+    if int(word[0]) == 0:
+        return out, True
+    return jpeg_decode(data, out=out, device=device, reject_ok=reject_ok), False
 
 
 def _flow_pair(a, b, names, what):

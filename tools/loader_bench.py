@@ -29,7 +29,10 @@ monocular layout for ``mono_vis``:
            (median, min and max are reported: the spread is the yardstick of a difference), the items compared bit for bit.  A
            package without the keyword reports ``device_resize`` alone (the parent commit's figure).  Per frame: Pillow's
            full decode, the host entropy decode (one thread; 16 frames on 16 threads), the reconstruction's two launches by
-           device events and each kernel's mean, with the bytes they move against the stream rate
+           device events and each kernel's mean, with the bytes they move against the stream rate.  ``device_entropy=True``
+            is a third variant beside the two where the package has the keyword, and per frame the scan on
+           the device at the ``--scan-sizes`` subsequence sizes (eight by default): host preparation, bytes uploaded, the scan's launches by device events,
+           each kernel's mean, the synchronisation rounds used, and the whole ``ops.jpeg_decode`` call both ways
 ``--legs nvidia,dycheck,resample,zoe,decode`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
 Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--legs dycheck] [--out FILE]"""
 import argparse
@@ -126,7 +129,8 @@ def loaders(nvidia_root, mono_root, scene, mono_scene, center):
     nv = dict(data_root=nvidia_root, raw_data_dir="raw", depth_data_dir="depths", mask_data_dir="masks", flow_data_dir="flows",
               max_hw=-1, scene_ids=[scene], device="cuda:0")
     vis = dict(vis_center_time=center, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32)
-    jk = lambda j: {"device_decode": True} if j else {}  # noqa: E731  (a package without the keyword still takes the rest)
+    # j: False, True (device_decode) or "entropy" (device_entropy too); a package without a keyword still takes the rest
+    jk = lambda j: ({"device_decode": True, "device_entropy": True} if j == "entropy" else {"device_decode": True}) if j else {}  # noqa: E731
     out = {"nvidia_eval": lambda r, d=False, j=False: NvidiaDynEvaluationDataset(mode="eval", resident=r, device_resize=d, **jk(j), **nv),
            "nvidia_pure_geo": lambda r, d=False: NvidiaDynPureGeoEvaluationDataset(mode="eval", resident=r, device_resize=d, **nv),
            "nvidia_vis": lambda r, d=False, j=False: NvidiaDynVisualizationDataset(mode="vis", resident=r, device_resize=d, **jk(j), **vis, **nv)}
@@ -304,7 +308,8 @@ def _spread(xs):
 
 
 def decode_loaders_case(make, n_items, rounds):
-    """fresh loaders each round, ``device_resize`` alone and with ``device_decode``, alternating; items/s of both passes"""
+    """fresh loaders each round, ``device_resize`` alone, with ``device_decode`` and with ``device_entropy`` on top, alternating;
+    items/s of both passes"""
     rec = {}
     for name in ("nvidia_eval", "nvidia_vis"):
         fn = make[name]
@@ -313,6 +318,11 @@ def decode_loaders_case(make, n_items, rounds):
             variants = (("device_resize", False), ("device_decode", True))
         except TypeError:
             variants = (("device_resize", False),)
+        try:
+            fn(True, True, "entropy")
+            variants += (("device_entropy", "entropy"),)
+        except TypeError:  # (a package without the keyword: the parent commit's columns alone)
+            pass
         probe = fn(True, True)
         idx = [int(round(j * (len(probe) - 1) / max(n_items - 1, 1))) for j in range(n_items)]
         probe[idx[0]]  # (warm-up: code objects, the resize plans)
@@ -339,7 +349,7 @@ def decode_loaders_case(make, n_items, rounds):
     return rec
 
 
-def decode_frame_case(path, reps):
+def decode_frame_case(path, reps, scan_sizes=(64,)):
     """one file: Pillow's decode, the host entropy decode and the reconstruction on the device"""
     import ctypes as C
     import io
@@ -395,10 +405,67 @@ def decode_frame_case(path, reps):
                 "kernels": {k: {"ms_mean": v, "bytes_moved": moved[k], "streaming_bound_ms": moved[k] / HBM_BYTES_PER_S * 1e3,
                                 "share_of_stream_rate": moved[k] / HBM_BYTES_PER_S * 1e3 / v} for k, v in kernels.items()},
                 "streaming_bound_ms": sum(moved.values()) / HBM_BYTES_PER_S * 1e3})
+    if hasattr(ops, "jpeg_scan_decode"):
+        rec["scan_on_device"] = scan_frame_case(data, info, reps, clock, event_median, scan_sizes)
     return rec
 
 
-def decode_case(nvidia_root, scene, center, n_items, reps, rounds, synthetic):
+def scan_frame_case(data, info, reps, clock, event_median, sizes):
+    """the scan of one file decoded on the device, per subsequence size: the host preparation, the bytes
+    uploaded, the launches of ``pgdvs_jpeg_scan_decode`` together (device events, median) and each kernel's mean, the rounds
+    the synchronisation used; and the whole ``ops.jpeg_decode`` call both ways, to its last byte (a host clock round a
+    synchronise)"""
+    import ctypes as C
+
+    from pgdvs_amd import _lib, ops
+
+    lib, dev = _lib.load(), torch.device("cuda:0")
+    rec = {"default_sub_bytes": ops.JPEG_SCAN_SUB_BYTES, "sizes": {}}
+    rc, want, _ = _host_coef(lib, data, info)
+    for sub in sizes:
+        prepared, _ = ops.jpeg_scan_prepare(data, sub)
+        coef, status, (rounds, fixups) = ops.jpeg_scan_decode(data, dev, sub, return_rounds=True)
+        hd = _lib.JpegScanHeader.from_address(prepared.data_ptr())
+        r = rec["sizes"][sub] = {"status": status, "equals_host_decoder": bool(rc == 0 and np.array_equal(coef.cpu().numpy(), want)),
+                                 "subsequences": hd.nsub, "workgroups": -(-hd.nsub // 256), "rounds_first_launch": rounds,
+                                 "fixup_launches_that_ran": fixups, "bytes_uploaded": prepared.numel(), "coef_bytes": info.coef_bytes,
+                                 "prepare_ms": clock(lambda: ops.jpeg_scan_prepare(data, sub), 10)}
+        d = prepared.to(dev)
+        out, st = torch.empty(info.coef_bytes // 2, dtype=torch.int16, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(lib.pgdvs_jpeg_scan_decode_workspace_bytes(C.c_void_p(prepared.data_ptr()), prepared.numel()), dtype=torch.uint8, device=dev)
+        run = lambda: _lib.check(lib.pgdvs_jpeg_scan_decode(C.c_void_p(prepared.data_ptr()), d.data_ptr(), prepared.numel(), out.data_ptr(),  # noqa: E731
+                                                            info.coef_bytes, st.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), "scan")
+        r["scan_decode_ms_median"], r["scan_decode_ms_min"] = event_median(run, reps, 4)
+        r["upload_ms_median"], _ = event_median(lambda: d.copy_(prepared, non_blocking=True), reps, 4)
+        lib.pgdvs_prof_enable(1)
+        for _ in range(reps):
+            run()
+        text = C.create_string_buffer(4096)
+        lib.pgdvs_prof_report(text, 4096)
+        lib.pgdvs_prof_enable(0)
+        r["kernels_ms_per_call"] = {ln.split()[0]: float(ln.split()[2]) / reps for ln in text.value.decode().splitlines()
+                                    if ln.startswith(("jpeg_scan", "jpeg_dc", "fill_bytes"))}
+
+    def whole(mode):
+        def fn():
+            ops.jpeg_decode(data, device=dev, entropy=mode)
+            torch.cuda.synchronize()
+        fn()
+        return clock(fn, 20)
+    rec["jpeg_decode_call_ms"] = {"host": whole("host"), "device": whole("device")}
+    return rec
+
+
+def _host_coef(lib, data, info):
+    import ctypes as C
+
+    arr = np.frombuffer(data, np.uint8)
+    coef = np.zeros(info.coef_bytes // 2, np.int16)
+    rc = lib.pgdvs_jpeg_entropy_decode(C.c_void_p(arr.ctypes.data), arr.size, C.c_void_p(coef.ctypes.data), info.coef_bytes)
+    return rc, coef, None
+
+
+def decode_case(nvidia_root, scene, center, n_items, reps, rounds, synthetic, scan_sizes):
     rec = {}
     for sub in (("4:2:0", "4:4:4") if synthetic else (None,)):
         if sub is not None:
@@ -406,7 +473,7 @@ def decode_case(nvidia_root, scene, center, n_items, reps, rounds, synthetic):
         r = rec[sub or "tree"] = {"loaders": decode_loaders_case(loaders(nvidia_root, None, scene, None, center), n_items, rounds)}
         first = sorted((pathlib.Path(nvidia_root) / "raw" / scene / "dense" / "mv_images").glob("*/*.jpg"))[0]
         try:
-            r["frame"] = decode_frame_case(first, reps)
+            r["frame"] = decode_frame_case(first, reps, scan_sizes)
         except AttributeError as e:  # (a package without the reader)
             r["frame"] = f"not in this package: {e}"
         print(f"decode frame {sub}: {r['frame']}", file=sys.stderr, flush=True)
@@ -559,6 +626,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe, decode")
     ap.add_argument("--rounds", type=int, default=3, help="decode leg: rounds of fresh loaders per variant")
+    ap.add_argument("--scan-sizes", default="16,32,48,64,96,128,256,512", help="decode leg: subsequence sizes (bytes) of the per-frame scan figures")
     ap.add_argument("--zoe-setting", default="moe", help="use_zoe_depth of the zoe leg")
     ap.add_argument("--zoe-path", default=None, help="zoe_depth_data_path under a real --data_root (the synthetic tree brings its own)")
     ap.add_argument("--out", default=None)
@@ -626,7 +694,8 @@ def main():
             rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
             rec["gather"] = gather_case(args.reps)
         if "decode" in legs:  # last: it rewrites the synthetic tree's image files
-            rec["decode"] = decode_case(nvidia_root, args.scene, center, args.items, args.reps, args.rounds, args.data_root is None)
+            rec["decode"] = decode_case(nvidia_root, args.scene, center, args.items, args.reps, args.rounds, args.data_root is None,
+                                        tuple(int(x) for x in args.scan_sizes.split(",")))
     finally:
         shutil.rmtree(scratch, ignore_errors=True)
     js = json.dumps(rec, indent=1)
