@@ -1162,6 +1162,57 @@ int pgdvs_jpeg_scan_decode(const void *prepared_host, const void *prepared, int6
 int pgdvs_jpeg_scan_decode_host(const void *prepared_host, const void *prepared, int64_t prepared_bytes, int16_t *coef, int64_t coef_bytes,
                                 uint32_t *status, void *workspace, int64_t workspace_bytes);
 
+/* PNG frames read on the device (csrc/png_inflate_core.h: the inflate core; csrc/png_inflate.hip and csrc/png_unfilter.hip:
+ * the kernels; csrc/png_decode_host.cpp: the host emulation): the zlib stream of a non-interlaced 8-bit RGB or RGBA file is
+ * inflated, checked against its Adler-32 and unfiltered into uint8 [H,W,out_channels], byte for byte what a PNG reader
+ * gives.  The host parses the chunks (Python: ops.png_info) and does no Huffman work; a launch takes a BATCH of streams, one
+ * workgroup each.
+ * The batch buffer: a table of nstreams pgdvs_png_stream, padded to 16 bytes, then the streams, each at a 16-byte aligned
+ * `offset` from the buffer's start with `size` bytes (the two zlib header bytes, which the caller has checked -- deflate,
+ * a window of at most 32K, no preset dictionary --, the deflate blocks and the four Adler bytes), padded to a multiple of 4
+ * bytes.  height, width: 1 .. 16384; channels: the file's, 3 or 4; out_channels: 3 (an RGBA file's alpha is dropped) or
+ * `channels`; out / row_stride: the image's first byte and the bytes between rows, row_stride >= width * out_channels, any
+ * alignment.  height * (1 + width * channels) and size stay at or below PGDVS_PNG_INFLATE_MAX_BYTES: positions fit 32 bits.
+ * pgdvs_png_decode: batch_host: HOST, the buffer as filled (only its table is read, and checked: the launches follow from
+ * it alone); batch: DEVICE, a copy of the same batch_bytes bytes, 16-byte aligned; sub_bytes: 0 for
+ * PGDVS_PNG_INFLATE_SUB_BYTES, else a multiple of 4 in 8 .. 1024; status: DEVICE, nstreams words; workspace: DEVICE, 256-byte
+ * aligned, >= pgdvs_png_inflate_workspace_bytes(table, nstreams) (-1 for a table it refuses).  Two launches on `stream`, no
+ * host synchronisation.  status[i] is 0 only if stream i inflated to exactly height * (1 + width * channels) bytes, the bytes
+ * behind its final block were exactly the four of the Adler-32 of those bytes, and every row's filter byte was 0 .. 4; else
+ * PGDVS_PNG_* bits say what was met (_BLOCK: block type 3, a length set that is over-subscribed or incomplete as zlib judges
+ * it, a bad repeat, no end-of-block code; _CODE: a code the table lacks, length symbols 286 / 287, distance symbols 30 / 31;
+ * _DISTANCE: a distance in front of the output; _STORED: LEN / NLEN disagree; _DATA_OUT: the data ran out; _SIZE: more or
+ * fewer bytes than the image's; _LEFT_OVER; _ADLER; _FILTER; _NOT_SYNCHRONISED: never set by construction) and out[i] holds
+ * no result: the caller hands the file to a host reader, which decides.  Whatever the streams' bytes hold, nothing outside
+ * the batch buffer is read and nothing outside the images' rows, status and the workspace is written.
+ * The workspace's first words, for tools, four per stream: windows, the most synchronisation rounds of a window, the most
+ * resolve rounds of a window, blocks.
+ * pgdvs_png_decode_host: the same walk on the CPU, HOST pointers throughout (batch_host and batch may be the same buffer;
+ * 8-byte alignment suffices): the same core, windows, rounds and workspace.  0, or -1 for argument errors. */
+#define PGDVS_PNG_INFLATE_SUB_BYTES 64
+#define PGDVS_PNG_INFLATE_MAX_BYTES (1 << 28)
+#define PGDVS_PNG_BLOCK 1
+#define PGDVS_PNG_CODE 2
+#define PGDVS_PNG_DISTANCE 4
+#define PGDVS_PNG_STORED 8
+#define PGDVS_PNG_DATA_OUT 16
+#define PGDVS_PNG_SIZE 32
+#define PGDVS_PNG_LEFT_OVER 64
+#define PGDVS_PNG_ADLER 128
+#define PGDVS_PNG_FILTER 256
+#define PGDVS_PNG_NOT_SYNCHRONISED 512
+typedef struct pgdvs_png_stream {
+  int64_t offset, size;
+  int32_t height, width, channels, out_channels;
+  int64_t row_stride;
+  void *out;
+} pgdvs_png_stream;
+int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_stream *streams, int32_t nstreams);
+int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                     void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
+                          uint32_t *status, void *workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

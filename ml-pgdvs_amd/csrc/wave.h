@@ -88,6 +88,12 @@ template <class Op, class T> __device__ __forceinline__ T wave_incl_scan_down(T 
   return x;
 }
 
+// The value of the lane in front (wave_shr:1 through the DPP path, no LDS round trip): lane l holds lane l - 1's x, lane 0
+// its own.  All 64 lanes call.  The skewed row pass of png_unfilter.hip hands a pixel from row to row with it.
+__device__ __forceinline__ uint32_t wave_prev_lane(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, 0x138, 0xf, 0xf, false);
+}
+
 // Block-wide exclusive offset of `c` (int, or unsigned where the sums may wrap) in thread order, for a block of kWaves
 // whole wavefronts; `total` = the block's sum (in every thread).  Every thread of the block calls it: it contains ONE __syncthreads().  The caller owns
 // s_wsum[kWaves] (shared memory) and puts a barrier of its own before the array is written again.

@@ -101,6 +101,14 @@ class JpegInfo(C.Structure):
     ]
 
 
+class PngStream(C.Structure):
+    """``pgdvs_png_stream`` (include/pgdvs_hip.h), field for field: one entry of the table at the front of a batch buffer."""
+    _fields_ = [
+        ("offset", _i64), ("size", _i64), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("out_channels", C.c_int32),
+        ("row_stride", _i64), ("out", _vp),
+    ]
+
+
 class JpegScanHeader(C.Structure):
     """The front of the buffer ``pgdvs_jpeg_scan_prepare`` fills (csrc/jpeg_scan_core.h ``jscan::Header``), field for field:
     the offsets are bytes from the buffer's start."""
@@ -175,6 +183,9 @@ SIGNATURES.update({
     "pgdvs_jpeg_scan_decode_workspace_bytes": (_i64, [_vp, _i64]),
     "pgdvs_jpeg_scan_decode": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
     "pgdvs_jpeg_scan_decode_host": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64]),
+    "pgdvs_png_inflate_workspace_bytes": (_i64, [_vp, C.c_int32]),
+    "pgdvs_png_decode": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp]),
+    "pgdvs_png_decode_host": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

@@ -100,6 +100,14 @@ def check_device_decode(device_decode, device_resize, owner):
     return bool(device_decode)
 
 
+def check_device_png(device_png, device_resize, owner):
+    """``device_png=True`` decodes PNG frames on the device at the file's size: refused without
+    ``device_resize=True``; independent of ``device_decode``"""
+    if device_png and not device_resize:
+        raise ValueError(f"{owner}(device_png=True) decodes PNG frames on the device at the file's size: it needs device_resize=True")
+    return bool(device_png)
+
+
 def group_entries(group, views, times=None, n_actual=None, depth=True):
     """The item's entries of one group of stacked source views: "spatial", "temporal" or "temporal_track_{fwd,bwd}2tgt".
     The temporal and tracker groups also carry their frames' ``times`` and ``n_actual``, the count before padding; the

@@ -31,7 +31,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, check_device_decode, check_device_entropy, check_device_resize, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
+from ._common import (F32, check_device_decode, check_device_entropy, check_device_png, check_device_resize, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
                       resize, stack_views, tracker_entries)
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
@@ -160,6 +160,10 @@ class iPhoneParser:  # noqa: N801 -- upstream's name
 
     def get_frame_name(self, time_id, camera_id):
         return self._frame_names_map[time_id, camera_id]
+
+    def rgb_path(self, time_id, camera_id):
+        """the file ``load_rgba`` opens"""
+        return os.path.join(self.data_dir, "rgb", f"{self._factor}x", self._frame_names_map[time_id, camera_id] + ".png")
 
     def load_rgba(self, time_id, camera_id):
         path = os.path.join(self.data_dir, "rgb", f"{self._factor}x", self._frame_names_map[time_id, camera_id] + ".png")
@@ -356,8 +360,9 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, mask_data_dir, flow_data_dir, max_hw, mode, rgb_range="0_1", use_aug=False,
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
                  n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
         check_device_entropy(device_entropy, device_decode, type(self).__name__)
+        check_device_png(device_png, device_resize, type(self).__name__)
         check_device_decode(device_decode, device_resize, type(self).__name__)  # (the dataset's images are PNG: Pillow reads them all)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
@@ -372,7 +377,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.device = None if device is None else torch.device(device)
         # resident source frames (datasets/resident.py): the store, and per scene the frame size and the cameras' derived values
-        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy) if resident else None
+        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy,
+                                device_png) if resident else None
         self._scene_shape, self._cam_cache = {}, {}
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.mask_data_dir, self.flow_data_dir = root / raw_data_dir, root / mask_data_dir, root / flow_data_dir
@@ -503,9 +509,10 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def _decode_frame(self, scene_id, time_id, shape):
         """(image uint8, dynamic mask, depth) of a train frame at the scene's size, as _process_view reads them"""
         p, cam_id, (h, w) = self.parser_dict[scene_id], self.get_train_cam_id(scene_id), shape
-        raw = p.load_rgba(time_id, cam_id)[..., :3]
-        if not self.store.device_resize:  # (else the image as decoded: the store resizes it)
-            raw = resize(raw, h, w, PIL.Image.Resampling.BOX)
+        if self.store.device_resize:  # the image as the store decodes it (device_png: on the device); the store resizes it
+            raw = self._store_rgb(p, time_id, cam_id, into=(self.store.scenes.get(scene_id), time_id))
+        else:
+            raw = resize(p.load_rgba(time_id, cam_id)[..., :3], h, w, PIL.Image.Resampling.BOX)
         name = p.get_frame_name(time_id, cam_id)
         m = np.array(PIL.Image.open(self.mask_data_dir / scene_id / f"masks/final/{name}_final.png"))
         depth = p.load_depth(time_id, cam_id)
@@ -513,6 +520,13 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
             raise ValueError(f"{p.depth_path(time_id, cam_id)}: the depth times the scene's scale is float64; resident=True keeps "
                              "float32 depths, and the disk path would take the depth range over the doubles")
         return raw, resize(m, h, w, PIL.Image.Resampling.NEAREST), resize(depth[..., 0], h, w, PIL.Image.Resampling.NEAREST)
+
+    def _store_rgb(self, p, time_id, cam_id, **kw):
+        """``load_rgba(...)[..., :3]`` through the store's ``decode_image``: the same bytes, the missing file's error included"""
+        path = p.rgb_path(time_id, cam_id)
+        if not os.path.exists(path):
+            raise ValueError(f"RGB image not found: {path}.")
+        return self.store.decode_image(path, channels="rgb", **kw)
 
     @staticmethod
     def _item_key_order():
@@ -540,8 +554,9 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         spatial_ids = select_spatial_frames(self.spatial_src_view_type, tgt_time_id, raw_c2w_tgt, info["time_ids"], info["train_c2w"],
                                             self.n_src_views_spatial, clusters)
         frame_ids = np.array([tgt_time_id, *spatial_ids, *sel["temporal"]]).astype(int)
-        tgt_rgb = p.load_rgba(tgt_time_id, tgt_cam_id)[..., :3]
-        tgt_shape = tgt_rgb.shape[:2]
+        tgt_rgb = (self._store_rgb(p, tgt_time_id, tgt_cam_id, target=True) if self.store.device_resize else
+                   p.load_rgba(tgt_time_id, tgt_cam_id)[..., :3])
+        tgt_shape = tuple(tgt_rgb.shape[:2])
         covis = p.load_covisible(tgt_time_id, tgt_cam_id, "val")
         assert covis.shape[:2] == tgt_shape, (covis.shape, tgt_shape)
         if tuple(tgt_shape) != shape:
@@ -553,8 +568,11 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
                 raise ValueError(f"{scene_id}: frame id {int(t)} is no train frame ({min(train)}..{max(train)})")
         host = {"seq_ids": torch.LongTensor(frame_ids), "flat_cam_tgt": F32(np.array(flat_cam_tgt)),
                 "time_tgt": torch.FloatTensor([tgt_time_id])}
-        as_bytes = dev is not None and tgt_rgb.dtype == np.uint8 and tgt_rgb.ndim == 3 and tgt_rgb.shape[2] == 3
-        if as_bytes:
+        on_device = isinstance(tgt_rgb, torch.Tensor)  # (device_png decoded it there: uint8 [H,W,3])
+        as_bytes = on_device or (dev is not None and tgt_rgb.dtype == np.uint8 and tgt_rgb.ndim == 3 and tgt_rgb.shape[2] == 3)
+        if on_device:
+            pass
+        elif as_bytes:
             host["__rgb_tgt"] = torch.from_numpy(np.ascontiguousarray(tgt_rgb))
         else:
             host["rgb_tgt"] = F32(tgt_rgb.astype(np.float32) / 255.0)
@@ -583,11 +601,12 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
                           host=host, cams=cams, sel=sel, spatial_ids=spatial_ids, spatial_depth=True, c2w_tgt=None,
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b),
                           trackers=True, owner=type(self).__name__, depth_range=depth_range,
-                          ray_rows=lambda ids: ray_rows([self._cam(scene_id, t, cam_id)["rays"] for t in ids]))
+                          ray_rows=lambda ids: ray_rows([self._cam(scene_id, t, cam_id)["rays"] for t in ids]),
+                          image_path=lambda t: (p.rgb_path(t, cam_id), "rgb"))
         if as_bytes:
             from .. import ops
 
-            rgb, mask = ops.item_target(item.pop("__rgb_tgt"), item.pop("__covisible", None))
+            rgb, mask = ops.item_target(tgt_rgb if on_device else item.pop("__rgb_tgt"), item.pop("__covisible", None))
             item["rgb_tgt"] = rgb
             if mask is not None:
                 item["eval_mask"] = mask

@@ -25,7 +25,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, check_device_decode, check_device_entropy, check_device_resize, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
+from ._common import (F32, check_device_decode, check_device_entropy, check_device_png, check_device_resize, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
                       tracker_entries)
 from .nvidia_eval import spatial_depth_range
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -119,8 +119,9 @@ class MonoVisualizationDataset(Dataset):
     def __init__(self, *, data_root, max_hw, mode, rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
                  vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
         check_device_entropy(device_entropy, device_decode, type(self).__name__)
+        check_device_png(device_png, device_resize, type(self).__name__)
         check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
@@ -131,7 +132,8 @@ class MonoVisualizationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
         # the source frames kept in memory (datasets/resident.py)
-        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy)
+        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy,
+                                 device_png)
                       if resident else None)
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
@@ -202,7 +204,7 @@ class MonoVisualizationDataset(Dataset):
             raw = self.store.decode_image(img_fs[f], into=(scene, f)) if self.store.device_resize else None
             return self._decode_frame(scene_dir, img_fs[f], shape, raw=raw, resize_rgb=not self.store.device_resize)
 
-        return build_item(self.store, scene, decode, cams=cams,
+        return build_item(self.store, scene, decode, cams=cams, image_path=lambda f: img_fs[f],
                           flow_path=lambda a, b: self._flow_path(scene_dir, img_fs, a, b), owner=type(self).__name__, **kw)
 
     def __getitem__(self, index):

@@ -61,7 +61,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, TGT_HEIGHT, check_device_decode, check_device_entropy, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
+from ._common import (F32, TGT_HEIGHT, check_device_decode, check_device_entropy, check_device_png, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
                       read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
 from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -230,8 +230,9 @@ class NvidiaDynEvaluationDataset(Dataset):
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
                  flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES,
-                 device_resize=False, device_decode=False, device_entropy=False):
+                 device_resize=False, device_decode=False, device_entropy=False, device_png=False):
         check_device_entropy(device_entropy, device_decode, type(self).__name__)
+        check_device_png(device_png, device_resize, type(self).__name__)
         check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
@@ -257,7 +258,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize, device_decode, device_entropy)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize, device_decode, device_entropy, device_png)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
@@ -290,9 +291,11 @@ class NvidiaDynEvaluationDataset(Dataset):
     # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
     store = None  # the SceneStore of ``resident=True``
 
-    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, device_resize=False, device_decode=False, device_entropy=False):
+    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, device_resize=False, device_decode=False, device_entropy=False,
+                       device_png=False):
         if resident:
-            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_resize, device_decode, device_entropy)
+            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_resize, device_decode, device_entropy,
+                                    device_png)
 
     def _decode_frame(self, scene_id, frame_id, tgt_shape):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
@@ -337,6 +340,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         if zoe:  # depths and range come from the predictions; the cameras keep _aug_c2w's double inversion
             kw["depths"] = lambda ids, range_cams, rays: self.store.zoe_depths(scene, ids, range_cams, rays, kw["c2w_tgt"])
         return build_item(self.store, scene, lambda f: self._decode_frame(scene_id, f, tgt_shape), cams=cams,
+                          image_path=lambda f: self._src_img_f(scene_id, f),
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b), owner=type(self).__name__, **kw)
 
     # ------------------------------------------------------------------ ZoeDepth
@@ -581,8 +585,9 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
 
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
-                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False):
+                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
         check_device_entropy(device_entropy, device_decode, type(self).__name__)
+        check_device_png(device_png, device_resize, type(self).__name__)
         check_device_decode(device_decode, device_resize, type(self).__name__)
         check_device_resize(device_resize, resident, device, type(self).__name__)
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
@@ -590,7 +595,7 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,
                          n_src_views_temporal_track_one_side=0, flow_consist_thres=flow_consist_thres)
         self.device = device
-        self._init_resident(resident, resident_scenes, resident_max_bytes, device, device_resize, device_decode, device_entropy)  # (where the cloud is built)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, device, device_resize, device_decode, device_entropy, device_png)  # (where the cloud is built)
         self.st_pcl_dict = {scene: self._aggregate_static_pcl(scene) for scene in sorted(self.scene_img_dict)}
 
     def _load_mono_video(self, scene_id):
@@ -602,7 +607,9 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
         n = all_hwf.shape[0]
         mono = scene_dir / f"images_{tgt_w}x{tgt_h}"
         if self.store is not None and self.store.device_resize:  # the frames of another size in one batched call
-            imgs = self.store.resize_stack([np.array(PIL.Image.open(mono / f"{i:05d}.png")) for i in range(n)], (tgt_h, tgt_w), "lanczos")
+            files = [mono / f"{i:05d}.png" for i in range(n)]
+            raws = self.store.decode_stack(files) if self.store.device_png else [np.array(PIL.Image.open(f)) for f in files]
+            imgs = self.store.resize_stack(raws, (tgt_h, tgt_w), "lanczos")
             imgs = np.stack(imgs).astype(np.float32) / 255.0
         else:
             imgs = np.stack([_resize(np.array(PIL.Image.open(mono / f"{i:05d}.png")), tgt_h, tgt_w, PIL.Image.Resampling.LANCZOS)

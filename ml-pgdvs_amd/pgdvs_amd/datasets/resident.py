@@ -46,6 +46,14 @@ takes a host one -- no second upload -- and a frame of the slot's size is decode
 (``ops.jpeg_decode(..., entropy="device")``): the file's bytes cross the bus, not its coefficients, and
 ``decode_image`` waits once per file for the scan's status word.  A scan the device gives up (``stats["entropy_fallbacks"]``) is
 read again by the host decoder, which serves it or leaves the file to Pillow as above.
+
+``device_png=True`` (with ``device_resize=True``; independent of ``device_decode``): ``decode_image`` serves PNG files on the
+device as well (``ops.png_decode_batch``): non-interlaced 8-bit RGB and RGBA files are inflated and unfiltered in
+HIP, byte for byte ``np.array(PIL.Image.open(path))`` (``channels="rgb"``: its first three channels).  ``prefetch_images`` decodes
+several files in one batched launch and one wait and keeps the results for the ``decode_image`` calls that follow; ``views``
+prefetches an item's missing frames that way where the loader names their files (``image_path``).  A file the path does not
+serve (``stats["png_fallbacks"]``: another colour type or bit depth, interlace, tRNS, a damaged file ...) is opened by Pillow
+as before, errors included.
 """
 from collections import OrderedDict
 
@@ -89,7 +97,7 @@ class SceneStore:
     """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``)."""
 
     def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False,
-                 device_decode=False, device_entropy=False):
+                 device_decode=False, device_entropy=False, device_png=False):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -105,10 +113,14 @@ class SceneStore:
             raise ValueError("SceneStore: device_decode=True hands over images at the file's size: it needs device_resize=True")
         if device_entropy and not device_decode:
             raise ValueError("SceneStore: device_entropy=True decodes the scan of the frames device_decode=True reads: it needs device_decode=True")
+        if device_png and not device_resize:
+            raise ValueError("SceneStore: device_png=True hands over images at the file's size: it needs device_resize=True")
         self.device_resize, self.device_decode, self.device_entropy = bool(device_resize), bool(device_decode), bool(device_entropy)
+        self.device_png = bool(device_png)
+        self._prefetched = {}  # (path, channels) -> the image prefetch_images decoded, until decode_image hands it out
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
                       "targets_resized_on_device": 0, "zoe_files_read": 0, "frames_decoded_on_device": 0, "targets_decoded_on_device": 0,
-                      "jpeg_fallbacks": 0, "scans_decoded_on_device": 0, "entropy_fallbacks": 0}
+                      "jpeg_fallbacks": 0, "scans_decoded_on_device": 0, "entropy_fallbacks": 0, "png_decoded_on_device": 0, "png_fallbacks": 0}
 
     @property
     def nbytes(self):
@@ -158,24 +170,94 @@ class SceneStore:
             raise ValueError(f"frame ids {[int(f) for f in frame_ids]} outside the scene's {scene.first_id}..{scene.first_id + scene.n_frames - 1}")
         return slots
 
-    def _fill(self, scene, frame_ids, decode):
-        for f in sorted(set(frame_ids)):
-            if not scene.filled[f - scene.first_id]:
+    def _fill(self, scene, frame_ids, decode, image_path=None):
+        missing = [f for f in sorted(set(frame_ids)) if not scene.filled[f - scene.first_id]]
+        if self.device_png and image_path is not None and len(missing) > 1:  # the item's missing frames in one launch, one wait
+            paths = [image_path(f) for f in missing]
+            self.prefetch_images([p if isinstance(p, tuple) else (p, "file") for p in paths], [(scene, f) for f in missing])
+        try:
+            for f in missing:
                 self.put(scene, f, *decode(f))
+        finally:
+            self._prefetched.clear()  # (also when a reader raises: the entries hold device tensors, some of them slots)
 
     # ------------------------------------------------------------------ the decode on the device
-    def decode_image(self, path, target=False, into=None):
-        """An image file's pixels.  Without ``device_decode``: ``np.array(PIL.Image.open(path))``.  With it the file's bytes
-        decide, as they do for Pillow, not its name: a JPEG stream (``FF D8``) that ``ops.jpeg_decode`` serves comes back as a
-        uint8 [H,W,3] tensor on the store's device (nothing waits for it); any other file takes the Pillow statement.
-        ``target``: counted as an item's target, not as a source frame.  ``into`` = (scene or None, frame id): a frame of the
-        slot's size is decoded straight into ``scene.rgb[slot]``, which ``put`` then recognises."""
-        if self.device_decode:
-            from .. import ops
+    def _slot_for(self, into, height, width, channels):
+        """the slot ``into`` = (scene or None, frame id) names, where an image of this size is exactly what it keeps"""
+        if into is None or into[0] is None or (height, width, channels) != (into[0].h, into[0].w, 3):
+            return None
+        return into[0].rgb[self.slots(into[0], [into[1]])[0]]
 
+    def prefetch_images(self, paths, intos=None):
+        """With ``device_png``: the files of ``paths`` (each a path, or (path, channels)) read once, and the PNG files among
+        them decoded in ONE batched launch with one wait.  The bytes and the outcome -- the image, or None for a file the
+        path refused or gave up -- are kept for the ``decode_image`` calls that follow, which then neither read, parse nor
+        launch again (``_fill`` and ``decode_stack`` drop what is left).  ``intos``: per path None or (scene, frame id), as
+        ``decode_image`` takes it."""
+        if not self.device_png:
+            return
+        from .. import ops
+
+        intos = [None] * len(paths) if intos is None else intos
+        by_mode = {}
+        for p, into in zip(paths, intos):
+            path, channels = p if isinstance(p, tuple) else (p, "file")
+            key = (str(path), channels)
+            if key in self._prefetched:
+                continue
             with open(path, "rb") as f:
                 data = f.read()
-            if data[:2] == b"\xff\xd8":
+            is_png = data[:8] == ops._PNG_SIGNATURE
+            parsed = ops._png_parse(data) if is_png else (None, None)
+            self._prefetched[key] = (data, None, is_png)  # (bytes, image, whether the PNG path has had its turn)
+            if parsed[0] is not None:
+                info = parsed[0]
+                out = self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])
+                by_mode.setdefault(channels, []).append((key, data, parsed, out))
+        for channels, batch in by_mode.items():
+            got = ops.png_decode_batch([b[1] for b in batch], outs=[b[3] for b in batch], channels=channels, device=self.device, reject_ok=True,
+                                       parsed=[b[2] for b in batch])
+            for (key, data, _, _), image in zip(batch, got):
+                self._prefetched[key] = (data, image, True)
+
+    def decode_stack(self, paths):
+        """``decode_image`` of every file as host arrays (the pure-geometry loader's stack, which ``resize_stack`` and the
+        cloud take from the host): the PNG files among them decoded in one batched launch, then copied back"""
+        self.prefetch_images(list(paths))
+        try:
+            images = [self.decode_image(p) for p in paths]
+        finally:
+            self._prefetched.clear()
+        return [im.cpu().numpy() if isinstance(im, torch.Tensor) else im for im in images]
+
+    def decode_image(self, path, target=False, into=None, channels="file"):
+        """An image file's pixels.  Without ``device_decode`` and ``device_png``: ``np.array(PIL.Image.open(path))``.  With
+        either the file's bytes decide, as they do for Pillow, not its name: under ``device_decode`` a JPEG stream (``FF D8``)
+        that ``ops.jpeg_decode`` serves, under ``device_png`` a PNG file that ``ops.png_decode`` serves comes back as a uint8
+        [H,W,C] tensor on the store's device (a JPEG without a wait, a PNG after one); any other file takes the Pillow
+        statement.  ``target``: counted as an item's target, not as a source frame.  ``into`` = (scene or None, frame id): a
+        frame of the slot's size is decoded straight into ``scene.rgb[slot]``, which ``put`` then recognises.  ``channels="rgb"``:
+        the first three channels of an RGBA image (``[..., :3]`` of Pillow's array; the DyCheck reader's)."""
+        if self.device_decode or self.device_png:
+            from .. import ops
+
+            data, image, tried = self._prefetched.pop((str(path), channels), (None, None, False))
+            if data is None:
+                with open(path, "rb") as f:
+                    data = f.read()
+            if self.device_png and data[:8] == ops._PNG_SIGNATURE:
+                if not tried:
+                    parsed = ops._png_parse(data)  # (the one chunk walk of this file)
+                    if parsed[0] is not None:
+                        info = parsed[0]
+                        out = self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])
+                        image = ops.png_decode_batch([data], outs=[out], channels=channels, device=self.device, reject_ok=True, parsed=[parsed])[0]
+                if image is not None:
+                    self.stats["png_decoded_on_device"] += 1
+                    self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
+                    return image
+                self.stats["png_fallbacks"] += 1
+            if self.device_decode and data[:2] == b"\xff\xd8":
                 info, out = ops.jpeg_info(data), None
                 if info is not None and into is not None and into[0] is not None and (info["height"], info["width"]) == (into[0].h, into[0].w):
                     out = into[0].rgb[self.slots(into[0], [into[1]])[0]]
@@ -190,7 +272,8 @@ class SceneStore:
                     self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
                     return image
                 self.stats["jpeg_fallbacks"] += 1
-        return np.array(PIL.Image.open(path))
+        image = np.array(PIL.Image.open(path))
+        return image[..., :3] if channels == "rgb" else image
 
     # ------------------------------------------------------------------ the resize on the device
     @staticmethod
@@ -293,12 +376,14 @@ class SceneStore:
         scene.filled[slot] = True
         self.stats["frames_decoded"] += 1
 
-    def views(self, scene, groups, decode):
+    def views(self, scene, groups, decode, image_path=None):
         """one dict per group ``(frame ids, with_depth)``: rgb, dyn_rgb, static_rgb [n,H,W,3], dyn_mask and (with_depth) depth
-        [n,H,W,1], float32 on the store's device; ``decode(frame id) -> (rgb uint8, mask, depth)`` fills missing slots"""
+        [n,H,W,1], float32 on the store's device; ``decode(frame id) -> (rgb uint8, mask, depth)`` fills missing slots;
+        ``image_path(frame id)`` -> the frame's image file (or (file, channels)): with ``device_png`` the missing frames'
+        files are prefetched in one launch"""
         frame_ids = [int(f) for ids, _ in groups for f in ids]
         groups = [(self.slots(scene, ids), with_depth) for ids, with_depth in groups]  # (checked before anything is decoded)
-        self._fill(scene, frame_ids, decode)
+        self._fill(scene, frame_ids, decode, image_path)
         if scene.prediction and any(with_depth for _, with_depth in groups):
             raise ValueError("a scene in prediction mode holds no depths: zoe_depths aligns its predictions")
         self.stats["items_built"] += 1
@@ -411,7 +496,7 @@ def group_host_entries(group, flat_cams, times=None, n_actual=None):
 
 
 def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner,
-               ray_rows=None, depth_range=None, depths=None):
+               ray_rows=None, depth_range=None, depths=None, image_path=None):
     """An item of the five loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
     non-tensor entries; ``host``: the host-made tensors (on a GPU store they travel in ONE packed copy, with the groups'
     cameras and times; entries named ``__...`` are the loader's own cargo: they come back in the item, on the device, for
@@ -425,7 +510,8 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
     ``rays`` the rows as a device tensor on a GPU store and as the numpy array on a host store; ``c2w_tgt`` is unused then.
     The NVIDIA evaluation loader's ZoeDepth inputs bring ``depths(ids per group, (K, c2w) of the spatial group or None, rays or
     None) -> ([depth [n,H,W,1] per group], depth_range or None)`` on the store's device (``SceneStore.zoe_depths`` over a
-    scene in prediction mode): the store then gathers colours and masks alone, and every depth and the range come from there."""
+    scene in prediction mode): the store then gathers colours and masks alone, and every depth and the range come from there.
+    ``image_path(frame id)``: the frame's image file, for ``SceneStore.views`` to prefetch under ``device_png``."""
     from . import nvidia_eval as NE
 
     dev = store.device
@@ -452,7 +538,7 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
         for side in ("fwd2tgt", "bwd2tgt"):
             add(f"temporal_track_{side}", sel[side], True, sel[side], sel[f"n_actual_{side}"])
     # the range needs the spatial depths even where the item carries none (the visualisation loaders)
-    views = store.views(scene, [(ids, depths is None and (with_depth or name == "spatial")) for name, ids, with_depth in groups], decode)
+    views = store.views(scene, [(ids, depths is None and (with_depth or name == "spatial")) for name, ids, with_depth in groups], decode, image_path)
     small = pack_to_device(host, dev) if dev is not None else host
     rays = small.pop("__rays", None)
     item = dict(fixed)

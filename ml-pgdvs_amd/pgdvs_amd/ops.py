@@ -1319,6 +1319,272 @@ def jpeg_decode_device(data, out=None, device=None, reject_ok: bool = False):
     return jpeg_decode(data, out=out, device=device, reject_ok=reject_ok), False
 
 
+PNG_INFLATE_SUB_BYTES = 64  # PGDVS_PNG_INFLATE_SUB_BYTES
+PNG_INFLATE_MAX_BYTES = 1 << 28  # PGDVS_PNG_INFLATE_MAX_BYTES
+PNG_MAX_SIZE = 16384
+PNG_CHANNEL_MODES = ("file", "rgb")
+PNG_STATUS_BITS = ("block", "code", "distance", "stored", "data_out", "size", "left_over", "adler", "filter", "not_synchronised")
+_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_png_side_streams = {}  # device -> the stream the PNG launches run on
+
+
+def _png_parse(data):
+    """(info, None) of a PNG file ``png_decode`` serves, else (None, reason).  The chunk walk of the host side: signature,
+    lengths, every CRC (``zlib.crc32``), chunk order, IHDR, and the two zlib header bytes -- no Huffman work, no inflate."""
+    import struct
+    import zlib
+
+    keep, _, n = _jpeg_bytes(data)
+    mv = memoryview(keep)
+    if n < 8 or bytes(mv[:8]) != _PNG_SIGNATURE:
+        return None, "not a PNG signature"
+    pos, ihdr, spans, state = 8, None, [], 0  # state: 0 before IDAT, 1 inside the IDAT run, 2 behind it, 3 after IEND
+    while state != 3:
+        if pos + 12 > n:
+            return None, "truncated: a chunk header or IEND is missing"
+        (length,) = struct.unpack_from(">I", mv, pos)
+        kind = bytes(mv[pos + 4:pos + 8])
+        if length > 0x7FFFFFFF or pos + 12 + length > n:
+            return None, f"truncated: chunk {kind!r} of {length} bytes runs past the file"
+        if zlib.crc32(mv[pos + 4:pos + 8 + length]) != struct.unpack_from(">I", mv, pos + 8 + length)[0]:
+            return None, f"bad CRC in chunk {kind!r}"
+        if (ihdr is None) != (kind == b"IHDR"):
+            return None, "chunk order: IHDR comes first, once"
+        if kind == b"IHDR":
+            if length != 13:
+                return None, "IHDR of another length than 13"
+            ihdr = struct.unpack_from(">IIBBBBB", mv, pos + 8)
+        elif kind == b"IDAT":
+            if state == 2:
+                return None, "chunk order: IDAT chunks must follow each other"
+            state = 1
+            if length:
+                spans.append((pos + 8, length))
+        elif kind == b"IEND":
+            if state == 0 or length:
+                return None, "chunk order: IEND without IDAT, or with data"
+            state = 3
+        else:
+            if kind in (b"tRNS", b"acTL", b"fcTL", b"fdAT"):
+                return None, f"chunk {kind!r} (transparency or APNG) is left to the host reader"
+            if not kind[0] & 0x20 and kind != b"PLTE":
+                return None, f"unknown critical chunk {kind!r}"
+            if state == 1:
+                state = 2
+        pos += 12 + length
+    width, height, depth, colour, compression, filt, interlace = ihdr
+    if depth != 8 or colour not in (2, 6):
+        return None, f"colour type {colour} at bit depth {depth}: 8-bit RGB and RGBA are served"
+    if compression or filt or interlace:
+        return None, "interlaced, or an unknown compression or filter method"
+    if not (1 <= width <= PNG_MAX_SIZE and 1 <= height <= PNG_MAX_SIZE):
+        return None, f"{width} x {height}: 1 .. {PNG_MAX_SIZE} pixels each way are served"
+    channels = 3 if colour == 2 else 4
+    size = sum(length for _, length in spans)
+    if height * (1 + width * channels) > PNG_INFLATE_MAX_BYTES or size > PNG_INFLATE_MAX_BYTES - 16:
+        return None, f"stream of {size} bytes or image of {height * (1 + width * channels)}: above PNG_INFLATE_MAX_BYTES"
+    if size < 6:
+        return None, "truncated: a zlib stream of fewer than 6 bytes"
+    head = bytearray()
+    for o, length in spans:  # (the two header bytes may lie in two chunks)
+        head += mv[o:o + min(length, 2 - len(head))]
+        if len(head) == 2:
+            break
+    cmf, flg = head[0], head[1]
+    if cmf & 15 != 8 or cmf >> 4 > 7 or (cmf * 256 + flg) % 31:
+        return None, "zlib header: not deflate with a window of 32K or less"
+    if flg & 0x20:
+        return None, "zlib header: preset dictionary"
+    return {"width": width, "height": height, "channels": channels, "stream_bytes": size, "idat": spans, "data": keep}, None
+
+
+def png_info(data):
+    """What the host side reads from a PNG file (bytes-like or a uint8 array; Python only): a dict of width, height, channels
+    (3 or 4), stream_bytes (the zlib stream over all IDAT chunks) and idat (the payloads' (offset, length) in the file) -- or
+    None when ``png_decode`` does not serve the file (``png_refusal`` gives the reason)."""
+    info = _png_parse(data)[0]
+    return None if info is None else {k: v for k, v in info.items() if k != "data"}
+
+
+def png_refusal(data):
+    """why ``png_decode`` refuses the file on the host, or None where it does not"""
+    return _png_parse(data)[1]
+
+
+def png_status_text(status: int) -> str:
+    return "+".join(name for bit, name in enumerate(PNG_STATUS_BITS) if status >> bit & 1) or "ok"
+
+
+def _png_batch(infos, out_channels, outs, pin):
+    """the batch buffer of ``pgdvs_png_decode``: the stream table, then every file's IDAT payloads joined, 16-byte aligned;
+    ``outs``: per stream (address, row stride in bytes)"""
+    n = len(infos)
+    offsets, at = [], -(-n * C.sizeof(_lib.PngStream) // 16) * 16
+    for info in infos:
+        offsets.append(at)
+        at += -(-info["stream_bytes"] // 16) * 16
+    buf = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)
+    view = buf.numpy()
+    table = (_lib.PngStream * n).from_address(buf.data_ptr())
+    for i, info in enumerate(infos):
+        src, o = info["data"], offsets[i]
+        for off, length in info["idat"]:
+            view[o:o + length] = src[off:off + length]
+            o += length
+        table[i].offset, table[i].size = offsets[i], info["stream_bytes"]
+        table[i].height, table[i].width, table[i].channels, table[i].out_channels = info["height"], info["width"], info["channels"], out_channels[i]
+        table[i].out, table[i].row_stride = outs[i]
+    return buf
+
+
+def _png_out(out, shape, device, what):
+    """``out`` after its check: uint8 ``shape`` on ``device`` whose pixels are contiguous (the row stride is free)"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    ok = (isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == torch.uint8 and tuple(out.shape) == tuple(shape)
+          and out.stride(2) == 1 and out.stride(1) == shape[2] and (out.stride(0) >= shape[1] * shape[2] or shape[0] == 1))
+    if not ok:
+        raise ValueError(f"{what} must be a uint8 {tuple(shape)} tensor on {device} with contiguous rows, got {getattr(out, 'dtype', type(out))} "
+                         f"{tuple(getattr(out, 'shape', ()))} strides {tuple(out.stride()) if isinstance(out, torch.Tensor) else ()} "
+                         f"on {getattr(out, 'device', None)}")
+    return out
+
+
+def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reject_ok: bool = False, sub_bytes: int = 0, reasons=None, stats=None, parsed=None):
+    """``np.array(PIL.Image.open(BytesIO(data)))`` of every PNG file of ``datas`` as uint8 [H,W,C] GPU tensors, byte for byte
+    (DESIGN.md 7j).  Served: non-interlaced 8-bit RGB (C = 3) and RGBA (C = 4) files of 1 .. 16384 pixels each way with one
+    zlib stream over any number of IDAT chunks; ``channels="rgb"`` gives an RGBA file's first three channels.  The host
+    walks the chunks and checks every CRC (Python; no Huffman work, no inflate) and joins all files' IDAT payloads behind
+    one stream table in ONE pinned buffer; one asynchronous copy takes it to ``device`` (default: the outs', else the current
+    GPU) and ONE batched ``pgdvs_png_decode`` -- a workgroup per file inflates it, then a wavefront per file undoes the row
+    filters -- runs on a side stream of this op's own, which first waits for the caller's stream (an ``out`` may have pending
+    work there) and which the caller's stream then waits for.  All status words come back through one pinned copy behind
+    one event and THIS CALL WAITS for that event, once per batch.  ``outs``: None, or per file None or a uint8 [H,W,C] tensor
+    on the device to fill, its rows contiguous and its row stride free (a frame's slot of the resident store).
+
+    A file the path does not serve is refused, never approximated: on the host, in front of any device work (another colour
+    type or bit depth, interlace, tRNS or APNG chunks, a bad signature, CRC or chunk order, a truncated file, a zlib header
+    that is not deflate / 32K or has a preset dictionary, sizes above ``PNG_INFLATE_MAX_BYTES``), or on the device by a
+    non-zero status word (include/pgdvs_hip.h lists the bits; the file's ``out`` then holds no result).  Either way the
+    file's entry of the result is None under ``reject_ok`` (``reasons``, a list, receives one text or None per file), else the
+    first such file raises ValueError -- the caller hands the file to Pillow, which decides.  ``stats`` (a list, for tools: it
+    waits for the device once more) receives per file None or the workspace's four words: windows, the most synchronisation
+    rounds of a window, the most resolve rounds of a window, blocks.  ``parsed``: what the chunk walk gave for each file, where
+    the caller has it already (``SceneStore.prefetch_images``): the files are not walked again."""
+    if channels not in PNG_CHANNEL_MODES:
+        raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
+    datas = list(datas)
+    outs = [None] * len(datas) if outs is None else list(outs)
+    if len(outs) != len(datas):
+        raise ValueError(f"png_decode_batch: {len(datas)} files, {len(outs)} outs")
+    why = [None] * len(datas)
+    images = [None] * len(datas)
+    walked, parsed = parsed, []
+    for i, data in enumerate(datas):
+        info, why[i] = _png_parse(data) if walked is None else walked[i]
+        if info is not None:
+            parsed.append((i, info))
+        elif not reject_ok:
+            raise ValueError(f"png_decode: file {i} is not served: {why[i]}")
+    if parsed:
+        if device is None:
+            device = next((o.device for o in outs if isinstance(o, torch.Tensor) and o.is_cuda), None)
+        device = _cuda_device(device, "png_decode: the files are decoded")
+        lib = _lib.load()
+        out_ch = [3 if channels == "rgb" else info["channels"] for _, info in parsed]
+        targets = [_png_out(outs[i], (info["height"], info["width"], c), device, f"png_decode: out of file {i}") for (i, info), c in zip(parsed, out_ch)]
+        batch = _png_batch([info for _, info in parsed], out_ch, [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]) for t in targets],
+                           pin=True)
+        n = len(parsed)
+        with torch.cuda.device(device):
+            main = torch.cuda.current_stream(device)
+            side = _png_side_streams.get(device)
+            if side is None:
+                side = _png_side_streams[device] = torch.cuda.Stream(device)
+            side.wait_stream(main)  # (an ``out`` may still be read or written there)
+            with torch.cuda.stream(side):
+                dev = batch.to(device, non_blocking=True)
+                status = torch.empty(n, dtype=torch.int32, device=device)
+                ws = _ws(lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n), device)
+                check(lib.pgdvs_png_decode(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(),
+                                           _stream()), "pgdvs_png_decode")
+                words = torch.empty(n, dtype=torch.int32, pin_memory=True)
+                words.copy_(status, non_blocking=True)
+                fetched = torch.cuda.Event()
+                fetched.record(side)
+            main.wait_stream(side)
+            for t in targets:
+                t.record_stream(side)  # (allocated on the caller's stream, written on this one)
+            fetched.synchronize()  # the batch's one wait
+            if stats is not None:
+                rows = ws[:16 * n].cpu().view(torch.int32).view(n, 4).tolist()
+                stats[:] = [None] * len(datas)
+                for (i, _), row in zip(parsed, rows):
+                    stats[i] = tuple(row)
+        for (i, _), target, word in zip(parsed, targets, words.tolist()):
+            if word == 0:
+                images[i] = target
+            else:
+                why[i] = f"the device gave the stream up: status {word & 0xFFFFFFFF:#x} ({png_status_text(word & 0xFFFFFFFF)})"
+                if not reject_ok:
+                    raise ValueError(f"png_decode: file {i} is not served: {why[i]}")
+    if reasons is not None:
+        reasons[:] = why
+    return images
+
+
+def png_decode(data, out=None, channels: str = "file", device=None, reject_ok: bool = False, sub_bytes: int = 0):
+    """``png_decode_batch`` of one file: the uint8 [H,W,C] GPU tensor, or None under ``reject_ok`` where the file is not served."""
+    return png_decode_batch([data], outs=[out], channels=channels, device=device, reject_ok=reject_ok, sub_bytes=sub_bytes)[0]
+
+
+def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: int = 0):
+    """The host emulation of the same batch (``pgdvs_png_decode_host``: the kernels' core, windows, rounds and workspace on
+    the CPU; for the tests and tools, no GPU): per file None where the host side refuses it, else a dict of status, image
+    (uint8 [H,W,C] numpy, meaningful at status 0), inflated (the workspace's inflated rows) and info (windows, most
+    synchronisation rounds, most resolve rounds, blocks).  ``guard``: that many bytes of 0xA5 are put around the images, the
+    status words and the workspace, and checked afterwards."""
+    if channels not in PNG_CHANNEL_MODES:
+        raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
+    lib = _lib.load()
+    results = [None] * len(datas)
+    parsed = [(i, info) for i, info in ((i, _png_parse(d)[0]) for i, d in enumerate(datas)) if info is not None]
+    if not parsed:
+        return results
+    n = len(parsed)
+    out_ch = [3 if channels == "rgb" else info["channels"] for _, info in parsed]
+
+    def guarded(nbytes, align=1):
+        raw = np.full(nbytes + 2 * guard + 256, 0xA5, np.uint8)
+        start = guard + (-(raw.ctypes.data + guard) % align)
+        return raw, raw[start:start + nbytes]
+
+    holds = [guarded(info["height"] * info["width"] * c) for (_, info), c in zip(parsed, out_ch)]
+    batch = _png_batch([info for _, info in parsed], out_ch, [(h[1].ctypes.data, info["width"] * c) for h, (_, info), c in zip(holds, parsed, out_ch)],
+                       pin=False)
+    need = lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n)
+    if need < 0:
+        check(int(need), "pgdvs_png_inflate_workspace_bytes")
+    ws_raw, ws = guarded(int(need), 256)
+    st_raw, st = guarded(4 * n, 8)
+    check(lib.pgdvs_png_decode_host(C.c_void_p(batch.data_ptr()), C.c_void_p(batch.data_ptr()), batch.numel(), n, sub_bytes, C.c_void_p(st.ctypes.data),
+                                    C.c_void_p(ws.ctypes.data), int(need)), "pgdvs_png_decode_host")
+    for raw, inner in [(ws_raw, ws), (st_raw, st)] + holds:
+        lo = inner.ctypes.data - raw.ctypes.data
+        if not ((raw[:lo] == 0xA5).all() and (raw[lo + inner.size:] == 0xA5).all()):
+            raise AssertionError("pgdvs_png_decode_host wrote outside a buffer")
+    table = (_lib.PngStream * n).from_address(batch.data_ptr())
+    at = -(-n * 16 // 256) * 256
+    pad16 = lambda v: -(-v // 16) * 16  # noqa: E731
+    for k, ((i, info), c, hold) in enumerate(zip(parsed, out_ch, holds)):
+        nbytes = info["height"] * (1 + info["width"] * info["channels"])
+        results[i] = {"status": int(st.view(np.uint32)[k]), "image": hold[1].reshape(info["height"], info["width"], c).copy(),
+                      "inflated": ws[at:at + nbytes].copy(), "info": tuple(int(v) for v in ws[16 * k:16 * k + 16].view(np.uint32))}
+        at += pad16(nbytes) + pad16(info["width"] * info["channels"])
+    del table
+    return results
+
+
 def _flow_pair(a, b, names, what):
     """two float32 [H,W,2] GPU tensors of one shape, H, W >= 2 (the preprocessing ops' inputs)"""
     a, b = _req(a, torch.float32, names[0]), _req(b, torch.float32, names[1])

@@ -131,12 +131,13 @@ def loaders(nvidia_root, mono_root, scene, mono_scene, center):
     vis = dict(vis_center_time=center, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32)
     # j: False, True (device_decode) or "entropy" (device_entropy too); a package without a keyword still takes the rest
     jk = lambda j: ({"device_decode": True, "device_entropy": True} if j == "entropy" else {"device_decode": True}) if j else {}  # noqa: E731
-    out = {"nvidia_eval": lambda r, d=False, j=False: NvidiaDynEvaluationDataset(mode="eval", resident=r, device_resize=d, **jk(j), **nv),
+    pk = lambda p: {"device_png": True} if p else {}  # noqa: E731  (the png leg's keyword)
+    out = {"nvidia_eval": lambda r, d=False, j=False, p=False: NvidiaDynEvaluationDataset(mode="eval", resident=r, device_resize=d, **jk(j), **pk(p), **nv),
            "nvidia_pure_geo": lambda r, d=False: NvidiaDynPureGeoEvaluationDataset(mode="eval", resident=r, device_resize=d, **nv),
            "nvidia_vis": lambda r, d=False, j=False: NvidiaDynVisualizationDataset(mode="vis", resident=r, device_resize=d, **jk(j), **vis, **nv)}
     if mono_root is not None:
-        out["mono_vis"] = lambda r, d=False: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[mono_scene],
-                                                                      device="cuda:0", resident=r, device_resize=d, **vis)
+        out["mono_vis"] = lambda r, d=False, j=False, p=False: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[mono_scene],
+                                                                                        device="cuda:0", resident=r, device_resize=d, **pk(p), **vis)
     return out
 
 
@@ -483,6 +484,134 @@ def decode_case(nvidia_root, scene, center, n_items, reps, rounds, synthetic, sc
 DY_H, DY_W, DY_F, DY_FACTOR, DY_SCENE = 360, 480, 48, 2, "synthetic-iphone"
 
 
+def rewrite_pngs(nvidia_root, mono_root, frames=F):
+    """every mv_images file of the synthetic scene (both cameras of a time step: every evaluation target too) and every
+    frame of the monocular tree behind frame 0 as a 1080 x 2062 PNG written by Pillow at its default level"""
+    dense = pathlib.Path(nvidia_root) / "raw" / SCENE / "dense"
+    for f in range(frames):
+        big = PIL.Image.open(dense / f"images_{W}x{H}" / f"{f:05d}.png").resize((SRC_W, SRC_H), resample=PIL.Image.Resampling.BICUBIC)
+        d = dense / "mv_images" / f"{f:05d}"
+        for old in d.iterdir():
+            old.unlink()
+        for cam in (f % N_CAMS, (f + 1) % N_CAMS):
+            big.save(d / f"cam{cam + 1:02d}.png")
+        if mono_root is not None and f:
+            big.save(pathlib.Path(mono_root) / MONO_SCENE / "rgbs" / f"{f:05d}.png")
+
+
+def png_loaders_case(factories, n_items, rounds):
+    """fresh loaders each round, ``device_resize=True`` alone and with ``device_png=True``, alternating; items/s of both passes.
+    ``factories``: name -> fn(device_png) -> loader (a package without the keyword: the first column alone)"""
+    rec = {}
+    for name, fn in factories.items():
+        variants = ("device_resize",)
+        try:
+            fn(True)
+            variants += ("device_png",)
+        except TypeError:  # (the parent commit's checkout)
+            pass
+        probe = fn(False)
+        idx = [int(round(j * (len(probe) - 1) / max(n_items - 1, 1))) for j in range(n_items)]
+        probe[idx[0]]  # (warm-up: code objects, the resize plans)
+        del probe
+        rates = {v: {"first": [], "second": []} for v in variants}
+        want, same, stats = None, True, {}
+        for _ in range(rounds):
+            for v in variants:
+                ds = fn(v == "device_png")
+                r1, got1 = timed_pass(ds, idx)
+                r2, got2 = timed_pass(ds, idx)
+                rates[v]["first"].append(r1)
+                rates[v]["second"].append(r2)
+                if want is None:
+                    want = got1
+                same = same and all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2))
+                stats[v] = dict(ds.store.stats)
+                del ds, got1, got2
+                torch.cuda.empty_cache()
+        r = rec[name] = {"items": len(idx), "rounds": rounds, "bit_identical": same, "stats": stats}
+        for v in variants:
+            r[f"{v}_first_pass_items_per_s"], r[f"{v}_second_pass_items_per_s"] = _spread(rates[v]["first"]), _spread(rates[v]["second"])
+        print(f"png {name}: {r}", file=sys.stderr, flush=True)
+    return rec
+
+
+def png_frame_case(path, reps, sub_sizes):
+    """one 1080 x 2062 file: Pillow's decode, ``zlib.decompress`` of its stream alone, and per subsequence size the call of
+    ``ops.png_decode_batch`` by device events for one file and for a batch of 12, the two launches of ``pgdvs_png_decode``
+    apart (the library's event brackets), and the windows, blocks and rounds the stream took"""
+    import ctypes as C
+    import io
+    import zlib
+
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import _lib, ops
+
+    lib = _lib.load()
+    data = pathlib.Path(path).read_bytes()
+    info = ops._png_parse(data)[0]
+    stream = b"".join(data[o:o + n] for o, n in info["idat"])
+
+    def clock(fn, n):
+        ts = []
+        for _ in range(n):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return sorted(ts)[n // 2]
+
+    rec = {"file_bytes": len(data), "stream_bytes": len(stream), "size": [info["height"], info["width"], info["channels"]],
+           "pillow_decode_ms": clock(lambda: np.array(PIL.Image.open(io.BytesIO(data))), 10), "zlib_decompress_ms": clock(lambda: zlib.decompress(stream), 10),
+           "host_chunk_walk_ms": clock(lambda: ops.png_info(data), 10)}
+    want = np.array(PIL.Image.open(io.BytesIO(data)))
+    for sub in sub_sizes:
+        stats = []
+        got = ops.png_decode_batch([data], device="cuda:0", sub_bytes=sub, stats=stats)[0]
+        r = rec[f"sub_bytes_{sub}"] = {"equal_pillow": bool(np.array_equal(got.cpu().numpy(), want)), "windows": stats[0][0], "sync_rounds_max": stats[0][1],
+                                       "resolve_rounds_max": stats[0][2], "blocks": stats[0][3]}
+        lib.pgdvs_prof_enable(1)
+        for _ in range(reps):
+            ops.png_decode_batch([data], device="cuda:0", sub_bytes=sub)
+        text = C.create_string_buffer(4096)
+        lib.pgdvs_prof_report(text, 4096)
+        lib.pgdvs_prof_enable(0)
+        r["kernels_ms_per_call"] = {ln.split()[0]: float(ln.split()[2]) / reps for ln in text.value.decode().splitlines() if ln.startswith("png_")}
+        for batch in (1, 12):
+            med, mn = event_median(lambda: ops.png_decode_batch([data] * batch, device="cuda:0", sub_bytes=sub), reps, 1)
+            r[f"batch_{batch}_call_ms"] = {"median": med, "min": mn, "per_file": med / batch}
+        print(f"png frame sub {sub}: {r}", file=sys.stderr, flush=True)
+    return rec
+
+
+PNG_PARTS = ("nvidia_eval", "mono_vis", "dycheck", "frame")
+
+
+def png_case(scratch, nvidia_root, mono_root, scene, center, n_items, reps, rounds, sub_sizes, parts):
+    """the png leg: the synthetic scenes with frames and targets rewritten as PNG; ``parts`` of nvidia_eval, mono_vis, dycheck
+    (the loaders, each on its own so that a run can be cut into calls) and frame (one file through the op)"""
+    from pgdvs_amd import ops
+    from pgdvs_amd.datasets.dycheck_iphone import DyCheckiPhoneEvaluationDataset
+
+    factories = {}
+    if set(parts) & {"nvidia_eval", "mono_vis", "frame"}:
+        rewrite_pngs(nvidia_root, mono_root if "mono_vis" in parts else None)
+        make = loaders(nvidia_root, mono_root, scene, MONO_SCENE, center)
+        for name in ("nvidia_eval", "mono_vis"):
+            if name in parts:
+                factories[name] = lambda p, fn=make[name]: fn(True, True, False, **({"p": True} if p else {}))
+    if "dycheck" in parts:
+        root = write_dycheck_tree(scratch / "dycheck_png")
+        kw = dict(data_root=root, raw_data_dir="iphone", mask_data_dir="flow_mask", flow_data_dir="flow_mask", max_hw=-1, mode="eval", scene_ids=[DY_SCENE],
+                  spatial_src_view_type="closest_wo_temporal", n_src_views_spatial=10, n_src_views_temporal_track_one_side=5, device="cuda:0", resident=True,
+                  device_resize=True)
+        factories["dycheck"] = lambda p: DyCheckiPhoneEvaluationDataset(**kw, **({"device_png": True} if p else {}))
+    rec = {"loaders": png_loaders_case(factories, n_items, rounds)}
+    if "frame" in parts and hasattr(ops, "png_decode_batch"):
+        dense = pathlib.Path(nvidia_root) / "raw" / scene / "dense" / "mv_images" / f"{center:05d}"
+        rec["frame"] = png_frame_case(sorted(dense.iterdir())[0], reps, sub_sizes)
+    return rec
+
+
 def write_dycheck_tree(root, frames=DY_F):
     """a synthetic DyCheck iPhone scene in the layout iPhoneParser reads: 360 x 480 (the 2x frames), ``frames`` train frames on
     camera 0 at time ids 0.., two val cameras at every second instant (val frames sit on train instants, as the dataset's do,
@@ -624,9 +753,11 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--vis-views", type=int, default=48)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe, decode")
+    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe, decode, png")
     ap.add_argument("--rounds", type=int, default=3, help="decode leg: rounds of fresh loaders per variant")
     ap.add_argument("--scan-sizes", default="16,32,48,64,96,128,256,512", help="decode leg: subsequence sizes (bytes) of the per-frame scan figures")
+    ap.add_argument("--png-sizes", default="16,32,64,128,256", help="png leg: subsequence sizes (bytes) of the per-frame figures")
+    ap.add_argument("--png-parts", default=",".join(PNG_PARTS), help="png leg: which of its parts run (a long leg is cut into calls)")
     ap.add_argument("--zoe-setting", default="moe", help="use_zoe_depth of the zoe leg")
     ap.add_argument("--zoe-path", default=None, help="zoe_depth_data_path under a real --data_root (the synthetic tree brings its own)")
     ap.add_argument("--out", default=None)
@@ -638,7 +769,7 @@ def main():
     scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
     rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
     legs = set(args.legs.split(","))
-    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe", "decode"}, args.legs
+    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe", "decode", "png"}, args.legs
     try:
         if "resample" in legs:
             rec["resample"] = resample_case(args.reps)
@@ -646,7 +777,8 @@ def main():
         if "dycheck" in legs:
             rec["dycheck"] = dycheck_case(scratch, args.items, args.reps)
             print(f"dycheck: {rec['dycheck']}", file=sys.stderr, flush=True)
-        if not legs & {"nvidia", "zoe", "decode"}:
+        png_tree = "png" in legs and set(args.png_parts.split(",")) != {"dycheck"}  # (the DyCheck part writes a tree of its own)
+        if not legs & {"nvidia", "zoe", "decode"} and not png_tree:
             nvidia_root = mono_root = center = None
         elif args.data_root is None:
             t0 = time.perf_counter()
@@ -693,6 +825,12 @@ def main():
         if "nvidia" in legs:
             rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
             rec["gather"] = gather_case(args.reps)
+        if "png" in legs:  # (it rewrites the synthetic tree's image files too)
+            assert args.data_root is None and "decode" not in legs, "the png leg rewrites the synthetic tree: a run of its own"
+            parts = tuple(args.png_parts.split(","))
+            assert parts and set(parts) <= set(PNG_PARTS), args.png_parts
+            rec["png"] = png_case(scratch, nvidia_root, mono_root, args.scene, center, args.items, args.reps, args.rounds,
+                                  tuple(int(x) for x in args.png_sizes.split(",")), parts)
         if "decode" in legs:  # last: it rewrites the synthetic tree's image files
             rec["decode"] = decode_case(nvidia_root, args.scene, center, args.items, args.reps, args.rounds, args.data_root is None,
                                         tuple(int(x) for x in args.scan_sizes.split(",")))
