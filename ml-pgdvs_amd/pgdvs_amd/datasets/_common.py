@@ -1,5 +1,6 @@
 """What the four loader modules (``nvidia_eval`` with its two classes, ``nvidia_vis``, ``mono_vis``, ``dycheck_iphone``) share: file readers, resizes,
 the per-view camera row and the item's per-group and flow entries.  Host numpy / PIL input plumbing."""
+import collections
 import pathlib
 
 import numpy as np
@@ -73,39 +74,24 @@ def refuse_gpu_in_worker(owner):
                            "touch: use n_dataloader_workers=0 (or device=None)")
 
 
-def check_device_resize(device_resize, resident, device, owner):
-    """``device_resize=True`` resizes into the resident store on a GPU: refused, naming what is missing, without either"""
-    if not device_resize:
-        return False
-    if not resident:
-        raise ValueError(f"{owner}(device_resize=True) resizes decoded frames into the resident store: it needs resident=True")
-    if device is None or torch.device(device).type != "cuda":
-        raise ValueError(f"{owner}(device_resize=True) resizes on the device: it needs the store on a GPU, got device={device!r}")
-    return True
+# which parts of the image input run on the device: ``device_input`` checks them, datasets/resident.py describes them
+DeviceInput = collections.namedtuple("DeviceInput", "resize decode entropy png")
 
 
-def check_device_entropy(device_entropy, device_decode, owner):
-    """``device_entropy=True`` moves the Huffman scan of the frames ``device_decode=True`` decodes onto the device too: refused
-    without it"""
+def device_input(owner, *, resident, device, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
+    """The four image-input keywords of ``owner`` (a loader, or the store) as a ``DeviceInput``.  Each option builds on
+    another: the first rule broken, in this order, is refused with a ValueError that names what is missing."""
     if device_entropy and not device_decode:
         raise ValueError(f"{owner}(device_entropy=True) decodes the scan of the JPEG frames that device_decode=True reads: it needs device_decode=True")
-    return bool(device_entropy)
-
-
-def check_device_decode(device_decode, device_resize, owner):
-    """``device_decode=True`` hands the store images that are already on the device, at the file's size: refused without
-    ``device_resize=True`` (which in turn asks for ``resident=True`` and a GPU store)"""
-    if device_decode and not device_resize:
-        raise ValueError(f"{owner}(device_decode=True) decodes JPEG frames on the device at the file's size: it needs device_resize=True")
-    return bool(device_decode)
-
-
-def check_device_png(device_png, device_resize, owner):
-    """``device_png=True`` decodes PNG frames on the device at the file's size: refused without
-    ``device_resize=True``; independent of ``device_decode``"""
     if device_png and not device_resize:
         raise ValueError(f"{owner}(device_png=True) decodes PNG frames on the device at the file's size: it needs device_resize=True")
-    return bool(device_png)
+    if device_decode and not device_resize:
+        raise ValueError(f"{owner}(device_decode=True) decodes JPEG frames on the device at the file's size: it needs device_resize=True")
+    if device_resize and not resident:
+        raise ValueError(f"{owner}(device_resize=True) resizes decoded frames into the resident store: it needs resident=True")
+    if device_resize and (device is None or torch.device(device).type != "cuda"):
+        raise ValueError(f"{owner}(device_resize=True) resizes on the device: it needs the store on a GPU, got device={device!r}")
+    return DeviceInput(bool(device_resize), bool(device_decode), bool(device_entropy), bool(device_png))
 
 
 def group_entries(group, views, times=None, n_actual=None, depth=True):

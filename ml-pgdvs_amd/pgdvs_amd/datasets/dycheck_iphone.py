@@ -18,7 +18,7 @@ and kept in a ``datasets.resident.SceneStore`` on ``device`` (None: host memory)
 from the camera JSON files is cached per scene, time id and camera; the items' source views are built from the store, on a
 GPU by ``ops.item_views`` in one launch, with ``depth_range`` left on the device and the target's colour and covisible bytes
 expanded by ``ops.item_target``: the same keys in the same order, shapes, dtypes and bits, every tensor on the store's
-device.  ``device_resize=True`` (with ``resident=True`` on a GPU): a train frame whose file is not of the
+device.  ``device_resize=True`` (what each ``device_*`` keyword builds on: datasets/resident.py): a train frame whose file is not of the
 scene's size goes to the store as decoded and is BOX-resized on the device; the target sets the item's size
 and is never resized.  The default is the disk path, unchanged.
 """
@@ -31,7 +31,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, check_device_decode, check_device_entropy, check_device_png, check_device_resize, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
+from ._common import (F32, device_input, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
                       resize, stack_views, tracker_entries)
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
@@ -361,10 +361,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
                  n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
                  resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
-        check_device_entropy(device_entropy, device_decode, type(self).__name__)
-        check_device_png(device_png, device_resize, type(self).__name__)
-        check_device_decode(device_decode, device_resize, type(self).__name__)  # (the dataset's images are PNG: Pillow reads them all)
-        check_device_resize(device_resize, resident, device, type(self).__name__)
+        options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
+                               device_entropy=device_entropy, device_png=device_png)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -377,8 +375,7 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.device = None if device is None else torch.device(device)
         # resident source frames (datasets/resident.py): the store, and per scene the frame size and the cameras' derived values
-        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy,
-                                device_png) if resident else None
+        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_input=options) if resident else None
         self._scene_shape, self._cam_cache = {}, {}
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.mask_data_dir, self.flow_data_dir = root / raw_data_dir, root / mask_data_dir, root / flow_data_dir

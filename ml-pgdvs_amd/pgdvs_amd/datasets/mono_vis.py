@@ -25,7 +25,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, check_device_decode, check_device_entropy, check_device_png, check_device_resize, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
+from ._common import (F32, device_input, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
                       tracker_entries)
 from .nvidia_eval import spatial_depth_range
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -120,10 +120,8 @@ class MonoVisualizationDataset(Dataset):
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
                  vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
                  resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
-        check_device_entropy(device_entropy, device_decode, type(self).__name__)
-        check_device_png(device_png, device_resize, type(self).__name__)
-        check_device_decode(device_decode, device_resize, type(self).__name__)
-        check_device_resize(device_resize, resident, device, type(self).__name__)
+        options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
+                               device_entropy=device_entropy, device_png=device_png)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
@@ -132,9 +130,7 @@ class MonoVisualizationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
         # the source frames kept in memory (datasets/resident.py)
-        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_resize, device_decode, device_entropy,
-                                 device_png)
-                      if resident else None)
+        self.store = SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_input=options) if resident else None
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
         self.c2w_dict, self.K_dict, self.valid_fs = {}, {}, []

@@ -44,7 +44,7 @@ range over the float64 depths of the spatial group; NumPy 2's result, as ``ops.n
 ``spatial_depth_range`` on a host store (the installed NumPy's, as the disk path).  There an unknown key or a missing path
 raises ``ValueError``, and so does, when its slot is filled, a file in other dtypes than the released ones.
 
-``device_resize=True`` (needs ``resident=True`` and a GPU ``device``): a source frame's image goes to the store as decoded and is
+``device_resize=True`` (what each ``device_*`` keyword builds on: datasets/resident.py): a source frame's image goes to the store as decoded and is
 BOX-resized on the device into its slot (``ops.resample_u8``, Pillow's resampler bit for bit); the target image is decoded
 once, its shape is the file's (height 288) or the monocular video's, and its bytes are resized and expanded on the device, so
 ``rgb_tgt`` is a device tensor; the pure-geometry loader's LANCZOS stack is one batched call.  Masks and depths keep the host
@@ -61,7 +61,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, TGT_HEIGHT, check_device_decode, check_device_entropy, check_device_png, check_device_resize, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
+from ._common import (F32, TGT_HEIGHT, device_input, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
                       read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
 from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -231,10 +231,8 @@ class NvidiaDynEvaluationDataset(Dataset):
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
                  flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES,
                  device_resize=False, device_decode=False, device_entropy=False, device_png=False):
-        check_device_entropy(device_entropy, device_decode, type(self).__name__)
-        check_device_png(device_png, device_resize, type(self).__name__)
-        check_device_decode(device_decode, device_resize, type(self).__name__)
-        check_device_resize(device_resize, resident, device, type(self).__name__)
+        options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
+                               device_entropy=device_entropy, device_png=device_png)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -258,7 +256,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, device_resize, device_decode, device_entropy, device_png)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, options)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
@@ -291,11 +289,9 @@ class NvidiaDynEvaluationDataset(Dataset):
     # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
     store = None  # the SceneStore of ``resident=True``
 
-    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, device_resize=False, device_decode=False, device_entropy=False,
-                       device_png=False):
+    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, options):
         if resident:
-            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_resize, device_decode, device_entropy,
-                                    device_png)
+            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_input=options)
 
     def _decode_frame(self, scene_id, frame_id, tgt_shape):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
@@ -586,16 +582,14 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
                  resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
-        check_device_entropy(device_entropy, device_decode, type(self).__name__)
-        check_device_png(device_png, device_resize, type(self).__name__)
-        check_device_decode(device_decode, device_resize, type(self).__name__)
-        check_device_resize(device_resize, resident, device, type(self).__name__)
+        options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
+                               device_entropy=device_entropy, device_png=device_png)
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
                          mask_data_dir=mask_data_dir, flow_data_dir=flow_data_dir, max_hw=max_hw, mode=mode,
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,
                          n_src_views_temporal_track_one_side=0, flow_consist_thres=flow_consist_thres)
         self.device = device
-        self._init_resident(resident, resident_scenes, resident_max_bytes, device, device_resize, device_decode, device_entropy, device_png)  # (where the cloud is built)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, device, options)  # (where the cloud is built)
         self.st_pcl_dict = {scene: self._aggregate_static_pcl(scene) for scene in sorted(self.scene_img_dict)}
 
     def _load_mono_video(self, scene_id):

@@ -30,37 +30,43 @@ GPU store, which writes the float32 depths of all groups and selects the range o
 ``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
 it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
 
-``device_resize=True`` (a GPU store only): the loaders hand over a frame's image as decoded, at the file's size, and the store
-uploads the bytes and resizes them on the device straight into the frame's slot (``ops.resample_u8``, Pillow's BOX filter bit
-for bit); the evaluation loaders' target image goes the same way (``expand_target``) and the pure-geometry loader's LANCZOS
-stack in one batched call (``resize_stack``).  An image the device path does not serve (not uint8 [H,W,3], or a size
-``ops.resample_plan`` refuses) takes the host statements.  Masks and depths keep their host NEAREST resize.
+The image input has four options, each building on another.  ``_common.device_input`` is the one statement of these rules,
+for the five loaders and for this store alike; the first rule broken, in this order, is refused with what is missing:
 
-``device_decode=True`` (with ``device_resize=True``): ``decode_image`` reads an image file's bytes and, where they are a JPEG
-stream that ``ops.jpeg_decode`` serves (baseline YCbCr, 4:4:4 / 4:2:2 / 4:2:0), decodes them on the device: Huffman scan on the
-host, everything behind it in HIP, byte for byte ``np.array(PIL.Image.open(path))``.  The store takes such an image where it
-takes a host one -- no second upload -- and a frame of the slot's size is decoded straight into its slot.  Every other file
-(PNG; progressive, greyscale, CMYK, truncated ... JPEG) is opened by Pillow as before, errors included.
+  device_entropy  needs device_decode
+  device_png      needs device_resize (it is independent of device_decode)
+  device_decode   needs device_resize
+  device_resize   needs resident=True, and the store on a GPU
 
-``device_entropy=True`` (with ``device_decode=True``): the Huffman scan of those files is decoded on the device as well
-(``ops.jpeg_decode(..., entropy="device")``): the file's bytes cross the bus, not its coefficients, and
-``decode_image`` waits once per file for the scan's status word.  A scan the device gives up (``stats["entropy_fallbacks"]``) is
-read again by the host decoder, which serves it or leaves the file to Pillow as above.
+``device_resize``: the loaders hand over a frame's image as decoded, at the file's size, and the store uploads the bytes and
+resizes them on the device straight into the frame's slot (``ops.resample_u8``, Pillow's BOX filter bit for bit); the
+evaluation loaders' target image goes the same way (``expand_target``) and the pure-geometry loader's LANCZOS stack in one
+batched call (``resize_stack``).  An image the device path does not serve (not uint8 [H,W,3], or a size ``ops.resample_plan``
+refuses) takes the host statements.  Masks and depths keep their host NEAREST resize.
 
-``device_png=True`` (with ``device_resize=True``; independent of ``device_decode``): ``decode_image`` serves PNG files on the
-device as well (``ops.png_decode_batch``): non-interlaced 8-bit RGB and RGBA files are inflated and unfiltered in
-HIP, byte for byte ``np.array(PIL.Image.open(path))`` (``channels="rgb"``: its first three channels).  ``prefetch_images`` decodes
-several files in one batched launch and one wait and keeps the results for the ``decode_image`` calls that follow; ``views``
-prefetches an item's missing frames that way where the loader names their files (``image_path``).  A file the path does not
-serve (``stats["png_fallbacks"]``: another colour type or bit depth, interlace, tRNS, a damaged file ...) is opened by Pillow
-as before, errors included.
+The other three decode on the device, and ``decode_image`` is their one dispatch: it takes the file's bytes (from
+``prefetch_images``' table, else from the file), asks the codec their signature names, counts the outcome, and hands every file
+no codec serves to Pillow as before, errors included.  An image decoded there is byte for byte ``np.array(PIL.Image.open(path))``;
+the store takes it where it takes a host one -- no second upload -- and a frame of the slot's size is decoded straight into its
+slot (``_slot_for``).
+``device_decode`` (``_decode_jpeg``): a JPEG stream that ``ops.jpeg_decode`` serves (baseline YCbCr, 4:4:4 / 4:2:2 /
+4:2:0), Huffman scan on the host, everything behind it in HIP; not served (``stats["jpeg_fallbacks"]``): progressive, greyscale,
+CMYK, truncated ... streams.  ``device_entropy`` (7i): the scan on the device as well: the file's bytes cross the bus, not its
+coefficients, and ``decode_image`` waits once per file for the scan's status word; a scan the device gives up
+(``stats["entropy_fallbacks"]``) is read again by the host decoder.
+``device_png`` (``_decode_png``; 7j): non-interlaced 8-bit RGB and RGBA files are inflated and unfiltered in HIP
+(``ops.png_decode_batch``; ``channels="rgb"``: the first three channels); not served (``stats["png_fallbacks"]``): another colour type
+or bit depth, interlace, tRNS, a damaged file ...  ``prefetch_images`` decodes several files in one batched launch and one wait
+and keeps the results for the ``decode_image`` calls that follow; ``views`` prefetches an item's missing frames that way where
+the loader names their files (``image_path``).
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import PIL.Image
 import torch
 
+from . import _common
 from ._common import F32, read_flow_npz, resize
 
 DEFAULT_MAX_BYTES = 4 << 30
@@ -93,11 +99,17 @@ class _Scene:
         self.flows = OrderedDict()  # (a, b) -> (flow [H,W,2], occ [H,W]), least recently used first
 
 
+# a file ``prefetch_images`` read, until the one ``decode_image`` that takes it: its bytes, what the PNG path decoded (None: refused,
+# given up, or not a PNG) and whether that path has had its turn
+_Prefetched = namedtuple("_Prefetched", "data image png_tried", defaults=(None, False))
+
+
 class SceneStore:
-    """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``)."""
+    """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``).  The four
+    ``device_*`` keywords (the module's text), or ``device_input``: the loader's checked record of them."""
 
     def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False,
-                 device_decode=False, device_entropy=False, device_png=False):
+                 device_decode=False, device_entropy=False, device_png=False, device_input=None):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -107,17 +119,11 @@ class SceneStore:
             raise TypeError(f"flow_consist_thres must be a Python number (a NumPy scalar changes the compare's type), got {type(occ_thres)}")
         self.resident_scenes, self.resident_max_bytes, self.occ_thres = int(resident_scenes), int(resident_max_bytes), occ_thres
         self.scenes = OrderedDict()  # key -> _Scene, least recently used first
-        if device_resize and self.device is None:
-            raise ValueError("SceneStore: device_resize=True resizes on a GPU, the store is in host memory (device=None)")
-        if device_decode and not device_resize:
-            raise ValueError("SceneStore: device_decode=True hands over images at the file's size: it needs device_resize=True")
-        if device_entropy and not device_decode:
-            raise ValueError("SceneStore: device_entropy=True decodes the scan of the frames device_decode=True reads: it needs device_decode=True")
-        if device_png and not device_resize:
-            raise ValueError("SceneStore: device_png=True hands over images at the file's size: it needs device_resize=True")
-        self.device_resize, self.device_decode, self.device_entropy = bool(device_resize), bool(device_decode), bool(device_entropy)
-        self.device_png = bool(device_png)
-        self._prefetched = {}  # (path, channels) -> the image prefetch_images decoded, until decode_image hands it out
+        if device_input is None:  # the four keywords themselves: the loaders' one check, in the store's name
+            device_input = _common.device_input("SceneStore", resident=True, device=self.device, device_resize=device_resize, device_decode=device_decode,
+                                                device_entropy=device_entropy, device_png=device_png)
+        self.device_resize, self.device_decode, self.device_entropy, self.device_png = device_input
+        self._prefetched = {}  # (path, channels) -> _Prefetched, from prefetch_images until decode_image hands it out
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
                       "targets_resized_on_device": 0, "zoe_files_read": 0, "frames_decoded_on_device": 0, "targets_decoded_on_device": 0,
                       "jpeg_fallbacks": 0, "scans_decoded_on_device": 0, "entropy_fallbacks": 0, "png_decoded_on_device": 0, "png_fallbacks": 0}
@@ -182,18 +188,35 @@ class SceneStore:
             self._prefetched.clear()  # (also when a reader raises: the entries hold device tensors, some of them slots)
 
     # ------------------------------------------------------------------ the decode on the device
-    def _slot_for(self, into, height, width, channels):
+    def _slot_for(self, into, height, width, channels=3):
         """the slot ``into`` = (scene or None, frame id) names, where an image of this size is exactly what it keeps"""
         if into is None or into[0] is None or (height, width, channels) != (into[0].h, into[0].w, 3):
             return None
         return into[0].rgb[self.slots(into[0], [into[1]])[0]]
 
+    def _png_images(self, files, channels):
+        """the images of the PNG ``files`` = [(bytes, into)]: each walked once, its slot picked, and those the host side serves
+        decoded in ONE batched launch with one wait; per file None where the host refuses it or the device gives it up"""
+        from .. import ops
+
+        images, batch = [None] * len(files), []
+        for i, (data, into) in enumerate(files):
+            parsed = ops.png_parse(data)  # (the one chunk walk of this file)
+            info = parsed[0]
+            if info is not None:
+                batch.append((i, data, parsed, self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])))
+        if batch:
+            got = ops.png_decode_batch([b[1] for b in batch], outs=[b[3] for b in batch], channels=channels, device=self.device, reject_ok=True,
+                                       parsed=[b[2] for b in batch])
+            for (i, *_), image in zip(batch, got):
+                images[i] = image
+        return images
+
     def prefetch_images(self, paths, intos=None):
         """With ``device_png``: the files of ``paths`` (each a path, or (path, channels)) read once, and the PNG files among
-        them decoded in ONE batched launch with one wait.  The bytes and the outcome -- the image, or None for a file the
-        path refused or gave up -- are kept for the ``decode_image`` calls that follow, which then neither read, parse nor
-        launch again (``_fill`` and ``decode_stack`` drop what is left).  ``intos``: per path None or (scene, frame id), as
-        ``decode_image`` takes it."""
+        them decoded in ONE batched launch with one wait.  Bytes and outcome are kept for the ``decode_image`` calls that
+        follow, which then neither read, parse nor launch again (``_fill`` and ``decode_stack`` drop what is left).  ``intos``:
+        per path None or (scene, frame id), as ``decode_image`` takes it."""
         if not self.device_png:
             return
         from .. import ops
@@ -207,18 +230,13 @@ class SceneStore:
                 continue
             with open(path, "rb") as f:
                 data = f.read()
-            is_png = data[:8] == ops._PNG_SIGNATURE
-            parsed = ops._png_parse(data) if is_png else (None, None)
-            self._prefetched[key] = (data, None, is_png)  # (bytes, image, whether the PNG path has had its turn)
-            if parsed[0] is not None:
-                info = parsed[0]
-                out = self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])
-                by_mode.setdefault(channels, []).append((key, data, parsed, out))
-        for channels, batch in by_mode.items():
-            got = ops.png_decode_batch([b[1] for b in batch], outs=[b[3] for b in batch], channels=channels, device=self.device, reject_ok=True,
-                                       parsed=[b[2] for b in batch])
-            for (key, data, _, _), image in zip(batch, got):
-                self._prefetched[key] = (data, image, True)
+            is_png = ops.image_kind(data) == "png"
+            self._prefetched[key] = _Prefetched(data, None, is_png)
+            if is_png:
+                by_mode.setdefault(channels, []).append((key, data, into))
+        for channels, files in by_mode.items():
+            for (key, data, _), image in zip(files, self._png_images([f[1:] for f in files], channels)):
+                self._prefetched[key] = _Prefetched(data, image, True)
 
     def decode_stack(self, paths):
         """``decode_image`` of every file as host arrays (the pure-geometry loader's stack, which ``resize_stack`` and the
@@ -231,49 +249,51 @@ class SceneStore:
         return [im.cpu().numpy() if isinstance(im, torch.Tensor) else im for im in images]
 
     def decode_image(self, path, target=False, into=None, channels="file"):
-        """An image file's pixels.  Without ``device_decode`` and ``device_png``: ``np.array(PIL.Image.open(path))``.  With
-        either the file's bytes decide, as they do for Pillow, not its name: under ``device_decode`` a JPEG stream (``FF D8``)
-        that ``ops.jpeg_decode`` serves, under ``device_png`` a PNG file that ``ops.png_decode`` serves comes back as a uint8
-        [H,W,C] tensor on the store's device (a JPEG without a wait, a PNG after one); any other file takes the Pillow
-        statement.  ``target``: counted as an item's target, not as a source frame.  ``into`` = (scene or None, frame id): a
-        frame of the slot's size is decoded straight into ``scene.rgb[slot]``, which ``put`` then recognises.  ``channels="rgb"``:
-        the first three channels of an RGBA image (``[..., :3]`` of Pillow's array; the DyCheck reader's)."""
+        """An image file's pixels: ``np.array(PIL.Image.open(path))``, or -- a PNG file under ``device_png``, a JPEG stream under
+        ``device_decode``, by the file's bytes, not its name, where its codec below serves it -- the same bytes as a uint8 [H,W,C]
+        tensor on the store's device (a JPEG without a wait unless ``device_entropy``, a PNG after one).  ``target``: counted as
+        an item's target, not as a source frame.  ``into`` = (scene or None, frame id): a frame of the slot's size is decoded
+        straight into ``scene.rgb[slot]``, which ``put`` then recognises.  ``channels="rgb"``: the first three channels of an RGBA
+        image (``[..., :3]`` of Pillow's array; the DyCheck reader's)."""
         if self.device_decode or self.device_png:
             from .. import ops
 
-            data, image, tried = self._prefetched.pop((str(path), channels), (None, None, False))
-            if data is None:
+            got = self._prefetched.pop((str(path), channels), None)
+            if got is None:
                 with open(path, "rb") as f:
-                    data = f.read()
-            if self.device_png and data[:8] == ops._PNG_SIGNATURE:
-                if not tried:
-                    parsed = ops._png_parse(data)  # (the one chunk walk of this file)
-                    if parsed[0] is not None:
-                        info = parsed[0]
-                        out = self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])
-                        image = ops.png_decode_batch([data], outs=[out], channels=channels, device=self.device, reject_ok=True, parsed=[parsed])[0]
-                if image is not None:
-                    self.stats["png_decoded_on_device"] += 1
-                    self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
-                    return image
-                self.stats["png_fallbacks"] += 1
-            if self.device_decode and data[:2] == b"\xff\xd8":
-                info, out = ops.jpeg_info(data), None
-                if info is not None and into is not None and into[0] is not None and (info["height"], info["width"]) == (into[0].h, into[0].w):
-                    out = into[0].rgb[self.slots(into[0], [into[1]])[0]]
-                if info is None:
-                    image = None
-                elif self.device_entropy:  # the scan on the device too; the call waits for its status word (DESIGN.md 7i)
-                    image, on_device = ops.jpeg_decode_device(data, out=out, device=self.device, reject_ok=True)
-                    self.stats["scans_decoded_on_device" if on_device else "entropy_fallbacks"] += 1
-                else:
-                    image = ops.jpeg_decode(data, out=out, device=self.device, reject_ok=True)
-                if image is not None:
-                    self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
-                    return image
-                self.stats["jpeg_fallbacks"] += 1
+                    got = _Prefetched(f.read())
+            kind, image = ops.image_kind(got.data), None
+            if kind == "png" and self.device_png:
+                image = self._decode_png(got, into, channels)
+            elif kind == "jpeg" and self.device_decode:
+                image = self._decode_jpeg(got.data, into)
+            if image is not None:
+                self.stats["targets_decoded_on_device" if target else "frames_decoded_on_device"] += 1
+                return image
         image = np.array(PIL.Image.open(path))
         return image[..., :3] if channels == "rgb" else image
+
+    def _decode_png(self, got, into, channels):
+        """a PNG file's image on the device, or None where the path refuses the file or gives it up (``png_fallbacks``)"""
+        image = got.image if got.png_tried else self._png_images([(got.data, into)], channels)[0]
+        self.stats["png_fallbacks" if image is None else "png_decoded_on_device"] += 1
+        return image
+
+    def _decode_jpeg(self, data, into):
+        """a JPEG stream's image on the device, or None where the path refuses the stream (``jpeg_fallbacks``)"""
+        from .. import ops
+
+        info, image = ops.jpeg_info(data), None
+        if info is not None:
+            out = self._slot_for(into, info["height"], info["width"])  # (a served stream has three channels)
+            if self.device_entropy:  # the scan on the device too; the call waits for its status word (DESIGN.md 7i)
+                image, on_device = ops.jpeg_decode_device(data, out=out, device=self.device, reject_ok=True)
+                self.stats["scans_decoded_on_device" if on_device else "entropy_fallbacks"] += 1
+            else:
+                image = ops.jpeg_decode(data, out=out, device=self.device, reject_ok=True)
+        if image is None:
+            self.stats["jpeg_fallbacks"] += 1
+        return image
 
     # ------------------------------------------------------------------ the resize on the device
     @staticmethod

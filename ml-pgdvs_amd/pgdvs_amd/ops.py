@@ -7,6 +7,7 @@ this module computes on the CPU; CPU tensors are rejected.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from collections import OrderedDict
@@ -1124,21 +1125,22 @@ def resample_u8(img, out_hw, filter, out=None):
 JPEG_SAMPLINGS = ("4:4:4", "4:2:2", "4:2:0")  # pgdvs_jpeg_info.sampling
 
 
-def _jpeg_bytes(data):
-    """the stream as a read-only byte buffer and its address (no copy for bytes, bytearray or a contiguous uint8 array)"""
+def _file_bytes(data, codec):
+    """the file as a read-only byte buffer and its address (no copy for bytes, bytearray or a contiguous uint8 array);
+    ``codec``: who asks, the first word of the TypeError's text"""
     if isinstance(data, np.ndarray):
         if data.dtype != np.uint8 or data.ndim != 1 or not data.flags.c_contiguous:
-            raise TypeError(f"jpeg: data as an array must be contiguous uint8 [n], got {data.dtype} {data.shape}")
+            raise TypeError(f"{codec}: data as an array must be contiguous uint8 [n], got {data.dtype} {data.shape}")
         return data, C.c_void_p(data.ctypes.data), data.size
     if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise TypeError(f"jpeg: data must be bytes, bytearray, memoryview or a uint8 array, got {type(data)}")
+        raise TypeError(f"{codec}: data must be bytes, bytearray, memoryview or a uint8 array, got {type(data)}")
     arr = np.frombuffer(data, dtype=np.uint8)
     return arr, C.c_void_p(arr.ctypes.data if arr.size else 0), arr.size
 
 
 def _jpeg_parse(data):
     """(JpegInfo, keep-alive, pointer, size) of a served stream, or None with the reason in ``pgdvs_last_error``"""
-    keep, ptr, n = _jpeg_bytes(data)
+    keep, ptr, n = _file_bytes(data, "jpeg")
     info = _lib.JpegInfo()
     rc = _lib.load().pgdvs_jpeg_parse(ptr, n, C.byref(info))
     if rc < 0:
@@ -1163,14 +1165,53 @@ def jpeg_info(data):
 JPEG_SCAN_SUB_BYTES = 64  # PGDVS_JPEG_SCAN_SUB_BYTES
 JPEG_SCAN_MAX_BYTES = 1 << 25  # PGDVS_JPEG_SCAN_MAX_BYTES
 JPEG_ENTROPY_MODES = ("host", "device")
-_jpeg_side_streams = {}  # device -> the stream entropy="device" launches on
+_side_streams = {}  # (codec, device) -> the stream that codec's decode launches run on
 
 
-def _cuda_device(device, what):
+def image_kind(data):
+    """ "png", "jpeg" or None by the file's first bytes: its signature decides, as it does for Pillow, not its name"""
+    head = bytes(data[:8])
+    return "png" if head == PNG_SIGNATURE else "jpeg" if head[:2] == b"\xff\xd8" else None
+
+
+def _cuda_device(device, what, outs=()):
+    """the GPU an op runs on, with its index: ``device`` where given, else that of the first GPU tensor of ``outs``, else the
+    current GPU; anything but a GPU is refused"""
+    if device is None:
+        device = next((o.device for o in outs if isinstance(o, torch.Tensor) and o.is_cuda), None)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if device.type != "cuda":
         raise ValueError(f"{what} on a GPU, got device {device}")
     return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+@contextlib.contextmanager
+def _side_stream(codec, device, written=()):
+    """A decode op's launches on the side stream of its codec and device.  On entry that stream waits for the caller's (an
+    ``out`` may still be read or written there) and becomes the current one; the body uploads, launches and calls the yielded
+    ``fetch(status)`` where the host's wait shall end: the status words are copied to pinned memory and an event is recorded
+    right there.  On exit the caller's stream waits for the side stream, the tensors of ``written`` (allocated on the caller's
+    stream, filled on this one) are recorded on it, and the host waits for that one event: ``fetch``'s words are then valid."""
+    with torch.cuda.device(device):
+        main = torch.cuda.current_stream(device)
+        side = _side_streams.get((codec, device))
+        if side is None:
+            side = _side_streams[codec, device] = torch.cuda.Stream(device)
+        fetched = torch.cuda.Event()
+
+        def fetch(status):
+            words = torch.empty(status.shape, dtype=torch.int32, pin_memory=True)
+            words.copy_(status, non_blocking=True)
+            fetched.record(side)
+            return words
+
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            yield fetch
+        main.wait_stream(side)
+        for t in written:
+            t.record_stream(side)
+        fetched.synchronize()  # the call's one wait
 
 
 def jpeg_scan_prepare(data, sub_bytes: int = 0):
@@ -1179,7 +1220,7 @@ def jpeg_scan_prepare(data, sub_bytes: int = 0):
     default, ``JPEG_SCAN_SUB_BYTES``), and the ``JpegInfo`` -- or None where the stream is refused (``pgdvs_last_error`` says
     why: what ``jpeg_info`` refuses, a bad RSTn marker, or a scan above ``JPEG_SCAN_MAX_BYTES``)."""
     lib = _lib.load()
-    keep, ptr, n = _jpeg_bytes(data)
+    keep, ptr, n = _file_bytes(data, "jpeg")
     need = lib.pgdvs_jpeg_scan_prepare_bytes(ptr, n, sub_bytes)
     if need < 0:
         check(int(need), "pgdvs_jpeg_scan_prepare_bytes")
@@ -1237,13 +1278,11 @@ def jpeg_decode(data, out=None, device=None, reject_ok: bool = False, entropy: s
 
     ``entropy="device"``: the scan is decoded on the GPU too.  The host only prepares it (``pgdvs_jpeg_scan_prepare``: one
     pass over the bytes, no Huffman work) into a pinned buffer; one asynchronous copy takes that buffer -- the file's size,
-    not the coefficients' -- to the device; ``pgdvs_jpeg_scan_decode`` and ``pgdvs_jpeg_reconstruct`` run on a side stream
-    of this op's own, which first waits for the caller's stream (``out`` may have pending work there) and which the caller's
-    stream then waits for through an event.  The scan's status word comes back through a pinned word and THIS CALL WAITS for
-    that one event: once per file, the mode's price -- "does not synchronise" belongs to ``entropy="host"`` alone.  A
-    non-zero status (a corrupt scan, or anything the device path does not settle) reruns the file through the host path
-    above, which serves it, refuses it or leaves it to the caller exactly as ``entropy="host"`` does; the second value of
-    ``jpeg_decode_device`` tells the two apart."""
+    not the coefficients' -- to the device; ``pgdvs_jpeg_scan_decode`` and ``pgdvs_jpeg_reconstruct`` run on this op's side
+    stream, ordered against the caller's (``_side_stream``), and THIS CALL WAITS for the scan's status word: once per file,
+    the mode's price -- "does not synchronise" belongs to ``entropy="host"`` alone.  A non-zero status (a corrupt scan, or
+    anything the device path does not settle) reruns the file through the host path above, which serves it, refuses it or
+    leaves it to the caller exactly as ``entropy="host"`` does; the second value of ``jpeg_decode_device`` tells the two apart."""
     if entropy not in JPEG_ENTROPY_MODES:
         raise ValueError(f"jpeg_decode: entropy {entropy!r}, expected one of {JPEG_ENTROPY_MODES}")
     if entropy == "device":
@@ -1259,13 +1298,7 @@ def jpeg_decode(data, out=None, device=None, reject_ok: bool = False, entropy: s
     if got is None:
         return refused()
     info, keep, ptr, n = got
-    if device is None:
-        device = out.device if isinstance(out, torch.Tensor) and out.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise ValueError(f"jpeg_decode: the image is reconstructed on a GPU, got device {device}")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = _cuda_device(device, "jpeg_decode: the image is reconstructed", (out,))
     out = _out(out, (info.height, info.width, 3), torch.uint8, device, "jpeg_decode: out")
     nq = C.sizeof(info.quant)
     host = torch.empty((info.coef_bytes + nq) // 2, dtype=torch.int16, pin_memory=True)
@@ -1292,28 +1325,15 @@ def jpeg_decode_device(data, out=None, device=None, reject_ok: bool = False):
     if got is None:  # what the markers refuse, a bad RSTn, an oversized scan: the host path says which and decides
         return jpeg_decode(data, out=out, device=device, reject_ok=reject_ok), False
     prepared, info = got
-    if device is None and isinstance(out, torch.Tensor) and out.is_cuda:
-        device = out.device
-    device = _cuda_device(device, "jpeg_decode: the image is reconstructed")
+    device = _cuda_device(device, "jpeg_decode: the image is reconstructed", (out,))
     out = _out(out, (info.height, info.width, 3), torch.uint8, device, "jpeg_decode: out")
     hd = _lib.JpegScanHeader.from_address(prepared.data_ptr())
-    with torch.cuda.device(device):
-        main = torch.cuda.current_stream(device)
-        side = _jpeg_side_streams.get(device)
-        if side is None:
-            side = _jpeg_side_streams[device] = torch.cuda.Stream(device)
-        side.wait_stream(main)  # (``out`` may still be read or written there)
-        with torch.cuda.stream(side):
-            dev, coef, status, _ = _jpeg_scan_launch(prepared, info, device)
-            word = torch.empty(1, dtype=torch.int32, pin_memory=True)
-            word.copy_(status, non_blocking=True)
-            fetched = torch.cuda.Event()
-            fetched.record(side)
-            ws = _ws(lib.pgdvs_jpeg_reconstruct_workspace_bytes(C.byref(info)), device)
-            check(lib.pgdvs_jpeg_reconstruct(_ptr(coef), C.c_void_p(dev.data_ptr() + hd.off_quant), C.byref(info), _ptr(out), info.width * 3,
-                                             _ptr(ws), ws.numel(), _stream()), "pgdvs_jpeg_reconstruct")
-        main.wait_stream(side)
-        fetched.synchronize()  # the mode's one wait
+    with _side_stream("jpeg", device) as fetch:
+        dev, coef, status, _ = _jpeg_scan_launch(prepared, info, device)
+        word = fetch(status)  # behind the scan, in front of the reconstruction: the mode's one wait is for the scan alone
+        ws = _ws(lib.pgdvs_jpeg_reconstruct_workspace_bytes(C.byref(info)), device)
+        check(lib.pgdvs_jpeg_reconstruct(_ptr(coef), C.c_void_p(dev.data_ptr() + hd.off_quant), C.byref(info), _ptr(out), info.width * 3,
+                                         _ptr(ws), ws.numel(), _stream()), "pgdvs_jpeg_reconstruct")
     if int(word[0]) == 0:
         return out, True
     return jpeg_decode(data, out=out, device=device, reject_ok=reject_ok), False
@@ -1324,19 +1344,20 @@ PNG_INFLATE_MAX_BYTES = 1 << 28  # PGDVS_PNG_INFLATE_MAX_BYTES
 PNG_MAX_SIZE = 16384
 PNG_CHANNEL_MODES = ("file", "rgb")
 PNG_STATUS_BITS = ("block", "code", "distance", "stored", "data_out", "size", "left_over", "adler", "filter", "not_synchronised")
-_PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
-_png_side_streams = {}  # device -> the stream the PNG launches run on
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
-def _png_parse(data):
+def png_parse(data):
     """(info, None) of a PNG file ``png_decode`` serves, else (None, reason).  The chunk walk of the host side: signature,
-    lengths, every CRC (``zlib.crc32``), chunk order, IHDR, and the two zlib header bytes -- no Huffman work, no inflate."""
+    lengths, every CRC (``zlib.crc32``), chunk order, IHDR, and the two zlib header bytes -- no Huffman work, no inflate.
+    ``info`` is ``png_info``'s dict and the file's bytes; a caller that walks a file itself (to size its ``out``) hands the
+    pair back to ``png_decode_batch(parsed=...)`` as it is."""
     import struct
     import zlib
 
-    keep, _, n = _jpeg_bytes(data)
+    keep, _, n = _file_bytes(data, "png")
     mv = memoryview(keep)
-    if n < 8 or bytes(mv[:8]) != _PNG_SIGNATURE:
+    if n < 8 or bytes(mv[:8]) != PNG_SIGNATURE:
         return None, "not a PNG signature"
     pos, ihdr, spans, state = 8, None, [], 0  # state: 0 before IDAT, 1 inside the IDAT run, 2 behind it, 3 after IEND
     while state != 3:
@@ -1402,13 +1423,13 @@ def png_info(data):
     """What the host side reads from a PNG file (bytes-like or a uint8 array; Python only): a dict of width, height, channels
     (3 or 4), stream_bytes (the zlib stream over all IDAT chunks) and idat (the payloads' (offset, length) in the file) -- or
     None when ``png_decode`` does not serve the file (``png_refusal`` gives the reason)."""
-    info = _png_parse(data)[0]
+    info = png_parse(data)[0]
     return None if info is None else {k: v for k, v in info.items() if k != "data"}
 
 
 def png_refusal(data):
     """why ``png_decode`` refuses the file on the host, or None where it does not"""
-    return _png_parse(data)[1]
+    return png_parse(data)[1]
 
 
 def png_status_text(status: int) -> str:
@@ -1457,10 +1478,9 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     walks the chunks and checks every CRC (Python; no Huffman work, no inflate) and joins all files' IDAT payloads behind
     one stream table in ONE pinned buffer; one asynchronous copy takes it to ``device`` (default: the outs', else the current
     GPU) and ONE batched ``pgdvs_png_decode`` -- a workgroup per file inflates it, then a wavefront per file undoes the row
-    filters -- runs on a side stream of this op's own, which first waits for the caller's stream (an ``out`` may have pending
-    work there) and which the caller's stream then waits for.  All status words come back through one pinned copy behind
-    one event and THIS CALL WAITS for that event, once per batch.  ``outs``: None, or per file None or a uint8 [H,W,C] tensor
-    on the device to fill, its rows contiguous and its row stride free (a frame's slot of the resident store).
+    filters -- runs on this op's side stream, ordered against the caller's (``_side_stream``).  THIS CALL WAITS for the status
+    words of all files, once per batch.  ``outs``: None, or per file None or a uint8 [H,W,C] tensor on the device to fill, its
+    rows contiguous and its row stride free (a frame's slot of the resident store).
 
     A file the path does not serve is refused, never approximated: on the host, in front of any device work (another colour
     type or bit depth, interlace, tRNS or APNG chunks, a bad signature, CRC or chunk order, a truncated file, a zlib header
@@ -1469,8 +1489,8 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     file's entry of the result is None under ``reject_ok`` (``reasons``, a list, receives one text or None per file), else the
     first such file raises ValueError -- the caller hands the file to Pillow, which decides.  ``stats`` (a list, for tools: it
     waits for the device once more) receives per file None or the workspace's four words: windows, the most synchronisation
-    rounds of a window, the most resolve rounds of a window, blocks.  ``parsed``: what the chunk walk gave for each file, where
-    the caller has it already (``SceneStore.prefetch_images``): the files are not walked again."""
+    rounds of a window, the most resolve rounds of a window, blocks.  ``parsed``: what ``png_parse`` gave for each file, where the
+    caller has walked them already (``SceneStore``, to find each file's slot): the files are not walked again."""
     if channels not in PNG_CHANNEL_MODES:
         raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
     datas = list(datas)
@@ -1481,46 +1501,31 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     images = [None] * len(datas)
     walked, parsed = parsed, []
     for i, data in enumerate(datas):
-        info, why[i] = _png_parse(data) if walked is None else walked[i]
+        info, why[i] = png_parse(data) if walked is None else walked[i]
         if info is not None:
             parsed.append((i, info))
         elif not reject_ok:
             raise ValueError(f"png_decode: file {i} is not served: {why[i]}")
     if parsed:
-        if device is None:
-            device = next((o.device for o in outs if isinstance(o, torch.Tensor) and o.is_cuda), None)
-        device = _cuda_device(device, "png_decode: the files are decoded")
+        device = _cuda_device(device, "png_decode: the files are decoded", outs)
         lib = _lib.load()
         out_ch = [3 if channels == "rgb" else info["channels"] for _, info in parsed]
         targets = [_png_out(outs[i], (info["height"], info["width"], c), device, f"png_decode: out of file {i}") for (i, info), c in zip(parsed, out_ch)]
         batch = _png_batch([info for _, info in parsed], out_ch, [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]) for t in targets],
                            pin=True)
         n = len(parsed)
-        with torch.cuda.device(device):
-            main = torch.cuda.current_stream(device)
-            side = _png_side_streams.get(device)
-            if side is None:
-                side = _png_side_streams[device] = torch.cuda.Stream(device)
-            side.wait_stream(main)  # (an ``out`` may still be read or written there)
-            with torch.cuda.stream(side):
-                dev = batch.to(device, non_blocking=True)
-                status = torch.empty(n, dtype=torch.int32, device=device)
-                ws = _ws(lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n), device)
-                check(lib.pgdvs_png_decode(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(),
-                                           _stream()), "pgdvs_png_decode")
-                words = torch.empty(n, dtype=torch.int32, pin_memory=True)
-                words.copy_(status, non_blocking=True)
-                fetched = torch.cuda.Event()
-                fetched.record(side)
-            main.wait_stream(side)
-            for t in targets:
-                t.record_stream(side)  # (allocated on the caller's stream, written on this one)
-            fetched.synchronize()  # the batch's one wait
-            if stats is not None:
-                rows = ws[:16 * n].cpu().view(torch.int32).view(n, 4).tolist()
-                stats[:] = [None] * len(datas)
-                for (i, _), row in zip(parsed, rows):
-                    stats[i] = tuple(row)
+        with _side_stream("png", device, written=targets) as fetch:
+            dev = batch.to(device, non_blocking=True)
+            status = torch.empty(n, dtype=torch.int32, device=device)
+            ws = _ws(lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n), device)
+            check(lib.pgdvs_png_decode(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(),
+                                       _stream()), "pgdvs_png_decode")
+            words = fetch(status)  # behind the whole batch: its one wait
+        if stats is not None:
+            rows = ws[:16 * n].cpu().view(torch.int32).view(n, 4).tolist()
+            stats[:] = [None] * len(datas)
+            for (i, _), row in zip(parsed, rows):
+                stats[i] = tuple(row)
         for (i, _), target, word in zip(parsed, targets, words.tolist()):
             if word == 0:
                 images[i] = target
@@ -1548,7 +1553,7 @@ def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: in
         raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
     lib = _lib.load()
     results = [None] * len(datas)
-    parsed = [(i, info) for i, info in ((i, _png_parse(d)[0]) for i, d in enumerate(datas)) if info is not None]
+    parsed = [(i, info) for i, info in ((i, png_parse(d)[0]) for i, d in enumerate(datas)) if info is not None]
     if not parsed:
         return results
     n = len(parsed)

@@ -163,7 +163,7 @@ def test_damaged_streams_are_given_up_or_equal_pillow():
         else:
             assert f"{emu['status']:#x}" in reasons[0], (label, reasons, hex(emu["status"]))
         # the C entry itself, guard bytes round the image, the status word and the workspace
-        info = ops._png_parse(data)[0]
+        info = ops.png_parse(data)[0]
         h, w, c = info["height"], info["width"], info["channels"]
         img = torch.full((64 + h * w * c + 64,), CANARY, dtype=torch.uint8, device=DEV)
         batch = ops._png_batch([info], [c], [(img.data_ptr() + 64, w * c)], pin=False)

@@ -190,14 +190,17 @@ def test_the_inflate_under_the_sanitizers(tmp_path):
 
 # ---------------------------------------------------------------------------- the keyword
 def test_device_png_needs_device_resize():
-    from pgdvs_amd.datasets._common import check_device_png
+    from pgdvs_amd.datasets._common import device_input
     from pgdvs_amd.datasets.resident import SceneStore
+
+    def png_option(device_png, device_resize, owner):
+        return device_input(owner, resident=True, device="cuda:0", device_resize=device_resize, device_png=device_png).png
 
     with pytest.raises(ValueError, match="device_png=True.*device_resize=True"):
         SceneStore(device="cuda:0", device_png=True)  # (refused in front of any device work)
     with pytest.raises(ValueError, match="device_png=True.*device_resize=True"):
-        check_device_png(True, False, "Loader")
-    assert check_device_png(False, False, "Loader") is False and check_device_png(True, True, "Loader") is True
+        png_option(True, False, "Loader")
+    assert png_option(False, False, "Loader") is False and png_option(True, True, "Loader") is True
     store = SceneStore()
     assert not store.device_png and store.stats["png_decoded_on_device"] == store.stats["png_fallbacks"] == 0
     store.prefetch_images(["/nonexistent.png"])  # off: nothing is opened

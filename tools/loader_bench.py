@@ -549,7 +549,7 @@ def png_frame_case(path, reps, sub_sizes):
 
     lib = _lib.load()
     data = pathlib.Path(path).read_bytes()
-    info = ops._png_parse(data)[0]
+    info = ops.png_parse(data)[0]
     stream = b"".join(data[o:o + n] for o, n in info["idat"])
 
     def clock(fn, n):
