@@ -1213,6 +1213,45 @@ int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_by
 int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
                           uint32_t *status, void *workspace, int64_t workspace_bytes);
 
+/* Mask files read on the device: the same batch with a table of pgdvs_png_image, which adds the sample format to
+ * pgdvs_png_stream's fields (same meaning, same limits).  An entry is either a colour stream as above (channels 3 or 4,
+ * bit_depth 8, scale 1) or a ONE-CHANNEL stream -- a non-interlaced file of colour type 0 (grey) or 3 (palette; its indices,
+ * the palette is never applied) -- with channels = out_channels = 1, bit_depth 1, 2, 4 or 8 and scale >= 1 with
+ * scale * (2^bit_depth - 1) <= 255: out is uint8 [H,W], every sample times scale (Pillow's array of a grey file: scale 1, 85,
+ * 17, 1 at depth 1, 2, 4, 8; of a palette file: 1).  Below 8 bits a row is ceil(width * bit_depth / 8) bytes behind its filter
+ * byte, the filters work on those bytes, each reconstructed byte gives 8 / bit_depth pixels from its most significant bits
+ * on, and pixels at x >= width are dropped whatever the padding bits hold.  The inflated size is
+ * height * (1 + ceil(width * channels * bit_depth / 8)).  The table is padded to 16 bytes; colour and mask streams may share
+ * a batch.  Everything else -- the buffers, sub_bytes, status bits, the two launches without a host synchronisation, what is
+ * read and written whatever the bytes hold, the workspace's first words, the host twin -- is pgdvs_png_decode's, and the three
+ * older entry points are these over a table of pgdvs_png_stream. */
+typedef struct pgdvs_png_image {
+  int64_t offset, size;
+  int32_t height, width, channels, out_channels;
+  int64_t row_stride;
+  void *out;
+  int32_t bit_depth, scale;
+} pgdvs_png_image;
+int64_t pgdvs_png_images_workspace_bytes(const pgdvs_png_image *images, int32_t nstreams);
+int pgdvs_png_decode_images(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                            void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+int pgdvs_png_decode_images_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
+                                 uint32_t *status, void *workspace, int64_t workspace_bytes);
+
+/* A decoded mask into its place (csrc/mask_place.hip): one gather over src uint8 [h,w,C] on the DEVICE, src_row_stride bytes
+ * between its rows (>= w * C), pixels contiguous.  map: nullptr (then H = h and W = w: pixel (y, x) comes from (y, x)), or
+ * DEVICE int32 [H,W], the source pixel's index y' * w + x' of every output pixel (a NEAREST resize's picks); an index outside
+ * 0 .. h * w - 1 reads as 0.
+ *   mode PGDVS_MASK_PLACE_U8      C = 1: out uint8 [H,W], out_row_stride bytes between rows (>= W): the picked byte
+ *   mode PGDVS_MASK_PLACE_BGR_F32 C = 1 or 3: out float32 [H,W,3], out_row_stride BYTES between rows (>= 12 W, a multiple
+ *                                 of 4): out[y,x,k] = src[..., C - 1 - k] > 0 ? 1 : 0 (C = 1: the one channel thrice) --
+ *                                 float32(convert("RGB")[..., ::-1] > 1e-3) of a grey or RGB mask file
+ * h, w, H, W: 1 .. 16384.  One launch on `stream`, no workspace, no atomics, no host synchronisation. */
+#define PGDVS_MASK_PLACE_U8 0
+#define PGDVS_MASK_PLACE_BGR_F32 1
+int pgdvs_mask_place(const uint8_t *src, int32_t h, int32_t w, int32_t channels, int64_t src_row_stride, const int32_t *map, int32_t H, int32_t W,
+                     int32_t mode, void *out, int64_t out_row_stride, pgdvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

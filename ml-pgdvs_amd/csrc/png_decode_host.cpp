@@ -1,6 +1,7 @@
 // The host side of the PNG reader's C ABI: the workspace size and pgdvs_png_decode_host, the emulation of the kernels of
 // csrc/png_inflate.hip and csrc/png_unfilter.hip over csrc/png_inflate_core.h.  include/pgdvs_hip.h states the contract.
 //
+// Both table layouts (pgdvs_png_stream, pgdvs_png_image) go through the one walk below: pnginf::Table reads either.
 // Plain C++: no HIP, no GPU, nothing of the rest of the library but set_error -- tools/png_inflate_fuzz.cpp builds this file
 // alone with the host compiler and its sanitizers.  The emulation runs every step of the core for thread 0 .. kThreads - 1
 // where the kernel runs it on its threads and puts a barrier: the same windows, the same rounds (a round reads what the
@@ -22,6 +23,7 @@ namespace pi = pgdvs::pnginf;
 using pgdvs::set_error;
 
 static_assert(sizeof(pgdvs_png_stream) == sizeof(pi::Stream), "pgdvs_png_stream and pnginf::Stream are one layout");
+static_assert(sizeof(pgdvs_png_image) == sizeof(pi::Image) && sizeof(pi::Image) % 8 == 0, "pgdvs_png_image and pnginf::Image are one layout");
 
 // one stream through the team's walk; returns the status bits
 uint32_t inflate_stream(pi::Shared &S, pi::Src &src, uint8_t *out, uint32_t cap, int sub_bits, int64_t max_iters, uint32_t *info) {
@@ -131,10 +133,11 @@ uint32_t inflate_stream(pi::Shared &S, pi::Src &src, uint8_t *out, uint32_t cap,
 }
 
 // the filters undone row by row, the filter byte and (out_channels < channels) the alpha byte dropped; the reconstructed
-// row in front is kept in the stream's carry row, the inflated rows stay as they are
-uint32_t unfilter(const pi::Stream &st, const uint8_t *rows, uint8_t *carry) {
-  const int64_t pitch = 1 + (int64_t)st.width * st.channels;
-  const int C = st.channels, OC = st.out_channels;
+// row in front is kept in the stream's carry row, the inflated rows stay as they are.  Below 8 bits the filter's unit is the
+// byte (one channel): each reconstructed byte leaves as its 8 / depth samples (unpack_byte)
+uint32_t unfilter(const pi::Image &st, const uint8_t *rows, uint8_t *carry) {
+  const int C = st.channels, OC = st.out_channels, D = st.bit_depth;
+  const int64_t units = D == 8 ? st.width : pi::row_bytes(st), pitch = 1 + units * C;
   uint32_t err = 0;
   for (int y = 0; y < st.height; ++y) {
     const uint8_t *row = rows + y * pitch + 1;
@@ -142,68 +145,88 @@ uint32_t unfilter(const pi::Stream &st, const uint8_t *rows, uint8_t *carry) {
     if (ft > 4) err = pi::kStFilter, ft = 0;
     uint8_t *dst = reinterpret_cast<uint8_t *>(st.out) + y * st.row_stride;
     uint8_t left[4] = {0, 0, 0, 0}, upleft[4] = {0, 0, 0, 0};
-    for (int x = 0; x < st.width; ++x)
+    for (int64_t x = 0; x < units; ++x)
       for (int c = 0; c < C; ++c) {
-        const int64_t k = (int64_t)x * C + c;
+        const int64_t k = x * C + c;
         const uint8_t b = y ? carry[k] : 0;
         const uint8_t v = (uint8_t)pi::unfilter_byte(ft, row[k], left[c], b, upleft[c]);
         left[c] = v, upleft[c] = b, carry[k] = v;
-        if (c < OC) dst[(int64_t)x * OC + c] = v;
+        if (D < 8) pi::unpack_byte(v, D, (uint32_t)st.scale, x, st.width, dst);
+        else if (c < OC) dst[x * OC + c] = v;
       }
   }
   return err;
 }
 
-}  // namespace
-
-extern "C" __attribute__((visibility("default"))) int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_stream *streams, int32_t nstreams) {
-  if (streams == nullptr || nstreams < 1 || nstreams > 65535) {
-    set_error("pgdvs_png_inflate_workspace_bytes: null table or a stream count outside 1 .. 65535");
+int64_t workspace_bytes(const char *who, const pi::Table &t) {
+  if (t.base == nullptr || t.n < 1 || t.n > 65535) {
+    set_error("%s: null table or a stream count outside 1 .. 65535", who);
     return -1;
   }
-  const pi::Stream *s = reinterpret_cast<const pi::Stream *>(streams);
-  for (int32_t i = 0; i < nstreams; ++i)
-    if (s[i].height < 1 || s[i].width < 1 || s[i].height > pi::kMaxSide || s[i].width > pi::kMaxSide || (s[i].channels != 3 && s[i].channels != 4) ||
-        pi::inflated_bytes(s[i]) > pi::kMaxBytes) {
-      set_error("pgdvs_png_inflate_workspace_bytes: stream %d: image size or channels out of range", i);
+  for (int32_t i = 0; i < t.n; ++i)
+    if (const char *why = pi::check_format(t, pi::at(t, i))) {
+      set_error("%s: stream %d: %s", who, i, why);
       return -1;
     }
-  return pi::up(pi::work_offset(s, nstreams, nstreams), 256);
+  return pi::up(pi::work_offset(t, t.n), 256);
 }
 
-extern "C" __attribute__((visibility("default"))) int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams,
-                                                                             int32_t sub_bytes, uint32_t *status, void *workspace,
-                                                                             int64_t workspace_bytes) {
+// both host entries: `entry` = the bytes of a table entry
+int decode_host(const char *who, int32_t entry, const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
+                uint32_t *status, void *workspace, int64_t workspace_bytes) {
   if (batch_host == nullptr || batch == nullptr || status == nullptr || workspace == nullptr || (reinterpret_cast<uintptr_t>(batch) & 7) != 0 ||
       (reinterpret_cast<uintptr_t>(batch_host) & 7) != 0 || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
-    set_error("pgdvs_png_decode_host: null pointer, or a buffer that is not 8-byte aligned");
+    set_error("%s: null pointer, or a buffer that is not 8-byte aligned", who);
     return -1;
   }
   if (sub_bytes == 0) sub_bytes = pi::kDefaultSubBytes;
-  const pi::Stream *s = static_cast<const pi::Stream *>(batch_host);
-  if (const char *why = nstreams >= 1 && batch_bytes >= (int64_t)nstreams * (int64_t)sizeof(pi::Stream) ? pi::check_streams(s, nstreams, batch_bytes, sub_bytes)
-                                                                                                        : "the batch buffer is shorter than its table") {
-    set_error("pgdvs_png_decode_host: %s", why);
+  const pi::Table t = {static_cast<const uint8_t *>(batch_host), nstreams, entry};
+  if (const char *why = nstreams >= 1 && batch_bytes >= (int64_t)nstreams * entry ? pi::check_streams(t, batch_bytes, sub_bytes)
+                                                                                  : "the batch buffer is shorter than its table") {
+    set_error("%s: %s", who, why);
     return -1;
   }
-  const int64_t need = pi::up(pi::work_offset(s, nstreams, nstreams), 256);
+  const int64_t need = pi::up(pi::work_offset(t, nstreams), 256);
   if (workspace_bytes < need) {
-    set_error("pgdvs_png_decode_host: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+    set_error("%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
     return -1;
   }
   uint8_t *ws = static_cast<uint8_t *>(workspace);
   memset(ws, 0, (size_t)pi::work_head(nstreams));
   pi::Shared *S = new pi::Shared;
   for (int32_t i = 0; i < nstreams; ++i) {
-    const pi::Stream st = s[i];
+    const pi::Image st = pi::at(t, i);
     pi::Src src;
     src.words = reinterpret_cast<const uint32_t *>(static_cast<const uint8_t *>(batch) + st.offset);
     src.nwords = (uint32_t)((st.size + 3) / 4), src.nbits = (uint32_t)st.size * 8;
     src.win = nullptr, src.win_first = 0, src.win_count = 0;
-    uint8_t *rows = ws + pi::work_offset(s, nstreams, i);
+    uint8_t *rows = ws + pi::work_offset(t, i);
     status[i] = inflate_stream(*S, src, rows, (uint32_t)pi::inflated_bytes(st), sub_bytes * 8, 2 * st.size + 2, reinterpret_cast<uint32_t *>(ws) + (int64_t)i * pi::kInfoWords);
-    if (status[i] == 0) status[i] = unfilter(st, rows, ws + pi::carry_offset(s, nstreams, i));
+    if (status[i] == 0) status[i] = unfilter(st, rows, ws + pi::carry_offset(t, i));
   }
   delete S;
   return 0;
+}
+
+}  // namespace
+
+#define PGDVS_HOST_API extern "C" __attribute__((visibility("default")))
+
+PGDVS_HOST_API int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_stream *streams, int32_t nstreams) {
+  return workspace_bytes("pgdvs_png_inflate_workspace_bytes", {reinterpret_cast<const uint8_t *>(streams), nstreams, (int32_t)sizeof(pi::Stream)});
+}
+
+PGDVS_HOST_API int64_t pgdvs_png_images_workspace_bytes(const pgdvs_png_image *images, int32_t nstreams) {
+  return workspace_bytes("pgdvs_png_images_workspace_bytes", {reinterpret_cast<const uint8_t *>(images), nstreams, (int32_t)sizeof(pi::Image)});
+}
+
+PGDVS_HOST_API int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                                         void *workspace, int64_t workspace_bytes) {
+  return decode_host("pgdvs_png_decode_host", (int32_t)sizeof(pi::Stream), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace, workspace_bytes);
+}
+
+PGDVS_HOST_API int pgdvs_png_decode_images_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
+                                                uint32_t *status, void *workspace, int64_t workspace_bytes) {
+  return decode_host("pgdvs_png_decode_images_host", (int32_t)sizeof(pi::Image), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace,
+                     workspace_bytes);
 }

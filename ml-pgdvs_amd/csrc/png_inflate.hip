@@ -28,7 +28,7 @@
 
 namespace pgdvs {
 
-int png_unfilter_launch(const pnginf::Stream *table, int nstreams, uint8_t *workspace, uint32_t *status, int max_rows, int max_width, hipStream_t st);
+int png_unfilter_launch(const pnginf::Table &table, uint8_t *workspace, uint32_t *status, int max_rows, int max_width, hipStream_t st);
 
 namespace {
 
@@ -37,18 +37,18 @@ constexpr int T = pi::kThreads;
 
 __device__ __forceinline__ void team_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); }
 
-__global__ void __launch_bounds__(T) png_inflate_kernel(const pi::Stream *__restrict__ table, int nstreams, const uint8_t *__restrict__ batch,
-                                                        uint8_t *workspace, uint32_t *__restrict__ status, int sub_bits, int max_iters) {
+__global__ void __launch_bounds__(T) png_inflate_kernel(const pi::Table table, const uint8_t *__restrict__ batch, uint8_t *workspace,
+                                                        uint32_t *__restrict__ status, int sub_bits, int max_iters) {
   __shared__ pi::Shared S;
   __shared__ uint32_t s_wsum[T / kWave];
   __shared__ int s_stop;
   const int t = threadIdx.x, i = blockIdx.x;
-  const pi::Stream st = table[i];
+  const pi::Image st = pi::at(table, i);
   pi::Src src;
   src.words = reinterpret_cast<const uint32_t *>(batch + st.offset);
   src.nwords = (uint32_t)((st.size + 3) / 4), src.nbits = (uint32_t)st.size * 8;
   src.win = nullptr, src.win_first = 0, src.win_count = 0;
-  uint8_t *out = workspace + pi::work_offset(table, nstreams, i);
+  uint8_t *out = workspace + pi::work_offset(table, i);
   const uint32_t cap = (uint32_t)pi::inflated_bytes(st);
   uint32_t err = 0, windows = 0, max_sync = 0, max_resolve = 0, blocks = 0;
   bool need_header = true, finished = false, gave_up = false;  // gave_up: the status word has the reason already
@@ -187,37 +187,50 @@ __global__ void __launch_bounds__(T) png_inflate_kernel(const pi::Stream *__rest
 
 using namespace pgdvs;
 
-PGDVS_API int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
-                               void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
-  PGDVS_REQUIRE(batch_host && batch && status && workspace, "pgdvs_png_decode: null pointer");
-  PGDVS_REQUIRE(nstreams >= 1 && batch_bytes >= (int64_t)nstreams * (int64_t)sizeof(pi::Stream), "pgdvs_png_decode: the batch buffer is shorter than its table");
+// both device entries: `entry` = the bytes of a table entry (pnginf::Table)
+static int png_decode(const char *who, int32_t entry, const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
+                      uint32_t *status, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
+  PGDVS_REQUIRE(batch_host && batch && status && workspace, "%s: null pointer", who);
+  PGDVS_REQUIRE(nstreams >= 1 && batch_bytes >= (int64_t)nstreams * entry, "%s: the batch buffer is shorter than its table", who);
   if (sub_bytes == 0) sub_bytes = pi::kDefaultSubBytes;
-  const pi::Stream *table = static_cast<const pi::Stream *>(batch_host);
-  const char *why = pi::check_streams(table, nstreams, batch_bytes, sub_bytes);
-  PGDVS_REQUIRE(why == nullptr, "pgdvs_png_decode: %s", why);
-  const int64_t need = pi::up(pi::work_offset(table, nstreams, nstreams), 256);
+  const pi::Table table = {static_cast<const uint8_t *>(batch_host), nstreams, entry};
+  const char *why = pi::check_streams(table, batch_bytes, sub_bytes);
+  PGDVS_REQUIRE(why == nullptr, "%s: %s", who, why);
+  const int64_t need = pi::up(pi::work_offset(table, nstreams), 256);
   PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(batch) & 15) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
-                "pgdvs_png_decode: the batch buffer must be 16-byte aligned, status 4-byte");
-  PGDVS_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-                "pgdvs_png_decode: workspace of %lld bytes, %lld needed (256-byte aligned)", (long long)workspace_bytes, (long long)need);
+                "%s: the batch buffer must be 16-byte aligned, status 4-byte", who);
+  PGDVS_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace of %lld bytes, %lld needed (256-byte aligned)", who,
+                (long long)workspace_bytes, (long long)need);
   int64_t max_size = 0;
   int max_rows = 0, max_width = 0;
   for (int32_t i = 0; i < nstreams; ++i) {
-    max_size = table[i].size > max_size ? table[i].size : max_size;
-    max_rows = table[i].height > max_rows ? table[i].height : max_rows;
-    max_width = table[i].width > max_width ? table[i].width : max_width;
+    const pi::Image im = pi::at(table, i);
+    max_size = im.size > max_size ? im.size : max_size;
+    max_rows = im.height > max_rows ? im.height : max_rows;
+    max_width = im.width > max_width ? im.width : max_width;  // (a row of packed samples has no more bytes than pixels)
   }
   const hipStream_t st = as_stream(stream);
   hipError_t e = hipMemsetAsync(workspace, 0, (size_t)pi::work_head(nstreams), st);
   if (e == hipSuccess) e = hipMemsetAsync(status, 0, (size_t)nstreams * 4, st);
   if (e != hipSuccess) {
-    set_error("pgdvs_png_decode: %s", hipGetErrorString(e));
+    set_error("%s: %s", who, hipGetErrorString(e));
     return PGDVS_ERR_LAUNCH;
   }
-  const pi::Stream *dtable = static_cast<const pi::Stream *>(batch);
+  const pi::Table dtable = {static_cast<const uint8_t *>(batch), nstreams, entry};
   // (a window without a header uses at least 10 bits together with the iteration in front of it: 2 * size + 2 iterations bound the walk)
-  PGDVS_LAUNCH("png_inflate", png_inflate_kernel, dim3((unsigned)nstreams), dim3(T), 0, st, dtable, nstreams, static_cast<const uint8_t *>(batch),
+  PGDVS_LAUNCH("png_inflate", png_inflate_kernel, dim3((unsigned)nstreams), dim3(T), 0, st, dtable, static_cast<const uint8_t *>(batch),
                static_cast<uint8_t *>(workspace), status, sub_bytes * 8, (int)(2 * max_size + 2));
-  if (int rc = png_unfilter_launch(dtable, nstreams, static_cast<uint8_t *>(workspace), status, max_rows, max_width, st)) return rc;
-  return check_launch("pgdvs_png_decode");
+  if (int rc = png_unfilter_launch(dtable, static_cast<uint8_t *>(workspace), status, max_rows, max_width, st)) return rc;
+  return check_launch(who);
+}
+
+PGDVS_API int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                               void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
+  return png_decode("pgdvs_png_decode", (int32_t)sizeof(pi::Stream), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace, workspace_bytes, stream);
+}
+
+PGDVS_API int pgdvs_png_decode_images(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                                      void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
+  return png_decode("pgdvs_png_decode_images", (int32_t)sizeof(pi::Image), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace,
+                    workspace_bytes, stream);
 }

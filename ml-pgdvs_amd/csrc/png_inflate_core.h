@@ -62,34 +62,71 @@ struct Stream {
   int64_t row_stride;    // bytes between two rows of out
   uint64_t out;          // address of the image's first byte
 };
+// The same with the sample format (pgdvs_png_image, field for field): 8-bit colour (channels 3 or 4, scale 1), or one
+// channel of bit_depth 1, 2, 4 or 8 -- grey or palette indices -- whose samples leave as bytes, times `scale`.
+struct Image : Stream {
+  int32_t bit_depth, scale;
+};
+// A batch's table: nstreams entries of `entry` bytes, sizeof(Stream) (every stream 8-bit colour) or sizeof(Image).
+struct Table {
+  const uint8_t *base;
+  int32_t n, entry;
+};
+PGDVS_PNG_HD Image at(const Table &t, int32_t i) {
+  const uint8_t *p = t.base + (int64_t)i * t.entry;
+  Image im;
+  static_cast<Stream &>(im) = *reinterpret_cast<const Stream *>(p);
+  im.bit_depth = 8, im.scale = 1;
+  if (t.entry == (int32_t)sizeof(Image)) im.bit_depth = reinterpret_cast<const Image *>(p)->bit_depth, im.scale = reinterpret_cast<const Image *>(p)->scale;
+  return im;
+}
 
 inline int64_t up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
-PGDVS_PNG_HD int64_t inflated_bytes(const Stream &s) { return (int64_t)s.height * (1 + (int64_t)s.width * s.channels); }
+// a row's bytes behind its filter byte: samples below a byte are packed, the last byte padded
+PGDVS_PNG_HD int64_t row_bytes(const Image &s) { return ((int64_t)s.width * s.channels * s.bit_depth + 7) / 8; }
+PGDVS_PNG_HD int64_t inflated_bytes(const Image &s) { return (int64_t)s.height * (1 + row_bytes(s)); }
 // the workspace: kInfoWords words per stream, then per stream its inflated rows (work_offset) and one reconstructed row
 // (carry_offset: the last row of a block of 64 rows, which the next block's first row needs), each 16-byte aligned
 PGDVS_PNG_HD int64_t work_head(int32_t n) { return ((int64_t)n * kInfoWords * 4 + 255) / 256 * 256; }
 PGDVS_PNG_HD int64_t pad16(int64_t a) { return (a + 15) / 16 * 16; }
-PGDVS_PNG_HD int64_t work_offset(const Stream *s, int32_t n, int32_t i) {
-  int64_t off = work_head(n);
-  for (int32_t k = 0; k < i && k < n; ++k) off += pad16(inflated_bytes(s[k])) + pad16((int64_t)s[k].width * s[k].channels);
+PGDVS_PNG_HD int64_t work_offset(const Table &t, int32_t i) {
+  int64_t off = work_head(t.n);
+  for (int32_t k = 0; k < i && k < t.n; ++k) {
+    const Image s = at(t, k);
+    off += pad16(inflated_bytes(s)) + pad16(row_bytes(s));
+  }
   return off;
 }
-PGDVS_PNG_HD int64_t carry_offset(const Stream *s, int32_t n, int32_t i) { return work_offset(s, n, i) + pad16(inflated_bytes(s[i])); }
+PGDVS_PNG_HD int64_t carry_offset(const Table &t, int32_t i) { return work_offset(t, i) + pad16(inflated_bytes(at(t, i))); }
+
+// an image's size and sample format alone (the workspace query's check); nullptr = fine, else why not
+inline const char *check_format(const Table &t, const Image &s) {
+  if (s.height < 1 || s.width < 1 || s.height > kMaxSide || s.width > kMaxSide) return "image size out of range";
+  if (s.channels == 1 && t.entry == (int32_t)sizeof(Image)) {
+    if (s.bit_depth != 1 && s.bit_depth != 2 && s.bit_depth != 4 && s.bit_depth != 8) return "one channel at bit depth 1, 2, 4 or 8";
+    if (s.scale < 1 || (int64_t)s.scale * ((1 << s.bit_depth) - 1) > 255) return "a sample scale that leaves the byte";
+  } else {
+    if (s.channels != 3 && s.channels != 4) return "3 or 4 channels";
+    if (s.bit_depth != 8 || s.scale != 1) return "colour streams have bit depth 8 and scale 1";
+  }
+  if (inflated_bytes(s) > kMaxBytes) return "inflated size above PGDVS_PNG_INFLATE_MAX_BYTES";
+  return nullptr;
+}
 
 // The table, checked on the host in front of any launch; nullptr = fine, else why not.
-inline const char *check_streams(const Stream *s, int32_t n, int64_t batch_bytes, int32_t sub_bytes) {
+inline const char *check_streams(const Table &t, int64_t batch_bytes, int32_t sub_bytes) {
+  const int32_t n = t.n;
   if (n < 1 || n > 65535) return "1 .. 65535 streams";
   if (sub_bytes < kMinSubBytes || sub_bytes > kMaxSubBytes || sub_bytes % 4) return "subsequence size out of range";
-  const int64_t table = up((int64_t)n * (int64_t)sizeof(Stream), 16);
+  const int64_t table = up((int64_t)n * t.entry, 16);
   if (batch_bytes < table) return "the batch buffer is shorter than its table";
   for (int32_t i = 0; i < n; ++i) {
-    if (s[i].height < 1 || s[i].width < 1 || s[i].height > kMaxSide || s[i].width > kMaxSide) return "image size out of range";
-    if (s[i].channels != 3 && s[i].channels != 4) return "3 or 4 channels";
-    if (s[i].out_channels != 3 && s[i].out_channels != s[i].channels) return "out_channels is 3 or the file's";
-    if (inflated_bytes(s[i]) > kMaxBytes) return "inflated size above PGDVS_PNG_INFLATE_MAX_BYTES";
-    if (s[i].size < 6 || s[i].size > kMaxBytes - 16) return "stream size out of range";
-    if (s[i].offset < table || s[i].offset % 16 || s[i].offset > batch_bytes || up(s[i].size, 4) > batch_bytes - s[i].offset) return "stream outside the batch buffer";
-    if (s[i].out == 0 || s[i].row_stride < (int64_t)s[i].width * s[i].out_channels) return "null out or a row stride below a row";
+    const Image s = at(t, i);
+    if (const char *why = check_format(t, s)) return why;
+    if (s.out_channels != s.channels && (s.out_channels != 3 || s.channels == 1)) return "out_channels is 3 or the file's";
+    if (s.size < 6 || s.size > kMaxBytes - 16) return "stream size out of range";
+    if (s.offset < table || s.offset % 16 || s.offset > batch_bytes || up(s.size, 4) > batch_bytes - s.offset) return "stream outside the batch buffer";
+    if (s.out == 0 || s.row_stride < (int64_t)s.width * s.out_channels) return "null out or a row stride below a row";
   }
   return nullptr;
 }
@@ -546,6 +583,17 @@ PGDVS_PNG_HD uint32_t unfilter_byte(uint32_t ft, uint32_t raw, uint32_t a, uint3
     pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
   }
   return (raw + pred) & 0xFF;
+}
+
+
+// the 8 / depth samples of a reconstructed byte (depth 1, 2 or 4), most significant bits first, as bytes times `scale`: byte
+// `unit` of its row holds pixels unit * (8 / depth) and on; those at or behind `width` are padding and dropped
+PGDVS_PNG_HD void unpack_byte(uint32_t v, int depth, uint32_t scale, int64_t unit, int width, uint8_t *row_out) {
+  const int per = 8 / depth;
+  for (int j = 0; j < 8; ++j) {
+    const int64_t x = unit * per + j;
+    if (j < per && x < width) row_out[x] = (uint8_t)(((v >> (8 - depth * (j + 1))) & ((1u << depth) - 1)) * scale);
+  }
 }
 
 }  // namespace pnginf

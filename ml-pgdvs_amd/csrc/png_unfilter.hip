@@ -10,7 +10,10 @@
 // its step: a pixel is read before it is replaced; the inflated rows themselves stay as they are).  Row blocks of one image
 // follow each other, images of a batch run side by side (the grid).  The same pass
 // drops the filter byte and, for out_channels < channels, the alpha byte, and writes [H,W,out_channels] with the caller's
-// row stride.  A stream whose status is not zero is left alone; a filter byte above 4 sets PGDVS_PNG_FILTER.
+// row stride.  A stream of samples below a byte (one channel, bit depth 1, 2 or 4: the mask files) has the BYTE as its filter
+// unit: a "pixel" of the skew is then one byte of the packed row, and each reconstructed byte leaves as its 8 / depth samples,
+// scaled, pixels at or behind the width dropped (unpack_byte of csrc/png_inflate_core.h, which the host emulation runs too).
+// A stream whose status is not zero is left alone; a filter byte above 4 sets PGDVS_PNG_FILTER.
 // Loop bounds are launch arguments; plain byte loads and stores; the one atomic is the status word's OR.
 #include "common.h"
 #include "png_inflate_core.h"
@@ -22,14 +25,15 @@ namespace {
 namespace pi = pnginf;
 constexpr int kGroup = 8;  // steps whose loads are issued together
 
-__global__ void __launch_bounds__(kWave) png_unfilter_kernel(const pi::Stream *__restrict__ table, int nstreams, uint8_t *workspace,
-                                                             uint32_t *__restrict__ status, int max_row_blocks, int max_width) {
+__global__ void __launch_bounds__(kWave) png_unfilter_kernel(const pi::Table table, uint8_t *workspace, uint32_t *__restrict__ status,
+                                                             int max_row_blocks, int max_width) {
   const int i = blockIdx.x, lane = threadIdx.x;
   if (__hip_atomic_load(status + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return;  // (the whole wavefront)
-  const pi::Stream st = table[i];
-  const uint8_t *rows = workspace + pi::work_offset(table, nstreams, i);
-  uint8_t *above = workspace + pi::carry_offset(table, nstreams, i);  // lane 0's upper row, reconstructed
-  const int H = st.height, W = st.width, C = st.channels, OC = st.out_channels;
+  const pi::Image st = pi::at(table, i);
+  const uint8_t *rows = workspace + pi::work_offset(table, i);
+  uint8_t *above = workspace + pi::carry_offset(table, i);  // lane 0's upper row, reconstructed
+  const int H = st.height, C = st.channels, OC = st.out_channels, D = st.bit_depth;
+  const int W = D == 8 ? st.width : (int)pi::row_bytes(st);  // the row's filter units: pixels, or the bytes of packed samples (C = 1)
   const int64_t pitch = 1 + (int64_t)W * C;
   uint8_t *dst = reinterpret_cast<uint8_t *>(st.out);
   bool bad = false;
@@ -72,7 +76,8 @@ __global__ void __launch_bounds__(kWave) png_unfilter_kernel(const pi::Stream *_
               const uint32_t v = pi::unfilter_byte(ft, (raw[g] >> (8 * c)) & 255, (cur >> (8 * c)) & 255, (up >> (8 * c)) & 255, (up_before >> (8 * c)) & 255);
               px |= v << (8 * c);
               if (lane == kWave - 1) above[(int64_t)x * C + c] = (uint8_t)v;  // the next row block's upper row
-              if (c < OC) o[(int64_t)x * OC + c] = (uint8_t)v;
+              if (D < 8) pi::unpack_byte(v, D, (uint32_t)st.scale, x, st.width, o);
+              else if (c < OC) o[(int64_t)x * OC + c] = (uint8_t)v;
             }
           }
           cur = px, up_before = up;
@@ -87,8 +92,8 @@ __global__ void __launch_bounds__(kWave) png_unfilter_kernel(const pi::Stream *_
 
 }  // namespace
 
-int png_unfilter_launch(const pnginf::Stream *table, int nstreams, uint8_t *workspace, uint32_t *status, int max_rows, int max_width, hipStream_t st) {
-  PGDVS_LAUNCH("png_unfilter", png_unfilter_kernel, dim3((unsigned)nstreams), dim3(kWave), 0, st, table, nstreams, workspace, status,
+int png_unfilter_launch(const pnginf::Table &table, uint8_t *workspace, uint32_t *status, int max_rows, int max_width, hipStream_t st) {
+  PGDVS_LAUNCH("png_unfilter", png_unfilter_kernel, dim3((unsigned)table.n), dim3(kWave), 0, st, table, workspace, status,
                (max_rows + kWave - 1) / kWave, max_width);
   return PGDVS_OK;
 }

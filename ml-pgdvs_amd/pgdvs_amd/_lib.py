@@ -109,6 +109,11 @@ class PngStream(C.Structure):
     ]
 
 
+class PngImage(C.Structure):
+    """``pgdvs_png_image`` (include/pgdvs_hip.h), field for field: ``PngStream`` with the sample format."""
+    _fields_ = PngStream._fields_ + [("bit_depth", C.c_int32), ("scale", C.c_int32)]
+
+
 class JpegScanHeader(C.Structure):
     """The front of the buffer ``pgdvs_jpeg_scan_prepare`` fills (csrc/jpeg_scan_core.h ``jscan::Header``), field for field:
     the offsets are bytes from the buffer's start."""
@@ -186,6 +191,10 @@ SIGNATURES.update({
     "pgdvs_png_inflate_workspace_bytes": (_i64, [_vp, C.c_int32]),
     "pgdvs_png_decode": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp]),
     "pgdvs_png_decode_host": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64]),
+    "pgdvs_png_images_workspace_bytes": (_i64, [_vp, C.c_int32]),
+    "pgdvs_png_decode_images": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp]),
+    "pgdvs_png_decode_images_host": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64]),
+    "pgdvs_mask_place": (_i, [_vp, C.c_int32, C.c_int32, C.c_int32, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

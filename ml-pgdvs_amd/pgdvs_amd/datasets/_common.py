@@ -75,23 +75,25 @@ def refuse_gpu_in_worker(owner):
 
 
 # which parts of the image input run on the device: ``device_input`` checks them, datasets/resident.py describes them
-DeviceInput = collections.namedtuple("DeviceInput", "resize decode entropy png")
+DeviceInput = collections.namedtuple("DeviceInput", "resize decode entropy png mask")
 
 
-def device_input(owner, *, resident, device, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
-    """The four image-input keywords of ``owner`` (a loader, or the store) as a ``DeviceInput``.  Each option builds on
+def device_input(owner, *, resident, device, device_resize=False, device_decode=False, device_entropy=False, device_png=False, device_mask=False):
+    """The five image-input keywords of ``owner`` (a loader, or the store) as a ``DeviceInput``.  Each option builds on
     another: the first rule broken, in this order, is refused with a ValueError that names what is missing."""
     if device_entropy and not device_decode:
         raise ValueError(f"{owner}(device_entropy=True) decodes the scan of the JPEG frames that device_decode=True reads: it needs device_decode=True")
     if device_png and not device_resize:
         raise ValueError(f"{owner}(device_png=True) decodes PNG frames on the device at the file's size: it needs device_resize=True")
+    if device_mask and not device_resize:
+        raise ValueError(f"{owner}(device_mask=True) decodes mask PNGs on the device into the resident store: it needs device_resize=True")
     if device_decode and not device_resize:
         raise ValueError(f"{owner}(device_decode=True) decodes JPEG frames on the device at the file's size: it needs device_resize=True")
     if device_resize and not resident:
         raise ValueError(f"{owner}(device_resize=True) resizes decoded frames into the resident store: it needs resident=True")
     if device_resize and (device is None or torch.device(device).type != "cuda"):
         raise ValueError(f"{owner}(device_resize=True) resizes on the device: it needs the store on a GPU, got device={device!r}")
-    return DeviceInput(bool(device_resize), bool(device_decode), bool(device_entropy), bool(device_png))
+    return DeviceInput(bool(device_resize), bool(device_decode), bool(device_entropy), bool(device_png), bool(device_mask))
 
 
 def group_entries(group, views, times=None, n_actual=None, depth=True):

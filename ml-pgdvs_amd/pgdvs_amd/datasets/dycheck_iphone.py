@@ -185,11 +185,15 @@ class iPhoneParser:  # noqa: N801 -- upstream's name
         return (DyCheckCamera.fromjson(os.path.join(self.data_dir, "camera", name + ".json"))
                 .rescale_image_domain(1 / self._factor).translate(-self._center).rescale(self._scale))
 
-    def load_covisible(self, time_id, camera_id, split):
+    def covisible_path(self, time_id, camera_id, split):
+        """the file ``load_covisible`` opens; a missing one is refused as there"""
         path = os.path.join(self.data_dir, "covisible", f"{self._factor}x", split, self._frame_names_map[time_id, camera_id] + ".png")
         if not os.path.exists(path):
             raise ValueError(f"Covisible image not found: {path}.")
-        return np.array(PIL.Image.open(path))
+        return path
+
+    def load_covisible(self, time_id, camera_id, split):
+        return np.array(PIL.Image.open(self.covisible_path(time_id, camera_id, split)))
 
     frame_names = property(lambda self: self._frame_names_map[self.time_ids, self.camera_ids])
     time_ids = property(lambda self: self._time_ids)
@@ -360,9 +364,10 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
     def __init__(self, *, data_root, raw_data_dir, mask_data_dir, flow_data_dir, max_hw, mode, rgb_range="0_1", use_aug=False,
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
                  n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False,
+                 device_mask=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
-                               device_entropy=device_entropy, device_png=device_png)
+                               device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -510,13 +515,20 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
             raw = self._store_rgb(p, time_id, cam_id, into=(self.store.scenes.get(scene_id), time_id))
         else:
             raw = resize(p.load_rgba(time_id, cam_id)[..., :3], h, w, PIL.Image.Resampling.BOX)
-        name = p.get_frame_name(time_id, cam_id)
-        m = np.array(PIL.Image.open(self.mask_data_dir / scene_id / f"masks/final/{name}_final.png"))
+        if self.store.device_mask:  # the mask as the store decodes it, in its slot where the device path serves the file
+            mask = self.store.decode_mask(self._mask_f(scene_id, time_id), (h, w), into=(self.store.scenes.get(scene_id), time_id))
+        else:
+            mask = resize(np.array(PIL.Image.open(self._mask_f(scene_id, time_id))), h, w, PIL.Image.Resampling.NEAREST)
         depth = p.load_depth(time_id, cam_id)
         if depth.dtype == np.float64:
             raise ValueError(f"{p.depth_path(time_id, cam_id)}: the depth times the scene's scale is float64; resident=True keeps "
                              "float32 depths, and the disk path would take the depth range over the doubles")
-        return raw, resize(m, h, w, PIL.Image.Resampling.NEAREST), resize(depth[..., 0], h, w, PIL.Image.Resampling.NEAREST)
+        return raw, mask, resize(depth[..., 0], h, w, PIL.Image.Resampling.NEAREST)
+
+    def _mask_f(self, scene_id, time_id):
+        """a train frame's final mask file"""
+        name = self.parser_dict[scene_id].get_frame_name(time_id, self.get_train_cam_id(scene_id))
+        return self.mask_data_dir / scene_id / f"masks/final/{name}_final.png"
 
     def _store_rgb(self, p, time_id, cam_id, **kw):
         """``load_rgba(...)[..., :3]`` through the store's ``decode_image``: the same bytes, the missing file's error included"""
@@ -554,8 +566,11 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         tgt_rgb = (self._store_rgb(p, tgt_time_id, tgt_cam_id, target=True) if self.store.device_resize else
                    p.load_rgba(tgt_time_id, tgt_cam_id)[..., :3])
         tgt_shape = tuple(tgt_rgb.shape[:2])
-        covis = p.load_covisible(tgt_time_id, tgt_cam_id, "val")
-        assert covis.shape[:2] == tgt_shape, (covis.shape, tgt_shape)
+        if self.store.device_mask:  # decoded on the device where that path serves the file: no host bytes cross
+            covis = self.store.decode_mask(p.covisible_path(tgt_time_id, tgt_cam_id, "val"))
+        else:
+            covis = p.load_covisible(tgt_time_id, tgt_cam_id, "val")
+        assert tuple(covis.shape[:2]) == tgt_shape, (covis.shape, tgt_shape)
         if tuple(tgt_shape) != shape:
             raise ValueError(f"{scene_id}: target {tgt_frame_name} is {tuple(tgt_shape)}, the scene's tables hold frames of {shape}")
         train = {int(t) for t in info["time_ids"]}
@@ -573,7 +588,12 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
             host["__rgb_tgt"] = torch.from_numpy(np.ascontiguousarray(tgt_rgb))
         else:
             host["rgb_tgt"] = F32(tgt_rgb.astype(np.float32) / 255.0)
-        if as_bytes and covis.ndim == 2 and covis.dtype in (np.bool_, np.uint8):
+        covis_on_device = isinstance(covis, torch.Tensor)  # (device_mask decoded it there: uint8 [H,W])
+        if covis_on_device and not as_bytes:  # (no byte target beside it: the host statement below)
+            covis, covis_on_device = covis.cpu().numpy(), False
+        if covis_on_device:
+            pass
+        elif as_bytes and covis.ndim == 2 and covis.dtype in (np.bool_, np.uint8):
             host["__covisible"] = torch.from_numpy(np.ascontiguousarray(covis).view(np.uint8))
         else:
             host["eval_mask"] = F32((covis > 0).astype(np.float32))[..., None]
@@ -599,11 +619,11 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b),
                           trackers=True, owner=type(self).__name__, depth_range=depth_range,
                           ray_rows=lambda ids: ray_rows([self._cam(scene_id, t, cam_id)["rays"] for t in ids]),
-                          image_path=lambda t: (p.rgb_path(t, cam_id), "rgb"))
+                          image_path=lambda t: (p.rgb_path(t, cam_id), "rgb"), mask_path=lambda t: self._mask_f(scene_id, t))
         if as_bytes:
             from .. import ops
 
-            rgb, mask = ops.item_target(tgt_rgb if on_device else item.pop("__rgb_tgt"), item.pop("__covisible", None))
+            rgb, mask = ops.item_target(tgt_rgb if on_device else item.pop("__rgb_tgt"), covis if covis_on_device else item.pop("__covisible", None))
             item["rgb_tgt"] = rgb
             if mask is not None:
                 item["eval_mask"] = mask

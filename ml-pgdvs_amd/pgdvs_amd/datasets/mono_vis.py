@@ -119,9 +119,10 @@ class MonoVisualizationDataset(Dataset):
     def __init__(self, *, data_root, max_hw, mode, rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
                  vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
-                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
+                 resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False,
+                 device_mask=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
-                               device_entropy=device_entropy, device_png=device_png)
+                               device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
@@ -148,15 +149,21 @@ class MonoVisualizationDataset(Dataset):
         return len(self.valid_fs)
 
     @staticmethod
-    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None, resize_rgb=True):
+    def _mask_f(scene_dir, img_f):
+        return scene_dir / "masks" / "final" / f"{pathlib.Path(img_f).stem}_final.png"
+
+    @staticmethod
+    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None, resize_rgb=True, mask=None):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size; ``raw``: the image file's pixels, where
-        the caller has opened it already; ``resize_rgb`` False (``device_resize``): the image as decoded, the store resizes it"""
+        the caller has opened it already; ``resize_rgb`` False (``device_resize``): the image as decoded, the store resizes it;
+        ``mask`` (``device_mask``): the mask at the target's size as the store decoded it"""
         h, w = tgt_shape
         rgb = np.array(PIL.Image.open(img_f)) if raw is None else raw
         if resize_rgb:
             rgb = resize(rgb, h, w, PIL.Image.Resampling.BOX)
         name = pathlib.Path(img_f).stem
-        mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w, PIL.Image.Resampling.NEAREST)
+        if mask is None:
+            mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w, PIL.Image.Resampling.NEAREST)
         depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
         return rgb, mask, depth
 
@@ -186,8 +193,12 @@ class MonoVisualizationDataset(Dataset):
         if scene is None:
             raw = self.store.decode_image(img_fs[0])  # (device_decode: a JPEG frame comes back on the device)
             scene = self.store.scene(scene_id, len(img_fs), tuple(raw.shape[:2]))
-            self.store.put(scene, 0, *self._decode_frame(scene_dir, img_fs[0], tuple(raw.shape[:2]), raw=raw))
+            self.store.put(scene, 0, *self._decode_frame(scene_dir, img_fs[0], tuple(raw.shape[:2]), raw=raw, mask=self._store_mask(scene_dir, img_fs[0], scene, 0)))
         return scene.h, scene.w
+
+    def _store_mask(self, scene_dir, img_f, scene, f):
+        """``device_mask``: the frame's mask as the store decodes it (in its slot where the device path serves the file); else None"""
+        return self.store.decode_mask(self._mask_f(scene_dir, img_f), (scene.h, scene.w), into=(scene, f)) if self.store.device_mask else None
 
     def _resident_item(self, scene_id, scene_dir, img_fs, shape, all_c2w, all_K, **kw):
         """``resident.build_item`` over this loader's readers and cameras"""
@@ -198,9 +209,10 @@ class MonoVisualizationDataset(Dataset):
 
         def decode(f):  # device_resize: the image as the store decodes it, at the file's size
             raw = self.store.decode_image(img_fs[f], into=(scene, f)) if self.store.device_resize else None
-            return self._decode_frame(scene_dir, img_fs[f], shape, raw=raw, resize_rgb=not self.store.device_resize)
+            return self._decode_frame(scene_dir, img_fs[f], shape, raw=raw, resize_rgb=not self.store.device_resize,
+                                      mask=self._store_mask(scene_dir, img_fs[f], scene, f))
 
-        return build_item(self.store, scene, decode, cams=cams, image_path=lambda f: img_fs[f],
+        return build_item(self.store, scene, decode, cams=cams, image_path=lambda f: img_fs[f], mask_path=lambda f: self._mask_f(scene_dir, img_fs[f]),
                           flow_path=lambda a, b: self._flow_path(scene_dir, img_fs, a, b), owner=type(self).__name__, **kw)
 
     def __getitem__(self, index):

@@ -230,9 +230,9 @@ class NvidiaDynEvaluationDataset(Dataset):
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
                  flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES,
-                 device_resize=False, device_decode=False, device_entropy=False, device_png=False):
+                 device_resize=False, device_decode=False, device_entropy=False, device_png=False, device_mask=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
-                               device_entropy=device_entropy, device_png=device_png)
+                               device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -296,7 +296,8 @@ class NvidiaDynEvaluationDataset(Dataset):
     def _decode_frame(self, scene_id, frame_id, tgt_shape):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
         ``device_resize`` the image as decoded: the store resizes it (``device_decode``: decoded on the device, where the file is
-        a JPEG that path serves, straight into the frame's slot when it has the slot's size)"""
+        a JPEG that path serves, straight into the frame's slot when it has the slot's size); with ``device_mask`` the mask as the
+        store decodes it, in its slot where the device path serves the file"""
         h, w = tgt_shape
         zoe = ()
         if self.use_zoe_depth != "none":  # the prediction and its (scale, shift): the store aligns them per item
@@ -307,7 +308,9 @@ class NvidiaDynEvaluationDataset(Dataset):
         img_f = self._src_img_f(scene_id, frame_id)
         rgb = (self.store.decode_image(img_f, into=(self.store.scenes.get(scene_id), frame_id)) if self.store.device_resize else
                self._read_src_rgb(img_f, h, w))
-        return (rgb, self._read_mask(scene_id, frame_id, h, w), depth, *zoe)
+        mask = (self.store.decode_mask(self._mask_f(scene_id, frame_id), (h, w), into=(self.store.scenes.get(scene_id), frame_id))
+                if self.store.device_mask else self._read_mask(scene_id, frame_id, h, w))
+        return (rgb, mask, depth, *zoe)
 
     def _decode_zoe(self, scene_id, frame_id):
         """(depth_pred float32, (scale, shift) 0-d float64, (model type, principle)) of a frame for its slot of the store:
@@ -336,7 +339,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         if zoe:  # depths and range come from the predictions; the cameras keep _aug_c2w's double inversion
             kw["depths"] = lambda ids, range_cams, rays: self.store.zoe_depths(scene, ids, range_cams, rays, kw["c2w_tgt"])
         return build_item(self.store, scene, lambda f: self._decode_frame(scene_id, f, tgt_shape), cams=cams,
-                          image_path=lambda f: self._src_img_f(scene_id, f),
+                          image_path=lambda f: self._src_img_f(scene_id, f), mask_path=lambda f: self._mask_f(scene_id, f),
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b), owner=type(self).__name__, **kw)
 
     # ------------------------------------------------------------------ ZoeDepth
@@ -385,8 +388,11 @@ class NvidiaDynEvaluationDataset(Dataset):
         hwf, c2w = self._cam_cache[scene_id]
         return hwf.copy(), c2w.copy()
 
+    def _mask_f(self, scene_id, frame_id):
+        return self.mask_data_dir / scene_id / "dense" / "masks" / "final" / f"{frame_id:05d}_final.png"
+
     def _read_mask(self, scene_id, frame_id, tgt_h, tgt_w):
-        m = np.array(PIL.Image.open(self.mask_data_dir / scene_id / "dense" / "masks" / "final" / f"{frame_id:05d}_final.png"))
+        m = np.array(PIL.Image.open(self._mask_f(scene_id, frame_id)))
         return _resize(m, tgt_h, tgt_w, PIL.Image.Resampling.NEAREST)  # True = dynamic
 
     def _read_depth(self, scene_id, frame_id):
@@ -405,7 +411,13 @@ class NvidiaDynEvaluationDataset(Dataset):
         return self.flow_data_dir / scene_id / "dense" / "flows" / f"interval_{k}" / f"{src_frame_id:05d}_{tgt_frame_id:05d}.npz"
 
     def _read_eval_mask(self, scene_id, frame_id, cam_id, h, w):
+        """float32 [h,w,3]; with ``device_mask`` a tensor on the store's device where it serves the file (a grey or 8-bit RGB PNG
+        of the target's size), else this host statement's array"""
         f = self.raw_data_dir / scene_id / "dense" / "mv_masks" / f"{frame_id:05d}" / f"cam{cam_id + 1:02d}.png"
+        if self.store is not None and self.store.device_mask:
+            m = self.store.decode_eval_mask(f, (h, w))
+            if m is not None:
+                return m
         m = np.float32(np.array(PIL.Image.open(f).convert("RGB"))[..., ::-1] > 1e-3)  # channel order as cv2.imread
         return _resize(m, h, w, PIL.Image.Resampling.NEAREST)
 
@@ -512,10 +524,11 @@ class NvidiaDynEvaluationDataset(Dataset):
             tgt = self._source_view(scene_id, tgt_frame_id, all_c2w[tgt_cam_id], all_hwf[tgt_cam_id], tgt_shape,
                                     with_geometry=False, img_f=img_f)
             rgb_tgt = ("rgb_tgt", F32(tgt["rgb"]))
+        eval_mask = self._read_eval_mask(scene_id, tgt_frame_id, tgt_cam_id, raw_h, raw_w)
         item = {
             "scene_id": scene_id,
             rgb_tgt[0]: rgb_tgt[1],
-            "eval_mask": F32(self._read_eval_mask(scene_id, tgt_frame_id, tgt_cam_id, raw_h, raw_w)),
+            "eval_mask": eval_mask if isinstance(eval_mask, torch.Tensor) else F32(eval_mask),  # (device_mask: on the device already)
             "flat_cam_tgt": F32(tgt["flat_cam"]),
             "time_tgt": torch.FloatTensor([tgt_frame_id]),
             "misc": {"scene_id": scene_id, "tgt_frame_id": tgt_frame_id, "tgt_cam_id": tgt_cam_id},
@@ -581,9 +594,10 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
 
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
-                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False):
+                 resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False,
+                 device_mask=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
-                               device_entropy=device_entropy, device_png=device_png)
+                               device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
                          mask_data_dir=mask_data_dir, flow_data_dir=flow_data_dir, max_hw=max_hw, mode=mode,
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,

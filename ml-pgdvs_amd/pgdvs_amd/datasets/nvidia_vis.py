@@ -35,9 +35,9 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_f=None,
                  flow_consist_thres=1.0, vis_center_time=50, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32,
                  device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False,
-                 device_decode=False, device_entropy=False, device_png=False):
+                 device_decode=False, device_entropy=False, device_png=False, device_mask=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
-                               device_entropy=device_entropy, device_png=device_png)
+                               device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["vis"], mode

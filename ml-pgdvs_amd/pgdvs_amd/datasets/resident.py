@@ -30,11 +30,12 @@ GPU store, which writes the float32 depths of all groups and selects the range o
 ``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
 it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
 
-The image input has four options, each building on another.  ``_common.device_input`` is the one statement of these rules,
+The image input has five options, each building on another.  ``_common.device_input`` is the one statement of these rules,
 for the five loaders and for this store alike; the first rule broken, in this order, is refused with what is missing:
 
   device_entropy  needs device_decode
   device_png      needs device_resize (it is independent of device_decode)
+  device_mask     needs device_resize (it is independent of the others)
   device_decode   needs device_resize
   device_resize   needs resident=True, and the store on a GPU
 
@@ -42,9 +43,19 @@ for the five loaders and for this store alike; the first rule broken, in this or
 resizes them on the device straight into the frame's slot (``ops.resample_u8``, Pillow's BOX filter bit for bit); the
 evaluation loaders' target image goes the same way (``expand_target``) and the pure-geometry loader's LANCZOS stack in one
 batched call (``resize_stack``).  An image the device path does not serve (not uint8 [H,W,3], or a size ``ops.resample_plan``
-refuses) takes the host statements.  Masks and depths keep their host NEAREST resize.
+refuses) takes the host statements.  Depths keep their host NEAREST resize, and so do masks unless ``device_mask`` is on.
 
-The other three decode on the device, and ``decode_image`` is their one dispatch: it takes the file's bytes (from
+``device_mask`` (``decode_mask``): a frame's mask file -- a non-interlaced grey or palette PNG of bit depth 1, 2, 4
+or 8 (``ops.png_decode_batch(kinds="mask")``) -- is inflated, unfiltered and unpacked in HIP straight into ``dyn_mask[slot]``, or,
+where the file has another size, gathered there through Pillow's own NEAREST picks (``ops.mask_place``); byte for byte the host
+statement ``resize(np.array(PIL.Image.open(f)), h, w, NEAREST)``, which still takes every other file (16-bit, grey + alpha,
+interlaced, tRNS, damaged, not a PNG ...), errors included.  The loaders name the files (``mask_path``) and ``_fill`` puts the
+missing frames' masks into the same batch as their images when ``device_png`` is on as well -- one launch pair and one wait per
+item fill -- or into one batch of their own.  The DyCheck covisible PNG goes the same way (``decode_mask`` at the file's size,
+then ``ops.item_target``), the NVIDIA evaluation mask through ``decode_eval_mask``.  ``stats["masks_decoded_on_device"]`` and
+``stats["mask_fallbacks"]`` count the outcomes; they exist under the option alone.  Only the float depth file is left to numpy.
+
+Three of the others decode images on the device, and ``decode_image`` is their one dispatch: it takes the file's bytes (from
 ``prefetch_images``' table, else from the file), asks the codec their signature names, counts the outcome, and hands every file
 no codec serves to Pillow as before, errors included.  An image decoded there is byte for byte ``np.array(PIL.Image.open(path))``;
 the store takes it where it takes a host one -- no second upload -- and a frame of the slot's size is decoded straight into its
@@ -105,11 +116,11 @@ _Prefetched = namedtuple("_Prefetched", "data image png_tried", defaults=(None, 
 
 
 class SceneStore:
-    """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``).  The four
+    """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``).  The five
     ``device_*`` keywords (the module's text), or ``device_input``: the loader's checked record of them."""
 
     def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False,
-                 device_decode=False, device_entropy=False, device_png=False, device_input=None):
+                 device_decode=False, device_entropy=False, device_png=False, device_input=None, device_mask=False):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -119,14 +130,16 @@ class SceneStore:
             raise TypeError(f"flow_consist_thres must be a Python number (a NumPy scalar changes the compare's type), got {type(occ_thres)}")
         self.resident_scenes, self.resident_max_bytes, self.occ_thres = int(resident_scenes), int(resident_max_bytes), occ_thres
         self.scenes = OrderedDict()  # key -> _Scene, least recently used first
-        if device_input is None:  # the four keywords themselves: the loaders' one check, in the store's name
+        if device_input is None:  # the five keywords themselves: the loaders' one check, in the store's name
             device_input = _common.device_input("SceneStore", resident=True, device=self.device, device_resize=device_resize, device_decode=device_decode,
-                                                device_entropy=device_entropy, device_png=device_png)
-        self.device_resize, self.device_decode, self.device_entropy, self.device_png = device_input
-        self._prefetched = {}  # (path, channels) -> _Prefetched, from prefetch_images until decode_image hands it out
+                                                device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
+        self.device_resize, self.device_decode, self.device_entropy, self.device_png, self.device_mask = device_input
+        self._prefetched = {}  # (path, channels or "mask") -> _Prefetched, from prefetch_images until decode_image / decode_mask hands it out
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
                       "targets_resized_on_device": 0, "zoe_files_read": 0, "frames_decoded_on_device": 0, "targets_decoded_on_device": 0,
                       "jpeg_fallbacks": 0, "scans_decoded_on_device": 0, "entropy_fallbacks": 0, "png_decoded_on_device": 0, "png_fallbacks": 0}
+        if self.device_mask:  # (counted under the option alone: without it the record is the one it was)
+            self.stats.update(masks_decoded_on_device=0, mask_fallbacks=0)
 
     @property
     def nbytes(self):
@@ -176,11 +189,13 @@ class SceneStore:
             raise ValueError(f"frame ids {[int(f) for f in frame_ids]} outside the scene's {scene.first_id}..{scene.first_id + scene.n_frames - 1}")
         return slots
 
-    def _fill(self, scene, frame_ids, decode, image_path=None):
+    def _fill(self, scene, frame_ids, decode, image_path=None, mask_path=None):
         missing = [f for f in sorted(set(frame_ids)) if not scene.filled[f - scene.first_id]]
-        if self.device_png and image_path is not None and len(missing) > 1:  # the item's missing frames in one launch, one wait
-            paths = [image_path(f) for f in missing]
-            self.prefetch_images([p if isinstance(p, tuple) else (p, "file") for p in paths], [(scene, f) for f in missing])
+        images = self.device_png and image_path is not None
+        masks = [(mask_path(f), (scene.h, scene.w), (scene, f)) for f in missing] if self.device_mask and mask_path is not None else []
+        if masks or (images and len(missing) > 1):  # the item's missing frames, images and masks, in one launch, one wait
+            paths = [image_path(f) for f in missing] if images else []
+            self.prefetch_images([p if isinstance(p, tuple) else (p, "file") for p in paths], [(scene, f) for f in missing], masks=masks)
         try:
             for f in missing:
                 self.put(scene, f, *decode(f))
@@ -194,9 +209,11 @@ class SceneStore:
             return None
         return into[0].rgb[self.slots(into[0], [into[1]])[0]]
 
-    def _png_images(self, files, channels):
+    def _png_images(self, files, channels, masks=()):
         """the images of the PNG ``files`` = [(bytes, into)]: each walked once, its slot picked, and those the host side serves
-        decoded in ONE batched launch with one wait; per file None where the host refuses it or the device gives it up"""
+        decoded in ONE batched launch with one wait; per file None where the host refuses it or the device gives it up.
+        ``masks`` = [(bytes, shape or None, into)] (``device_mask``): the mask files of the same launch and wait; then the
+        pair (images, masks), a mask at ``shape`` (None: the file's size), in its slot where ``into`` names one"""
         from .. import ops
 
         images, batch = [None] * len(files), []
@@ -205,22 +222,47 @@ class SceneStore:
             info = parsed[0]
             if info is not None:
                 batch.append((i, data, parsed, self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])))
+        placed, slots = [None] * len(masks), [None] * len(masks)
+        for k, (data, shape, into) in enumerate(masks):
+            parsed = ops.png_parse(data, kinds=("mask",)) if ops.image_kind(data) == "png" else (None, "not a PNG file")
+            info = parsed[0]
+            if info is not None:
+                if shape is not None and into is not None and into[0] is not None and tuple(shape) == (into[0].h, into[0].w):
+                    slots[k] = into[0].dyn_mask[self.slots(into[0], [into[1]])[0]]
+                same = shape is None or (info["height"], info["width"]) == tuple(shape)
+                batch.append((len(files) + k, data, parsed, slots[k] if same else None))
         if batch:
+            kw = {"kinds": ("colour", "mask")} if masks else {}
             got = ops.png_decode_batch([b[1] for b in batch], outs=[b[3] for b in batch], channels=channels, device=self.device, reject_ok=True,
-                                       parsed=[b[2] for b in batch])
+                                       parsed=[b[2] for b in batch], **kw)
             for (i, *_), image in zip(batch, got):
-                images[i] = image
-        return images
+                if i < len(files):
+                    images[i] = image
+                elif image is not None:  # a mask of another size: Pillow's NEAREST picks, gathered on the device
+                    k = i - len(files)
+                    shape = masks[k][1]
+                    placed[k] = image if shape is None or tuple(image.shape) == tuple(shape) else ops.mask_place(image, shape, out=slots[k])
+        return (images, placed) if masks else images
 
-    def prefetch_images(self, paths, intos=None):
+    def prefetch_images(self, paths, intos=None, masks=()):
         """With ``device_png``: the files of ``paths`` (each a path, or (path, channels)) read once, and the PNG files among
         them decoded in ONE batched launch with one wait.  Bytes and outcome are kept for the ``decode_image`` calls that
         follow, which then neither read, parse nor launch again (``_fill`` and ``decode_stack`` drop what is left).  ``intos``:
-        per path None or (scene, frame id), as ``decode_image`` takes it."""
-        if not self.device_png:
+        per path None or (scene, frame id), as ``decode_image`` takes it.  With ``device_mask``: ``masks`` = [(path, shape,
+        into)], the mask files ``decode_mask`` will be asked for, in the same launch and wait as the images (or, without
+        ``device_png``, in one of their own)."""
+        masks = list(masks) if self.device_mask else []
+        if not self.device_png and not masks:
             return
         from .. import ops
 
+        mask_files = []
+        for path, shape, into in masks:
+            key = (str(path), "mask")
+            if key not in self._prefetched:
+                with open(path, "rb") as f:
+                    mask_files.append((key, f.read(), shape, into))
+        paths = paths if self.device_png else []
         intos = [None] * len(paths) if intos is None else intos
         by_mode = {}
         for p, into in zip(paths, intos):
@@ -234,9 +276,16 @@ class SceneStore:
             self._prefetched[key] = _Prefetched(data, None, is_png)
             if is_png:
                 by_mode.setdefault(channels, []).append((key, data, into))
+        if mask_files and not by_mode:
+            by_mode["file"] = []
         for channels, files in by_mode.items():
-            for (key, data, _), image in zip(files, self._png_images([f[1:] for f in files], channels)):
+            got = self._png_images([f[1:] for f in files], channels, [m[1:] for m in mask_files])  # (the masks ride with the first mode)
+            images, placed = got if mask_files else (got, [])
+            for (key, data, _), image in zip(files, images):
                 self._prefetched[key] = _Prefetched(data, image, True)
+            for (key, data, *_), mask in zip(mask_files, placed):
+                self._prefetched[key] = _Prefetched(data, mask, True)
+            mask_files = []
 
     def decode_stack(self, paths):
         """``decode_image`` of every file as host arrays (the pure-geometry loader's stack, which ``resize_stack`` and the
@@ -272,6 +321,42 @@ class SceneStore:
                 return image
         image = np.array(PIL.Image.open(path))
         return image[..., :3] if channels == "rgb" else image
+
+    def decode_mask(self, path, shape=None, into=None):
+        """A mask file's values at ``shape`` (None: the file's size): ``resize(np.array(PIL.Image.open(path)), *shape, NEAREST)``
+        -- the loaders' host statement, which also takes every file the device path does not serve, errors included -- or,
+        under ``device_mask`` and for a non-interlaced grey or palette PNG of bit depth 1, 2, 4 or 8, the same values as a uint8
+        [h,w] tensor on the store's device (bool becomes 0 / 1, as the table keeps it): decoded by
+        ``ops.png_decode_batch(kinds="mask")`` and, where the file has another size, gathered through Pillow's own NEAREST
+        picks (``ops.mask_place``).  ``into`` = (scene or None, frame id): the mask lands in ``scene.dyn_mask[slot]`` itself,
+        which ``put`` then recognises.  One wait, unless ``prefetch_images`` has had the file in its batch."""
+        if self.device_mask:
+            got = self._prefetched.pop((str(path), "mask"), None)
+            if got is None:
+                with open(path, "rb") as f:
+                    got = _Prefetched(f.read())
+            mask = got.image if got.png_tried else self._png_images([], "file", [(got.data, shape, into)])[1][0]
+            self.stats["mask_fallbacks" if mask is None else "masks_decoded_on_device"] += 1
+            if mask is not None:
+                return mask
+        mask = np.array(PIL.Image.open(path))
+        return mask if shape is None else resize(mask, *shape, PIL.Image.Resampling.NEAREST)
+
+    def decode_eval_mask(self, path, shape):
+        """the NVIDIA evaluation mask ``np.float32(np.array(PIL.Image.open(path).convert("RGB"))[..., ::-1] > 1e-3)`` as a float32
+        [h,w,3] tensor on the store's device, where ``device_mask`` serves it: a grey PNG (through the mask path) or an 8-bit RGB
+        one (through the colour path) of exactly ``shape``, expanded by ``ops.mask_place``; else None -- a palette file, another
+        size, anything the decode refuses or gives up -- and the caller's host statement reads the file.  One wait."""
+        from .. import ops
+
+        with open(path, "rb") as f:
+            data = f.read()
+        parsed = ops.png_parse(data, kinds=("colour", "mask")) if ops.image_kind(data) == "png" else (None, "not a PNG file")
+        info, image = parsed[0], None
+        if info is not None and (info["height"], info["width"]) == tuple(shape) and info["channels"] != 4 and not info.get("palette", False):
+            image = ops.png_decode_batch([data], device=self.device, reject_ok=True, parsed=[parsed], kinds=("colour", "mask"))[0]
+        self.stats["mask_fallbacks" if image is None else "masks_decoded_on_device"] += 1
+        return None if image is None else ops.mask_place(image, mode="bgr_f32")
 
     def _decode_png(self, got, into, channels):
         """a PNG file's image on the device, or None where the path refuses the file or gives it up (``png_fallbacks``)"""
@@ -368,8 +453,8 @@ class SceneStore:
                 rgb = resize(rgb, *shape, PIL.Image.Resampling.BOX)  # the host statement
         if plan is None and (not self._is_u8_rgb(rgb) or tuple(rgb.shape) != shape + (3,)):
             raise ValueError(f"frame {f}: image {rgb.dtype} {rgb.shape}, the store keeps uint8 {shape + (3,)}")
-        if mask.dtype not in (np.bool_, np.uint8) or mask.shape != shape:
-            raise ValueError(f"frame {f}: mask {mask.dtype} {mask.shape}, the store keeps bool or uint8 {shape}")
+        if mask.dtype not in (np.bool_, np.uint8, torch.uint8) or tuple(mask.shape) != shape:
+            raise ValueError(f"frame {f}: mask {mask.dtype} {tuple(mask.shape)}, the store keeps bool or uint8 {shape}")
         if depth.shape != shape:
             raise ValueError(f"frame {f}: depth {depth.shape}, expected {shape}")
         if scene.prediction != (scale_shift is not None):
@@ -391,19 +476,23 @@ class SceneStore:
                 scene.rgb[slot].copy_(rgb)
         else:
             scene.rgb[slot].copy_(torch.from_numpy(np.ascontiguousarray(rgb)))
-        scene.dyn_mask[slot].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
+        if isinstance(mask, torch.Tensor):
+            if mask.data_ptr() != scene.dyn_mask[slot].data_ptr():  # (else decode_mask wrote the slot)
+                scene.dyn_mask[slot].copy_(mask)
+        else:
+            scene.dyn_mask[slot].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
         scene.depth[slot].copy_(F32(depth))
         scene.filled[slot] = True
         self.stats["frames_decoded"] += 1
 
-    def views(self, scene, groups, decode, image_path=None):
+    def views(self, scene, groups, decode, image_path=None, mask_path=None):
         """one dict per group ``(frame ids, with_depth)``: rgb, dyn_rgb, static_rgb [n,H,W,3], dyn_mask and (with_depth) depth
         [n,H,W,1], float32 on the store's device; ``decode(frame id) -> (rgb uint8, mask, depth)`` fills missing slots;
         ``image_path(frame id)`` -> the frame's image file (or (file, channels)): with ``device_png`` the missing frames'
-        files are prefetched in one launch"""
+        files are prefetched in one launch; ``mask_path(frame id)`` -> the frame's mask file: with ``device_mask`` in the same one"""
         frame_ids = [int(f) for ids, _ in groups for f in ids]
         groups = [(self.slots(scene, ids), with_depth) for ids, with_depth in groups]  # (checked before anything is decoded)
-        self._fill(scene, frame_ids, decode, image_path)
+        self._fill(scene, frame_ids, decode, image_path, **({"mask_path": mask_path} if self.device_mask and mask_path is not None else {}))
         if scene.prediction and any(with_depth for _, with_depth in groups):
             raise ValueError("a scene in prediction mode holds no depths: zoe_depths aligns its predictions")
         self.stats["items_built"] += 1
@@ -516,7 +605,7 @@ def group_host_entries(group, flat_cams, times=None, n_actual=None):
 
 
 def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner,
-               ray_rows=None, depth_range=None, depths=None, image_path=None):
+               ray_rows=None, depth_range=None, depths=None, image_path=None, mask_path=None):
     """An item of the five loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
     non-tensor entries; ``host``: the host-made tensors (on a GPU store they travel in ONE packed copy, with the groups'
     cameras and times; entries named ``__...`` are the loader's own cargo: they come back in the item, on the device, for
@@ -531,7 +620,8 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
     The NVIDIA evaluation loader's ZoeDepth inputs bring ``depths(ids per group, (K, c2w) of the spatial group or None, rays or
     None) -> ([depth [n,H,W,1] per group], depth_range or None)`` on the store's device (``SceneStore.zoe_depths`` over a
     scene in prediction mode): the store then gathers colours and masks alone, and every depth and the range come from there.
-    ``image_path(frame id)``: the frame's image file, for ``SceneStore.views`` to prefetch under ``device_png``."""
+    ``image_path(frame id)``: the frame's image file, for ``SceneStore.views`` to prefetch under ``device_png``;
+    ``mask_path(frame id)``: its mask file, for the same batch under ``device_mask``."""
     from . import nvidia_eval as NE
 
     dev = store.device
@@ -558,7 +648,8 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
         for side in ("fwd2tgt", "bwd2tgt"):
             add(f"temporal_track_{side}", sel[side], True, sel[side], sel[f"n_actual_{side}"])
     # the range needs the spatial depths even where the item carries none (the visualisation loaders)
-    views = store.views(scene, [(ids, depths is None and (with_depth or name == "spatial")) for name, ids, with_depth in groups], decode, image_path)
+    views = store.views(scene, [(ids, depths is None and (with_depth or name == "spatial")) for name, ids, with_depth in groups], decode, image_path,
+                        mask_path)
     small = pack_to_device(host, dev) if dev is not None else host
     rays = small.pop("__rays", None)
     item = dict(fixed)

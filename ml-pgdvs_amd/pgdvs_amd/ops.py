@@ -1345,13 +1345,24 @@ PNG_MAX_SIZE = 16384
 PNG_CHANNEL_MODES = ("file", "rgb")
 PNG_STATUS_BITS = ("block", "code", "distance", "stored", "data_out", "size", "left_over", "adler", "filter", "not_synchronised")
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+PNG_KINDS = ("colour", "mask")  # what a call admits: 8-bit RGB / RGBA files; grey and palette files of 1, 2, 4 or 8 bits
+PNG_GREY_SCALE = {1: 1, 2: 85, 4: 17, 8: 1}  # what Pillow's array multiplies a grey sample by (depth 1: its bool array)
 
 
-def png_parse(data):
+def _png_kinds(kinds):
+    kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+    if not kinds or any(k not in PNG_KINDS for k in kinds):
+        raise ValueError(f"png_decode: kinds {kinds!r}, expected some of {PNG_KINDS}")
+    return kinds
+
+
+def png_parse(data, kinds=("colour",)):
     """(info, None) of a PNG file ``png_decode`` serves, else (None, reason).  The chunk walk of the host side: signature,
     lengths, every CRC (``zlib.crc32``), chunk order, IHDR, and the two zlib header bytes -- no Huffman work, no inflate.
     ``info`` is ``png_info``'s dict and the file's bytes; a caller that walks a file itself (to size its ``out``) hands the
-    pair back to ``png_decode_batch(parsed=...)`` as it is."""
+    pair back to ``png_decode_batch(parsed=...)`` as it is.  ``kinds``: "colour" admits 8-bit RGB and RGBA files, "mask"
+    grey (colour type 0) and palette (3) files of bit depth 1, 2, 4 or 8, whose info has channels 1 and bit_depth and scale."""
+    kinds = _png_kinds(kinds)
     import struct
     import zlib
 
@@ -1394,16 +1405,19 @@ def png_parse(data):
                 state = 2
         pos += 12 + length
     width, height, depth, colour, compression, filt, interlace = ihdr
-    if depth != 8 or colour not in (2, 6):
-        return None, f"colour type {colour} at bit depth {depth}: 8-bit RGB and RGBA are served"
+    is_mask = "mask" in kinds and colour in (0, 3) and depth in (1, 2, 4, 8)
+    if not is_mask and not ("colour" in kinds and depth == 8 and colour in (2, 6)):
+        served = {"colour": "8-bit RGB and RGBA", "mask": "grey and palette files of 1, 2, 4 or 8 bits"}
+        return None, f"colour type {colour} at bit depth {depth}: {' and '.join(served[k] for k in PNG_KINDS if k in kinds)} are served"
     if compression or filt or interlace:
         return None, "interlaced, or an unknown compression or filter method"
     if not (1 <= width <= PNG_MAX_SIZE and 1 <= height <= PNG_MAX_SIZE):
         return None, f"{width} x {height}: 1 .. {PNG_MAX_SIZE} pixels each way are served"
-    channels = 3 if colour == 2 else 4
+    channels = 1 if is_mask else 3 if colour == 2 else 4
     size = sum(length for _, length in spans)
-    if height * (1 + width * channels) > PNG_INFLATE_MAX_BYTES or size > PNG_INFLATE_MAX_BYTES - 16:
-        return None, f"stream of {size} bytes or image of {height * (1 + width * channels)}: above PNG_INFLATE_MAX_BYTES"
+    inflated = height * (1 + -(-width * channels * depth // 8))
+    if inflated > PNG_INFLATE_MAX_BYTES or size > PNG_INFLATE_MAX_BYTES - 16:
+        return None, f"stream of {size} bytes or image of {inflated}: above PNG_INFLATE_MAX_BYTES"
     if size < 6:
         return None, "truncated: a zlib stream of fewer than 6 bytes"
     head = bytearray()
@@ -1416,39 +1430,53 @@ def png_parse(data):
         return None, "zlib header: not deflate with a window of 32K or less"
     if flg & 0x20:
         return None, "zlib header: preset dictionary"
-    return {"width": width, "height": height, "channels": channels, "stream_bytes": size, "idat": spans, "data": keep}, None
+    info = {"width": width, "height": height, "channels": channels, "stream_bytes": size, "idat": spans, "data": keep}
+    if is_mask:  # the samples leave as bytes: a grey file's as Pillow scales them, a palette file's indices as they are
+        info.update(bit_depth=depth, scale=PNG_GREY_SCALE[depth] if colour == 0 else 1, palette=colour == 3)
+    return info, None
 
 
-def png_info(data):
+def png_info(data, kinds=("colour",)):
     """What the host side reads from a PNG file (bytes-like or a uint8 array; Python only): a dict of width, height, channels
-    (3 or 4), stream_bytes (the zlib stream over all IDAT chunks) and idat (the payloads' (offset, length) in the file) -- or
-    None when ``png_decode`` does not serve the file (``png_refusal`` gives the reason)."""
-    info = png_parse(data)[0]
+    (3 or 4; a mask file: 1, with bit_depth and scale), stream_bytes (the zlib stream over all IDAT chunks) and idat (the
+    payloads' (offset, length) in the file) -- or None when ``png_decode`` does not serve the file (``png_refusal`` gives the
+    reason)."""
+    info = png_parse(data, kinds)[0]
     return None if info is None else {k: v for k, v in info.items() if k != "data"}
 
 
-def png_refusal(data):
+def png_refusal(data, kinds=("colour",)):
     """why ``png_decode`` refuses the file on the host, or None where it does not"""
-    return png_parse(data)[1]
+    return png_parse(data, kinds)[1]
+
+
+def _png_inflated(info):
+    """(the bytes a file inflates to, the bytes of a row behind its filter byte)"""
+    row = -(-info["width"] * info["channels"] * info.get("bit_depth", 8) // 8)
+    return info["height"] * (1 + row), row
 
 
 def png_status_text(status: int) -> str:
     return "+".join(name for bit, name in enumerate(PNG_STATUS_BITS) if status >> bit & 1) or "ok"
 
 
-def _png_batch(infos, out_channels, outs, pin):
+def _png_batch(infos, out_channels, outs, pin, images=False):
     """the batch buffer of ``pgdvs_png_decode``: the stream table, then every file's IDAT payloads joined, 16-byte aligned;
-    ``outs``: per stream (address, row stride in bytes)"""
+    ``outs``: per stream (address, row stride in bytes).  ``images``: the table of ``pgdvs_png_decode_images``, whose entries
+    carry bit depth and scale (a batch with mask files in it)"""
     n = len(infos)
-    offsets, at = [], -(-n * C.sizeof(_lib.PngStream) // 16) * 16
+    entry = _lib.PngImage if images else _lib.PngStream
+    offsets, at = [], -(-n * C.sizeof(entry) // 16) * 16
     for info in infos:
         offsets.append(at)
         at += -(-info["stream_bytes"] // 16) * 16
     buf = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)
     view = buf.numpy()
-    table = (_lib.PngStream * n).from_address(buf.data_ptr())
+    table = (entry * n).from_address(buf.data_ptr())
     for i, info in enumerate(infos):
         src, o = info["data"], offsets[i]
+        if images:
+            table[i].bit_depth, table[i].scale = info.get("bit_depth", 8), info.get("scale", 1)
         for off, length in info["idat"]:
             view[o:o + length] = src[off:off + length]
             o += length
@@ -1459,11 +1487,13 @@ def _png_batch(infos, out_channels, outs, pin):
 
 
 def _png_out(out, shape, device, what):
-    """``out`` after its check: uint8 ``shape`` on ``device`` whose pixels are contiguous (the row stride is free)"""
+    """``out`` after its check: uint8 ``shape`` ([H,W,C], or a mask's [H,W]) on ``device`` whose pixels are contiguous (the row
+    stride is free)"""
     if out is None:
         return torch.empty(shape, dtype=torch.uint8, device=device)
+    row = shape[1] * (shape[2] if len(shape) == 3 else 1)
     ok = (isinstance(out, torch.Tensor) and out.is_cuda and out.device == device and out.dtype == torch.uint8 and tuple(out.shape) == tuple(shape)
-          and out.stride(2) == 1 and out.stride(1) == shape[2] and (out.stride(0) >= shape[1] * shape[2] or shape[0] == 1))
+          and out.stride(-1) == 1 and (len(shape) == 2 or out.stride(1) == shape[2]) and (out.stride(0) >= row or shape[0] == 1))
     if not ok:
         raise ValueError(f"{what} must be a uint8 {tuple(shape)} tensor on {device} with contiguous rows, got {getattr(out, 'dtype', type(out))} "
                          f"{tuple(getattr(out, 'shape', ()))} strides {tuple(out.stride()) if isinstance(out, torch.Tensor) else ()} "
@@ -1471,7 +1501,12 @@ def _png_out(out, shape, device, what):
     return out
 
 
-def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reject_ok: bool = False, sub_bytes: int = 0, reasons=None, stats=None, parsed=None):
+def _png_shape(info, out_channels):
+    return (info["height"], info["width"]) if "bit_depth" in info else (info["height"], info["width"], out_channels)
+
+
+def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reject_ok: bool = False, sub_bytes: int = 0, reasons=None, stats=None, parsed=None,
+                     kinds=("colour",)):
     """``np.array(PIL.Image.open(BytesIO(data)))`` of every PNG file of ``datas`` as uint8 [H,W,C] GPU tensors, byte for byte
     (DESIGN.md 7j).  Served: non-interlaced 8-bit RGB (C = 3) and RGBA (C = 4) files of 1 .. 16384 pixels each way with one
     zlib stream over any number of IDAT chunks; ``channels="rgb"`` gives an RGBA file's first three channels.  The host
@@ -1490,9 +1525,15 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     first such file raises ValueError -- the caller hands the file to Pillow, which decides.  ``stats`` (a list, for tools: it
     waits for the device once more) receives per file None or the workspace's four words: windows, the most synchronisation
     rounds of a window, the most resolve rounds of a window, blocks.  ``parsed``: what ``png_parse`` gave for each file, where the
-    caller has walked them already (``SceneStore``, to find each file's slot): the files are not walked again."""
+    caller has walked them already (``SceneStore``, to find each file's slot): the files are not walked again.
+
+    ``kinds`` (``png_parse``): with "mask" in it, non-interlaced grey and palette files of bit depth 1, 2, 4 or 8 are served as
+    well, each as a uint8 [H,W] tensor, byte for byte ``np.array(PIL.Image.open(...)).astype(np.uint8)``: grey
+    samples as Pillow scales them, a palette file's indices; ``outs``: [H,W] with a free row stride.  A batch with such a file
+    in it goes through ``pgdvs_png_decode_images``, colour files and all: the same one buffer, copy, launch pair and wait."""
     if channels not in PNG_CHANNEL_MODES:
         raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
+    kinds = _png_kinds(kinds)
     datas = list(datas)
     outs = [None] * len(datas) if outs is None else list(outs)
     if len(outs) != len(datas):
@@ -1501,7 +1542,7 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     images = [None] * len(datas)
     walked, parsed = parsed, []
     for i, data in enumerate(datas):
-        info, why[i] = png_parse(data) if walked is None else walked[i]
+        info, why[i] = (png_parse(data) if kinds == ("colour",) else png_parse(data, kinds)) if walked is None else walked[i]
         if info is not None:
             parsed.append((i, info))
         elif not reject_ok:
@@ -1509,17 +1550,20 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     if parsed:
         device = _cuda_device(device, "png_decode: the files are decoded", outs)
         lib = _lib.load()
-        out_ch = [3 if channels == "rgb" else info["channels"] for _, info in parsed]
-        targets = [_png_out(outs[i], (info["height"], info["width"], c), device, f"png_decode: out of file {i}") for (i, info), c in zip(parsed, out_ch)]
-        batch = _png_batch([info for _, info in parsed], out_ch, [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]) for t in targets],
-                           pin=True)
+        out_ch = [3 if channels == "rgb" and info["channels"] != 1 else info["channels"] for _, info in parsed]
+        targets = [_png_out(outs[i], _png_shape(info, c), device, f"png_decode: out of file {i}") for (i, info), c in zip(parsed, out_ch)]
+        with_masks = any("bit_depth" in info for _, info in parsed)  # (a mask file among them: the table with bit depth and scale)
+        batch = _png_batch([info for _, info in parsed], out_ch, [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t[0].numel()) for t in targets],
+                           pin=True, images=with_masks)
         n = len(parsed)
+        query, entry = (("pgdvs_png_images_workspace_bytes", "pgdvs_png_decode_images") if with_masks else
+                        ("pgdvs_png_inflate_workspace_bytes", "pgdvs_png_decode"))
         with _side_stream("png", device, written=targets) as fetch:
             dev = batch.to(device, non_blocking=True)
             status = torch.empty(n, dtype=torch.int32, device=device)
-            ws = _ws(lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n), device)
-            check(lib.pgdvs_png_decode(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(),
-                                       _stream()), "pgdvs_png_decode")
+            ws = _ws(getattr(lib, query)(C.c_void_p(batch.data_ptr()), n), device)
+            check(getattr(lib, entry)(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(), _stream()),
+                  entry)
             words = fetch(status)  # behind the whole batch: its one wait
         if stats is not None:
             rows = ws[:16 * n].cpu().view(torch.int32).view(n, 4).tolist()
@@ -1538,26 +1582,31 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     return images
 
 
-def png_decode(data, out=None, channels: str = "file", device=None, reject_ok: bool = False, sub_bytes: int = 0):
-    """``png_decode_batch`` of one file: the uint8 [H,W,C] GPU tensor, or None under ``reject_ok`` where the file is not served."""
-    return png_decode_batch([data], outs=[out], channels=channels, device=device, reject_ok=reject_ok, sub_bytes=sub_bytes)[0]
+def png_decode(data, out=None, channels: str = "file", device=None, reject_ok: bool = False, sub_bytes: int = 0, kinds=("colour",)):
+    """``png_decode_batch`` of one file: the uint8 [H,W,C] (a mask file: [H,W]) GPU tensor, or None under ``reject_ok`` where the
+    file is not served."""
+    return png_decode_batch([data], outs=[out], channels=channels, device=device, reject_ok=reject_ok, sub_bytes=sub_bytes, kinds=kinds)[0]
 
 
-def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: int = 0):
+def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: int = 0, kinds=("colour",)):
     """The host emulation of the same batch (``pgdvs_png_decode_host``: the kernels' core, windows, rounds and workspace on
     the CPU; for the tests and tools, no GPU): per file None where the host side refuses it, else a dict of status, image
     (uint8 [H,W,C] numpy, meaningful at status 0), inflated (the workspace's inflated rows) and info (windows, most
     synchronisation rounds, most resolve rounds, blocks).  ``guard``: that many bytes of 0xA5 are put around the images, the
-    status words and the workspace, and checked afterwards."""
+    status words and the workspace, and checked afterwards.  ``kinds``: as ``png_decode_batch``; a mask file's image is [H,W]."""
     if channels not in PNG_CHANNEL_MODES:
         raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
+    kinds = _png_kinds(kinds)
     lib = _lib.load()
     results = [None] * len(datas)
-    parsed = [(i, info) for i, info in ((i, png_parse(d)[0]) for i, d in enumerate(datas)) if info is not None]
+    parsed = [(i, info) for i, info in ((i, png_parse(d, kinds)[0]) for i, d in enumerate(datas)) if info is not None]
     if not parsed:
         return results
     n = len(parsed)
-    out_ch = [3 if channels == "rgb" else info["channels"] for _, info in parsed]
+    out_ch = [3 if channels == "rgb" and info["channels"] != 1 else info["channels"] for _, info in parsed]
+    images = any("bit_depth" in info for _, info in parsed)
+    query, entry = (("pgdvs_png_images_workspace_bytes", "pgdvs_png_decode_images_host") if images else
+                    ("pgdvs_png_inflate_workspace_bytes", "pgdvs_png_decode_host"))
 
     def guarded(nbytes, align=1):
         raw = np.full(nbytes + 2 * guard + 256, 0xA5, np.uint8)
@@ -1566,28 +1615,81 @@ def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: in
 
     holds = [guarded(info["height"] * info["width"] * c) for (_, info), c in zip(parsed, out_ch)]
     batch = _png_batch([info for _, info in parsed], out_ch, [(h[1].ctypes.data, info["width"] * c) for h, (_, info), c in zip(holds, parsed, out_ch)],
-                       pin=False)
-    need = lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n)
+                       pin=False, images=images)
+    need = getattr(lib, query)(C.c_void_p(batch.data_ptr()), n)
     if need < 0:
-        check(int(need), "pgdvs_png_inflate_workspace_bytes")
+        check(int(need), query)
     ws_raw, ws = guarded(int(need), 256)
     st_raw, st = guarded(4 * n, 8)
-    check(lib.pgdvs_png_decode_host(C.c_void_p(batch.data_ptr()), C.c_void_p(batch.data_ptr()), batch.numel(), n, sub_bytes, C.c_void_p(st.ctypes.data),
-                                    C.c_void_p(ws.ctypes.data), int(need)), "pgdvs_png_decode_host")
+    check(getattr(lib, entry)(C.c_void_p(batch.data_ptr()), C.c_void_p(batch.data_ptr()), batch.numel(), n, sub_bytes, C.c_void_p(st.ctypes.data),
+                              C.c_void_p(ws.ctypes.data), int(need)), entry)
     for raw, inner in [(ws_raw, ws), (st_raw, st)] + holds:
         lo = inner.ctypes.data - raw.ctypes.data
         if not ((raw[:lo] == 0xA5).all() and (raw[lo + inner.size:] == 0xA5).all()):
             raise AssertionError("pgdvs_png_decode_host wrote outside a buffer")
-    table = (_lib.PngStream * n).from_address(batch.data_ptr())
     at = -(-n * 16 // 256) * 256
     pad16 = lambda v: -(-v // 16) * 16  # noqa: E731
     for k, ((i, info), c, hold) in enumerate(zip(parsed, out_ch, holds)):
-        nbytes = info["height"] * (1 + info["width"] * info["channels"])
-        results[i] = {"status": int(st.view(np.uint32)[k]), "image": hold[1].reshape(info["height"], info["width"], c).copy(),
+        nbytes, row = _png_inflated(info)
+        results[i] = {"status": int(st.view(np.uint32)[k]), "image": hold[1].reshape(_png_shape(info, c)).copy(),
                       "inflated": ws[at:at + nbytes].copy(), "info": tuple(int(v) for v in ws[16 * k:16 * k + 16].view(np.uint32))}
-        at += pad16(nbytes) + pad16(info["width"] * info["channels"])
-    del table
+        at += pad16(nbytes) + pad16(row)
     return results
+
+
+MASK_PLACE_MODES = {"u8": 0, "bgr_f32": 1}  # PGDVS_MASK_PLACE_*
+_nearest_maps = {}  # ((h, w), (H, W), device) -> int32 [H,W] on the device: Pillow's NEAREST picks
+
+
+def nearest_map(src_hw, dst_hw, device):
+    """int32 [H,W] on ``device``: the index y' * w + x' of the source pixel Pillow's NEAREST resize of an [h,w] image to [H,W]
+    picks for every output pixel -- taken from Pillow itself, by resizing the indices (``_common.resize_nearest_f64``'s way),
+    once per size pair and device"""
+    import PIL.Image
+
+    key = (tuple(int(v) for v in src_hw), tuple(int(v) for v in dst_hw), str(device))
+    got = _nearest_maps.get(key)
+    if got is None:
+        (h, w), (H, W) = key[:2]
+        idx = np.arange(h * w, dtype=np.int32).reshape(h, w)
+        picks = np.array(PIL.Image.fromarray(idx).resize((W, H), resample=PIL.Image.Resampling.NEAREST))
+        host = torch.empty(picks.shape, dtype=torch.int32, pin_memory=True)  # (pinned: the copy is asynchronous, nothing waits)
+        host.copy_(torch.from_numpy(np.ascontiguousarray(picks, dtype=np.int32)))
+        got = _nearest_maps[key] = host.to(device, non_blocking=True)
+    return got
+
+
+def mask_place(src, shape=None, mode: str = "u8", out=None):
+    """A decoded mask into its place (``pgdvs_mask_place``; include/pgdvs_hip.h): ``src`` uint8 [h,w] or [h,w,C] on the GPU
+    (pixels contiguous, the row stride free).  ``mode="u8"`` (C = 1): uint8 [H,W] = Pillow's NEAREST resize of ``src`` to
+    ``shape`` (default: its own size), byte for byte, through ``nearest_map``; ``out``: a uint8 [H,W] tensor with a free row
+    stride, e.g. a frame's slot of the resident store.  ``mode="bgr_f32"`` (C = 1 or 3): float32 [H,W,3] =
+    ``np.float32(np.array(image.convert("RGB"))[..., ::-1] > 1e-3)`` of a grey or RGB mask file at its own size.  One launch
+    on the current stream; does not synchronise (a size pair's map is uploaded once, without a wait)."""
+    if mode not in MASK_PLACE_MODES:
+        raise ValueError(f"mask_place: mode {mode!r}, expected one of {tuple(MASK_PLACE_MODES)}")
+    ok = isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.ndim in (2, 3) and src.numel() > 0
+    if ok:
+        c = src.shape[2] if src.ndim == 3 else 1
+        ok = (src.stride(-1) == 1 and (src.ndim == 2 or src.stride(1) == c) and (src.stride(0) >= src.shape[1] * c or src.shape[0] == 1) and
+              (c == 1 or (c == 3 and mode == "bgr_f32")))
+    if not ok:
+        raise ValueError(f"mask_place: src must be a uint8 [h,w] or [h,w,C] GPU tensor with contiguous pixels (C = 3: mode 'bgr_f32' alone), got "
+                         f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+    h, w = src.shape[:2]
+    H, W = (h, w) if shape is None else (int(shape[0]), int(shape[1]))
+    if mode == "bgr_f32" and (H, W) != (h, w):
+        raise ValueError(f"mask_place: mode 'bgr_f32' keeps the size, got {(h, w)} -> {(H, W)}")
+    index = None if (H, W) == (h, w) else nearest_map((h, w), (H, W), src.device)
+    if mode == "u8":
+        out = _png_out(out, (H, W), src.device, "mask_place: out")
+        stride = out.stride(0) if H > 1 else W
+    else:
+        out = _out(out, (H, W, 3), torch.float32, src.device, "mask_place: out")
+        stride = W * 12
+    check(_lib.load().pgdvs_mask_place(_ptr(src), h, w, c, src.stride(0) if h > 1 else w * c, None if index is None else _ptr(index), H, W,
+                                       MASK_PLACE_MODES[mode], _ptr(out), stride, _stream()), "pgdvs_mask_place")
+    return out
 
 
 def _flow_pair(a, b, names, what):
