@@ -1162,22 +1162,32 @@ int pgdvs_jpeg_scan_decode(const void *prepared_host, const void *prepared, int6
 int pgdvs_jpeg_scan_decode_host(const void *prepared_host, const void *prepared, int64_t prepared_bytes, int16_t *coef, int64_t coef_bytes,
                                 uint32_t *status, void *workspace, int64_t workspace_bytes);
 
-/* PNG frames read on the device (csrc/png_inflate_core.h: the inflate core; csrc/png_inflate.hip and csrc/png_unfilter.hip:
- * the kernels; csrc/png_decode_host.cpp: the host emulation): the zlib stream of a non-interlaced 8-bit RGB or RGBA file is
- * inflated, checked against its Adler-32 and unfiltered into uint8 [H,W,out_channels], byte for byte what a PNG reader
+/* PNG frames and mask files read on the device (csrc/png_inflate_core.h: the inflate core; csrc/png_inflate.hip and
+ * csrc/png_unfilter.hip: the kernels; csrc/png_decode_host.cpp: the host emulation): the zlib stream of a non-interlaced file
+ * is inflated, checked against its Adler-32 and unfiltered into uint8 [H,W,out_channels], byte for byte what a PNG reader
  * gives.  The host parses the chunks (Python: ops.png_info) and does no Huffman work; a launch takes a BATCH of streams, one
  * workgroup each.
- * The batch buffer: a table of nstreams pgdvs_png_stream, padded to 16 bytes, then the streams, each at a 16-byte aligned
+ * The batch buffer: a table of nstreams pgdvs_png_image, padded to 16 bytes, then the streams, each at a 16-byte aligned
  * `offset` from the buffer's start with `size` bytes (the two zlib header bytes, which the caller has checked -- deflate,
  * a window of at most 32K, no preset dictionary --, the deflate blocks and the four Adler bytes), padded to a multiple of 4
- * bytes.  height, width: 1 .. 16384; channels: the file's, 3 or 4; out_channels: 3 (an RGBA file's alpha is dropped) or
- * `channels`; out / row_stride: the image's first byte and the bytes between rows, row_stride >= width * out_channels, any
- * alignment.  height * (1 + width * channels) and size stay at or below PGDVS_PNG_INFLATE_MAX_BYTES: positions fit 32 bits.
+ * bytes.  height, width: 1 .. 16384; out / row_stride: the image's first byte and the bytes between rows, row_stride >=
+ * width * out_channels, any alignment.  An entry is one of two, and both may share a batch:
+ *   a COLOUR stream  an 8-bit RGB or RGBA file.  channels: the file's, 3 or 4; out_channels: 3 (an RGBA file's alpha is
+ *                    dropped) or `channels`; bit_depth 8 and scale 1, stated.
+ *   a ONE-CHANNEL stream  a file of colour type 0 (grey) or 3 (palette; its indices, the palette is never applied) -- the mask
+ *                    files.  channels = out_channels = 1, bit_depth 1, 2, 4 or 8 and scale >= 1 with
+ *                    scale * (2^bit_depth - 1) <= 255: out is uint8 [H,W], every sample times scale (Pillow's array of a grey
+ *                    file: scale 1, 85, 17, 1 at depth 1, 2, 4, 8; of a palette file: 1).  Below 8 bits a row is
+ *                    ceil(width * bit_depth / 8) bytes behind its filter byte, the filters work on those bytes, each
+ *                    reconstructed byte gives 8 / bit_depth pixels from its most significant bits on, and pixels at
+ *                    x >= width are dropped whatever the padding bits hold.
+ * The inflated size, height * (1 + ceil(width * channels * bit_depth / 8)), and size stay at or below
+ * PGDVS_PNG_INFLATE_MAX_BYTES: positions fit 32 bits.
  * pgdvs_png_decode: batch_host: HOST, the buffer as filled (only its table is read, and checked: the launches follow from
  * it alone); batch: DEVICE, a copy of the same batch_bytes bytes, 16-byte aligned; sub_bytes: 0 for
  * PGDVS_PNG_INFLATE_SUB_BYTES, else a multiple of 4 in 8 .. 1024; status: DEVICE, nstreams words; workspace: DEVICE, 256-byte
  * aligned, >= pgdvs_png_inflate_workspace_bytes(table, nstreams) (-1 for a table it refuses).  Two launches on `stream`, no
- * host synchronisation.  status[i] is 0 only if stream i inflated to exactly height * (1 + width * channels) bytes, the bytes
+ * host synchronisation.  status[i] is 0 only if stream i inflated to exactly its inflated size, the bytes
  * behind its final block were exactly the four of the Adler-32 of those bytes, and every row's filter byte was 0 .. 4; else
  * PGDVS_PNG_* bits say what was met (_BLOCK: block type 3, a length set that is over-subscribed or incomplete as zlib judges
  * it, a bad repeat, no end-of-block code; _CODE: a code the table lacks, length symbols 286 / 287, distance symbols 30 / 31;
@@ -1201,30 +1211,6 @@ int pgdvs_jpeg_scan_decode_host(const void *prepared_host, const void *prepared,
 #define PGDVS_PNG_ADLER 128
 #define PGDVS_PNG_FILTER 256
 #define PGDVS_PNG_NOT_SYNCHRONISED 512
-typedef struct pgdvs_png_stream {
-  int64_t offset, size;
-  int32_t height, width, channels, out_channels;
-  int64_t row_stride;
-  void *out;
-} pgdvs_png_stream;
-int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_stream *streams, int32_t nstreams);
-int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
-                     void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
-int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
-                          uint32_t *status, void *workspace, int64_t workspace_bytes);
-
-/* Mask files read on the device: the same batch with a table of pgdvs_png_image, which adds the sample format to
- * pgdvs_png_stream's fields (same meaning, same limits).  An entry is either a colour stream as above (channels 3 or 4,
- * bit_depth 8, scale 1) or a ONE-CHANNEL stream -- a non-interlaced file of colour type 0 (grey) or 3 (palette; its indices,
- * the palette is never applied) -- with channels = out_channels = 1, bit_depth 1, 2, 4 or 8 and scale >= 1 with
- * scale * (2^bit_depth - 1) <= 255: out is uint8 [H,W], every sample times scale (Pillow's array of a grey file: scale 1, 85,
- * 17, 1 at depth 1, 2, 4, 8; of a palette file: 1).  Below 8 bits a row is ceil(width * bit_depth / 8) bytes behind its filter
- * byte, the filters work on those bytes, each reconstructed byte gives 8 / bit_depth pixels from its most significant bits
- * on, and pixels at x >= width are dropped whatever the padding bits hold.  The inflated size is
- * height * (1 + ceil(width * channels * bit_depth / 8)).  The table is padded to 16 bytes; colour and mask streams may share
- * a batch.  Everything else -- the buffers, sub_bytes, status bits, the two launches without a host synchronisation, what is
- * read and written whatever the bytes hold, the workspace's first words, the host twin -- is pgdvs_png_decode's, and the three
- * older entry points are these over a table of pgdvs_png_stream. */
 typedef struct pgdvs_png_image {
   int64_t offset, size;
   int32_t height, width, channels, out_channels;
@@ -1232,11 +1218,11 @@ typedef struct pgdvs_png_image {
   void *out;
   int32_t bit_depth, scale;
 } pgdvs_png_image;
-int64_t pgdvs_png_images_workspace_bytes(const pgdvs_png_image *images, int32_t nstreams);
-int pgdvs_png_decode_images(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
-                            void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
-int pgdvs_png_decode_images_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
-                                 uint32_t *status, void *workspace, int64_t workspace_bytes);
+int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_image *streams, int32_t nstreams);
+int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                     void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream);
+int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
+                          uint32_t *status, void *workspace, int64_t workspace_bytes);
 
 /* A decoded mask into its place (csrc/mask_place.hip): one gather over src uint8 [h,w,C] on the DEVICE, src_row_stride bytes
  * between its rows (>= w * C), pixels contiguous.  map: nullptr (then H = h and W = w: pixel (y, x) comes from (y, x)), or

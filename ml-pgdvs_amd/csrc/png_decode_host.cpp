@@ -1,7 +1,6 @@
 // The host side of the PNG reader's C ABI: the workspace size and pgdvs_png_decode_host, the emulation of the kernels of
 // csrc/png_inflate.hip and csrc/png_unfilter.hip over csrc/png_inflate_core.h.  include/pgdvs_hip.h states the contract.
 //
-// Both table layouts (pgdvs_png_stream, pgdvs_png_image) go through the one walk below: pnginf::Table reads either.
 // Plain C++: no HIP, no GPU, nothing of the rest of the library but set_error -- tools/png_inflate_fuzz.cpp builds this file
 // alone with the host compiler and its sanitizers.  The emulation runs every step of the core for thread 0 .. kThreads - 1
 // where the kernel runs it on its threads and puts a barrier: the same windows, the same rounds (a round reads what the
@@ -22,7 +21,6 @@ namespace {
 namespace pi = pgdvs::pnginf;
 using pgdvs::set_error;
 
-static_assert(sizeof(pgdvs_png_stream) == sizeof(pi::Stream), "pgdvs_png_stream and pnginf::Stream are one layout");
 static_assert(sizeof(pgdvs_png_image) == sizeof(pi::Image) && sizeof(pi::Image) % 8 == 0, "pgdvs_png_image and pnginf::Image are one layout");
 
 // one stream through the team's walk; returns the status bits
@@ -158,37 +156,41 @@ uint32_t unfilter(const pi::Image &st, const uint8_t *rows, uint8_t *carry) {
   return err;
 }
 
-int64_t workspace_bytes(const char *who, const pi::Table &t) {
+}  // namespace
+
+#define PGDVS_HOST_API extern "C" __attribute__((visibility("default")))
+
+PGDVS_HOST_API int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_image *streams, int32_t nstreams) {
+  const pi::Table t = {reinterpret_cast<const pi::Image *>(streams), nstreams};
   if (t.base == nullptr || t.n < 1 || t.n > 65535) {
-    set_error("%s: null table or a stream count outside 1 .. 65535", who);
+    set_error("pgdvs_png_inflate_workspace_bytes: null table or a stream count outside 1 .. 65535");
     return -1;
   }
   for (int32_t i = 0; i < t.n; ++i)
-    if (const char *why = pi::check_format(t, pi::at(t, i))) {
-      set_error("%s: stream %d: %s", who, i, why);
+    if (const char *why = pi::check_format(pi::at(t, i))) {
+      set_error("pgdvs_png_inflate_workspace_bytes: stream %d: %s", i, why);
       return -1;
     }
   return pi::up(pi::work_offset(t, t.n), 256);
 }
 
-// both host entries: `entry` = the bytes of a table entry
-int decode_host(const char *who, int32_t entry, const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
-                uint32_t *status, void *workspace, int64_t workspace_bytes) {
+PGDVS_HOST_API int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                                         void *workspace, int64_t workspace_bytes) {
   if (batch_host == nullptr || batch == nullptr || status == nullptr || workspace == nullptr || (reinterpret_cast<uintptr_t>(batch) & 7) != 0 ||
       (reinterpret_cast<uintptr_t>(batch_host) & 7) != 0 || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0) {
-    set_error("%s: null pointer, or a buffer that is not 8-byte aligned", who);
+    set_error("pgdvs_png_decode_host: null pointer, or a buffer that is not 8-byte aligned");
     return -1;
   }
   if (sub_bytes == 0) sub_bytes = pi::kDefaultSubBytes;
-  const pi::Table t = {static_cast<const uint8_t *>(batch_host), nstreams, entry};
-  if (const char *why = nstreams >= 1 && batch_bytes >= (int64_t)nstreams * entry ? pi::check_streams(t, batch_bytes, sub_bytes)
-                                                                                  : "the batch buffer is shorter than its table") {
-    set_error("%s: %s", who, why);
+  const pi::Table t = {static_cast<const pi::Image *>(batch_host), nstreams};
+  if (const char *why = nstreams >= 1 && batch_bytes >= (int64_t)nstreams * (int64_t)sizeof(pi::Image) ? pi::check_streams(t, batch_bytes, sub_bytes)
+                                                                                                      : "the batch buffer is shorter than its table") {
+    set_error("pgdvs_png_decode_host: %s", why);
     return -1;
   }
   const int64_t need = pi::up(pi::work_offset(t, nstreams), 256);
   if (workspace_bytes < need) {
-    set_error("%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
+    set_error("pgdvs_png_decode_host: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
     return -1;
   }
   uint8_t *ws = static_cast<uint8_t *>(workspace);
@@ -206,27 +208,4 @@ int decode_host(const char *who, int32_t entry, const void *batch_host, const vo
   }
   delete S;
   return 0;
-}
-
-}  // namespace
-
-#define PGDVS_HOST_API extern "C" __attribute__((visibility("default")))
-
-PGDVS_HOST_API int64_t pgdvs_png_inflate_workspace_bytes(const pgdvs_png_stream *streams, int32_t nstreams) {
-  return workspace_bytes("pgdvs_png_inflate_workspace_bytes", {reinterpret_cast<const uint8_t *>(streams), nstreams, (int32_t)sizeof(pi::Stream)});
-}
-
-PGDVS_HOST_API int64_t pgdvs_png_images_workspace_bytes(const pgdvs_png_image *images, int32_t nstreams) {
-  return workspace_bytes("pgdvs_png_images_workspace_bytes", {reinterpret_cast<const uint8_t *>(images), nstreams, (int32_t)sizeof(pi::Image)});
-}
-
-PGDVS_HOST_API int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
-                                         void *workspace, int64_t workspace_bytes) {
-  return decode_host("pgdvs_png_decode_host", (int32_t)sizeof(pi::Stream), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace, workspace_bytes);
-}
-
-PGDVS_HOST_API int pgdvs_png_decode_images_host(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
-                                                uint32_t *status, void *workspace, int64_t workspace_bytes) {
-  return decode_host("pgdvs_png_decode_images_host", (int32_t)sizeof(pi::Image), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace,
-                     workspace_bytes);
 }

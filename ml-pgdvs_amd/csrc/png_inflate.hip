@@ -187,24 +187,23 @@ __global__ void __launch_bounds__(T) png_inflate_kernel(const pi::Table table, c
 
 using namespace pgdvs;
 
-// both device entries: `entry` = the bytes of a table entry (pnginf::Table)
-static int png_decode(const char *who, int32_t entry, const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes,
-                      uint32_t *status, void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
-  PGDVS_REQUIRE(batch_host && batch && status && workspace, "%s: null pointer", who);
-  PGDVS_REQUIRE(nstreams >= 1 && batch_bytes >= (int64_t)nstreams * entry, "%s: the batch buffer is shorter than its table", who);
+PGDVS_API int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
+                               void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
+  PGDVS_REQUIRE(batch_host && batch && status && workspace, "pgdvs_png_decode: null pointer");
+  PGDVS_REQUIRE(nstreams >= 1 && batch_bytes >= (int64_t)nstreams * (int64_t)sizeof(pi::Image), "pgdvs_png_decode: the batch buffer is shorter than its table");
   if (sub_bytes == 0) sub_bytes = pi::kDefaultSubBytes;
-  const pi::Table table = {static_cast<const uint8_t *>(batch_host), nstreams, entry};
+  const pi::Table table = {static_cast<const pi::Image *>(batch_host), nstreams};
   const char *why = pi::check_streams(table, batch_bytes, sub_bytes);
-  PGDVS_REQUIRE(why == nullptr, "%s: %s", who, why);
+  PGDVS_REQUIRE(why == nullptr, "pgdvs_png_decode: %s", why);
   const int64_t need = pi::up(pi::work_offset(table, nstreams), 256);
   PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(batch) & 15) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
-                "%s: the batch buffer must be 16-byte aligned, status 4-byte", who);
-  PGDVS_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "%s: workspace of %lld bytes, %lld needed (256-byte aligned)", who,
+                "pgdvs_png_decode: the batch buffer must be 16-byte aligned, status 4-byte");
+  PGDVS_REQUIRE(workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "pgdvs_png_decode: workspace of %lld bytes, %lld needed (256-byte aligned)",
                 (long long)workspace_bytes, (long long)need);
   int64_t max_size = 0;
   int max_rows = 0, max_width = 0;
   for (int32_t i = 0; i < nstreams; ++i) {
-    const pi::Image im = pi::at(table, i);
+    const pi::Image &im = pi::at(table, i);
     max_size = im.size > max_size ? im.size : max_size;
     max_rows = im.height > max_rows ? im.height : max_rows;
     max_width = im.width > max_width ? im.width : max_width;  // (a row of packed samples has no more bytes than pixels)
@@ -213,24 +212,13 @@ static int png_decode(const char *who, int32_t entry, const void *batch_host, co
   hipError_t e = hipMemsetAsync(workspace, 0, (size_t)pi::work_head(nstreams), st);
   if (e == hipSuccess) e = hipMemsetAsync(status, 0, (size_t)nstreams * 4, st);
   if (e != hipSuccess) {
-    set_error("%s: %s", who, hipGetErrorString(e));
+    set_error("pgdvs_png_decode: %s", hipGetErrorString(e));
     return PGDVS_ERR_LAUNCH;
   }
-  const pi::Table dtable = {static_cast<const uint8_t *>(batch), nstreams, entry};
+  const pi::Table dtable = {static_cast<const pi::Image *>(batch), nstreams};
   // (a window without a header uses at least 10 bits together with the iteration in front of it: 2 * size + 2 iterations bound the walk)
   PGDVS_LAUNCH("png_inflate", png_inflate_kernel, dim3((unsigned)nstreams), dim3(T), 0, st, dtable, static_cast<const uint8_t *>(batch),
                static_cast<uint8_t *>(workspace), status, sub_bytes * 8, (int)(2 * max_size + 2));
   if (int rc = png_unfilter_launch(dtable, static_cast<uint8_t *>(workspace), status, max_rows, max_width, st)) return rc;
-  return check_launch(who);
-}
-
-PGDVS_API int pgdvs_png_decode(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
-                               void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
-  return png_decode("pgdvs_png_decode", (int32_t)sizeof(pi::Stream), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace, workspace_bytes, stream);
-}
-
-PGDVS_API int pgdvs_png_decode_images(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t nstreams, int32_t sub_bytes, uint32_t *status,
-                                      void *workspace, int64_t workspace_bytes, pgdvs_stream_t stream) {
-  return png_decode("pgdvs_png_decode_images", (int32_t)sizeof(pi::Image), batch_host, batch, batch_bytes, nstreams, sub_bytes, status, workspace,
-                    workspace_bytes, stream);
+  return check_launch("pgdvs_png_decode");
 }

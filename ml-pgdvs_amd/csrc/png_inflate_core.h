@@ -55,31 +55,22 @@ constexpr uint32_t kInvalid = 0xFFFFFFFFu, kStall = 0xFFFFFFFEu, kEob = 0x800000
 constexpr uint32_t kStBlock = 1, kStCode = 2, kStDistance = 4, kStStored = 8, kStDataOut = 16, kStSize = 32, kStLeftOver = 64, kStAdler = 128,
                    kStFilter = 256, kStNotSynchronised = 512;
 
-// One stream of a batch, as the caller states it (pgdvs_png_stream in include/pgdvs_hip.h, field for field).
-struct Stream {
+// One stream of a batch, as the caller states it (pgdvs_png_image in include/pgdvs_hip.h, field for field): 8-bit colour
+// (channels 3 or 4, bit_depth 8, scale 1), or one channel of bit_depth 1, 2, 4 or 8 -- grey or palette indices -- whose
+// samples leave as bytes, times `scale`.
+struct Image {
   int64_t offset, size;  // the zlib stream (header and Adler-32 included) in the batch buffer, offset a multiple of 16
   int32_t height, width, channels, out_channels;
   int64_t row_stride;    // bytes between two rows of out
   uint64_t out;          // address of the image's first byte
-};
-// The same with the sample format (pgdvs_png_image, field for field): 8-bit colour (channels 3 or 4, scale 1), or one
-// channel of bit_depth 1, 2, 4 or 8 -- grey or palette indices -- whose samples leave as bytes, times `scale`.
-struct Image : Stream {
   int32_t bit_depth, scale;
 };
-// A batch's table: nstreams entries of `entry` bytes, sizeof(Stream) (every stream 8-bit colour) or sizeof(Image).
+// A batch's table: n entries at the batch buffer's start.
 struct Table {
-  const uint8_t *base;
-  int32_t n, entry;
+  const Image *base;
+  int32_t n;
 };
-PGDVS_PNG_HD Image at(const Table &t, int32_t i) {
-  const uint8_t *p = t.base + (int64_t)i * t.entry;
-  Image im;
-  static_cast<Stream &>(im) = *reinterpret_cast<const Stream *>(p);
-  im.bit_depth = 8, im.scale = 1;
-  if (t.entry == (int32_t)sizeof(Image)) im.bit_depth = reinterpret_cast<const Image *>(p)->bit_depth, im.scale = reinterpret_cast<const Image *>(p)->scale;
-  return im;
-}
+PGDVS_PNG_HD const Image &at(const Table &t, int32_t i) { return t.base[i]; }
 
 inline int64_t up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 // a row's bytes behind its filter byte: samples below a byte are packed, the last byte padded
@@ -100,9 +91,9 @@ PGDVS_PNG_HD int64_t work_offset(const Table &t, int32_t i) {
 PGDVS_PNG_HD int64_t carry_offset(const Table &t, int32_t i) { return work_offset(t, i) + pad16(inflated_bytes(at(t, i))); }
 
 // an image's size and sample format alone (the workspace query's check); nullptr = fine, else why not
-inline const char *check_format(const Table &t, const Image &s) {
+inline const char *check_format(const Image &s) {
   if (s.height < 1 || s.width < 1 || s.height > kMaxSide || s.width > kMaxSide) return "image size out of range";
-  if (s.channels == 1 && t.entry == (int32_t)sizeof(Image)) {
+  if (s.channels == 1) {
     if (s.bit_depth != 1 && s.bit_depth != 2 && s.bit_depth != 4 && s.bit_depth != 8) return "one channel at bit depth 1, 2, 4 or 8";
     if (s.scale < 1 || (int64_t)s.scale * ((1 << s.bit_depth) - 1) > 255) return "a sample scale that leaves the byte";
   } else {
@@ -118,11 +109,11 @@ inline const char *check_streams(const Table &t, int64_t batch_bytes, int32_t su
   const int32_t n = t.n;
   if (n < 1 || n > 65535) return "1 .. 65535 streams";
   if (sub_bytes < kMinSubBytes || sub_bytes > kMaxSubBytes || sub_bytes % 4) return "subsequence size out of range";
-  const int64_t table = up((int64_t)n * t.entry, 16);
+  const int64_t table = up((int64_t)n * (int64_t)sizeof(Image), 16);
   if (batch_bytes < table) return "the batch buffer is shorter than its table";
   for (int32_t i = 0; i < n; ++i) {
     const Image s = at(t, i);
-    if (const char *why = check_format(t, s)) return why;
+    if (const char *why = check_format(s)) return why;
     if (s.out_channels != s.channels && (s.out_channels != 3 || s.channels == 1)) return "out_channels is 3 or the file's";
     if (s.size < 6 || s.size > kMaxBytes - 16) return "stream size out of range";
     if (s.offset < table || s.offset % 16 || s.offset > batch_bytes || up(s.size, 4) > batch_bytes - s.offset) return "stream outside the batch buffer";

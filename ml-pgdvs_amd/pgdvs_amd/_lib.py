@@ -101,17 +101,12 @@ class JpegInfo(C.Structure):
     ]
 
 
-class PngStream(C.Structure):
-    """``pgdvs_png_stream`` (include/pgdvs_hip.h), field for field: one entry of the table at the front of a batch buffer."""
+class PngImage(C.Structure):
+    """``pgdvs_png_image`` (include/pgdvs_hip.h), field for field: one entry of the table at the front of a batch buffer."""
     _fields_ = [
         ("offset", _i64), ("size", _i64), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("out_channels", C.c_int32),
-        ("row_stride", _i64), ("out", _vp),
+        ("row_stride", _i64), ("out", _vp), ("bit_depth", C.c_int32), ("scale", C.c_int32),
     ]
-
-
-class PngImage(C.Structure):
-    """``pgdvs_png_image`` (include/pgdvs_hip.h), field for field: ``PngStream`` with the sample format."""
-    _fields_ = PngStream._fields_ + [("bit_depth", C.c_int32), ("scale", C.c_int32)]
 
 
 class JpegScanHeader(C.Structure):
@@ -191,9 +186,6 @@ SIGNATURES.update({
     "pgdvs_png_inflate_workspace_bytes": (_i64, [_vp, C.c_int32]),
     "pgdvs_png_decode": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp]),
     "pgdvs_png_decode_host": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64]),
-    "pgdvs_png_images_workspace_bytes": (_i64, [_vp, C.c_int32]),
-    "pgdvs_png_decode_images": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp]),
-    "pgdvs_png_decode_images_host": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64]),
     "pgdvs_mask_place": (_i, [_vp, C.c_int32, C.c_int32, C.c_int32, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),

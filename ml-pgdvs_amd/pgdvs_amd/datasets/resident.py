@@ -113,6 +113,9 @@ class _Scene:
 # a file ``prefetch_images`` read, until the one ``decode_image`` that takes it: its bytes, what the PNG path decoded (None: refused,
 # given up, or not a PNG) and whether that path has had its turn
 _Prefetched = namedtuple("_Prefetched", "data image png_tried", defaults=(None, False))
+# one file of a ``_png_decode`` batch: its bytes; "file" or "rgb" (an image, read with these ``channels``) or "mask"; a mask's wanted
+# shape (None: the file's size); ``into`` = (scene or None, frame id), as ``decode_image`` and ``decode_mask`` take it
+_PngRequest = namedtuple("_PngRequest", "data kind shape into")
 
 
 class SceneStore:
@@ -209,40 +212,44 @@ class SceneStore:
             return None
         return into[0].rgb[self.slots(into[0], [into[1]])[0]]
 
-    def _png_images(self, files, channels, masks=()):
-        """the images of the PNG ``files`` = [(bytes, into)]: each walked once, its slot picked, and those the host side serves
-        decoded in ONE batched launch with one wait; per file None where the host refuses it or the device gives it up.
-        ``masks`` = [(bytes, shape or None, into)] (``device_mask``): the mask files of the same launch and wait; then the
-        pair (images, masks), a mask at ``shape`` (None: the file's size), in its slot where ``into`` names one"""
+    def _png_decode(self, requests):
+        """The PNG files of ``requests`` (``_PngRequest``) on the device, position for position: an image, a mask at its ``shape``
+        (in its slot where ``into`` names one), or None where the host side refuses the file or the device gives it up.  Each
+        file is walked once and its slot picked; then ONE batched launch with one wait per channels mode among the images.  The
+        masks (``device_mask``) ride with the first mode's batch, or make one of their own where there is no image."""
         from .. import ops
 
-        images, batch = [None] * len(files), []
-        for i, (data, into) in enumerate(files):
-            parsed = ops.png_parse(data)  # (the one chunk walk of this file)
+        results, walked = [None] * len(requests), {}  # walked: position -> (what png_parse gave, the decode's out, a mask's slot)
+        for i, r in enumerate(requests):
+            mask = r.kind == "mask"
+            if mask and ops.image_kind(r.data) != "png":
+                continue
+            parsed = ops.png_parse(r.data, kinds=("mask",) if mask else ("colour",))  # (the one chunk walk of this file)
             info = parsed[0]
-            if info is not None:
-                batch.append((i, data, parsed, self._slot_for(into, info["height"], info["width"], 3 if channels == "rgb" else info["channels"])))
-        placed, slots = [None] * len(masks), [None] * len(masks)
-        for k, (data, shape, into) in enumerate(masks):
-            parsed = ops.png_parse(data, kinds=("mask",)) if ops.image_kind(data) == "png" else (None, "not a PNG file")
-            info = parsed[0]
-            if info is not None:
-                if shape is not None and into is not None and into[0] is not None and tuple(shape) == (into[0].h, into[0].w):
-                    slots[k] = into[0].dyn_mask[self.slots(into[0], [into[1]])[0]]
-                same = shape is None or (info["height"], info["width"]) == tuple(shape)
-                batch.append((len(files) + k, data, parsed, slots[k] if same else None))
-        if batch:
-            kw = {"kinds": ("colour", "mask")} if masks else {}
-            got = ops.png_decode_batch([b[1] for b in batch], outs=[b[3] for b in batch], channels=channels, device=self.device, reject_ok=True,
-                                       parsed=[b[2] for b in batch], **kw)
-            for (i, *_), image in zip(batch, got):
-                if i < len(files):
-                    images[i] = image
-                elif image is not None:  # a mask of another size: Pillow's NEAREST picks, gathered on the device
-                    k = i - len(files)
-                    shape = masks[k][1]
-                    placed[k] = image if shape is None or tuple(image.shape) == tuple(shape) else ops.mask_place(image, shape, out=slots[k])
-        return (images, placed) if masks else images
+            if info is None:
+                continue
+            if not mask:
+                slot = self._slot_for(r.into, info["height"], info["width"], 3 if r.kind == "rgb" else info["channels"])
+                walked[i] = (parsed, slot, slot)
+            else:
+                fits = r.shape is not None and r.into is not None and r.into[0] is not None and tuple(r.shape) == (r.into[0].h, r.into[0].w)
+                slot = r.into[0].dyn_mask[self.slots(r.into[0], [r.into[1]])[0]] if fits else None
+                same = r.shape is None or (info["height"], info["width"]) == tuple(r.shape)
+                walked[i] = (parsed, slot if same else None, slot)
+        masks = [i for i in walked if requests[i].kind == "mask"]
+        for channels in list(dict.fromkeys(r.kind for r in requests if r.kind != "mask")) or ["file"]:
+            batch = [i for i in walked if requests[i].kind == channels] + masks
+            if not batch:
+                continue
+            got = ops.png_decode_batch([requests[i].data for i in batch], outs=[walked[i][1] for i in batch], channels=channels, device=self.device,
+                                       reject_ok=True, parsed=[walked[i][0] for i in batch], kinds=("colour", "mask") if masks else ("colour",))
+            for i, image in zip(batch, got):
+                shape = requests[i].shape
+                if image is not None and shape is not None and tuple(image.shape) != tuple(shape):
+                    image = ops.mask_place(image, shape, out=walked[i][2])  # a mask of another size: Pillow's NEAREST picks, gathered on the device
+                results[i] = image
+            masks = []
+        return results
 
     def prefetch_images(self, paths, intos=None, masks=()):
         """With ``device_png``: the files of ``paths`` (each a path, or (path, channels)) read once, and the PNG files among
@@ -256,36 +263,24 @@ class SceneStore:
             return
         from .. import ops
 
-        mask_files = []
-        for path, shape, into in masks:
-            key = (str(path), "mask")
-            if key not in self._prefetched:
-                with open(path, "rb") as f:
-                    mask_files.append((key, f.read(), shape, into))
-        paths = paths if self.device_png else []
+        paths = [p if isinstance(p, tuple) else (p, "file") for p in paths] if self.device_png else []
         intos = [None] * len(paths) if intos is None else intos
-        by_mode = {}
-        for p, into in zip(paths, intos):
-            path, channels = p if isinstance(p, tuple) else (p, "file")
-            key = (str(path), channels)
+        wanted = [(path, channels, None, into) for (path, channels), into in zip(paths, intos)]
+        wanted += [(path, "mask", shape, into) for path, shape, into in masks]
+        keys, requests = [], []
+        for path, kind, shape, into in wanted:
+            key = (str(path), kind)
             if key in self._prefetched:
                 continue
             with open(path, "rb") as f:
                 data = f.read()
-            is_png = ops.image_kind(data) == "png"
+            is_png = kind == "mask" or ops.image_kind(data) == "png"  # (a mask file goes to the one batch function whatever it holds)
             self._prefetched[key] = _Prefetched(data, None, is_png)
             if is_png:
-                by_mode.setdefault(channels, []).append((key, data, into))
-        if mask_files and not by_mode:
-            by_mode["file"] = []
-        for channels, files in by_mode.items():
-            got = self._png_images([f[1:] for f in files], channels, [m[1:] for m in mask_files])  # (the masks ride with the first mode)
-            images, placed = got if mask_files else (got, [])
-            for (key, data, _), image in zip(files, images):
-                self._prefetched[key] = _Prefetched(data, image, True)
-            for (key, data, *_), mask in zip(mask_files, placed):
-                self._prefetched[key] = _Prefetched(data, mask, True)
-            mask_files = []
+                keys.append(key)
+                requests.append(_PngRequest(data, kind, shape, into))
+        for key, request, image in zip(keys, requests, self._png_decode(requests)):
+            self._prefetched[key] = _Prefetched(request.data, image, True)
 
     def decode_stack(self, paths):
         """``decode_image`` of every file as host arrays (the pure-geometry loader's stack, which ``resize_stack`` and the
@@ -335,7 +330,7 @@ class SceneStore:
             if got is None:
                 with open(path, "rb") as f:
                     got = _Prefetched(f.read())
-            mask = got.image if got.png_tried else self._png_images([], "file", [(got.data, shape, into)])[1][0]
+            mask = got.image if got.png_tried else self._png_decode([_PngRequest(got.data, "mask", shape, into)])[0]
             self.stats["mask_fallbacks" if mask is None else "masks_decoded_on_device"] += 1
             if mask is not None:
                 return mask
@@ -360,7 +355,7 @@ class SceneStore:
 
     def _decode_png(self, got, into, channels):
         """a PNG file's image on the device, or None where the path refuses the file or gives it up (``png_fallbacks``)"""
-        image = got.image if got.png_tried else self._png_images([(got.data, into)], channels)[0]
+        image = got.image if got.png_tried else self._png_decode([_PngRequest(got.data, channels, None, into)])[0]
         self.stats["png_fallbacks" if image is None else "png_decoded_on_device"] += 1
         return image
 

@@ -1460,23 +1460,21 @@ def png_status_text(status: int) -> str:
     return "+".join(name for bit, name in enumerate(PNG_STATUS_BITS) if status >> bit & 1) or "ok"
 
 
-def _png_batch(infos, out_channels, outs, pin, images=False):
+def _png_batch(infos, out_channels, outs, pin):
     """the batch buffer of ``pgdvs_png_decode``: the stream table, then every file's IDAT payloads joined, 16-byte aligned;
-    ``outs``: per stream (address, row stride in bytes).  ``images``: the table of ``pgdvs_png_decode_images``, whose entries
-    carry bit depth and scale (a batch with mask files in it)"""
+    ``outs``: per stream (address, row stride in bytes).  An entry carries bit depth and scale: a mask file's, 8 and 1 for a
+    colour file"""
     n = len(infos)
-    entry = _lib.PngImage if images else _lib.PngStream
-    offsets, at = [], -(-n * C.sizeof(entry) // 16) * 16
+    offsets, at = [], -(-n * C.sizeof(_lib.PngImage) // 16) * 16
     for info in infos:
         offsets.append(at)
         at += -(-info["stream_bytes"] // 16) * 16
     buf = torch.zeros(at, dtype=torch.uint8, pin_memory=pin)
     view = buf.numpy()
-    table = (entry * n).from_address(buf.data_ptr())
+    table = (_lib.PngImage * n).from_address(buf.data_ptr())
     for i, info in enumerate(infos):
         src, o = info["data"], offsets[i]
-        if images:
-            table[i].bit_depth, table[i].scale = info.get("bit_depth", 8), info.get("scale", 1)
+        table[i].bit_depth, table[i].scale = info.get("bit_depth", 8), info.get("scale", 1)
         for off, length in info["idat"]:
             view[o:o + length] = src[off:off + length]
             o += length
@@ -1529,8 +1527,8 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
 
     ``kinds`` (``png_parse``): with "mask" in it, non-interlaced grey and palette files of bit depth 1, 2, 4 or 8 are served as
     well, each as a uint8 [H,W] tensor, byte for byte ``np.array(PIL.Image.open(...)).astype(np.uint8)``: grey
-    samples as Pillow scales them, a palette file's indices; ``outs``: [H,W] with a free row stride.  A batch with such a file
-    in it goes through ``pgdvs_png_decode_images``, colour files and all: the same one buffer, copy, launch pair and wait."""
+    samples as Pillow scales them, a palette file's indices; ``outs``: [H,W] with a free row stride.  Such files share the batch
+    with the colour files: the same one buffer, copy, launch pair and wait."""
     if channels not in PNG_CHANNEL_MODES:
         raise ValueError(f"png_decode: channels {channels!r}, expected one of {PNG_CHANNEL_MODES}")
     kinds = _png_kinds(kinds)
@@ -1542,7 +1540,7 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
     images = [None] * len(datas)
     walked, parsed = parsed, []
     for i, data in enumerate(datas):
-        info, why[i] = (png_parse(data) if kinds == ("colour",) else png_parse(data, kinds)) if walked is None else walked[i]
+        info, why[i] = png_parse(data, kinds) if walked is None else walked[i]
         if info is not None:
             parsed.append((i, info))
         elif not reject_ok:
@@ -1552,18 +1550,15 @@ def png_decode_batch(datas, outs=None, channels: str = "file", device=None, reje
         lib = _lib.load()
         out_ch = [3 if channels == "rgb" and info["channels"] != 1 else info["channels"] for _, info in parsed]
         targets = [_png_out(outs[i], _png_shape(info, c), device, f"png_decode: out of file {i}") for (i, info), c in zip(parsed, out_ch)]
-        with_masks = any("bit_depth" in info for _, info in parsed)  # (a mask file among them: the table with bit depth and scale)
         batch = _png_batch([info for _, info in parsed], out_ch, [(t.data_ptr(), t.stride(0) if t.shape[0] > 1 else t[0].numel()) for t in targets],
-                           pin=True, images=with_masks)
+                           pin=True)
         n = len(parsed)
-        query, entry = (("pgdvs_png_images_workspace_bytes", "pgdvs_png_decode_images") if with_masks else
-                        ("pgdvs_png_inflate_workspace_bytes", "pgdvs_png_decode"))
         with _side_stream("png", device, written=targets) as fetch:
             dev = batch.to(device, non_blocking=True)
             status = torch.empty(n, dtype=torch.int32, device=device)
-            ws = _ws(getattr(lib, query)(C.c_void_p(batch.data_ptr()), n), device)
-            check(getattr(lib, entry)(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(), _stream()),
-                  entry)
+            ws = _ws(lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n), device)
+            check(lib.pgdvs_png_decode(C.c_void_p(batch.data_ptr()), _ptr(dev), batch.numel(), n, sub_bytes, _ptr(status), _ptr(ws), ws.numel(), _stream()),
+                  "pgdvs_png_decode")
             words = fetch(status)  # behind the whole batch: its one wait
         if stats is not None:
             rows = ws[:16 * n].cpu().view(torch.int32).view(n, 4).tolist()
@@ -1604,9 +1599,6 @@ def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: in
         return results
     n = len(parsed)
     out_ch = [3 if channels == "rgb" and info["channels"] != 1 else info["channels"] for _, info in parsed]
-    images = any("bit_depth" in info for _, info in parsed)
-    query, entry = (("pgdvs_png_images_workspace_bytes", "pgdvs_png_decode_images_host") if images else
-                    ("pgdvs_png_inflate_workspace_bytes", "pgdvs_png_decode_host"))
 
     def guarded(nbytes, align=1):
         raw = np.full(nbytes + 2 * guard + 256, 0xA5, np.uint8)
@@ -1615,14 +1607,14 @@ def png_decode_host(datas, channels: str = "file", sub_bytes: int = 0, guard: in
 
     holds = [guarded(info["height"] * info["width"] * c) for (_, info), c in zip(parsed, out_ch)]
     batch = _png_batch([info for _, info in parsed], out_ch, [(h[1].ctypes.data, info["width"] * c) for h, (_, info), c in zip(holds, parsed, out_ch)],
-                       pin=False, images=images)
-    need = getattr(lib, query)(C.c_void_p(batch.data_ptr()), n)
+                       pin=False)
+    need = lib.pgdvs_png_inflate_workspace_bytes(C.c_void_p(batch.data_ptr()), n)
     if need < 0:
-        check(int(need), query)
+        check(int(need), "pgdvs_png_inflate_workspace_bytes")
     ws_raw, ws = guarded(int(need), 256)
     st_raw, st = guarded(4 * n, 8)
-    check(getattr(lib, entry)(C.c_void_p(batch.data_ptr()), C.c_void_p(batch.data_ptr()), batch.numel(), n, sub_bytes, C.c_void_p(st.ctypes.data),
-                              C.c_void_p(ws.ctypes.data), int(need)), entry)
+    check(lib.pgdvs_png_decode_host(C.c_void_p(batch.data_ptr()), C.c_void_p(batch.data_ptr()), batch.numel(), n, sub_bytes, C.c_void_p(st.ctypes.data),
+                                    C.c_void_p(ws.ctypes.data), int(need)), "pgdvs_png_decode_host")
     for raw, inner in [(ws_raw, ws), (st_raw, st)] + holds:
         lo = inner.ctypes.data - raw.ctypes.data
         if not ((raw[:lo] == 0xA5).all() and (raw[lo + inner.size:] == 0xA5).all()):

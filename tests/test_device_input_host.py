@@ -2,7 +2,7 @@
 ``datasets.resident.SceneStore``): the truth table of the four options' rules, through the one function and through the
 store's constructor, against this file's own statement of them in precedence order; and ``decode_image``,
 ``prefetch_images``, ``decode_stack`` and ``_fill`` with the three decode ops replaced by recorders -- which op is asked, in
-which order and with which arguments, what a give-up ends in, the complete ``stats`` after every call, that a prefetched file
+which order and with which arguments (the ``kinds`` of a PNG call among them), what a give-up ends in, the complete ``stats`` after every call, that a prefetched file
 is neither read nor walked again, and that the prefetch table is left empty."""
 import builtins
 import io
@@ -108,12 +108,13 @@ class Recorders:
     def __init__(self, monkeypatch, serve=True, scan=True):
         from pgdvs_amd import ops
 
-        self.calls, self.walks, self.serve, self.scan = [], 0, serve, scan
+        self.calls, self.walks, self.walk_kinds, self.serve, self.scan = [], 0, [], serve, scan
         walk = getattr(ops, PNG_WALK)
 
-        def counted_walk(data):
+        def counted_walk(data, kinds=("colour",)):
             self.walks += 1
-            return walk(data)
+            self.walk_kinds.append(tuple(kinds))
+            return walk(data, kinds)
 
         monkeypatch.setattr(ops, PNG_WALK, counted_walk)
         monkeypatch.setattr(ops, "png_decode_batch", self.png_decode_batch)
@@ -124,10 +125,12 @@ class Recorders:
         if not self.serve:
             return None
         im = PIL.Image.open(io.BytesIO(bytes(data)))
-        return torch.full((im.size[1], im.size[0], 3 if channels == "rgb" else len(im.getbands())), MARK, dtype=torch.uint8)
+        bands = len(im.getbands())  # (one band: a mask file, [H,W])
+        return torch.full((im.size[1], im.size[0]) + ((3 if channels == "rgb" else bands,) if bands > 1 else ()), MARK, dtype=torch.uint8)
 
-    def png_decode_batch(self, datas, outs=None, channels="file", device=None, reject_ok=False, sub_bytes=0, reasons=None, stats=None, parsed=None):
-        self.calls.append(("png", len(datas), channels, str(device), reject_ok, list(outs), parsed is not None and len(parsed) == len(datas)))
+    def png_decode_batch(self, datas, outs=None, channels="file", device=None, reject_ok=False, sub_bytes=0, reasons=None, stats=None, parsed=None,
+                         kinds=("colour",)):
+        self.calls.append(("png", len(datas), channels, str(device), reject_ok, list(outs), parsed is not None and len(parsed) == len(datas), tuple(kinds)))
         return [self.image(d, channels) for d in datas]
 
     def jpeg_decode(self, data, out=None, device=None, reject_ok=False, entropy="host"):
@@ -150,7 +153,7 @@ def expected(options, kind, target, serve, scan):
     calls, up, served = [], [], False
     if png and kind in ("rgb_png", "rgba_png", "png16"):
         if kind != "png16":  # (the host side refuses 16 bits: no launch)
-            calls.append(("png", 1, CHANNELS.get(kind, "file"), "cuda:0", True, [None], True))
+            calls.append(("png", 1, CHANNELS.get(kind, "file"), "cuda:0", True, [None], True, ("colour",)))
             served = serve
         up.append("png_decoded_on_device" if served else "png_fallbacks")
     if not served and decode and kind in ("jpeg", "progressive"):
@@ -219,7 +222,9 @@ def test_a_prefetched_file_is_neither_read_nor_walked_again(files, monkeypatch, 
     store.prefetch_images(paths)
     store.prefetch_images(paths[:2])  # (what is there already is not read again)
     assert sorted(opens) == sorted(files[k] for k in kinds) and rec.walks == 3  # every file read once, every PNG walked once
-    assert rec.take() == [("png", 1, "file", "cuda:0", True, [None], True), ("png", 1, "rgb", "cuda:0", True, [None], True)]  # a launch per mode
+    assert rec.take() == [("png", 1, "file", "cuda:0", True, [None], True, ("colour",)),
+                          ("png", 1, "rgb", "cuda:0", True, [None], True, ("colour",))]  # a launch per mode, image-only: the default kinds
+    assert rec.walk_kinds == [("colour",)] * 3
     assert store.stats == dict.fromkeys(store.stats, 0)  # (counted when the image is handed out)
     stats = dict.fromkeys(store.stats, 0)
     for kind in kinds:
@@ -265,3 +270,39 @@ def test_fill_and_decode_stack_leave_the_prefetch_table_empty(files, monkeypatch
     with pytest.raises(OSError, match="frame 0"):
         store._fill(scene, [0, 1, 2], reader, frames.get)
     assert not store._prefetched and [c[:3] for c in rec.take()] == [("png", 2, "file")]  # (prefetched, then dropped)
+
+
+def test_masks_ride_with_the_first_mode_and_the_batch_carries_both_kinds(files, monkeypatch, tmp_path):
+    from pgdvs_amd.datasets.resident import SceneStore
+
+    rec = Recorders(monkeypatch)
+    masks = [str(tmp_path / f"mask{k}.png") for k in range(2)]
+    for k, path in enumerate(masks):
+        PIL.Image.fromarray(np.random.default_rng(k).integers(0, 2, (16, 16)).astype(bool)).save(path)
+    paths = [files["rgb_png"], (files["rgba_png"], "rgb"), files["png16"], files["jpeg"]]
+    store = SceneStore("cuda:0", device_resize=True, device_png=True, device_mask=True)
+    assert len(store.stats) == 15
+    opens = count_opens(monkeypatch)
+    store.prefetch_images(paths, masks=[(m, None, None) for m in masks])
+    assert sorted(opens) == sorted([files["rgb_png"], files["rgba_png"], files["png16"], files["jpeg"], *masks]) and rec.walks == 5
+    assert rec.walk_kinds == [("colour",)] * 3 + [("mask",)] * 2
+    # a launch per mode: the masks in the first one's batch, behind its images, which alone carries both kinds
+    assert rec.take() == [("png", 3, "file", "cuda:0", True, [None] * 3, True, ("colour", "mask")), ("png", 1, "rgb", "cuda:0", True, [None], True, ("colour",))]
+    assert store.stats == dict.fromkeys(store.stats, 0)  # (counted when the image or mask is handed out)
+    del opens[:]
+    for k, path in enumerate(masks):
+        got = store.decode_mask(path)
+        assert isinstance(got, torch.Tensor) and tuple(got.shape) == (16, 16) and store.stats["masks_decoded_on_device"] == k + 1
+    assert isinstance(store.decode_image(files["rgb_png"]), torch.Tensor) and store.stats["png_decoded_on_device"] == 1
+    assert opens == [] and rec.walks == 5 and rec.take() == []  # nothing is read, walked or launched again
+    store._prefetched.clear()
+
+    alone = SceneStore("cuda:0", device_resize=True, device_mask=True)  # without device_png: the images stay out, the masks are a batch of their own
+    alone.prefetch_images(paths, masks=[(m, None, None) for m in masks])
+    assert sorted(opens) == sorted(masks) and rec.take() == [("png", 2, "file", "cuda:0", True, [None] * 2, True, ("colour", "mask"))]
+    assert sorted(alone._prefetched) == sorted((m, "mask") for m in masks)
+    del opens[:]
+    got = alone.decode_mask(masks[0])  # handed out: counted, not read again
+    assert isinstance(got, torch.Tensor) and opens == [] and alone.stats["masks_decoded_on_device"] == 1 and alone.stats["mask_fallbacks"] == 0
+    got = alone.decode_mask(files["png16"])  # not prefetched: read, walked, refused by the host side (16 bits), Pillow's statement
+    assert isinstance(got, np.ndarray) and opens == [files["png16"]] * 2 and alone.stats["mask_fallbacks"] == 1 and rec.take() == []

@@ -1,6 +1,6 @@
-"""The mask PNG reader on the GPU (``pgdvs_png_decode_images``, ``pgdvs_mask_place``): every file of
+"""The mask PNG reader on the GPU (``pgdvs_png_decode``, ``pgdvs_mask_place``): every file of
 tests/png_mask_cases.py byte for byte Pillow's through ``ops.png_decode_batch(kinds="mask")``, alone and in one mixed batch with
-RGB and RGBA files that costs one call of the C entry and writes rows with a stride; ``ops.mask_place`` against Pillow's NEAREST
+RGB and RGBA files that costs one call of the C entry (as the colour files alone do) and writes rows with a stride; ``ops.mask_place`` against Pillow's NEAREST
 and against the evaluation mask's numpy expression; and the five loaders with ``device_mask`` on trees whose masks mix the
 formats: items bit for bit the ``device_resize`` loaders', the counters the tree implies, one wait per item fill."""
 import io
@@ -49,18 +49,21 @@ def test_one_mixed_batch_is_one_call_and_writes_strided_rows(monkeypatch):
     wide = [torch.full((w.shape[0], int(np.prod(w.shape[1:])) + PAD), CANARY, dtype=torch.uint8, device=DEV) for w in wants]
     outs = [b[:, :b.shape[1] - PAD].view(w.shape[0], w.shape[1], -1) if w.ndim == 3 else b[:, :w.shape[1]] for b, w in zip(wide, wants)]
     ops.png_decode(masks[0], device=DEV, kinds="mask")  # (warm-up: the code object, the side stream)
-    lib, calls = _lib.load(), {"images": 0, "streams": 0}
-    for name, key in (("pgdvs_png_decode_images", "images"), ("pgdvs_png_decode", "streams")):
-        real = getattr(lib, name)
+    lib, calls = _lib.load(), []
+    real = lib.pgdvs_png_decode
 
-        def counted(*a, real=real, key=key):
-            calls[key] += 1
-            return real(*a)
+    def counted(*a):
+        calls.append(a[3])  # (nstreams)
+        return real(*a)
 
-        monkeypatch.setattr(lib, name, counted)
+    monkeypatch.setattr(lib, "pgdvs_png_decode", counted)
     got = ops.png_decode_batch(datas, outs=outs, device=DEV, kinds=("colour", "mask"))
+    alone = ops.png_decode_batch(colour, device=DEV)  # the colour files alone: the same one entry, once
     monkeypatch.undo()
-    assert calls == {"images": 1, "streams": 0}
+    assert calls == [len(datas), len(colour)]  # one call of the one entry per batch, masks or not
+    for k, (g, d) in enumerate(zip(alone, colour)):
+        want = PC.pillow(d)
+        assert g.dtype == torch.uint8 and tuple(g.shape) == want.shape and np.array_equal(g.cpu().numpy(), want), k
     for k, (g, o, b, w) in enumerate(zip(got, outs, wide, wants)):
         assert g is o and tuple(g.shape) == w.shape and (g.stride(0) > int(np.prod(w.shape[1:])) or w.shape[0] == 1), k
         host = b.cpu().numpy()

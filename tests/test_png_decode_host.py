@@ -145,8 +145,16 @@ def test_c_entry_argument_checks():
     from pgdvs_amd import _lib
 
     lib = _lib.load()
-    table = (_lib.PngStream * 1)()
-    table[0].offset, table[0].size, table[0].height, table[0].width, table[0].channels, table[0].out_channels = 48, 12, 1, 1, 3, 3
+    table = (_lib.PngImage * 1)()
+    table[0].offset, table[0].size, table[0].height, table[0].width, table[0].channels, table[0].out_channels = 64, 12, 1, 1, 3, 3
+    table[0].bit_depth, table[0].scale = 8, 1
+    assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) > 0
+    for field in ("bit_depth", "scale"):  # a colour entry states its depth and scale
+        keep = getattr(table[0], field)
+        setattr(table[0], field, 0)
+        assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) == -1, field
+        assert b"colour streams have bit depth 8 and scale 1" in lib.pgdvs_last_error(), field
+        setattr(table[0], field, keep)
     assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) > 0
     table[0].channels = 2
     assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) == -1

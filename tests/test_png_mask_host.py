@@ -1,4 +1,4 @@
-"""The mask PNG reader without a GPU (``pgdvs_png_decode_images_host``: the kernels' host emulation, which runs their inflate
+"""The mask PNG reader without a GPU (``pgdvs_png_decode_host``: the kernels' host emulation, which runs their inflate
 core, their byte-unit row filters and their unpack; ``ops.png_parse(kinds=...)``): over the files of tests/png_mask_cases.py the
 emulation's image equals ``np.array(PIL.Image.open(f)).astype(np.uint8)``, between guard bytes, at three subsequence sizes,
 alone and in one table with RGB and RGBA streams; the refusals on the host side and by the status word; the default ``kinds``,
@@ -124,31 +124,32 @@ def test_c_entry_argument_checks():
     from pgdvs_amd import _lib
 
     lib = _lib.load()
-    assert C.sizeof(_lib.PngImage) == 56 and C.sizeof(_lib.PngStream) == 48
+    assert C.sizeof(_lib.PngImage) == 56
     table = (_lib.PngImage * 1)()
     t = table[0]
     t.offset, t.size, t.height, t.width, t.channels, t.out_channels, t.bit_depth, t.scale = 64, 12, 3, 9, 1, 1, 2, 85
-    need = lib.pgdvs_png_images_workspace_bytes(C.byref(table), 1)
+    need = lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1)
     assert need == 512  # the head of 256, 3 rows of 1 + 3 bytes and the carry row of 3, each padded to 16: 288, to a multiple of 256
     t.height = 64  # 64 * 4 = 256 bytes of rows: 256 + 256 + 16
-    assert lib.pgdvs_png_images_workspace_bytes(C.byref(table), 1) == 768
+    assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) == 768
     t.height = 3
     for field, value in (("bit_depth", 3), ("bit_depth", 16), ("scale", 86), ("scale", 0), ("channels", 2), ("width", 16385)):
         keep = getattr(t, field)
         setattr(t, field, value)
-        assert lib.pgdvs_png_images_workspace_bytes(C.byref(table), 1) == -1, (field, value)
-        assert b"pgdvs_png_images_workspace_bytes" in lib.pgdvs_last_error()
+        assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) == -1, (field, value)
+        assert b"pgdvs_png_inflate_workspace_bytes" in lib.pgdvs_last_error()
         setattr(t, field, keep)
     t.channels, t.out_channels, t.bit_depth, t.scale = 3, 3, 4, 1  # colour streams are 8-bit
-    assert lib.pgdvs_png_images_workspace_bytes(C.byref(table), 1) == -1
-    old = (_lib.PngStream * 1)()
-    old[0].offset, old[0].size, old[0].height, old[0].width, old[0].channels, old[0].out_channels = 48, 12, 1, 1, 1, 1
-    assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(old), 1) == -1  # the older table has no one-channel streams
+    assert lib.pgdvs_png_inflate_workspace_bytes(C.byref(table), 1) == -1
+    for gone in ("images_workspace_bytes", "decode_images", "decode_images_host"):  # the second table's entry points went with it
+        assert not hasattr(lib, f"pgdvs_png_{gone}") and f"pgdvs_png_{gone}" not in _lib.SIGNATURES, gone
+    assert {n for n in _lib.SIGNATURES if n.startswith("pgdvs_png_") and ("inflate" in n or "decode" in n)} == {
+        "pgdvs_png_inflate_workspace_bytes", "pgdvs_png_decode", "pgdvs_png_decode_host"}
     buf = np.zeros(64, np.uint64)
     st = np.zeros(2, np.uint32)
     ptr = C.c_void_p(buf.ctypes.data)
-    assert lib.pgdvs_png_decode_images_host(ptr, ptr, 512, 1, 0, C.c_void_p(st.ctypes.data), ptr, 512) == -1
-    assert b"pgdvs_png_decode_images_host" in lib.pgdvs_last_error()
+    assert lib.pgdvs_png_decode_host(ptr, ptr, 512, 1, 0, C.c_void_p(st.ctypes.data), ptr, 512) == -1
+    assert b"pgdvs_png_decode_host" in lib.pgdvs_last_error()
 
 
 # ---------------------------------------------------------------------------- the sanitizers, on a stand-alone program

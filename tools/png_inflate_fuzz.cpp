@@ -67,15 +67,15 @@ static bool read_png(const std::vector<uint8_t> &f, Image *im) {
 
 // one variant at one subsequence size into `image` (exactly h * w * c bytes); the status, or 0xFFFFFFFF for a refused call
 static uint32_t run(const Image &im, const uint8_t *z, size_t n, int32_t sub_bytes, uint8_t *image, Counts *k) {
-  const size_t table = sizeof(pgdvs_png_stream) + (16 - sizeof(pgdvs_png_stream) % 16) % 16, bytes = table + (n + 3) / 4 * 4;
+  const size_t table = sizeof(pgdvs_png_image) + (16 - sizeof(pgdvs_png_image) % 16) % 16, bytes = table + (n + 3) / 4 * 4;
   uint8_t *batch = static_cast<uint8_t *>(malloc(bytes));
   memset(batch, 0, bytes);
-  pgdvs_png_stream st;
+  pgdvs_png_image st;
   st.offset = (int64_t)table, st.size = (int64_t)n, st.height = im.h, st.width = im.w, st.channels = im.c, st.out_channels = im.c;
-  st.row_stride = (int64_t)im.w * im.c, st.out = image;
+  st.row_stride = (int64_t)im.w * im.c, st.out = image, st.bit_depth = 8, st.scale = 1;
   memcpy(batch, &st, sizeof(st));
   memcpy(batch + table, z, n);
-  const int64_t need = pgdvs_png_inflate_workspace_bytes(reinterpret_cast<const pgdvs_png_stream *>(batch), 1);
+  const int64_t need = pgdvs_png_inflate_workspace_bytes(reinterpret_cast<const pgdvs_png_image *>(batch), 1);
   uint32_t status = 0xFFFFFFFFu;
   if (need <= 0) {
     ++k->bad;

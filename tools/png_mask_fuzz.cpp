@@ -1,4 +1,4 @@
-// Stand-alone driver of the mask PNG reader's host emulation -- pgdvs_png_decode_images_host of csrc/png_decode_host.cpp:
+// Stand-alone driver of the mask PNG reader's host emulation -- pgdvs_png_decode_host of csrc/png_decode_host.cpp:
 // the inflate core, the byte-unit row filters and unpack_byte of csrc/png_inflate_core.h, the code the device kernels run --
 // for the host compiler's sanitizers (tests/test_png_mask_host.py builds and runs it; nothing here touches a GPU or Python):
 //
@@ -88,7 +88,7 @@ static uint32_t run(const Mask &im, const uint8_t *z, size_t n, int32_t sub_byte
   m.row_stride = im.w, m.out = image, m.bit_depth = im.depth, m.scale = im.scale;
   memcpy(batch, st, (size_t)ns * sizeof(pgdvs_png_image));
   memcpy(batch + table + first, z, n);
-  const int64_t need = pgdvs_png_images_workspace_bytes(reinterpret_cast<const pgdvs_png_image *>(batch), ns);
+  const int64_t need = pgdvs_png_inflate_workspace_bytes(reinterpret_cast<const pgdvs_png_image *>(batch), ns);
   uint32_t status = 0xFFFFFFFFu;
   if (need <= 0) {
     ++k->bad;
@@ -96,7 +96,7 @@ static uint32_t run(const Mask &im, const uint8_t *z, size_t n, int32_t sub_byte
   } else {
     void *ws = malloc((size_t)need);
     uint32_t *words = static_cast<uint32_t *>(malloc(4 * (size_t)ns));
-    const int rc = pgdvs_png_decode_images_host(batch, batch, (int64_t)bytes, ns, sub_bytes, words, ws, need);
+    const int rc = pgdvs_png_decode_host(batch, batch, (int64_t)bytes, ns, sub_bytes, words, ws, need);
     if (rc != 0) {
       ++k->bad;
       fprintf(stderr, "argument error (%d): %s\n", rc, pgdvs::g_err);
