@@ -1238,6 +1238,49 @@ int pgdvs_png_decode_host(const void *batch_host, const void *batch, int64_t bat
 int pgdvs_mask_place(const uint8_t *src, int32_t h, int32_t w, int32_t channels, int64_t src_row_stride, const int32_t *map, int32_t H, int32_t W,
                      int32_t mode, void *out, int64_t out_row_stride, pgdvs_stream_t stream);
 
+/* The float32 payloads of a batch of depth files into their places (csrc/depth_place.hip): what the loaders'
+ * numpy statements make of a `.npy` / stored `.npz` payload, bit for bit, written straight into the frames' slots of the
+ * resident store.  The batch buffer, as pgdvs_png_decode's: a table of n pgdvs_depth_entry, padded to 16 bytes, then the
+ * payloads as the files store them (little-endian float32 [h,w], C order), each at its entry's `offset` from the buffer's
+ * start, a multiple of 4 (a caller that stages payloads at multiples of 16 gets 16-byte loads).  Per entry:
+ *   h, w            the source's size; H, W: the output's; each 1 .. 16384
+ *   op              PGDVS_DEPTH_COPY out = x;  PGDVS_DEPTH_RECIPROCAL out = 1.0f / (x + 1e-8f), NumPy 2's `1 / (disp + 1e-8)` on
+ *                   a float32 array;  PGDVS_DEPTH_SCALE out = x * scale.  Each add, multiply and divide is one correctly
+ *                   rounded float32 operation; denormals are kept; NaN, +-inf and -0 propagate as IEEE 754 has it.
+ *   map             nullptr (then H = h and W = w), or DEVICE int32 [H,W]: the source index y' * w + x' of every output pixel
+ *                   (a NEAREST resize's picks, as pgdvs_mask_place takes them); an index outside 0 .. h * w - 1 reads x = 0
+ *   out             DEVICE float32 [H,W], 4-byte aligned, out_row_stride BYTES between rows (>= 4 W, a multiple of 4)
+ * batch_host: HOST, the buffer as filled (only its table is read, and checked: sizes, ops, strides, and that every payload
+ * lies behind the table and inside batch_bytes); batch: DEVICE, a copy of the same batch_bytes bytes, 16-byte aligned.
+ * One launch on `stream`; no workspace, no atomics, no host synchronisation, no status: nothing can fail on the device.
+ * Nothing outside the entries' rows is written.  0, or PGDVS_ERR_INVALID (nothing is launched). */
+#define PGDVS_DEPTH_COPY 0
+#define PGDVS_DEPTH_RECIPROCAL 1
+#define PGDVS_DEPTH_SCALE 2
+#define PGDVS_DEPTH_MAX_ENTRIES 4096
+typedef struct pgdvs_depth_entry {
+  int64_t offset;
+  int32_t h, w;
+  int32_t op;
+  float scale;
+  const int32_t *map;
+  void *out;
+  int64_t out_row_stride;
+  int32_t H, W;
+} pgdvs_depth_entry;
+int pgdvs_depth_place(const void *batch_host, const void *batch, int64_t batch_bytes, int32_t n, pgdvs_stream_t stream);
+
+/* np.percentile(values, q) of the installed NumPy 2 (method "linear") over float32 values, per frame of a batch, bit for
+ * bit (csrc/depth_range.hip, over radix_select.h as the depth-range ops): q / 100 is formed in float32, the virtual index is
+ * (n - 1) q in float32, its two neighbouring ranks are selected exactly and joined by NumPy's _lerp in float32.  Any NaN
+ * among a frame's values gives NaN.  (-0.0 and +0.0 compare equal; a zero comes back as +0.0.)
+ * values: HOST array of nframes DEVICE pointers, 4-byte aligned; counts: HOST, each 1 .. 2^31 - 1; q_percent in [0, 100];
+ * out: DEVICE float32 [nframes]; workspace >= pgdvs_percentile_f32_workspace_bytes(counts, nframes), 256-byte aligned.
+ * Launches on `stream` alone, no host synchronisation. */
+int64_t pgdvs_percentile_f32_workspace_bytes(const int64_t *counts, int32_t nframes);
+int pgdvs_percentile_f32(const float *const *values, const int64_t *counts, int32_t nframes, double q_percent, float *out, void *workspace,
+                         int64_t workspace_bytes, pgdvs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -492,10 +492,78 @@ int nv_setup(const char *op, int64_t n, float *depth_range, double *near_far, vo
   return setup<double>(op, kNvLabels, n, 0, ranks, workspace, workspace_bytes, st, w);
 }
 
+// ---- np.percentile of float32 values (mono_vis' near depths under device_depth) ----
+
+typedef State<2> PctState;  // ranks: the virtual index's floor and floor + 1
+constexpr Labels kPctLabels = {"percentile_init", "percentile_hist", "percentile_select"};
+
+__global__ void __launch_bounds__(kBlock) pct_keys_kernel(const float *__restrict__ values, int64_t n, Key<float>::U *__restrict__ keys,
+                                                          PctState *__restrict__ st) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) store_key<float>(values[i], keys, i, &st->nan_seen);
+}
+
+struct PctFinish {
+  typedef PctState State;
+  float gamma;
+  float *out;
+  __device__ void operator()(PctState *st) const {
+    const float q = radix::lerp_np(radix::rank_value<float, 2>(&st->sel, 0), radix::rank_value<float, 2>(&st->sel, 1), gamma);
+    *out = st->nan_seen ? NAN : q;
+  }
+};
+
+int64_t pct_frame_bytes(int64_t n) { return layout(n, 4, radix::passes_for(32), 2, 0).total; }
+
+bool pct_counts_ok(const int64_t *counts, int32_t nframes) {
+  if (!counts || nframes < 1) return false;
+  for (int32_t f = 0; f < nframes; ++f)
+    if (counts[f] < 1 || counts[f] >= (1ll << 31)) return false;
+  return true;
+}
+
 }  // namespace
 }  // namespace pgdvs
 
 using namespace pgdvs;
+
+#define PCT_COUNTS_MSG "%s: at least one frame, each of 1 .. 2^31 - 1 values"
+
+PGDVS_API int64_t pgdvs_percentile_f32_workspace_bytes(const int64_t *counts, int32_t nframes) {
+  if (!pct_counts_ok(counts, nframes)) {
+    set_error(PCT_COUNTS_MSG, "pgdvs_percentile_f32_workspace_bytes");
+    return PGDVS_ERR_INVALID;
+  }
+  int64_t total = 0;
+  for (int32_t f = 0; f < nframes; ++f) total += pct_frame_bytes(counts[f]);
+  return total;
+}
+
+PGDVS_API int pgdvs_percentile_f32(const float *const *values, const int64_t *counts, int32_t nframes, double q_percent, float *out, void *workspace,
+                                   int64_t workspace_bytes, pgdvs_stream_t stream) {
+  const char *op = "pgdvs_percentile_f32";
+  PGDVS_REQUIRE(values && out && workspace, "%s: null pointer", op);
+  PGDVS_REQUIRE(pct_counts_ok(counts, nframes), PCT_COUNTS_MSG, op);
+  PGDVS_REQUIRE(q_percent >= 0.0 && q_percent <= 100.0, "%s: q = %g percent (0 .. 100)", op, q_percent);
+  PGDVS_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
+                "%s: the workspace must be 256-byte aligned, out 4-byte", op);
+  const float q = (float)q_percent / 100.0f;  // np.true_divide(q, float32(100)): the weak Python scalar becomes float32
+  hipStream_t st = as_stream(stream);
+  int64_t at = 0;
+  for (int32_t f = 0; f < nframes; ++f) {
+    PGDVS_REQUIRE(values[f] && (reinterpret_cast<uintptr_t>(values[f]) & 3) == 0, "%s: frame %d's values are NULL or not 4-byte aligned", op, f);
+    const int64_t n = counts[f];
+    Ranks<2> ranks;
+    PctFinish fin;
+    radix::quantile_setup<float>(n, q, ranks.rank[0], ranks.rank[1], fin.gamma);
+    fin.out = out + f;
+    Work<float, PctState> w;
+    if (const int rc = setup<float>(op, kPctLabels, n, 0, ranks, static_cast<char *>(workspace) + at, workspace_bytes - at, st, w)) return rc;
+    at += pct_frame_bytes(n);
+    PGDVS_LAUNCH("percentile_keys", pct_keys_kernel, dim3(radix::hist_grid(n)), dim3(kBlock), 0, st, values[f], n, w.keys, w.state);
+    select_passes<float, 2>(kPctLabels, w, n, fin, st);
+  }
+  return check_launch(op);
+}
 
 #define DYR_SHAPE_MSG "pgdvs_dycheck_depth_range: bad shape V=%d H=%d W=%d (each > 0, V H W < 2^31)"
 

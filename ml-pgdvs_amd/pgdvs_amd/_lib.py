@@ -109,6 +109,14 @@ class PngImage(C.Structure):
     ]
 
 
+class DepthEntry(C.Structure):
+    """``pgdvs_depth_entry`` (include/pgdvs_hip.h), field for field: one entry of the table at the front of a depth batch buffer."""
+    _fields_ = [
+        ("offset", _i64), ("h", C.c_int32), ("w", C.c_int32), ("op", C.c_int32), ("scale", C.c_float), ("map", _vp), ("out", _vp),
+        ("out_row_stride", _i64), ("H", C.c_int32), ("W", C.c_int32),
+    ]
+
+
 class JpegScanHeader(C.Structure):
     """The front of the buffer ``pgdvs_jpeg_scan_prepare`` fills (csrc/jpeg_scan_core.h ``jscan::Header``), field for field:
     the offsets are bytes from the buffer's start."""
@@ -187,6 +195,9 @@ SIGNATURES.update({
     "pgdvs_png_decode": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp]),
     "pgdvs_png_decode_host": (_i, [_vp, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64]),
     "pgdvs_mask_place": (_i, [_vp, C.c_int32, C.c_int32, C.c_int32, _i64, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, _vp]),
+    "pgdvs_depth_place": (_i, [_vp, _vp, _i64, C.c_int32, _vp]),
+    "pgdvs_percentile_f32_workspace_bytes": (_i64, [_vp, C.c_int32]),
+    "pgdvs_percentile_f32": (_i, [_vp, _vp, C.c_int32, C.c_double, _vp, _vp, _i64, _vp]),
     "pgdvs_view_geo_desc_size": (_i64, []),
     "pgdvs_view_geo_workspace_bytes": (_i64, [C.POINTER(ViewGeoDesc)]),
     "pgdvs_view_geo_forward": (_i, [C.POINTER(ViewGeoDesc), _vp, _i64, _vp]),

@@ -96,6 +96,15 @@ def device_input(owner, *, resident, device, device_resize=False, device_decode=
     return DeviceInput(bool(device_resize), bool(device_decode), bool(device_entropy), bool(device_png), bool(device_mask))
 
 
+def device_depth(owner, options, device_depth=False):
+    """The sixth keyword of ``owner``, checked behind the five of ``options`` (the ``DeviceInput`` that ``device_input`` returned,
+    which stays the five-field record): ``device_depth`` places the depth files' floats in the resident store on the device
+    (datasets/resident.py), so it needs ``device_resize`` -- and with it ``resident=True`` and the store on a GPU."""
+    if device_depth and not options.resize:
+        raise ValueError(f"{owner}(device_depth=True) places the depth files' payloads in the resident store on the device: it needs device_resize=True")
+    return bool(device_depth)
+
+
 def group_entries(group, views, times=None, n_actual=None, depth=True):
     """The item's entries of one group of stacked source views: "spatial", "temporal" or "temporal_track_{fwd,bwd}2tgt".
     The temporal and tracker groups also carry their frames' ``times`` and ``n_actual``, the count before padding; the

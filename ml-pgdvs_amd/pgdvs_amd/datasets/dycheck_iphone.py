@@ -31,7 +31,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, device_input, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
+from ._common import (F32, device_depth as check_device_depth, device_input, flat_cam, flow_entries, group_entries, ray_rows, read_flow_pair_or_zeros, refuse_gpu_in_worker,
                       resize, stack_views, tracker_entries)
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 
@@ -365,9 +365,10 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
                  scene_ids=None, spatial_src_view_type="clustered", n_src_views_spatial=10, n_src_views_spatial_cluster=None,
                  n_src_views_temporal_track_one_side=5, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
                  resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False,
-                 device_mask=False):
+                 device_mask=False, device_depth=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
                                device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
+        device_depth = check_device_depth(type(self).__name__, options, device_depth)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -380,7 +381,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.device = None if device is None else torch.device(device)
         # resident source frames (datasets/resident.py): the store, and per scene the frame size and the cameras' derived values
-        self.store = SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_input=options) if resident else None
+        self.store = (SceneStore(self.device, resident_scenes, resident_max_bytes, flow_consist_thres, device_input=options, device_depth=device_depth)
+                      if resident else None)
         self._scene_shape, self._cam_cache = {}, {}
         root = pathlib.Path(data_root)
         self.raw_data_dir, self.mask_data_dir, self.flow_data_dir = root / raw_data_dir, root / mask_data_dir, root / flow_data_dir
@@ -519,11 +521,22 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
             mask = self.store.decode_mask(self._mask_f(scene_id, time_id), (h, w), into=(self.store.scenes.get(scene_id), time_id))
         else:
             mask = resize(np.array(PIL.Image.open(self._mask_f(scene_id, time_id))), h, w, PIL.Image.Resampling.NEAREST)
+        staged = self.store.staged_depth(self.store.scenes.get(scene_id), time_id)
+        if staged is not None and staged.depth is not None:  # (device_depth: the fill placed depth * scale, float32, in the slot)
+            return raw, mask, staged.depth
         depth = p.load_depth(time_id, cam_id)
         if depth.dtype == np.float64:
             raise ValueError(f"{p.depth_path(time_id, cam_id)}: the depth times the scene's scale is float64; resident=True keeps "
                              "float32 depths, and the disk path would take the depth range over the doubles")
         return raw, mask, resize(depth[..., 0], h, w, PIL.Image.Resampling.NEAREST)
+
+    def _depth_request(self, scene_id, time_id):
+        """``device_depth``: a train frame's depth file and ``load_depth``'s statement over it, as ``SceneStore._stage_depths`` takes
+        them -- where ``depth * scale`` is float32 on the host (a Python number as the scale); else None: the host statement"""
+        p = self.parser_dict[scene_id]
+        if (np.zeros(1, np.float32) * p.scale).dtype != np.float32:
+            return None
+        return p.depth_path(time_id, self.get_train_cam_id(scene_id)), None, "scale", np.float32(p.scale)
 
     def _mask_f(self, scene_id, time_id):
         """a train frame's final mask file"""
@@ -619,7 +632,8 @@ class DyCheckiPhoneEvaluationDataset(Dataset):
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b),
                           trackers=True, owner=type(self).__name__, depth_range=depth_range,
                           ray_rows=lambda ids: ray_rows([self._cam(scene_id, t, cam_id)["rays"] for t in ids]),
-                          image_path=lambda t: (p.rgb_path(t, cam_id), "rgb"), mask_path=lambda t: self._mask_f(scene_id, t))
+                          image_path=lambda t: (p.rgb_path(t, cam_id), "rgb"), mask_path=lambda t: self._mask_f(scene_id, t),
+                          depth_request=lambda t: self._depth_request(scene_id, t))
         if as_bytes:
             from .. import ops
 

@@ -25,7 +25,7 @@ import PIL.Image
 import torch
 from torch.utils.data import Dataset
 
-from ._common import (F32, device_input, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
+from ._common import (F32, device_depth as check_device_depth, device_input, flat_cam, flow_entries, group_entries, read_flow_pair_or_zeros, resize, stack_views,
                       tracker_entries)
 from .nvidia_eval import spatial_depth_range
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
@@ -120,9 +120,10 @@ class MonoVisualizationDataset(Dataset):
                  n_src_views_temporal_track_one_side=5, vis_center_time=50, n_render_frames=200, vis_time_interval=10,
                  vis_bt_max_disp=32, flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1,
                  resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False,
-                 device_mask=False):
+                 device_mask=False, device_depth=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
                                device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
+        device_depth = check_device_depth(type(self).__name__, options, device_depth)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug and mode in ["vis"] and rgb_range == "0_1" and scene_ids is not None
         self.mode, self.max_hw, self.use_aug, self.rgb_range = mode, max_hw, use_aug, rgb_range
@@ -131,7 +132,8 @@ class MonoVisualizationDataset(Dataset):
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
         # the source frames kept in memory (datasets/resident.py)
-        self.store = SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_input=options) if resident else None
+        self.store = (SceneStore(self.depth_device, resident_scenes, resident_max_bytes, flow_consist_thres, device_input=options, device_depth=device_depth)
+                      if resident else None)
         self.data_root = pathlib.Path(data_root)
         assert self.data_root.exists(), self.data_root
         self.c2w_dict, self.K_dict, self.valid_fs = {}, {}, []
@@ -139,7 +141,10 @@ class MonoVisualizationDataset(Dataset):
             sd = self.data_root / scene
             cams = [np.load(f) for f in sorted((sd / "poses").glob("*.npz"))]
             all_K, all_c2w = np.array([c["K"] for c in cams]), np.array([c["c2w"] for c in cams])
-            near = np.array([np.percentile(np.load(f)["depth"].reshape(-1), 5) for f in sorted((sd / "depths").glob("*.npz"))])
+            if device_depth:  # each file read once, the payloads selected on the device, one wait per scene (resident.py)
+                near = np.array(self.store.depth_percentiles(sorted((sd / "depths").glob("*.npz")), "depth", 5))
+            else:
+                near = np.array([np.percentile(np.load(f)["depth"].reshape(-1), 5) for f in sorted((sd / "depths").glob("*.npz"))])
             self.c2w_dict[scene], self.K_dict[scene] = all_c2w.copy(), all_K.copy()
             for t, i, c2w in render_path(all_K[0, 0, 0], all_c2w, near, vis_center_time=vis_center_time, n_render_frames=n_render_frames,
                                          vis_time_interval=vis_time_interval, vis_bt_max_disp=vis_bt_max_disp):
@@ -153,10 +158,11 @@ class MonoVisualizationDataset(Dataset):
         return scene_dir / "masks" / "final" / f"{pathlib.Path(img_f).stem}_final.png"
 
     @staticmethod
-    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None, resize_rgb=True, mask=None):
+    def _decode_frame(scene_dir, img_f, tgt_shape, raw=None, resize_rgb=True, mask=None, depth=None):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size; ``raw``: the image file's pixels, where
         the caller has opened it already; ``resize_rgb`` False (``device_resize``): the image as decoded, the store resizes it;
-        ``mask`` (``device_mask``): the mask at the target's size as the store decoded it"""
+        ``mask`` (``device_mask``): the mask at the target's size as the store decoded it; ``depth`` (``device_depth``): the depth
+        as the fill placed it in its slot"""
         h, w = tgt_shape
         rgb = np.array(PIL.Image.open(img_f)) if raw is None else raw
         if resize_rgb:
@@ -164,7 +170,8 @@ class MonoVisualizationDataset(Dataset):
         name = pathlib.Path(img_f).stem
         if mask is None:
             mask = resize(np.array(PIL.Image.open(scene_dir / "masks" / "final" / f"{name}_final.png")), h, w, PIL.Image.Resampling.NEAREST)
-        depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
+        if depth is None:
+            depth = resize(np.load(scene_dir / "depths" / f"{name}.npz")["depth"], h, w, PIL.Image.Resampling.NEAREST)
         return rgb, mask, depth
 
     def _source_view(self, scene_dir, img_f, c2w, K, tgt_shape):
@@ -193,12 +200,27 @@ class MonoVisualizationDataset(Dataset):
         if scene is None:
             raw = self.store.decode_image(img_fs[0])  # (device_decode: a JPEG frame comes back on the device)
             scene = self.store.scene(scene_id, len(img_fs), tuple(raw.shape[:2]))
-            self.store.put(scene, 0, *self._decode_frame(scene_dir, img_fs[0], tuple(raw.shape[:2]), raw=raw, mask=self._store_mask(scene_dir, img_fs[0], scene, 0)))
+            decode = lambda f: self._decode_frame(scene_dir, img_fs[0], tuple(raw.shape[:2]), raw=raw, mask=self._store_mask(scene_dir, img_fs[0], scene, 0),  # noqa: E731
+                                                  depth=self._store_depth(scene, 0))
+            if self.store.device_depth:  # a fill of the one frame: its depth is placed like every other frame's
+                self.store._fill(scene, [0], decode, depth_request=lambda f: self._depth_request(scene_dir, img_fs[f]))
+            else:
+                self.store.put(scene, 0, *decode(0))
         return scene.h, scene.w
 
     def _store_mask(self, scene_dir, img_f, scene, f):
         """``device_mask``: the frame's mask as the store decodes it (in its slot where the device path serves the file); else None"""
         return self.store.decode_mask(self._mask_f(scene_dir, img_f), (scene.h, scene.w), into=(scene, f)) if self.store.device_mask else None
+
+    def _store_depth(self, scene, f):
+        """``device_depth``: the frame's depth where the fill placed it in its slot; else None (the host statement reads the file)"""
+        staged = self.store.staged_depth(scene, f)
+        return None if staged is None else staged.depth
+
+    @staticmethod
+    def _depth_request(scene_dir, img_f):
+        """the frame's depth file and this loader's statement over it, as ``SceneStore._stage_depths`` takes them: ``depth`` as it is"""
+        return scene_dir / "depths" / f"{pathlib.Path(img_f).stem}.npz", "depth", "copy", 1.0
 
     def _resident_item(self, scene_id, scene_dir, img_fs, shape, all_c2w, all_K, **kw):
         """``resident.build_item`` over this loader's readers and cameras"""
@@ -210,9 +232,10 @@ class MonoVisualizationDataset(Dataset):
         def decode(f):  # device_resize: the image as the store decodes it, at the file's size
             raw = self.store.decode_image(img_fs[f], into=(scene, f)) if self.store.device_resize else None
             return self._decode_frame(scene_dir, img_fs[f], shape, raw=raw, resize_rgb=not self.store.device_resize,
-                                      mask=self._store_mask(scene_dir, img_fs[f], scene, f))
+                                      mask=self._store_mask(scene_dir, img_fs[f], scene, f), depth=self._store_depth(scene, f))
 
         return build_item(self.store, scene, decode, cams=cams, image_path=lambda f: img_fs[f], mask_path=lambda f: self._mask_f(scene_dir, img_fs[f]),
+                          depth_request=lambda f: self._depth_request(scene_dir, img_fs[f]),
                           flow_path=lambda a, b: self._flow_path(scene_dir, img_fs, a, b), owner=type(self).__name__, **kw)
 
     def __getitem__(self, index):

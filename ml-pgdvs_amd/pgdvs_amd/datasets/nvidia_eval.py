@@ -63,7 +63,7 @@ from torch.utils.data import Dataset
 
 from ._common import (F32, TGT_HEIGHT, device_input, flat_cam, flow_entries, group_entries, mono_size, read_flow_npz,  # noqa: F401
                       read_flow_pair_or_zeros, refuse_gpu_in_worker, stack_views, tracker_entries)
-from ._common import ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
+from ._common import device_depth as check_device_depth, ray_rows as _ray_rows, resize as _resize, resize_nearest_f64 as _resize_nearest_f64
 from .resident import DEFAULT_MAX_BYTES, SceneStore, build_item
 from .static_aggregation import hwf_to_K
 
@@ -230,9 +230,10 @@ class NvidiaDynEvaluationDataset(Dataset):
                  rgb_range="0_1", use_aug=False, scene_ids=None, n_src_views_spatial=10,
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_path=None,
                  flow_consist_thres=1.0, device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES,
-                 device_resize=False, device_decode=False, device_entropy=False, device_png=False, device_mask=False):
+                 device_resize=False, device_decode=False, device_entropy=False, device_png=False, device_mask=False, device_depth=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
                                device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
+        device_depth = check_device_depth(type(self).__name__, options, device_depth)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["eval"], mode
@@ -256,7 +257,7 @@ class NvidiaDynEvaluationDataset(Dataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, options)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, options, device_depth)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         exts = {ex for ex, f in PIL.Image.registered_extensions().items() if f in PIL.Image.OPEN}
@@ -289,22 +290,27 @@ class NvidiaDynEvaluationDataset(Dataset):
     # ------------------------------------------------------------------ resident source frames (datasets/resident.py)
     store = None  # the SceneStore of ``resident=True``
 
-    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, options):
+    def _init_resident(self, resident, resident_scenes, resident_max_bytes, device, options, device_depth=False):
         if resident:
-            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_input=options)
+            self.store = SceneStore(device, resident_scenes, resident_max_bytes, self.flow_consist_thres, device_input=options, device_depth=device_depth)
 
     def _decode_frame(self, scene_id, frame_id, tgt_shape):
         """(image uint8, dynamic mask, depth) of an input frame at the target's size, as _source_view reads them; with
         ``device_resize`` the image as decoded: the store resizes it (``device_decode``: decoded on the device, where the file is
         a JPEG that path serves, straight into the frame's slot when it has the slot's size); with ``device_mask`` the mask as the
-        store decodes it, in its slot where the device path serves the file"""
+        store decodes it, in its slot where the device path serves the file; with ``device_depth`` the depth as the fill placed it in
+        its slot, where ``npy_file`` serves the file"""
         h, w = tgt_shape
         zoe = ()
+        staged = self.store.staged_depth(self.store.scenes.get(scene_id), frame_id)  # (device_depth, inside a fill; else None)
         if self.use_zoe_depth != "none":  # the prediction and its (scale, shift): the store aligns them per item
-            depth, *zoe = self._decode_zoe(scene_id, frame_id)
+            depth, *zoe = self._decode_zoe(scene_id, frame_id, staged)
+        elif staged is not None and staged.depth is not None:
+            depth = staged.depth
         else:
             depth = self._read_depth(scene_id, frame_id)
-        depth = _resize(depth, h, w, PIL.Image.Resampling.NEAREST)
+        if not isinstance(depth, torch.Tensor):  # (a placed depth went through Pillow's NEAREST picks on the device)
+            depth = _resize(depth, h, w, PIL.Image.Resampling.NEAREST)
         img_f = self._src_img_f(scene_id, frame_id)
         rgb = (self.store.decode_image(img_f, into=(self.store.scenes.get(scene_id), frame_id)) if self.store.device_resize else
                self._read_src_rgb(img_f, h, w))
@@ -312,15 +318,24 @@ class NvidiaDynEvaluationDataset(Dataset):
                 if self.store.device_mask else self._read_mask(scene_id, frame_id, h, w))
         return (rgb, mask, depth, *zoe)
 
-    def _decode_zoe(self, scene_id, frame_id):
+    def _decode_zoe(self, scene_id, frame_id, staged=None):
         """(depth_pred float32, (scale, shift) 0-d float64, (model type, principle)) of a frame for its slot of the store:
         the pair is selected once, and a file in other dtypes than the released ones is refused (the store keeps float32
-        predictions; the disk path would follow such a file's own promotion)"""
-        known = (scene_id, frame_id) in self.__dict__.get("_zoe_pairs", {})
-        pred, scale, shift = self._read_zoe(scene_id, frame_id)
+        predictions; the disk path would follow such a file's own promotion).  ``staged`` (``device_depth``): the file's bytes as
+        ``_zoe_depth_request`` read them, and the prediction in its slot where the fill placed it: scale and shift come from the
+        same bytes, and so does a prediction the device path did not serve"""
+        fresh = self.__dict__.setdefault("_zoe_fresh", set())  # (pairs the depth request selected a moment ago: counted here, as before)
+        known = (scene_id, frame_id) in self.__dict__.get("_zoe_pairs", {}) and (scene_id, frame_id) not in fresh
+        fresh.discard((scene_id, frame_id))
+        if staged is not None and staged.data is not None:
+            info = np.load(io.BytesIO(staged.data), allow_pickle=True)
+            k_scale, k_shift = zoe_scale_shift_keys(self._zoe_pairs[scene_id, frame_id][1])
+            pred, scale, shift = (staged.depth if staged.depth is not None else info["depth_pred"]), info[k_scale], info[k_shift]
+        else:
+            pred, scale, shift = self._read_zoe(scene_id, frame_id)
         pair = self._zoe_pairs[scene_id, frame_id]
         self.store.stats["zoe_files_read"] += 1 + (len(ZOE_TYPES) if self.use_zoe_depth == "moe" and not known else 0)
-        if pred.dtype != np.float32 or scale.dtype != np.float64 or shift.dtype != np.float64:
+        if (not isinstance(pred, torch.Tensor) and pred.dtype != np.float32) or scale.dtype != np.float64 or shift.dtype != np.float64:
             rel = f"{scene_id}/dense/zoe_depths_{pair[0]}/{frame_id:05d}.npz"
             k_scale, k_shift = zoe_scale_shift_keys(pair[1])
             raise ValueError(f"{self.zoe_depth_data_path} : {rel}: depth_pred is {pred.dtype}, {k_scale} {scale.dtype}, {k_shift} "
@@ -340,7 +355,29 @@ class NvidiaDynEvaluationDataset(Dataset):
             kw["depths"] = lambda ids, range_cams, rays: self.store.zoe_depths(scene, ids, range_cams, rays, kw["c2w_tgt"])
         return build_item(self.store, scene, lambda f: self._decode_frame(scene_id, f, tgt_shape), cams=cams,
                           image_path=lambda f: self._src_img_f(scene_id, f), mask_path=lambda f: self._mask_f(scene_id, f),
+                          depth_request=lambda f: self._depth_request(scene_id, f),
                           flow_path=lambda a, b: self._flow_path(scene_id, a, b), owner=type(self).__name__, **kw)
+
+    def _depth_request(self, scene_id, frame_id):
+        """``device_depth``: the frame's depth file and this loader's statement over it, as ``SceneStore._stage_depths`` takes them:
+        the DynIBaR disparity ``disp/%05d.npy`` with ``1 / (disp + 1e-8)``, or the ZoeDepth file's bytes with ``depth_pred`` as it is"""
+        if self.use_zoe_depth != "none":
+            return self._zoe_depth_request(scene_id, frame_id)
+        return self.depth_data_dir / scene_id / "disp" / f"{frame_id:05d}.npy", None, "reciprocal", 1.0
+
+    def _zoe_depth_request(self, scene_id, frame_id):
+        """the bytes of the frame's ``.npz`` of the selected model type -- from the directory, or the zip's member -- read once: the
+        store places ``depth_pred`` from them, ``_decode_zoe`` takes scale and shift from them"""
+        zobj, cache = self._zoe_zip_obj(), self.__dict__.setdefault("_zoe_pairs", {})
+        if (scene_id, frame_id) not in cache:
+            cache[scene_id, frame_id] = select_zoe_pair(self.zoe_depth_data_path, zobj, scene_id, frame_id, self.use_zoe_depth, self.zoe_k_dict)
+            self.__dict__.setdefault("_zoe_fresh", set()).add((scene_id, frame_id))
+        rel = f"{scene_id}/dense/zoe_depths_{cache[scene_id, frame_id][0]}/{frame_id:05d}.npz"
+        if zobj is None:
+            data = (pathlib.Path(self.zoe_depth_data_path) / rel).read_bytes()
+        else:
+            data = zobj.read(f"{pathlib.Path(self.zoe_depth_data_path).stem}/{rel}")
+        return data, "depth_pred", "copy", 1.0
 
     # ------------------------------------------------------------------ ZoeDepth
     use_zoe_depth, zoe_depth_data_path = "none", None  # (subclasses that build themselves never read ZoeDepth)
@@ -595,15 +632,16 @@ class NvidiaDynPureGeoEvaluationDataset(NvidiaDynEvaluationDataset):
     def __init__(self, *, data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir, max_hw, mode,
                  rgb_range="0_1", use_aug=False, scene_ids=None, flow_consist_thres=1.0, device="cuda", resident=False,
                  resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False, device_decode=False, device_entropy=False, device_png=False,
-                 device_mask=False):
+                 device_mask=False, device_depth=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
                                device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
+        device_depth = check_device_depth(type(self).__name__, options, device_depth)
         super().__init__(data_root=data_root, raw_data_dir=raw_data_dir, depth_data_dir=depth_data_dir,
                          mask_data_dir=mask_data_dir, flow_data_dir=flow_data_dir, max_hw=max_hw, mode=mode,
                          rgb_range=rgb_range, use_aug=use_aug, scene_ids=scene_ids, n_src_views_spatial=0,
                          n_src_views_temporal_track_one_side=0, flow_consist_thres=flow_consist_thres)
         self.device = device
-        self._init_resident(resident, resident_scenes, resident_max_bytes, device, options)  # (where the cloud is built)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, device, options, device_depth)  # (where the cloud is built)
         self.st_pcl_dict = {scene: self._aggregate_static_pcl(scene) for scene in sorted(self.scene_img_dict)}
 
     def _load_mono_video(self, scene_id):

@@ -18,7 +18,7 @@ images are resized on the device; ``device_decode=True``: their .
 import numpy as np
 import torch
 
-from ._common import F32, device_input, flat_cam, flow_entries, group_entries, mono_size, tracker_entries
+from ._common import F32, device_depth as check_device_depth, device_input, flat_cam, flow_entries, group_entries, mono_size, tracker_entries
 from .mono_vis import render_path, select_frames_for_time
 from .nvidia_eval import (ALL_SCENE_IDS_NVIDIA_DYN, N_CAMS, TGT_HEIGHT, NvidiaDynEvaluationDataset, read_llff_cams,
                           spatial_depth_range)
@@ -35,9 +35,10 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
                  n_src_views_temporal_track_one_side=5, use_zoe_depth="none", zoe_depth_data_f=None,
                  flow_consist_thres=1.0, vis_center_time=50, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32,
                  device=None, resident=False, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, device_resize=False,
-                 device_decode=False, device_entropy=False, device_png=False, device_mask=False):
+                 device_decode=False, device_entropy=False, device_png=False, device_mask=False, device_depth=False):
         options = device_input(type(self).__name__, resident=resident, device=device, device_resize=device_resize, device_decode=device_decode,
                                device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
+        device_depth = check_device_depth(type(self).__name__, options, device_depth)
         assert max_hw == -1, f"We enforce to use raw resolution. However, we receive max_hw of {max_hw}"
         assert not use_aug
         assert mode in ["vis"], mode
@@ -50,7 +51,7 @@ class NvidiaDynVisualizationDataset(NvidiaDynEvaluationDataset):
         self.n_src_views_temporal_track_one_side = n_src_views_temporal_track_one_side
         self.flow_consist_thres = flow_consist_thres
         self.depth_device = None if device is None else torch.device(device)
-        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, options)
+        self._init_resident(resident, resident_scenes, resident_max_bytes, self.depth_device, options, device_depth)
         self._set_dirs(data_root, raw_data_dir, depth_data_dir, mask_data_dir, flow_data_dir)
         scene_ids = ALL_SCENE_IDS_NVIDIA_DYN if scene_ids is None else scene_ids
         self.c2w_dict, self.hwf_dict, self.valid_fs = {}, {}, []

@@ -30,20 +30,23 @@ GPU store, which writes the float32 depths of all groups and selects the range o
 ``resident_scenes`` most recently used scenes stay; ``resident_max_bytes`` caps the store: a scene whose tables alone exceed
 it is refused before anything is allocated, older scenes and then the least recently used flow pairs go when it is reached.
 
-The image input has five options, each building on another.  ``_common.device_input`` is the one statement of these rules,
-for the five loaders and for this store alike; the first rule broken, in this order, is refused with what is missing:
+A frame's input has six options, each building on another.  ``_common.device_input`` is the one statement of the first five
+rules and ``_common.device_depth`` of the sixth, for the five loaders and for this store alike; the first rule broken, in this
+order, is refused with what is missing:
 
   device_entropy  needs device_decode
   device_png      needs device_resize (it is independent of device_decode)
   device_mask     needs device_resize (it is independent of the others)
   device_decode   needs device_resize
   device_resize   needs resident=True, and the store on a GPU
+  device_depth    needs device_resize (checked behind the five; it is independent of the others)
 
 ``device_resize``: the loaders hand over a frame's image as decoded, at the file's size, and the store uploads the bytes and
 resizes them on the device straight into the frame's slot (``ops.resample_u8``, Pillow's BOX filter bit for bit); the
 evaluation loaders' target image goes the same way (``expand_target``) and the pure-geometry loader's LANCZOS stack in one
 batched call (``resize_stack``).  An image the device path does not serve (not uint8 [H,W,3], or a size ``ops.resample_plan``
-refuses) takes the host statements.  Depths keep their host NEAREST resize, and so do masks unless ``device_mask`` is on.
+refuses) takes the host statements.  Depths keep their host NEAREST resize unless ``device_depth`` is on, masks unless
+``device_mask`` is.
 
 ``device_mask`` (``decode_mask``): a frame's mask file -- a non-interlaced grey or palette PNG of bit depth 1, 2, 4
 or 8 (``ops.png_decode_batch(kinds="mask")``) -- is inflated, unfiltered and unpacked in HIP straight into ``dyn_mask[slot]``, or,
@@ -53,7 +56,19 @@ interlaced, tRNS, damaged, not a PNG ...), errors included.  The loaders name th
 missing frames' masks into the same batch as their images when ``device_png`` is on as well -- one launch pair and one wait per
 item fill -- or into one batch of their own.  The DyCheck covisible PNG goes the same way (``decode_mask`` at the file's size,
 then ``ops.item_target``), the NVIDIA evaluation mask through ``decode_eval_mask``.  ``stats["masks_decoded_on_device"]`` and
-``stats["mask_fallbacks"]`` count the outcomes; they exist under the option alone.  Only the float depth file is left to numpy.
+``stats["mask_fallbacks"]`` count the outcomes; they exist under the option alone.
+
+``device_depth`` (``_stage_depths``): a frame's depth file -- an ``.npy``, or a stored member of an ``.npz``, holding
+little-endian float32 in C order (``npy_file`` finds the payload; no array is made on the host) -- crosses the bus as stored.  The
+loaders name the file and their statement over it (``depth_request``: "reciprocal" ``1 / (disp + 1e-8)`` for the NVIDIA family,
+"copy" for ``mono_vis`` and the ZoeDepth predictions, "scale" ``depth * scale`` for DyCheck); ``_fill`` gathers the missing frames'
+payloads in one pinned buffer, uploads it once, and ONE ``ops.depth_place`` writes the float32 depths straight into
+``depth[slot]``, through Pillow's own NEAREST picks where a file has another size: bit for bit the host statements, which still
+take every other file (float16, float64, big-endian, Fortran order, a compressed member, damaged ...), errors included.
+``stats["depths_placed_on_device"]`` and ``stats["depth_fallbacks"]`` count the outcomes; they exist under the option alone.  With
+``device_png`` and ``device_mask`` on as well, an item fill touches no pixel on the host.  Under the option a GPU store also reads
+a flow pair once, as stored, in one copy (``_upload_flow_pair``), and ``mono_vis`` takes its near depths from
+``ops.percentile_f32`` over the uploaded payloads (``depth_percentiles``).
 
 Three of the others decode images on the device, and ``decode_image`` is their one dispatch: it takes the file's bytes (from
 ``prefetch_images``' table, else from the file), asks the codec their signature names, counts the outcome, and hands every file
@@ -116,14 +131,17 @@ _Prefetched = namedtuple("_Prefetched", "data image png_tried", defaults=(None, 
 # one file of a ``_png_decode`` batch: its bytes; "file" or "rgb" (an image, read with these ``channels``) or "mask"; a mask's wanted
 # shape (None: the file's size); ``into`` = (scene or None, frame id), as ``decode_image`` and ``decode_mask`` take it
 _PngRequest = namedtuple("_PngRequest", "data kind shape into")
+# a frame's depth as ``_fill`` staged it under ``device_depth`` (``SceneStore.staged_depth``)
+_StagedDepth = namedtuple("_StagedDepth", "depth data")
 
 
 class SceneStore:
     """The per-dataset store.  ``device``: None (host memory, numpy gather) or a GPU device (``ops.item_views``).  The five
-    ``device_*`` keywords (the module's text), or ``device_input``: the loader's checked record of them."""
+    image-input ``device_*`` keywords (the module's text), or ``device_input``: the loader's checked record of them; and
+    ``device_depth``, the sixth, its own keyword either way."""
 
     def __init__(self, device=None, resident_scenes=1, resident_max_bytes=DEFAULT_MAX_BYTES, occ_thres=1.0, device_resize=False,
-                 device_decode=False, device_entropy=False, device_png=False, device_input=None, device_mask=False):
+                 device_decode=False, device_entropy=False, device_png=False, device_input=None, device_mask=False, device_depth=False):
         if resident_scenes < 1 or resident_max_bytes < 0:
             raise ValueError(f"resident_scenes {resident_scenes} (>= 1), resident_max_bytes {resident_max_bytes} (>= 0)")
         self.device = None if device is None else torch.device(device)
@@ -137,20 +155,27 @@ class SceneStore:
             device_input = _common.device_input("SceneStore", resident=True, device=self.device, device_resize=device_resize, device_decode=device_decode,
                                                 device_entropy=device_entropy, device_png=device_png, device_mask=device_mask)
         self.device_resize, self.device_decode, self.device_entropy, self.device_png, self.device_mask = device_input
+        self.device_depth = _common.device_depth("SceneStore", device_input, device_depth)  # (the sixth keyword: checked behind the five)
+        self._staged_depths = {}  # (id(scene), frame id) -> _StagedDepth, from _fill's one depth_place until the frame's decode takes it
         self._prefetched = {}  # (path, channels or "mask") -> _Prefetched, from prefetch_images until decode_image / decode_mask hands it out
         self.stats = {"frames_decoded": 0, "flow_files_read": 0, "items_built": 0, "frames_resized_on_device": 0,
                       "targets_resized_on_device": 0, "zoe_files_read": 0, "frames_decoded_on_device": 0, "targets_decoded_on_device": 0,
                       "jpeg_fallbacks": 0, "scans_decoded_on_device": 0, "entropy_fallbacks": 0, "png_decoded_on_device": 0, "png_fallbacks": 0}
         if self.device_mask:  # (counted under the option alone: without it the record is the one it was)
             self.stats.update(masks_decoded_on_device=0, mask_fallbacks=0)
+        if self.device_depth:
+            self.stats.update(depths_placed_on_device=0, depth_fallbacks=0)
 
     @property
     def nbytes(self):
-        return sum(s.nbytes + sum(self._pair_bytes(s) for _ in s.flows) for s in self.scenes.values())
+        return sum(s.nbytes + sum(self._pair_bytes(s, pair) for pair in s.flows.values()) for s in self.scenes.values())
 
     @staticmethod
-    def _pair_bytes(scene):
-        return scene.h * scene.w * 12
+    def _pair_bytes(scene, pair=None):
+        """a flow pair's bytes: flow and occlusion mask; a pair read under ``device_depth`` keeps the uploaded buffer its flow is a
+        view of, coord_diff included"""
+        held = 0 if pair is None else max(pair[0].untyped_storage().nbytes() - scene.h * scene.w * 8, 0)
+        return scene.h * scene.w * 12 + held
 
     # ------------------------------------------------------------------ scenes
     def scene(self, key, n_frames, shape, first_id=0, prediction=False):
@@ -192,7 +217,7 @@ class SceneStore:
             raise ValueError(f"frame ids {[int(f) for f in frame_ids]} outside the scene's {scene.first_id}..{scene.first_id + scene.n_frames - 1}")
         return slots
 
-    def _fill(self, scene, frame_ids, decode, image_path=None, mask_path=None):
+    def _fill(self, scene, frame_ids, decode, image_path=None, mask_path=None, *, depth_request=None):
         missing = [f for f in sorted(set(frame_ids)) if not scene.filled[f - scene.first_id]]
         images = self.device_png and image_path is not None
         masks = [(mask_path(f), (scene.h, scene.w), (scene, f)) for f in missing] if self.device_mask and mask_path is not None else []
@@ -200,10 +225,90 @@ class SceneStore:
             paths = [image_path(f) for f in missing] if images else []
             self.prefetch_images([p if isinstance(p, tuple) else (p, "file") for p in paths], [(scene, f) for f in missing], masks=masks)
         try:
+            if self.device_depth and depth_request is not None and missing:  # the missing frames' depth payloads: one buffer, one copy, one launch
+                self._stage_depths(scene, missing, depth_request)
             for f in missing:
                 self.put(scene, f, *decode(f))
         finally:
             self._prefetched.clear()  # (also when a reader raises: the entries hold device tensors, some of them slots)
+            self._staged_depths.clear()
+
+    # ------------------------------------------------------------------ the depth files on the device
+    def _stage_depths(self, scene, frames, depth_request):
+        """``device_depth``: ``depth_request(frame id) -> (path or bytes, member or None, op, scale)`` names each
+        frame's depth file -- an ``.npy``, or the stored member of an ``.npz`` -- and the statement the loader makes of it
+        (``ops.DEPTH_OPS``; None: the loader has no float32 statement for this frame).  The payloads ``npy_file`` finds (float32,
+        C order, [h,w]; with "scale", the DyCheck files' [h,w,1] too) cross the bus as stored in ONE pinned buffer and ONE
+        ``ops.depth_place`` writes them straight into ``scene.depth[slot]``, through Pillow's NEAREST picks where a file has
+        another size.  ``staged_depth`` hands each frame's outcome to its decode; a file the reader refuses is left to the loader's
+        own host statement, errors included."""
+        from .. import ops
+        from . import npy_file
+
+        placed, staged = [], {}
+        for f, slot in zip(frames, self.slots(scene, frames)):
+            request, data, served = depth_request(f), None, None
+            if request is not None:
+                source, member, op, scale = request
+                raw = data = source if isinstance(source, (bytes, bytearray, memoryview)) else None
+                if raw is None:
+                    try:
+                        with open(source, "rb") as fh:
+                            raw = fh.read()
+                    except OSError:  # (a missing file: the host statement says so)
+                        raw = None
+                if raw is not None:
+                    offset, shape, _ = npy_file.npy_payload(raw) if member is None else npy_file.npz_member(raw, member)
+                    if offset is not None and op == "scale" and len(shape) == 3 and shape[2] == 1:
+                        shape = shape[:2]
+                    if offset is not None and len(shape) == 2 and 1 <= min(shape) and max(shape) <= 16384:
+                        served = ops.DepthRequest(raw, offset, shape, op, scale, scene.depth[slot])
+            if served is not None:
+                placed.append(served)
+            staged[id(scene), int(f)] = _StagedDepth(None if served is None else served.out, data)
+        if placed:
+            ops.depth_place(placed, device=self.device)
+        self._staged_depths.update(staged)
+        self.stats["depths_placed_on_device"] += len(placed)
+        self.stats["depth_fallbacks"] += len(frames) - len(placed)
+
+    def staged_depth(self, scene, f):
+        """what ``_fill`` staged for frame id ``f`` of ``scene`` under ``device_depth``: a ``_StagedDepth`` -- ``depth``: the frame's
+        slot, filled on the device (``put`` recognises it), or None: the loader's host statement reads the file; ``data``: the
+        file's bytes where the loader's request handed bytes over -- or None outside such a fill"""
+        return self._staged_depths.get((id(scene), int(f))) if scene is not None else None
+
+    def depth_percentiles(self, files, member, q):
+        """``np.percentile(np.load(file)[member].reshape(-1), q)`` of every ``.npz`` file as a list of NumPy scalars (``mono_vis``'
+        near depths).  Under ``device_depth`` each file is read once, the payloads of the members ``npy_file`` serves travel in
+        ONE pinned buffer, ``ops.percentile_f32`` selects on the device and the host waits once; a file the reader refuses takes
+        the host statement from the same bytes."""
+        import io
+
+        from .. import ops
+        from . import npy_file
+
+        out, spans, total = [None] * len(files), [], 0
+        for i, path in enumerate(files):
+            with open(path, "rb") as fh:
+                data = fh.read()
+            offset, shape, _ = npy_file.npz_member(data, member) if self.device_depth else (None, None, None)
+            count = 0 if offset is None else int(np.prod(shape, dtype=np.int64))
+            if 1 <= count < 1 << 31:
+                spans.append((i, data, offset, total, count))
+                total += _pad16(count * 4)
+            else:
+                out[i] = np.percentile(np.load(io.BytesIO(data))[member].reshape(-1), q)
+        if spans:
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            view = host.numpy()
+            for _, data, offset, at, count in spans:
+                view[at:at + count * 4] = np.frombuffer(data, np.uint8, count * 4, offset)
+            dev = host.to(self.device, non_blocking=True)
+            got = ops.percentile_f32([dev[at:at + count * 4].view(torch.float32) for *_, at, count in spans], q).cpu().numpy()  # the one wait
+            for (i, *_), value in zip(spans, got):
+                out[i] = value
+        return out
 
     # ------------------------------------------------------------------ the decode on the device
     def _slot_for(self, into, height, width, channels=3):
@@ -450,13 +555,13 @@ class SceneStore:
             raise ValueError(f"frame {f}: image {rgb.dtype} {rgb.shape}, the store keeps uint8 {shape + (3,)}")
         if mask.dtype not in (np.bool_, np.uint8, torch.uint8) or tuple(mask.shape) != shape:
             raise ValueError(f"frame {f}: mask {mask.dtype} {tuple(mask.shape)}, the store keeps bool or uint8 {shape}")
-        if depth.shape != shape:
-            raise ValueError(f"frame {f}: depth {depth.shape}, expected {shape}")
+        if tuple(depth.shape) != shape or (isinstance(depth, torch.Tensor) and depth.dtype != torch.float32):
+            raise ValueError(f"frame {f}: depth {depth.dtype} {tuple(depth.shape)}, expected {shape} (a tensor: float32)")
         if scene.prediction != (scale_shift is not None):
             raise ValueError(f"frame {f}: a scene in prediction mode takes a prediction with its scale and shift, any other scene a depth alone")
         if scene.prediction:
             scale, shift = (np.asarray(x) for x in scale_shift)
-            if depth.dtype != np.float32 or scale.dtype != np.float64 or shift.dtype != np.float64 or scale.ndim or shift.ndim:
+            if depth.dtype not in (np.float32, torch.float32) or scale.dtype != np.float64 or shift.dtype != np.float64 or scale.ndim or shift.ndim:
                 raise ValueError(f"frame {f}: depth_pred {depth.dtype}, scale {scale.dtype} {scale.shape}, shift {shift.dtype} {shift.shape}; "
                                  "the store keeps float32 predictions and 0-d float64 scales and shifts")
             scene.scale_shift[slot] = (scale, shift)
@@ -476,18 +581,25 @@ class SceneStore:
                 scene.dyn_mask[slot].copy_(mask)
         else:
             scene.dyn_mask[slot].copy_(torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)))
-        scene.depth[slot].copy_(F32(depth))
+        if isinstance(depth, torch.Tensor):
+            if depth.data_ptr() != scene.depth[slot].data_ptr():  # (else _fill's depth_place wrote the slot)
+                scene.depth[slot].copy_(depth)
+        else:
+            scene.depth[slot].copy_(F32(depth))
         scene.filled[slot] = True
         self.stats["frames_decoded"] += 1
 
-    def views(self, scene, groups, decode, image_path=None, mask_path=None):
+    def views(self, scene, groups, decode, image_path=None, mask_path=None, *, depth_request=None):
         """one dict per group ``(frame ids, with_depth)``: rgb, dyn_rgb, static_rgb [n,H,W,3], dyn_mask and (with_depth) depth
         [n,H,W,1], float32 on the store's device; ``decode(frame id) -> (rgb uint8, mask, depth)`` fills missing slots;
         ``image_path(frame id)`` -> the frame's image file (or (file, channels)): with ``device_png`` the missing frames'
-        files are prefetched in one launch; ``mask_path(frame id)`` -> the frame's mask file: with ``device_mask`` in the same one"""
+        files are prefetched in one launch; ``mask_path(frame id)`` -> the frame's mask file: with ``device_mask`` in the same one;
+        ``depth_request(frame id)`` -> the frame's depth file and statement (``_stage_depths``): with ``device_depth`` the missing
+        frames' depths are placed in one launch"""
         frame_ids = [int(f) for ids, _ in groups for f in ids]
         groups = [(self.slots(scene, ids), with_depth) for ids, with_depth in groups]  # (checked before anything is decoded)
-        self._fill(scene, frame_ids, decode, image_path, **({"mask_path": mask_path} if self.device_mask and mask_path is not None else {}))
+        self._fill(scene, frame_ids, decode, image_path, **({"mask_path": mask_path} if self.device_mask and mask_path is not None else {}),
+                   **({"depth_request": depth_request} if self.device_depth and depth_request is not None else {}))
         if scene.prediction and any(with_depth for _, with_depth in groups):
             raise ValueError("a scene in prediction mode holds no depths: zoe_depths aligns its predictions")
         self.stats["items_built"] += 1
@@ -552,6 +664,24 @@ class SceneStore:
             scene.flows.move_to_end((a, b))
         return pair[0].clone(), pair[1].clone()[..., None]
 
+    def _upload_flow_pair(self, scene, path):
+        """``device_depth``: (flow, coord_diff) float32 [H,W,2] on the device, views of ONE uploaded buffer that holds both payloads
+        as the file stores them -- where both are stored ``<f4`` members of the scene's size; else None: ``_read_flow``'s own
+        statement reads the file, errors included.  The pair's flow keeps the buffer (``_pair_bytes`` counts it)."""
+        from . import npy_file
+
+        with open(path, "rb") as f:
+            data = f.read()
+        spans = [npy_file.npz_member(data, name)[:2] for name in ("flow", "coord_diff")]
+        if any(offset is None or tuple(shape) != (scene.h, scene.w, 2) for offset, shape in spans):
+            return None
+        nbytes = scene.h * scene.w * 8
+        host = torch.empty(2 * _pad16(nbytes), dtype=torch.uint8, pin_memory=True)
+        for k, (offset, _) in enumerate(spans):
+            host.numpy()[k * _pad16(nbytes):k * _pad16(nbytes) + nbytes] = np.frombuffer(data, np.uint8, nbytes, offset)
+        dev = host.to(self.device, non_blocking=True)
+        return tuple(dev[k * _pad16(nbytes):k * _pad16(nbytes) + nbytes].view(torch.float32).view(scene.h, scene.w, 2) for k in range(2))
+
     def _read_flow(self, scene, path):
         self.stats["flow_files_read"] += 1
         if self.device is None:
@@ -560,6 +690,10 @@ class SceneStore:
             return F32(flow), F32(occ)
         from .. import ops
 
+        if self.device_depth:  # the file read once, both members as stored in one pinned buffer, one asynchronous copy
+            pair = self._upload_flow_pair(scene, path)
+            if pair is not None:
+                return pair[0], ops.flow_occ(pair[1], self.occ_thres)
         info = np.load(path)
         flow, cd = info["flow"], info["coord_diff"]
         assert flow.shape[:2] == (scene.h, scene.w), (flow.shape, (scene.h, scene.w))
@@ -600,7 +734,7 @@ def group_host_entries(group, flat_cams, times=None, n_actual=None):
 
 
 def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spatial_depth, c2w_tgt, flow_path, trackers, owner,
-               ray_rows=None, depth_range=None, depths=None, image_path=None, mask_path=None):
+               ray_rows=None, depth_range=None, depths=None, image_path=None, mask_path=None, depth_request=None):
     """An item of the five loaders from the store, key for key and bit for bit the disk path's.  ``fixed``: the
     non-tensor entries; ``host``: the host-made tensors (on a GPU store they travel in ONE packed copy, with the groups'
     cameras and times; entries named ``__...`` are the loader's own cargo: they come back in the item, on the device, for
@@ -616,7 +750,8 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
     None) -> ([depth [n,H,W,1] per group], depth_range or None)`` on the store's device (``SceneStore.zoe_depths`` over a
     scene in prediction mode): the store then gathers colours and masks alone, and every depth and the range come from there.
     ``image_path(frame id)``: the frame's image file, for ``SceneStore.views`` to prefetch under ``device_png``;
-    ``mask_path(frame id)``: its mask file, for the same batch under ``device_mask``."""
+    ``mask_path(frame id)``: its mask file, for the same batch under ``device_mask``; ``depth_request(frame id)``: its depth file
+    and the loader's statement over it (``SceneStore._stage_depths``), for the fill's one ``ops.depth_place`` under ``device_depth``."""
     from . import nvidia_eval as NE
 
     dev = store.device
@@ -644,7 +779,7 @@ def build_item(store, scene, decode, *, fixed, host, cams, sel, spatial_ids, spa
             add(f"temporal_track_{side}", sel[side], True, sel[side], sel[f"n_actual_{side}"])
     # the range needs the spatial depths even where the item carries none (the visualisation loaders)
     views = store.views(scene, [(ids, depths is None and (with_depth or name == "spatial")) for name, ids, with_depth in groups], decode, image_path,
-                        mask_path)
+                        mask_path, **({"depth_request": depth_request} if store.device_depth and depth_request is not None else {}))
     small = pack_to_device(host, dev) if dev is not None else host
     rays = small.pop("__rays", None)
     item = dict(fixed)

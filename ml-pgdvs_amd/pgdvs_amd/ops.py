@@ -10,7 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import math
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -1681,6 +1681,83 @@ def mask_place(src, shape=None, mode: str = "u8", out=None):
         stride = W * 12
     check(_lib.load().pgdvs_mask_place(_ptr(src), h, w, c, src.stride(0) if h > 1 else w * c, None if index is None else _ptr(index), H, W,
                                        MASK_PLACE_MODES[mode], _ptr(out), stride, _stream()), "pgdvs_mask_place")
+    return out
+
+
+DEPTH_OPS = {"copy": 0, "reciprocal": 1, "scale": 2}  # PGDVS_DEPTH_*
+DEPTH_MAX_ENTRIES = 4096  # PGDVS_DEPTH_MAX_ENTRIES
+# one depth payload of a ``depth_place`` batch: ``data`` (bytes-like) holds the little-endian float32 [h,w] array ``shape`` at
+# byte ``offset`` (``datasets.npy_file`` finds it); ``op`` of DEPTH_OPS with its ``scale`` (a float32 value; used by "scale"
+# alone); ``out``: the float32 [H,W] GPU tensor to fill, pixels contiguous, the row stride free
+DepthRequest = namedtuple("DepthRequest", "data offset shape op scale out")
+
+
+def depth_place(requests, device=None, align: int = 16):
+    """The float32 payloads of depth files, as stored, into their places (``pgdvs_depth_place``; include/pgdvs_hip.h; DESIGN.md
+    7l).  ``requests``: ``DepthRequest``s.  Every payload is copied once, as bytes, into ONE pinned buffer behind the entry
+    table (each at a multiple of ``align`` bytes: 16, so the kernel loads 16 bytes per lane; the ABI asks for 4), one asynchronous
+    copy takes the buffer to ``device`` (default: the outs') and ONE launch on the current stream writes every ``out``: "copy" the
+    values themselves, "reciprocal" ``1 / (x + 1e-8)`` as NumPy 2 evaluates it on a float32 array, "scale" ``x * scale``, each
+    bit for bit the numpy statement.  An ``out`` of another size than its source is filled through Pillow's own NEAREST
+    picks (``nearest_map``).  Does not synchronise.  Returns the outs."""
+    requests = list(requests)
+    n = len(requests)
+    if not 1 <= n <= DEPTH_MAX_ENTRIES:
+        raise ValueError(f"depth_place: {n} requests (1 .. {DEPTH_MAX_ENTRIES})")
+    if align < 4 or align % 4:
+        raise ValueError(f"depth_place: align {align} (a multiple of 4)")
+    device = _cuda_device(device, "depth_place: the payloads are placed", [r.out for r in requests])
+    offsets, at = [], -(-n * C.sizeof(_lib.DepthEntry) // 16) * 16
+    for i, r in enumerate(requests):
+        h, w = (int(v) for v in r.shape)
+        o = r.out
+        ok = (isinstance(o, torch.Tensor) and o.is_cuda and o.device == device and o.dtype == torch.float32 and o.ndim == 2 and o.numel() > 0 and
+              o.stride(1) == 1 and (o.stride(0) >= o.shape[1] or o.shape[0] == 1))
+        if not ok:
+            raise ValueError(f"depth_place: out of request {i} must be a float32 [H,W] tensor on {device} with contiguous rows, got "
+                             f"{getattr(o, 'dtype', type(o))} {tuple(getattr(o, 'shape', ()))} on {getattr(o, 'device', None)}")
+        if r.op not in DEPTH_OPS:
+            raise ValueError(f"depth_place: request {i}: op {r.op!r}, expected one of {tuple(DEPTH_OPS)}")
+        if h < 1 or w < 1 or r.offset < 0 or r.offset + h * w * 4 > len(r.data):
+            raise ValueError(f"depth_place: request {i}: {h} x {w} floats at byte {r.offset} of {len(r.data)}")
+        at = -(-at // align) * align
+        offsets.append(at)
+        at += h * w * 4
+    buf = torch.empty(-(-at // 16) * 16, dtype=torch.uint8, pin_memory=True)
+    view = buf.numpy()
+    table = (_lib.DepthEntry * n).from_address(buf.data_ptr())
+    for i, (r, off) in enumerate(zip(requests, offsets)):
+        h, w = (int(v) for v in r.shape)
+        H, W = (int(v) for v in r.out.shape)
+        view[off:off + h * w * 4] = np.frombuffer(r.data, np.uint8, h * w * 4, r.offset)
+        index = None if (H, W) == (h, w) else nearest_map((h, w), (H, W), device)
+        e = table[i]
+        e.offset, e.h, e.w, e.op, e.scale = off, h, w, DEPTH_OPS[r.op], float(np.float32(r.scale))
+        e.map, e.out, e.out_row_stride, e.H, e.W = (None if index is None else index.data_ptr()), r.out.data_ptr(), (r.out.stride(0) if H > 1 else W) * 4, H, W
+    with torch.cuda.device(device):
+        dev = buf.to(device, non_blocking=True)
+        check(_lib.load().pgdvs_depth_place(C.c_void_p(buf.data_ptr()), _ptr(dev), buf.numel(), n, _stream()), "pgdvs_depth_place")
+    return [r.out for r in requests]
+
+
+def percentile_f32(frames, q):
+    """``np.percentile(frame, q)`` (NumPy 2, method "linear") of every frame of ``frames`` -- float32 GPU tensors of any shape, at
+    least one value each -- as a float32 [len(frames)] tensor on their device, bit for bit (``pgdvs_percentile_f32``;
+    include/pgdvs_hip.h): an exact radix select of the two neighbouring ranks and NumPy's ``_lerp``; any NaN in a frame gives NaN.
+    Launches only: the caller's one ``.cpu()`` is the batch's one wait."""
+    frames = [_req(f, torch.float32, "frames").reshape(-1) for f in frames]
+    if not frames or any(f.numel() < 1 for f in frames) or any(f.device != frames[0].device for f in frames):
+        raise ValueError("percentile_f32: at least one frame, each with at least one value, all on one GPU")
+    if type(q) not in (int, float) or not 0 <= q <= 100:
+        raise ValueError(f"percentile_f32: q must be a Python number in 0 .. 100 (NumPy forms q / 100 in the array's type then), got {q!r}")
+    n, device = len(frames), frames[0].device
+    lib = _lib.load()
+    counts = (C.c_int64 * n)(*[f.numel() for f in frames])
+    ptrs = (C.c_void_p * n)(*[f.data_ptr() for f in frames])
+    with torch.cuda.device(device):
+        ws = _ws(lib.pgdvs_percentile_f32_workspace_bytes(counts, n), device)
+        out = torch.empty(n, dtype=torch.float32, device=device)
+        check(lib.pgdvs_percentile_f32(ptrs, counts, n, float(q), _ptr(out), _ptr(ws), ws.numel(), _stream()), "pgdvs_percentile_f32")
     return out
 
 

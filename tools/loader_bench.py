@@ -33,7 +33,14 @@ monocular layout for ``mono_vis``:
             is a third variant beside the two where the package has the keyword, and per frame the scan on
            the device at the ``--scan-sizes`` subsequence sizes (eight by default): host preparation, bytes uploaded, the scan's launches by device events,
            each kernel's mean, the synchronisation rounds used, and the whole ``ops.jpeg_decode`` call both ways
-``--legs nvidia,dycheck,resample,zoe,decode`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
+  depth    ``device_depth=True`` against every other device option alone (``device_resize``, ``device_decode``,
+           ``device_entropy``, ``device_png``, ``device_mask``): the five loaders (``--depth-parts``), first and second pass items/s of
+           fresh loaders, the two variants alternating over ``--rounds`` rounds in one process (median, min and max: the spread
+           between the "off" rounds is the yardstick of a difference), the items compared bit for bit, the construction time of
+           each variant (``mono_vis`` takes its near depths there); and ``ops.depth_place`` alone for one 288 x 550 frame and a
+           batch of 12: the kernel by the library's event brackets against its streaming bound (4 bytes in, 4 out per pixel at
+           6.29 TB/s), and the whole call (staging, upload and launch) by device events and on the host's clock
+``--legs nvidia,dycheck,resample,zoe,decode,png,depth`` picks what runs (nvidia: items, vis_run and gather).  Prints one JSON object.
 Usage (GPU box): timeout -k 10 900 python tools/loader_bench.py [--data_root DIR --scene Balloon1] [--items 32] [--legs dycheck] [--out FILE]"""
 import argparse
 import json
@@ -612,6 +619,115 @@ def png_case(scratch, nvidia_root, mono_root, scene, center, n_items, reps, roun
     return rec
 
 
+DEPTH_PARTS = ("nvidia_eval", "nvidia_pure_geo", "nvidia_vis", "mono_vis", "dycheck", "op")
+OTHER_DEVICE_OPTIONS = dict(device_resize=True, device_decode=True, device_entropy=True, device_png=True, device_mask=True)
+
+
+def depth_loaders_case(factories, n_items, rounds):
+    """fresh loaders each round, every other device option on, without and with ``device_depth=True``, alternating; items/s of both
+    passes and the seconds each construction took.  ``factories``: name -> fn(device_depth) -> loader"""
+    rec = {}
+    for name, fn in factories.items():
+        variants = ("off", "device_depth")
+        probe = fn(True)
+        idx = [int(round(j * (len(probe) - 1) / max(n_items - 1, 1))) for j in range(n_items)]
+        probe[idx[0]]  # (warm-up: code objects, the resize plans, the side streams)
+        del probe
+        rates = {v: {"first": [], "second": [], "construct_s": []} for v in variants}
+        want, same, stats = None, True, {}
+        for _ in range(rounds):
+            for v in variants:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ds = fn(v == "device_depth")
+                torch.cuda.synchronize()
+                rates[v]["construct_s"].append(time.perf_counter() - t0)
+                r1, got1 = timed_pass(ds, idx)
+                r2, got2 = timed_pass(ds, idx)
+                rates[v]["first"].append(r1)
+                rates[v]["second"].append(r2)
+                if want is None:
+                    want = got1
+                same = same and all(same_bits(a, b) and same_bits(c, b) for a, b, c in zip(got1, want, got2))
+                stats[v] = dict(ds.store.stats)
+                del ds, got1, got2
+                torch.cuda.empty_cache()
+        r = rec[name] = {"items": len(idx), "rounds": rounds, "bit_identical": same, "stats": stats}
+        for v in variants:
+            r[f"{v}_first_pass_items_per_s"], r[f"{v}_second_pass_items_per_s"] = _spread(rates[v]["first"]), _spread(rates[v]["second"])
+            r[f"{v}_construct_s"] = _spread(rates[v]["construct_s"])
+        off, on = r["off_first_pass_items_per_s"], r["device_depth_first_pass_items_per_s"]
+        r["first_pass_on_over_off"] = on["median"] / off["median"]
+        r["faster_than_the_off_spread"] = bool(on["median"] > off["max"])
+        print(f"depth {name}: {r}", file=sys.stderr, flush=True)
+    return rec
+
+
+def depth_op_case(reps):
+    """``ops.depth_place`` of 288 x 550 frames ("reciprocal", straight into padded slots): the kernel alone and the whole call"""
+    import ctypes as C
+
+    from eval_lpips_bench import event_median
+    from pgdvs_amd import _lib, ops
+
+    lib = _lib.load()
+    rng = np.random.default_rng(5)
+    rec = {"size": [H, W]}
+    for batch in (1, 12):
+        datas = [rng.uniform(0.2, 0.6, (H, W)).astype(np.float32) for _ in range(batch)]
+        slots = torch.empty((batch, -(-H * W // 4) * 4), dtype=torch.float32, device="cuda:0")
+        outs = [slots[k, :H * W].view(H, W) for k in range(batch)]
+        requests = [ops.DepthRequest(d.tobytes(), 0, d.shape, "reciprocal", 1.0, o) for d, o in zip(datas, outs)]
+        call = lambda: ops.depth_place(requests, device="cuda:0")  # noqa: E731
+        call()
+        equal = all(np.array_equal(o.cpu().numpy(), 1 / (d + 1e-8)) for d, o in zip(datas, outs))
+        lib.pgdvs_prof_enable(1)
+        for _ in range(reps):
+            call()
+        text = C.create_string_buffer(4096)
+        lib.pgdvs_prof_report(text, 4096)
+        lib.pgdvs_prof_enable(0)
+        kernel_ms = [float(ln.split()[2]) / reps for ln in text.value.decode().splitlines() if ln.startswith("depth_place")][0]
+        med, mn = event_median(call, reps, 1)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            call()
+        host_ms = (time.perf_counter() - t0) * 1e3 / reps
+        torch.cuda.synchronize()
+        nbytes = batch * H * W * 8
+        rec[f"batch_{batch}"] = {"equal_numpy": bool(equal), "bytes_in_and_out": nbytes, "streaming_bound_us": nbytes / HBM_BYTES_PER_S * 1e6,
+                                 "kernel_us": kernel_ms * 1e3, "kernel_share_of_stream_rate": nbytes / HBM_BYTES_PER_S / (kernel_ms * 1e-3),
+                                 "call_events_ms": {"median": med, "min": mn}, "call_host_ms": host_ms}
+        print(f"depth op batch {batch}: {rec[f'batch_{batch}']}", file=sys.stderr, flush=True)
+    return rec
+
+
+def depth_case(scratch, nvidia_root, mono_root, scene, center, n_items, reps, rounds, parts):
+    """the depth leg: the synthetic scenes as written; ``parts`` of the five loaders (each on its own, so that a run can be cut into
+    calls) and op (``ops.depth_place`` alone)"""
+    from pgdvs_amd.datasets.dycheck_iphone import DyCheckiPhoneEvaluationDataset
+    from pgdvs_amd.datasets.mono_vis import MonoVisualizationDataset
+    from pgdvs_amd.datasets.nvidia_eval import NvidiaDynEvaluationDataset, NvidiaDynPureGeoEvaluationDataset
+    from pgdvs_amd.datasets.nvidia_vis import NvidiaDynVisualizationDataset
+
+    on = dict(device="cuda:0", resident=True, **OTHER_DEVICE_OPTIONS)
+    nv = dict(data_root=nvidia_root, raw_data_dir="raw", depth_data_dir="depths", mask_data_dir="masks", flow_data_dir="flows", max_hw=-1, scene_ids=[scene], **on)
+    vis = dict(vis_center_time=center, n_render_frames=200, vis_time_interval=10, vis_bt_max_disp=32)
+    factories = {"nvidia_eval": lambda d: NvidiaDynEvaluationDataset(mode="eval", device_depth=d, **nv),
+                 "nvidia_pure_geo": lambda d: NvidiaDynPureGeoEvaluationDataset(mode="eval", device_depth=d, **nv),
+                 "nvidia_vis": lambda d: NvidiaDynVisualizationDataset(mode="vis", device_depth=d, **vis, **nv),
+                 "mono_vis": lambda d: MonoVisualizationDataset(data_root=mono_root, max_hw=-1, mode="vis", scene_ids=[MONO_SCENE], device_depth=d, **vis, **on)}
+    if "dycheck" in parts:
+        root = write_dycheck_tree(scratch / "dycheck_depth")
+        kw = dict(data_root=root, raw_data_dir="iphone", mask_data_dir="flow_mask", flow_data_dir="flow_mask", max_hw=-1, mode="eval", scene_ids=[DY_SCENE],
+                  spatial_src_view_type="closest_wo_temporal", n_src_views_spatial=10, n_src_views_temporal_track_one_side=5, **on)
+        factories["dycheck"] = lambda d: DyCheckiPhoneEvaluationDataset(device_depth=d, **kw)
+    rec = {"loaders": depth_loaders_case({k: v for k, v in factories.items() if k in parts}, n_items, rounds)}
+    if "op" in parts:
+        rec["op"] = depth_op_case(reps)
+    return rec
+
+
 def write_dycheck_tree(root, frames=DY_F):
     """a synthetic DyCheck iPhone scene in the layout iPhoneParser reads: 360 x 480 (the 2x frames), ``frames`` train frames on
     camera 0 at time ids 0.., two val cameras at every second instant (val frames sit on train instants, as the dataset's do,
@@ -753,11 +869,12 @@ def main():
     ap.add_argument("--items", type=int, default=32)
     ap.add_argument("--vis-views", type=int, default=48)
     ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe, decode, png")
+    ap.add_argument("--legs", default="nvidia,dycheck", help="comma-separated: nvidia (the four loaders, vis_run, gather), dycheck, resample, zoe, decode, png, depth")
     ap.add_argument("--rounds", type=int, default=3, help="decode leg: rounds of fresh loaders per variant")
     ap.add_argument("--scan-sizes", default="16,32,48,64,96,128,256,512", help="decode leg: subsequence sizes (bytes) of the per-frame scan figures")
     ap.add_argument("--png-sizes", default="16,32,64,128,256", help="png leg: subsequence sizes (bytes) of the per-frame figures")
     ap.add_argument("--png-parts", default=",".join(PNG_PARTS), help="png leg: which of its parts run (a long leg is cut into calls)")
+    ap.add_argument("--depth-parts", default=",".join(DEPTH_PARTS), help="depth leg: which of its parts run (a long leg is cut into calls)")
     ap.add_argument("--zoe-setting", default="moe", help="use_zoe_depth of the zoe leg")
     ap.add_argument("--zoe-path", default=None, help="zoe_depth_data_path under a real --data_root (the synthetic tree brings its own)")
     ap.add_argument("--out", default=None)
@@ -769,7 +886,7 @@ def main():
     scratch = pathlib.Path(tempfile.mkdtemp(prefix="loader_bench_"))
     rec = {"device": torch.cuda.get_device_name(0), "host_threads": torch.get_num_threads(), "items": args.items, "loaders": {}}
     legs = set(args.legs.split(","))
-    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe", "decode", "png"}, args.legs
+    assert legs and legs <= {"nvidia", "dycheck", "resample", "zoe", "decode", "png", "depth"}, args.legs
     try:
         if "resample" in legs:
             rec["resample"] = resample_case(args.reps)
@@ -778,7 +895,10 @@ def main():
             rec["dycheck"] = dycheck_case(scratch, args.items, args.reps)
             print(f"dycheck: {rec['dycheck']}", file=sys.stderr, flush=True)
         png_tree = "png" in legs and set(args.png_parts.split(",")) != {"dycheck"}  # (the DyCheck part writes a tree of its own)
-        if not legs & {"nvidia", "zoe", "decode"} and not png_tree:
+        depth_parts = tuple(args.depth_parts.split(",")) if "depth" in legs else ()
+        assert set(depth_parts) <= set(DEPTH_PARTS), args.depth_parts
+        depth_tree = bool(set(depth_parts) - {"dycheck", "op"})  # (the DyCheck part writes a tree of its own, the op needs none)
+        if not legs & {"nvidia", "zoe", "decode"} and not png_tree and not depth_tree:
             nvidia_root = mono_root = center = None
         elif args.data_root is None:
             t0 = time.perf_counter()
@@ -825,6 +945,9 @@ def main():
         if "nvidia" in legs:
             rec["vis_run"] = vis_run_case(make["nvidia_vis"], args.vis_views, scratch)
             rec["gather"] = gather_case(args.reps)
+        if "depth" in legs:  # (in front of the legs that rewrite the synthetic tree's image files)
+            assert args.data_root is None or not {"mono_vis"} & set(depth_parts), "mono_vis runs on the synthetic tree"
+            rec["depth"] = depth_case(scratch, nvidia_root, mono_root, args.scene, center, args.items, args.reps, args.rounds, depth_parts)
         if "png" in legs:  # (it rewrites the synthetic tree's image files too)
             assert args.data_root is None and "decode" not in legs, "the png leg rewrites the synthetic tree: a run of its own"
             parts = tuple(args.png_parts.split(","))
